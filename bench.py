@@ -14,6 +14,10 @@ For N > 1 either launch this file under torch.distributed.run (one rank per GPU;
 MASTER_* from the environment), or call it directly: without WORLD_SIZE in the environment ``python bench.py --gpus N``
 starts its own N ranks as fresh child processes (self_launch) and relays rank 0's line.
 Prints ONE JSON line on rank 0.
+
+``--dump-outputs DIR`` also writes what the last timed step returned on rank 0 -- the gathered (n_total, 800) descriptors
+and the rank's (n_local, 800) GAT embeddings -- as DIR/descriptors.npy and DIR/embeddings.npy (float32, 64 MB at most).
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -505,11 +509,31 @@ def measure_latencies(enc, model, dev):
     return out
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array.  When together they exceed DUMP_BYTES_MAX (a larger --clouds), each
+    array keeps a fixed, seeded sample of its rows, in order, so that two runs with the same arguments still compare row
+    for row."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES_MAX:
+            keep = max(1, len(a) * DUMP_BYTES_MAX // total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        print(f"[bench] wrote {name}.npy {a.shape} {a.dtype}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0: the gathered descriptors and its embedding rows) "
+                         "as DIR/<name>.npy in float32, for output-for-output comparison of two builds")
     ap.add_argument("--clouds", type=int, default=N_CLOUDS, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-sample", type=int, default=1024, help=argparse.SUPPRESS)
     ap.add_argument("--no-cpu-baseline", action="store_true", help=argparse.SUPPRESS)
@@ -782,6 +806,9 @@ def main():
         sync()
         dt = time.perf_counter() - t0
         gc.enable()
+        # read back before anything else runs on the device (the path's buffers rotate, a captured forward's output is reused)
+        dumped = ({"descriptors": desc_all.float().cpu().numpy(), "embeddings": emb.float().cpu().numpy()}
+                  if args.dump_outputs and rank == 0 else None)
         if chosen != "serial":
             desc_local = desc_all[rank * n_local:(rank + 1) * n_local] if multi else desc_all
         # outside the timed region: the same kernel alone on the device (no GNN co-running), for reference --
@@ -931,6 +958,8 @@ def main():
                 "descriptor_max_abs_err_vs_oracle": float(np.abs(got - odesc).max()),
                 "ok": bool(np.all(np.abs(got - odesc) <= 1e-6 * np.abs(odesc) + 1e-9)),
             }
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(line), flush=True)
     if multi:
         dist.destroy_process_group()

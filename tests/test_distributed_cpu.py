@@ -183,7 +183,9 @@ def _grad_worker(rank, world, port, q):
         nd.all_reduce_gradients(ps)
         trip = np.arange(30).reshape(10, 3)
         part, wgt = nd.split_triplets(trip, rank, world)
-        q.put((rank, ps[0].grad.clone(), ps[1].grad.clone(), part, wgt))
+        # numpy copies, not tensors: torch pickles a tensor as a file descriptor that the parent can only fetch while
+        # this process is still alive, and it may already have exited by then
+        q.put((rank, ps[0].grad.numpy().copy(), ps[1].grad.numpy().copy(), part, wgt))
     finally:
         dist.destroy_process_group()
 
@@ -202,6 +204,7 @@ def test_gradient_all_reduce_and_triplet_split():
         assert p.exitcode == 0
     rows, wsum = [], 0.0
     for rank, g0, g1, part, wgt in res:
+        g0, g1 = torch.from_numpy(g0), torch.from_numpy(g1)
         assert torch.equal(g0, torch.full((3, 5), 3.0))                 # 1 + 2
         assert torch.equal(g1, torch.arange(7, dtype=torch.float32) * 3)
         rows.append(part)
