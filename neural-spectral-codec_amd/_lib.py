@@ -195,6 +195,22 @@ def stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+# Parameter epoch: bumped after every optimizer step of the process.  torch's fused Adam / AdamW / SGD write the parameters
+# without bumping their version counters, so caches derived from parameter VALUES (the GNN's folded attention vectors, the
+# encoder's bin LUT) carry this integer in their keys next to (data_ptr, _version).  Writes through ``.data`` bypass both.
+param_epoch = 0
+
+
+def _bump_param_epoch(optimizer, args, kwargs):
+    global param_epoch
+    param_epoch += 1
+
+
+from torch.optim.optimizer import register_optimizer_step_post_hook  # noqa: E402
+
+register_optimizer_step_post_hook(_bump_param_epoch)
+
+
 def require_cuda(t, name):
     if not t.is_cuda:
         raise NscError(f"{name} must live on a HIP device (got {t.device}); the MI355X path has no "

@@ -422,11 +422,17 @@ class ShardedDescriptorPath:
         if hasattr(inner, "_model_struct"):
             # the capture bakes in the folded attention vectors the model caches: make sure they exist for the current
             # weights, and key on their generation -- an optimizer that writes through a multi-tensor kernel does not bump
-            # the parameters' version counters, GNNTrainer drops the cache after every step instead (a new generation)
+            # the parameters' version counters; every optimizer step bumps _lib.param_epoch instead (a new generation)
             inner._model_struct(live)
             folded = inner._struct_cache[2]
+        # the capture also bakes in the window graph's CSR arrays: key on that GraphCSR and keep it (and the graph) in the
+        # entry, so that its memory cannot go back to the allocator while a replay may read it
+        csr = None
+        if hasattr(inner, "_csr"):
+            use_edge = getattr(self._graph, "edge_attr", None) is not None and getattr(inner, "edge_dim", None) is not None
+            csr = inner._csr(self._graph, use_edge)
         key = (x.data_ptr(), tuple(x.shape), tuple((t.data_ptr(), t._version) for t in live),
-               getattr(inner, "coresident", False), getattr(inner, "_fold_generation", 0))
+               getattr(inner, "coresident", False), getattr(inner, "_fold_generation", 0), id(csr))
         ent = self._gnn_graphs.get(slot)
         if ent is not None and ent[0] == key:
             ent[1].replay()
@@ -446,7 +452,8 @@ class ShardedDescriptorPath:
             self.gnn_graph = False
             self._gnn_graphs.clear()
             return self.gnn(self._graph)
-        self._gnn_graphs[slot] = (key, cg, out, folded)      # (folded: kept alive as long as the capture that reads it)
+        # (folded, csr, graph: kept alive as long as the capture that reads them)
+        self._gnn_graphs[slot] = (key, cg, out, folded, csr, self._graph)
         return out
 
     def release(self):

@@ -124,8 +124,9 @@ class SpectralEncoder(nn.Module):
 
     def _lut(self, dev) -> torch.Tensor:
         # alpha lives on the device; read it back only when it was modified (a .item() is a full
-        # host-device sync and would stall the launch pipeline on every call)
-        key = (self.alpha.data_ptr(), self.alpha._version)
+        # host-device sync and would stall the launch pipeline on every call).  _lib.param_epoch: an optimizer stepped
+        # (fused optimizers do not bump alpha's version counter)
+        key = (self.alpha.data_ptr(), self.alpha._version, _lib.param_epoch)
         if getattr(self, "_alpha_key", None) != key:
             self._alpha_host = float(self.alpha.detach())
             self._alpha_key = key

@@ -6,6 +6,7 @@ pass is one call into the C ABI (nsc_gat_forward, csrc/nsc_gat.hip): f32-MFMA pr
 fused BatchNorm/ReLU/residual epilogues and a wavefront-per-node attention/aggregation kernel.
 The module must live on a HIP device; there is no CPU fallback.
 """
+import collections
 import ctypes as C
 import os
 from typing import Optional
@@ -188,6 +189,12 @@ def _train_backward_raw(gnn, state, grad_out, grads, accumulate, need_x):
     return gx
 
 
+def _direct_ok(params) -> bool:
+    """The backward may add straight into the .grad tensors of ``params`` (_train_params() order): every one is trained and
+    has a contiguous .grad.  A frozen parameter (requires_grad False) takes the autograd path, which drops its gradient."""
+    return all(p.requires_grad and p.grad is not None and p.grad.is_contiguous() for p in params)
+
+
 class _GatTrainFunction(torch.autograd.Function):
     """model.train(); model(data) with autograd: nsc_gat_forward_train / nsc_gat_backward."""
 
@@ -204,7 +211,7 @@ class _GatTrainFunction(torch.autograd.Function):
         params = gnn._train_params()
         # GNNTrainer's steps: the kernels ADD into the existing .grad tensors (NscGatTrainCfg.accumulate_grads) and autograd
         # gets no parameter gradients back -- no AccumulateGrad axpy per parameter (30 small kernels per batch)
-        direct = bool(getattr(gnn, "_direct_grads", False)) and all(p.grad is not None and p.grad.is_contiguous() for p in params)
+        direct = bool(getattr(gnn, "_direct_grads", False)) and _direct_ok(params)
         grads = [p.grad for p in params] if direct else [torch.empty_like(p) for p in params]
         go = grad_out.contiguous().float()
         gx = _train_backward_raw(gnn, ctx.state, go, grads, direct, ctx.need_x)
@@ -237,8 +244,8 @@ class SpectralGNN(nn.Module):
             self.residual_proj = nn.Linear(input_dim, output_dim)
         else:
             self.residual_proj = None
-        self._csr_cache = {}
-        self._struct_cache = None          # (key, GatModel, folded tensor)
+        self._csr_cache = collections.OrderedDict()     # graph key -> GraphCSR, least recently used first
+        self._struct_cache = None          # (key, GatModel, folded tensor, the tensors of the key)
         # True: launch the LDS-free, low-VGPR kernel set (NSC_GAT_CORESIDENT) whose workgroups fit beside a
         # resident encoder grid -- used by distributed.ShardedDescriptorPath(pipeline=True).  "shared_b": that set with
         # the small-LDS GEMMs (NSC_GAT_SHARED_B).  "lds_tiled": the stand-alone forward with the round-2 GEMMs
@@ -252,7 +259,7 @@ class SpectralGNN(nn.Module):
     def __getstate__(self):
         # device-pointer caches are rebuilt on demand; keep them out of deepcopy / pickle / torch.save
         state = self.__dict__.copy()
-        state["_csr_cache"] = {}
+        state["_csr_cache"] = collections.OrderedDict()
         state["_struct_cache"] = None
         state["_train_struct_cache"] = None
         state["_seed_dev"] = None
@@ -268,13 +275,16 @@ class SpectralGNN(nn.Module):
         n = int(data.x.shape[0])
         key = (ei.data_ptr(), ei._version, tuple(ei.shape), n,
                None if ea is None else (ea.data_ptr(), ea._version, tuple(ea.shape)))
-        csr = self._csr_cache.get(key)
+        cache = self._csr_cache
+        csr = cache.get(key)
         if csr is None:
-            if len(self._csr_cache) >= 8:
-                self._csr_cache.clear()
+            while len(cache) >= 8:
+                cache.popitem(last=False)    # least recently used graph
             csr = GraphCSR(ei, ea, n)
             csr._keepalive = (ei, ea)        # pointers in the key stay valid while cached
-            self._csr_cache[key] = csr
+            cache[key] = csr
+        else:
+            cache.move_to_end(key)
         return csr
 
     @staticmethod
@@ -309,8 +319,11 @@ class SpectralGNN(nn.Module):
 
     def _model_struct(self, live=None) -> _lib.GatModel:
         """NscGatModel over the live parameter storage.  Rebuilt (and the attention vectors re-folded
-        by nsc_gat_fold_weights) only when a parameter was modified or moved.  ``live``: the caller's _live_tensors()."""
-        key = tuple((t.data_ptr(), t._version) for t in (live if live is not None else self._live_tensors()))
+        by nsc_gat_fold_weights) only when a parameter was modified or moved, or an optimizer stepped (_lib.param_epoch: fused
+        optimizers do not bump version counters).  ``live``: the caller's _live_tensors()."""
+        if live is None:
+            live = self._live_tensors()
+        key = (_lib.param_epoch, tuple((t.data_ptr(), t._version) for t in live))
         if self._struct_cache is not None and self._struct_cache[0] == key:
             return self._struct_cache[1]
         m = self._build_struct()
@@ -321,7 +334,9 @@ class SpectralGNN(nn.Module):
         with torch.cuda.device(dev):
             st = L.nsc_gat_fold_weights(C.byref(m), _lib.ptr(folded), _lib.stream_ptr(dev))
         _lib.check(st, "nsc_gat_fold_weights")
-        self._struct_cache = (key, m, folded)
+        # the entry holds the tensors of its key: a replaced parameter cannot be freed and its address handed to the
+        # replacement (same address, version 0 again) while the cache still describes it
+        self._struct_cache = (key, m, folded, live)
         self._fold_generation = getattr(self, "_fold_generation", 0) + 1     # a captured forward bakes `folded` in: see
         return m                                                              # ShardedDescriptorPath._enhance
 
@@ -400,8 +415,8 @@ class SpectralGNN(nn.Module):
         edge_attr = getattr(data, 'edge_attr', None)
         csr = self._csr(data, edge_attr is not None and self.edge_dim is not None)
         params = self._train_params()
-        if any(p.grad is None or not p.grad.is_contiguous() for p in params):
-            raise _lib.NscError("train_step_direct adds into existing contiguous .grad tensors")
+        if not _direct_ok(params):
+            raise _lib.NscError("train_step_direct adds into the existing contiguous .grad tensors of trained parameters")
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (self.dropout > 0 and getattr(self, "_seed_dev", None) is None) else 0
         out, state = _train_forward_raw(self, x, csr, float(self.dropout), seed)
         L = _lib.lib()

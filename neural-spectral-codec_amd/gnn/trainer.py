@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.optim as optim
 
 from .. import _lib
+from .model import _direct_ok
 
 
 class _TripletFn(torch.autograd.Function):
@@ -271,9 +272,10 @@ class GNNTrainer:
     # -- the per-batch step, captured --------------------------------------------------------------------------
     def _eager_step(self, graph, ia, ip, in_, scale):
         inner = getattr(self.model, "gnn", self.model)
-        # the backward adds straight into the .grad tensors (they exist: zero_grad keeps them) -- no AccumulateGrad pass
-        direct = (self.direct_grads and hasattr(inner, "_direct_grads")
-                  and all(p.grad is not None for p in self.model.parameters() if p.requires_grad))
+        # the backward adds straight into the .grad tensors (they exist: zero_grad keeps them) -- no AccumulateGrad pass.
+        # Every tensor the backward writes must be trained and have its .grad: a frozen parameter takes the autograd path
+        direct = (self.direct_grads and hasattr(inner, "_direct_grads") and hasattr(inner, "_train_params")
+                  and _direct_ok(inner._train_params()))
         if direct and os.environ.get("NSC_TRAINER_NO_DIRECT") != "1" and hasattr(inner, "train_step_direct") and self.model.training and all(
                 isinstance(i, torch.Tensor) and i.is_cuda and i.dtype == torch.int64 for i in (ia, ip, in_)):
             # device-resident indices (the captured step's static buffers, an epoch's uploaded triplets): the three ABI calls

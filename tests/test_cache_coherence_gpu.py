@@ -1,0 +1,443 @@
+"""Device state the fast paths derive from tensors and cache -- the folded attention vectors, the CSR arrays of a graph, the
+captured GNN forward of the pipelined path, the captured training step, the encoder's bin LUT -- checked against the oracle
+AFTER the tensors they derive from have changed: optimizer steps (fused ones do not bump version counters), in-place
+writes, replaced parameters, frozen parameters, and more graphs than the CSR cache holds.
+
+Bars: GNN output |gpu - ref| <= 1e-4 |ref| + 1e-6 element-wise against oracle/gat_oracle.py in float32 and float64;
+descriptors |gpu - ref| <= 1e-6 |ref| + 1e-9 against oracle/nsc_oracle; pipelined and captured paths bit-equal to the
+serial / eager path."""
+import copy
+import gc
+import weakref
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+import gat_oracle as go
+import nsc_oracle as orc
+from neural_spectral_codec_amd import distributed as nd, synth
+from neural_spectral_codec_amd.encoding import SpectralEncoder
+from neural_spectral_codec_amd.gnn.model import create_spectral_gnn
+from neural_spectral_codec_amd.gnn.trainer import GNNTrainer
+from neural_spectral_codec_amd.keyframe import graph_manager as gm
+
+pytestmark = pytest.mark.gpu
+
+OPTIMIZERS = {"Adam": torch.optim.Adam, "AdamW": torch.optim.AdamW, "SGD": torch.optim.SGD}
+
+
+def _check(out, model, g):
+    """Element-wise |gpu - ref| <= 1e-4 |ref| + 1e-6 against the restatement in float32 and in float64."""
+    go.assert_within_bar(out, go.forward_reference(model, g), what="vs float32 restatement")
+    return go.assert_within_bar(out, go.forward_reference(model, g, dtype=torch.float64), what="vs float64 restatement")
+
+
+def _model(edge_dim=2, seed=0, **kw):
+    torch.manual_seed(seed)
+    m = create_spectral_gnn(edge_dim=edge_dim, **kw)
+    go.randomize_bn_stats(m, seed + 1)
+    with torch.no_grad():
+        for c in m.gnn.convs:
+            c.bias.normal_(0, 0.1)
+    return m.to("cuda").eval()
+
+
+def _forward_checked(m, g, kernel_sets=(False,)):
+    """Eval forward checked against the oracle, once per kernel set (SpectralGNN.coresident); all of them give the same bits."""
+    m.eval()
+    outs = []
+    try:
+        for ks in kernel_sets:
+            m.gnn.coresident = ks
+            with torch.no_grad():
+                outs.append(m(g))
+            _check(outs[-1], m, g)
+    finally:
+        m.gnn.coresident = False
+    for o in outs[1:]:
+        assert torch.equal(o, outs[0])
+    return outs[0]
+
+
+# the stand-alone forward, the LDS-free set of the pipelined path, and the generic one (no one-launch banded layers)
+ALL_SETS = (False, True, "generic")
+
+
+def _seeded_grads(params, seed, scale=1.0):
+    gen = torch.Generator().manual_seed(seed)
+    for p in params:
+        p.grad = (torch.randn(p.shape, generator=gen) * scale).to(p.device)
+
+
+def _train_setup(n, seed=0):
+    """Dropout off (parity), a chain graph with edge_attr and two full batches of 256 random triplets."""
+    m = _model(edge_dim=2, seed=seed, dropout=0.0)
+    g = gm.synthetic_chain_graph(n, device="cuda", seed=seed + 2)
+    rng = np.random.default_rng(seed)
+    trip = np.stack([rng.integers(0, n, 512), rng.integers(0, n, 512), rng.integers(0, n, 512)], 1)
+    return m, g, trip
+
+
+# ---- GNN eval forward: the folded attention vectors ------------------------------------------------------------------
+@pytest.mark.parametrize("edge_dim", [2, None])
+@pytest.mark.parametrize("opt_name", sorted(OPTIMIZERS))
+def test_fused_optimizer_step_refolds_attention_vectors(opt_name, edge_dim):
+    """A caller's fused optimizer updates the weights without bumping their version counters; the next eval forward must
+    run on the new weights, attention logits included."""
+    m = _model(edge_dim=edge_dim)
+    g = gm.synthetic_chain_graph(300, device="cuda", seed=1)
+    before = _forward_checked(m, g, ALL_SETS)
+    opt = OPTIMIZERS[opt_name](m.parameters(), lr=1e-2, fused=True)
+    _seeded_grads(m.parameters(), 7)
+    opt.step()
+    after = _forward_checked(m, g, ALL_SETS)
+    assert not torch.equal(before, after)
+
+
+def test_trainer_optimizer_step_called_directly():
+    """The reference's own loop style: ``trainer.optimizer.step()`` outside train_batches."""
+    m = _model()
+    g = gm.synthetic_chain_graph(300, device="cuda", seed=1)
+    tr = GNNTrainer(m, device="cuda", learning_rate=1e-2)
+    _forward_checked(m, g, ALL_SETS)
+    _seeded_grads(m.parameters(), 8)
+    tr.optimizer.step()
+    _forward_checked(m.eval(), g, ALL_SETS)
+
+
+@pytest.mark.parametrize("how", ["mul_", "load_state_dict", "load_checkpoint"])
+def test_version_bumping_writes(how, tmp_path):
+    m = _model()
+    g = gm.synthetic_chain_graph(300, device="cuda", seed=1)
+    before = _forward_checked(m, g, ALL_SETS)
+    if how == "mul_":
+        with torch.no_grad():
+            m.gnn.convs[1].att_src.mul_(-1.5)
+            m.gnn.convs[2].att_edge.mul_(2.0)
+    elif how == "load_state_dict":
+        m.load_state_dict(_model(seed=5).state_dict())
+    else:
+        GNNTrainer(_model(seed=5), device="cuda", checkpoint_dir=str(tmp_path)).save_checkpoint("other.pth")
+        GNNTrainer(m, device="cuda", checkpoint_dir=str(tmp_path)).load_checkpoint("other.pth")
+    after = _forward_checked(m, g, ALL_SETS)
+    assert not torch.equal(before, after)
+
+
+def test_folded_parameter_replaced_twice():
+    """Each replacement frees the old parameter before the new one is allocated, so the caching allocator may hand the
+    new one the old one's address, with the same (zero) version counter."""
+    m = _model()
+    g = gm.synthetic_chain_graph(300, device="cuda", seed=1)
+    conv = m.gnn.convs[1]
+    outs = [_forward_checked(m, g, ALL_SETS)]
+    for k in range(2):
+        shape = conv.att_src.shape
+        conv.att_src = None
+        gen = torch.Generator().manual_seed(20 + k)
+        conv.att_src = nn.Parameter((torch.randn(shape, generator=gen) * 0.3).cuda())
+        outs.append(_forward_checked(m, g, ALL_SETS))
+    assert not torch.equal(outs[1], outs[2])
+
+
+def test_cpu_round_trip_with_in_place_change():
+    """m.cpu(), an in-place change, m.cuda(): the caching allocator hands the parameters their old addresses back."""
+    m = _model()
+    g = gm.synthetic_chain_graph(300, device="cuda", seed=1)
+    before = _forward_checked(m, g)
+    m.cpu()
+    with torch.no_grad():
+        m.gnn.convs[0].att_dst.mul_(-2.0)
+        m.gnn.convs[2].lin_edge.weight.mul_(0.5)
+    m.cuda()
+    after = _forward_checked(m, g)
+    assert not torch.equal(before, after)
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_eval_forward_after_train_batches(use_graph):
+    """Training writes the BatchNorm running statistics through raw pointers (no version bump); the oracle reads them
+    from state_dict()."""
+    m, g, trip = _train_setup(300)
+    _forward_checked(m, g)
+    rm = m.gnn.batch_norms[1].running_mean.clone()
+    tr = GNNTrainer(m, device="cuda", learning_rate=1e-3, batch_size=128, accumulation_steps=1, use_graph=use_graph)
+    tr.train_batches(g, trip)
+    assert bool(tr._captured) == use_graph and not tr._capture_failed
+    assert not torch.equal(rm, m.gnn.batch_norms[1].running_mean)
+    _forward_checked(m, g)
+
+
+# ---- the pipelined path's captured GNN forwards ----------------------------------------------------------------------
+def _pipe_setup(n=96, n_batches=10):
+    enc = SpectralEncoder(n_elevation=16).to("cuda")
+    m = _model()
+    poses = synth.make_pose_chain(n, 0)
+    batches = [synth.make_clouds_device(n, 3000, "cuda", seed=s) for s in range(1, n_batches + 1)]
+    serial = nd.ShardedDescriptorPath(enc, m, n, poses)
+    piped = nd.ShardedDescriptorPath(enc, m, n, poses, pipeline=True, gnn_graph=True)
+    return enc, m, batches, serial, piped
+
+
+def _run_both(m, serial, piped, batches):
+    """Every pipelined step bit-equal to the serial path; returns the serial results."""
+    with torch.no_grad():
+        m.gnn.coresident = False
+        want = [tuple(t.clone() for t in serial.step(b)) for b in batches]
+        m.gnn.coresident = True                                   # the pipelined path's kernel set
+        got = []
+        for b in batches:
+            d, e = piped.step(b)
+            torch.cuda.current_stream().wait_event(piped.last_event)
+            got.append((d.clone(), e.clone()))
+        piped.synchronize()
+        torch.cuda.synchronize()
+    m.gnn.coresident = False
+    for k, ((wd, we), (gd, ge)) in enumerate(zip(want, got)):
+        assert torch.equal(wd, gd) and torch.equal(we, ge), f"step {k}: pipelined differs from serial"
+    return want
+
+
+def _check_window(m, piped, d, e):
+    """One rank: the window is the whole chain, the embeddings are the full-graph forward over the descriptors."""
+    gr = piped._graph
+    g = gm.Data(x=d, edge_index=gr.edge_index, edge_attr=gr.edge_attr, num_nodes=gr.num_nodes)
+    _check(e, m, g)
+
+
+def test_pipelined_captures_after_fused_adam_step():
+    enc, m, batches, serial, piped = _pipe_setup()
+    _run_both(m, serial, piped, batches)
+    assert len(piped._gnn_graphs) == nd.ShardedDescriptorPath._PIPE_BUFFERS      # every rotating slot has a capture
+    opt = torch.optim.Adam(m.parameters(), lr=1e-2, fused=True)
+    _seeded_grads(m.parameters(), 9)
+    with torch.no_grad():
+        opt.step()
+    want = _run_both(m, serial, piped, batches[:6])
+    for d, e in want:
+        _check_window(m, piped, d, e)
+
+
+def test_pipelined_capture_keeps_its_csr_alive():
+    """Nine and more other graphs through the same model (the online add_keyframe + model(get_graph()) sequence) must
+    not free the CSR arrays the captures read.  The check comes BEFORE the next step: no replay over freed memory."""
+    enc, m, batches, serial, piped = _pipe_setup()
+    _run_both(m, serial, piped, batches)
+    assert len(piped._gnn_graphs) == nd.ShardedDescriptorPath._PIPE_BUFFERS
+    use_edge = piped._graph.edge_attr is not None and m.gnn.edge_dim is not None
+    csr_ref = weakref.ref(m.gnn._csr(piped._graph, use_edge))     # the CSR the captures were built on (a cache hit)
+    mgr = gm.TemporalGraphManager(temporal_neighbors=5, max_active_nodes=1000, feature_dim=800, device="cuda")
+    rng = np.random.default_rng(3)
+    with torch.no_grad():
+        for k in range(12):
+            desc = rng.random(800, dtype=np.float32)
+            mgr.add_keyframe(SimpleNamespace(keyframe_id=k, descriptor=desc / desc.sum(), embedding=None))
+            out = m(mgr.get_graph())
+    _check(out, m, mgr.get_graph())
+    gc.collect()
+    assert csr_ref() is not None, "the GraphCSR baked into the pipelined captures was freed while they can be replayed"
+    want = _run_both(m, serial, piped, batches)
+    _check_window(m, piped, *want[-1])
+
+
+# ---- the CSR cache ---------------------------------------------------------------------------------------------------
+def test_csr_cache_evicts_least_recently_used():
+    m = _model()
+    inner = m.gnn
+    graphs = [gm.synthetic_chain_graph(40 + k, device="cuda", seed=k) for k in range(10)]
+    graphs.append(gm.Data(x=graphs[3].x, edge_index=graphs[3].edge_index, num_nodes=43))     # no edge_attr
+    hot = graphs[0]
+    hot_out = _forward_checked(m, hot)
+    hot_csr = inner._csr(hot, True)
+    csrs = {}
+    for k, g in enumerate(graphs[1:], 1):
+        _forward_checked(m, g)
+        use_edge = getattr(g, "edge_attr", None) is not None
+        csrs[k] = inner._csr(g, use_edge)
+        with torch.no_grad():
+            assert torch.equal(m(hot), hot_out)
+        assert inner._csr(hot, True) is hot_csr, f"the graph used after every other one lost its CSR after graph {k}"
+    for k in range(len(graphs) - 6, len(graphs)):                 # the six most recent graphs keep their CSR
+        g = graphs[k]
+        assert inner._csr(g, getattr(g, "edge_attr", None) is not None) is csrs[k], k
+        _forward_checked(m, g)
+
+
+def test_graph_changes_between_forwards():
+    m = _model()
+    g = gm.synthetic_chain_graph(200, device="cuda", seed=4)
+    _forward_checked(m, g)
+    g.edge_attr.mul_(-3.0).add_(0.5)                              # in place: the version counter moves
+    _forward_checked(m, g)
+    # the edge_index freed, then a new tensor of the same shape with different edges (the address may be reused)
+    ei = g.edge_index.cpu()
+    g.edge_index = None
+    gc.collect()
+    perm = torch.from_numpy(np.random.default_rng(5).permutation(200))
+    g.edge_index = perm[ei].contiguous().cuda()
+    assert not torch.equal(g.edge_index.cpu(), ei)
+    _forward_checked(m, g)
+
+
+# ---- the captured training step --------------------------------------------------------------------------------------
+def test_captured_step_survives_csr_cache_turnover():
+    """Between two train_batches calls on one graph (capture, then replay), eleven other graphs pass through the model.
+    Per-batch losses and the gradients handed to every optimizer step must match a use_graph=False trainer."""
+    n = 600
+    rng = np.random.default_rng(6)
+    trip = np.stack([rng.integers(0, n, 4 * 128) for _ in range(3)], 1)
+    others = [gm.synthetic_chain_graph(50 + k, device="cuda", seed=30 + k) for k in range(11)]
+    runs = []
+    for use_graph in (False, True):
+        m, g, _ = _train_setup(n, seed=9)
+        tr = GNNTrainer(m, device="cuda", learning_rate=5e-4, weight_decay=1e-5, margin=0.1, batch_size=128,
+                        accumulation_steps=2, use_graph=use_graph)
+        seen, losses, step = [], [], tr.optimizer.step
+        params = dict(m.gnn.named_parameters())
+        eager, captured = tr._eager_step, tr._captured_step
+
+        def hooked(*a, _seen=seen, _params=params, _step=step, **kw):
+            _seen.append({k: v.grad.detach().clone() for k, v in _params.items()})
+            return _step(*a, **kw)
+
+        def eager_rec(*a, _losses=losses, _f=eager, **kw):
+            loss = _f(*a, **kw)
+            if not torch.cuda.is_current_stream_capturing():
+                _losses.append(float(loss))
+            return loss
+
+        def captured_rec(*a, _losses=losses, _f=captured, **kw):
+            loss = _f(*a, **kw)
+            if loss is not None:
+                _losses.append(float(loss))
+            return loss
+        tr.optimizer.step, tr._eager_step, tr._captured_step = hooked, eager_rec, captured_rec
+        tr.train_batches(g, trip)
+        assert bool(tr._captured) == use_graph and not tr._capture_failed
+        m.eval()
+        with torch.no_grad():
+            for o in others:
+                m(o)
+        tr.train_batches(g, trip)
+        assert bool(tr._captured) == use_graph and not tr._capture_failed
+        runs.append((losses, seen))
+    (l0, s0), (l1, s1) = runs
+    assert len(l0) == len(l1) == 8 and len(s0) == len(s1) == 4
+    for b, (a, c) in enumerate(zip(l0, l1)):
+        # before the first optimizer step both runs hold the same weights; after it they differ by +-lr on elements whose
+        # gradient is rounding noise (see test_captured_step_gradients_match_eager)
+        assert abs(a - c) <= (1e-5 if b < 2 else 1e-4) * abs(a) + 1e-7, (b, a, c)
+    zero = {"input_proj.bias", "output_proj.bias", "batch_norms.2.bias"} | {f"convs.{l}.bias" for l in range(3)}
+    for step_no, (ga, gb) in enumerate(zip(s0, s1)):
+        scale = max(float(v.abs().max()) for v in ga.values())
+        for k in ga:
+            assert torch.isfinite(gb[k]).all(), (step_no, k)
+            ref = float(ga[k].abs().max())
+            d = float((ga[k] - gb[k]).abs().max())
+            if k in zero:                                   # exactly-zero gradients: rounding noise on both sides
+                assert ref < 1e-3 * scale and float(gb[k].abs().max()) < 1e-3 * scale, (step_no, k)
+                continue
+            assert d <= (2e-4 if step_no == 0 else 5e-2) * max(ref, 1e-6 * scale), (step_no, k, d, ref)
+
+
+# ---- frozen parameters -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_frozen_parameter_without_grad(use_graph):
+    """One parameter with requires_grad=False and no .grad: training runs (the second batch is captured when use_graph), the
+    frozen parameter stays bit-unchanged, the gradients match the restatement's and the others take Adam's step on them."""
+    m, g, trip = _train_setup(400)
+    frozen = m.gnn.convs[1].att_edge
+    frozen.requires_grad_(False)
+    assert frozen.grad is None
+    before = frozen.detach().clone()
+    cpu_model = copy.deepcopy(m).cpu()
+    tr = GNNTrainer(m, device="cuda", learning_rate=5e-4, weight_decay=1e-5, margin=0.1, batch_size=256,
+                    accumulation_steps=2, use_graph=use_graph)
+    seen, step = [], tr.optimizer.step
+
+    def hooked(*a, **kw):
+        seen.append({k: v.grad.detach().cpu().clone() for k, v in m.gnn.named_parameters() if v.grad is not None})
+        return step(*a, **kw)
+    tr.optimizer.step = hooked
+    tr.train_batches(g, trip)                                     # two batches, one optimizer step
+    assert bool(tr._captured) == use_graph and not tr._capture_failed
+    assert torch.equal(frozen, before) and frozen.grad is None
+    tt = torch.from_numpy(trip)
+
+    def loss_fn(e):
+        return sum(go.triplet_loss_reference(e, tt[b:b + 256, 0], tt[b:b + 256, 1], tt[b:b + 256, 2], 0.1) / 2
+                   for b in (0, 256))
+    _, grads_ref, _, _ = go.reference_gradients(cpu_model, g, loss_fn)
+    # the gradients handed to the optimizer against the restatement's (test_forward_train_and_gradients' bar) ...
+    assert len(seen) == 1 and set(seen[0]) == set(grads_ref) - {"convs.1.att_edge"}
+    zero = {"input_proj.bias", "output_proj.bias", "batch_norms.2.bias"} | {f"convs.{l}.bias" for l in range(3)}
+    gscale = max(v.abs().max().item() for v in grads_ref.values())
+    for k, got in seen[0].items():
+        ref = grads_ref[k].reshape(got.shape)
+        if k in zero:                                             # exactly-zero gradients: rounding noise on both sides
+            assert got.abs().max().item() < 1e-3 * gscale and ref.abs().max().item() < 1e-3 * gscale, k
+            continue
+        assert ((got - ref).abs().max() / ref.abs().max()).item() < 2e-3, k
+    # ... and the update: Adam on those gradients, the frozen parameter left out (Adam's first step moves every element by
+    # +-lr, so the sign of a rounding-noise gradient decides it: the update is checked on the gradients the GPU produced)
+    params = dict(cpu_model.gnn.named_parameters())
+    opt = torch.optim.Adam(cpu_model.parameters(), lr=5e-4, weight_decay=1e-5)
+    for k, gr in seen[0].items():
+        params[k].grad = gr
+    opt.step()
+    assert torch.equal(params["convs.1.att_edge"], before.cpu())
+    for k, p in m.gnn.named_parameters():
+        assert torch.allclose(p.detach().cpu(), params[k].detach(), rtol=1e-5, atol=1e-7), k
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_parameter_frozen_after_a_step_gets_no_gradient(use_graph):
+    """Frozen after one step, the parameter still has its (zeroed) .grad tensor; later batches must not add into it."""
+    m, g, trip = _train_setup(400)
+    tr = GNNTrainer(m, device="cuda", learning_rate=5e-4, batch_size=256, accumulation_steps=1, use_graph=use_graph)
+    tr.train_batches(g, trip[:256])
+    p = m.gnn.convs[1].att_edge
+    p.requires_grad_(False)
+    assert p.grad is not None and not p.grad.any()
+    at_step, step = [], tr.optimizer.step
+
+    def hooked(*a, **kw):                                         # what the optimizer sees, before zero_grad clears it
+        at_step.append(p.grad.detach().clone())
+        return step(*a, **kw)
+    tr.optimizer.step = hooked
+    tr.train_batches(g, trip)                                     # two batches: the second one captured when use_graph
+    assert bool(tr._captured) == use_graph and not tr._capture_failed
+    assert len(at_step) == 2
+    for gr in at_step + [p.grad]:
+        assert not gr.any(), "a frozen parameter's .grad received a gradient"
+
+
+# ---- the encoder's bin LUT -------------------------------------------------------------------------------------------
+def test_encoder_lut_follows_alpha():
+    enc = SpectralEncoder(n_elevation=16, n_azimuth=360, n_bins=50, alpha=2.0, target_elevation_bins=16).to("cuda")
+    clouds = [synth.make_cloud(s, 20000, k) for s, k in ((40, "uniform"), (41, "ring"))]
+    p = orc.default_params()
+
+    def check():
+        d = enc.encode_points_batch(clouds).cpu().numpy()
+        lut = orc.bin_lut(float(enc.alpha))[1]
+        for i, c in enumerate(clouds):
+            ref = orc.encode_points(c, p, lut=lut)
+            assert np.all(np.abs(d[i] - ref) <= 1e-6 * np.abs(ref) + 1e-9), f"cloud {i} at alpha {float(enc.alpha)}"
+        return lut
+
+    luts = [check()]
+    opt = torch.optim.Adam(enc.parameters(), lr=0.3, fused=True)
+    enc.alpha.grad = torch.tensor(-1.0, device="cuda")
+    opt.step()
+    luts.append(check())
+    with torch.no_grad():
+        enc.alpha.fill_(1.0)
+    luts.append(check())
+    other = SpectralEncoder(n_elevation=16, n_azimuth=360, n_bins=50, alpha=3.0, target_elevation_bins=16)
+    enc.load_state_dict(other.state_dict())
+    luts.append(check())
+    for a, b in zip(luts, luts[1:]):
+        assert not np.array_equal(a, b)                           # every change moved the bin LUT
