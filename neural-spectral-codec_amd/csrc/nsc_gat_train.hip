@@ -180,19 +180,16 @@ __global__ __launch_bounds__(256) void gemm_gen_kernel(const float *__restrict__
         }
 }
 
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float *__restrict__ part, int S, long long MN,
-                                                          float *__restrict__ out, int accumulate)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= MN) return;
-    float s = 0.0f;
-    for (int z = 0; z < S; ++z) s += part[(long long)z * MN + i];     // fixed order: deterministic
-    out[i] = accumulate ? out[i] + s : s;
-}
+constexpr int SPLITK_SLABS = 16;                                    // K slabs of a weight-gradient product at most
+
+struct Region {                                                     // a workspace region and its size
+    float *p;
+    size_t n;                                                       // floats
+};
 
 // The slab sums of ALL weight-gradient products of a backward together, in the backward's last launch (round 4): nothing inside the backward reads a weight
-// gradient, so every product keeps its slabs in a region of its own and the sums -- same fixed order, same (out + s) -- run once at
-// the end: five 5 us launches per batch become one.
+// gradient, so every product keeps its slabs in a region of its own (TrainWs::slabs) and the sums -- fixed order, (out + s) -- run once at
+// the end, in backward_end_finals_kernel.
 struct SlabJob {
     const float *part;
     float *out;
@@ -200,33 +197,18 @@ struct SlabJob {
     int S, accumulate;
     unsigned blk0;                                                  // first workgroup of this job
 };
-constexpr int SLAB_JOBS = 8;
+constexpr int SLAB_JOBS = NSC_GAT_MAX_LAYERS + 3;                   // out_w, res_w, every layer's lin_w, in_w
 struct SlabBatch {
     SlabJob j[SLAB_JOBS];
     int n;
     unsigned blocks;
 };
-struct SlabDefer {                                                  // host side: the regions handed out so far
-    SlabBatch b;
-    float *base;
-    size_t cap, used;                                               // floats
-};
 
-inline float *slab_defer_take(SlabDefer *d, long long MN, int S)
+inline void slab_push(SlabBatch &b, const float *part, float *out, long long MN, int S, int accumulate)
 {
-    if (!d || !d->base || d->b.n >= SLAB_JOBS) return nullptr;
-    const size_t need = ((size_t)MN * (size_t)S + 63) / 64 * 64;
-    if (d->used + need > d->cap) return nullptr;
-    float *p = d->base + d->used;
-    d->used += need;
-    return p;
-}
-
-inline void slab_defer_push(SlabDefer *d, const float *part, float *out, long long MN, int S, int accumulate)
-{
-    SlabJob &J = d->b.j[d->b.n++];
-    J.part = part; J.out = out; J.MN = MN; J.S = S; J.accumulate = accumulate; J.blk0 = d->b.blocks;
-    d->b.blocks += (unsigned)((MN + 255) / 256);
+    SlabJob &J = b.j[b.n++];
+    J.part = part; J.out = out; J.MN = MN; J.S = S; J.accumulate = accumulate; J.blk0 = b.blocks;
+    b.blocks += (unsigned)((MN + 255) / 256);
 }
 
 __device__ __forceinline__ void slab_reduce_multi_body(const SlabBatch &b, unsigned bid)
@@ -259,7 +241,7 @@ __device__ __forceinline__ void slab_reduce_multi_body(const SlabBatch &b, unsig
 // groups.  64 x 64 tiles of 2 x 2 waves (a 32 x 32 wave tile = four accumulators share two A and two B reads per k-step),
 // four computing + four staging waves, three stages, one raw barrier per 64-deep chunk with the younger chunk's pieces in flight
 // across it, split over K slabs
-// (blockIdx.z) whose sums slab_reduce_kernel adds in fixed order: deterministic.  k order of every output element: ascending.
+// (blockIdx.z) whose sums backward_end_finals_kernel adds in fixed order: deterministic.  k order of every output element: ascending.
 // ---------------------------------------------------------------------------------------------
 template <int TM>   // tile (64 TM) x 64: TM = 2 for the wide products (a computing wave owns a 64 x 32 tile: eight accumulators)
 __global__ __launch_bounds__(512) void gemm_tn_glds_kernel(const float *__restrict__ A, int lda, const float *__restrict__ B,
@@ -378,50 +360,50 @@ __global__ __launch_bounds__(512) void gemm_tn_glds_kernel(const float *__restri
         }
 }
 
-// dW = A^T B over K slabs on gemm_tn_glds_kernel; false when the operands do not fit it (the caller takes gemm_gen_kernel)
+// dW = A^T B over K slabs on gemm_tn_glds_kernel, their sums pushed to `batch`: NSC_OK, NSC_EWORKSPACE when the slabs do not fit
+// `slabs` (nothing launched), or NSC_EUNSUPPORTED when the operands do not fit the kernel (the caller takes gemm_gen_kernel)
 template <int TM>
-bool launch_tn_glds_cfg(hipStream_t st, const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C,
-                        int accumulate, float *slabs, int max_slabs, SlabDefer *defer)
+int launch_tn_glds_cfg(hipStream_t st, const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C,
+                       int accumulate, Region slabs, SlabBatch &batch)
 {
     constexpr unsigned lds = 3 * (64 * 64 * TM + 64 * 64) * 4;     // 96 / 144 KB: above 64 KB a kernel is opted in, per device
     static std::atomic<int> opted[16];
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return NSC_EUNSUPPORTED;
     int o = opted[dev].load(std::memory_order_acquire);
     if (o == 0) {
         o = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_glds_kernel<TM>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds) == hipSuccess ? 1 : 2;
         opted[dev].store(o, std::memory_order_release);
     }
-    if (o != 1) return false;
+    if (o != 1) return NSC_EUNSUPPORTED;
     const int tiles = ((M + 64 * TM - 1) / (64 * TM)) * ((N + 63) / 64);
     int splits = 256 / tiles;                                       // about one round of workgroups on the 256 CUs
-    splits = splits < 1 ? 1 : (splits > max_slabs ? max_slabs : splits);
+    splits = splits < 1 ? 1 : (splits > SPLITK_SLABS ? SPLITK_SLABS : splits);
     int kslab = (K + splits - 1) / splits;
     kslab = (kslab + 63) / 64 * 64;
     splits = (K + kslab - 1) / kslab;                               // no empty slab
     const long long MN = (long long)M * N;
-    float *own = slab_defer_take(defer, MN, splits);                // a region of this product's own: its sums wait for the batched launch
-    float *dst = own ? own : slabs;
+    if ((size_t)MN * splits > slabs.n) return NSC_EWORKSPACE;
     hipLaunchKernelGGL(gemm_tn_glds_kernel<TM>, dim3((N + 63) / 64, (M + 64 * TM - 1) / (64 * TM), splits), dim3(512), lds, st, A, lda, B,
-                       ldb, M, N, K, kslab, dst, MN);
-    if (own) slab_defer_push(defer, own, C, MN, splits, accumulate);
-    else hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((MN + 255) / 256)), dim3(256), 0, st, slabs, splits, MN, C, accumulate);
-    return true;
+                       ldb, M, N, K, kslab, slabs.p, MN);
+    slab_push(batch, slabs.p, C, MN, splits, accumulate);
+    return NSC_OK;
 }
 
-bool launch_tn_glds(hipStream_t st, const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C,
-                    int accumulate, float *slabs, int max_slabs, SlabDefer *defer = nullptr)
+int launch_tn_glds(hipStream_t st, const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C,
+                   int accumulate, Region slabs, SlabBatch &batch)
 {
-    if ((lda & 3) || (ldb & 3) || M < 4 || N < 4 || (M & 3) || (N & 3) || K < 1 || !slabs ||
+    if ((lda & 3) || (ldb & 3) || M < 4 || N < 4 || (M & 3) || (N & 3) || K < 1 ||
         (reinterpret_cast<unsigned long long>(A) & 15) || (reinterpret_cast<unsigned long long>(B) & 15))
-        return false;
+        return NSC_EUNSUPPORTED;
     // the wide products (800 x 256 / 256 x 800: 52 tiles of 64 x 64 x 4 slabs would leave 48 CUs idle) take 128 x 64 tiles:
     // 28 / 26 tiles x 9 slabs = one round of 252 / 234 workgroups
-    if (((M + 63) / 64) * ((N + 63) / 64) >= 40 && M >= 128 &&
-        launch_tn_glds_cfg<2>(st, A, lda, B, ldb, M, N, K, C, accumulate, slabs, max_slabs, defer))
-        return true;
-    return launch_tn_glds_cfg<1>(st, A, lda, B, ldb, M, N, K, C, accumulate, slabs, max_slabs, defer);
+    if (((M + 63) / 64) * ((N + 63) / 64) >= 40 && M >= 128) {
+        const int s = launch_tn_glds_cfg<2>(st, A, lda, B, ldb, M, N, K, C, accumulate, slabs, batch);
+        if (s != NSC_EUNSUPPORTED) return s;
+    }
+    return launch_tn_glds_cfg<1>(st, A, lda, B, ldb, M, N, K, C, accumulate, slabs, batch);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1307,6 +1289,7 @@ struct EndFinals {
     int H, edge_dim, accumulate;
     SlabBatch slabs;
 };
+static_assert(sizeof(EndFinals) < 4096, "backward_end_finals_kernel's arguments must stay under 4 KB");
 __global__ __launch_bounds__(256) void backward_end_finals_kernel(EndFinals p)
 {
     unsigned b = blockIdx.x;
@@ -1426,72 +1409,83 @@ __global__ __launch_bounds__(256) void triplet_reduce_kernel(const float *__rest
 // ---------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------
-constexpr int SPLITK_SLABS = 16;
 constexpr int COLRED_MAXR = 64;
 
-struct TrainWs {
-    // saved by the forward
-    size_t z0, mean0, invstd0, h, g, a_src, a_dst, alpha, y, mean, invstd, vvec;
-    // backward scratch
-    size_t dh, dh2, dv, dg, draw, edgepart, da_src, da_dst, s1, s2, dvvec, slabs, slab_cap, colpart, colpart2, colpart2_stride, attpart, attpart_stride, colpart_ob, total;
-    size_t nh, nn, hh, nz;
+template <class T> struct Slots {                                   // `count` equal regions, `stride` elements apart
+    T *p;
+    size_t stride;
+    T *operator()(int i) const { return p + stride * i; }
 };
 
-// floats of ONE slab of the largest weight-gradient product: input / output projection, a layer's H x H lin weight (round 4: this
-// term was missing -- a model whose hidden width exceeds both its input and output widths wrote its lin slabs past the region;
-// every configuration of the path has 800 > 256), residual_proj
-inline size_t slab_region0_floats(const NscGatModel *m)
-{
-    const size_t H = (size_t)m->hidden;
-    size_t big = std::max((size_t)std::max(m->in_dim, m->out_dim) * H, H * H);
-    if (m->residual && m->in_dim != m->out_dim) big = std::max(big, (size_t)m->in_dim * m->out_dim);   // dW of residual_proj
-    return big;
-}
+struct Carver {                                                      // consecutive regions from base (0: offsets only)
+    uintptr_t base;
+    size_t o;
+    template <class T> T *take(size_t n) { T *p = reinterpret_cast<T *>(base + o); o += align256(n * sizeof(T)); return p; }
+    template <class T> Slots<T> slots(size_t n, int count)
+    {
+        const size_t s = align256(n * sizeof(T)) / sizeof(T);
+        return {take<T>(s * count), s};
+    }
+    Region region(size_t n) { return {take<float>(n), n}; }
+};
 
-TrainWs train_ws(const NscGatModel *m, int N, int nnz)
+// The training workspace.  train_ws() is the one place that knows its layout: nsc_gat_train_workspace_bytes takes the size from it,
+// the forward and the backward their pointers, so both see the same saved-state regions.  Every region starts on 256 bytes.
+struct TrainWs {
+    // saved by the forward: the input BatchNorm, then per layer (h: L + 1 slots)
+    float *z0, *mean0, *invstd0;
+    Slots<float> h, g, a_src, a_dst, alpha, y, mean, invstd, vvec;
+    // backward scratch; draw / da_src / da_dst per layer: reduced in the backward's last two launches
+    float *dh, *dh2, *dv, *dg;
+    Slots<float> draw, da_src, da_dst;
+    double *edgepart, *colpart, *colpart_ob;
+    Slots<double> colpart2, attpart;                                // per BatchNorm (L + 1) / per layer: their finals run at the end
+    Region tw;                                                      // the transposed weight of a dX = dY W product (gemm)
+    struct {                                                        // the split-K slabs of each weight-gradient product
+        Region out_w, res_w, lin_w[NSC_GAT_MAX_LAYERS], in_w;       // (res_w: residual_proj only)
+    } slabs;
+    size_t total;                                                   // bytes
+};
+
+// base = nullptr: sizes only
+TrainWs train_ws(const NscGatModel *m, int N, int nnz, void *base)
 {
-    TrainWs w;
-    const int H = m->hidden, L = m->n_layers;
-    w.nh = align256((size_t)N * H * 4); w.nn = align256((size_t)N * 4); w.hh = align256((size_t)H * 4);
-    w.nz = align256((size_t)nnz * 4);
-    size_t o = 0;
-    w.z0 = o; o += w.nh;
-    w.mean0 = o; o += w.hh;
-    w.invstd0 = o; o += w.hh;
-    w.h = o; o += w.nh * (L + 1);
-    w.g = o; o += w.nh * L;
-    w.a_src = o; o += w.nn * L;
-    w.a_dst = o; o += w.nn * L;
-    w.alpha = o; o += w.nz * L;
-    w.y = o; o += w.nh * L;
-    w.mean = o; o += w.hh * L;
-    w.invstd = o; o += w.hh * L;
-    w.vvec = o; o += 256 * L;
-    w.dh = o; o += w.nh;
-    w.dh2 = o; o += w.nh;
-    w.dv = o; o += w.nh;
-    w.dg = o; o += w.nh;
-    w.draw = o; o += w.nz * L;                                      // per layer: the edge terms of all layers are reduced in one launch at the end
-    w.edgepart = o; o += align256((size_t)NSC_GAT_MAX_LAYERS * EDGE_BWD_WGS * NSC_GAT_MAX_EDGE_DIM * 8);
-    w.da_src = o; o += w.nn * L;                                    // per layer: reduced against G at the end of the backward
-    w.da_dst = o; o += w.nn * L;
-    w.s1 = o; o += align256((size_t)std::max(H, m->out_dim) * 4);
-    w.s2 = o; o += align256((size_t)std::max(H, m->out_dim) * 4);
-    w.dvvec = o; o += 256;
-    const size_t big = slab_region0_floats(m);
-    w.slabs = o; o += align256(big * 4 * SPLITK_SLABS);            // region 0: a product that sums its slabs at once, transposed weights
-    // ... and a region per weight-gradient product of a backward whose sums wait for the backward's last launch (backward_end_finals_kernel)
-    size_t all_w = (size_t)m->in_dim * H + (size_t)m->out_dim * H + (size_t)L * H * H;
-    if (m->residual && m->in_dim != m->out_dim) all_w += (size_t)m->in_dim * m->out_dim;
-    w.slab_cap = all_w * SPLITK_SLABS + 64 * SLAB_JOBS;            // floats
-    o += align256(w.slab_cap * 4);
-    w.colpart = o; o += align256((size_t)COLRED_MAXR * std::max(std::max(H, m->out_dim), m->in_dim) * 2 * 8);
-    w.colpart2_stride = align256((size_t)COLRED_MAXR * H * 8);      // partials of a bias gradient (bn_apply_colsum_kernel): one slot
-    w.colpart2 = o; o += w.colpart2_stride * (L + 1);               // per BatchNorm, their finals run together at the end
-    w.attpart_stride = align256((size_t)COLRED_MAXR * H * 2 * 8);   // partials of a layer's two attention-vector gradients
-    w.attpart = o; o += w.attpart_stride * L;
-    w.colpart_ob = o; o += align256((size_t)COLRED_MAXR * m->out_dim * 2 * 8);   // partials of the output bias gradient
-    w.total = o;
+    Carver c = {reinterpret_cast<uintptr_t>(base), 0};
+    TrainWs w = {};
+    const size_t H = m->hidden, Din = m->in_dim, Dout = m->out_dim, NH = (size_t)N * H;
+    const int L = m->n_layers;
+    const bool res_proj = m->residual && Din != Dout;
+    w.z0 = c.take<float>(NH);
+    w.mean0 = c.take<float>(H);
+    w.invstd0 = c.take<float>(H);
+    w.h = c.slots<float>(NH, L + 1);
+    w.g = c.slots<float>(NH, L);
+    w.a_src = c.slots<float>(N, L);
+    w.a_dst = c.slots<float>(N, L);
+    w.alpha = c.slots<float>(nnz, L);
+    w.y = c.slots<float>(NH, L);
+    w.mean = c.slots<float>(H, L);
+    w.invstd = c.slots<float>(H, L);
+    w.vvec = c.slots<float>(64, L);
+    w.dh = c.take<float>(NH);
+    w.dh2 = c.take<float>(NH);
+    w.dv = c.take<float>(NH);
+    w.dg = c.take<float>(NH);
+    w.draw = c.slots<float>(nnz, L);
+    w.edgepart = c.take<double>((size_t)NSC_GAT_MAX_LAYERS * EDGE_BWD_WGS * NSC_GAT_MAX_EDGE_DIM);
+    w.da_src = c.slots<float>(N, L);
+    w.da_dst = c.slots<float>(N, L);
+    // the dX = dY W products: dOut W_out (Dout x H), dOut W_res (Dout x Din), dG W_lin (H x H), dZ0 W_in (H x Din)
+    w.tw = c.region(std::max({Dout * H, res_proj ? Dout * Din : 0, H * H, H * Din}));
+    w.slabs.out_w = c.region(Dout * H * SPLITK_SLABS);
+    if (res_proj) w.slabs.res_w = c.region(Dout * Din * SPLITK_SLABS);
+    for (int l = 0; l < L; ++l) w.slabs.lin_w[l] = c.region(H * H * SPLITK_SLABS);
+    w.slabs.in_w = c.region(H * Din * SPLITK_SLABS);
+    w.colpart = c.take<double>((size_t)COLRED_MAXR * std::max(std::max(H, Dout), Din) * 2);
+    w.colpart2 = c.slots<double>((size_t)COLRED_MAXR * H, L + 1);   // partials of a bias gradient (bn_apply_colsum_kernel)
+    w.attpart = c.slots<double>((size_t)COLRED_MAXR * H * 2, L);    // partials of a layer's two attention-vector gradients
+    w.colpart_ob = c.take<double>((size_t)COLRED_MAXR * Dout * 2);  // partials of the output bias gradient
+    w.total = c.o;
     return w;
 }
 
@@ -1514,59 +1508,64 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float *__restrict_
     }
 }
 
-// slabs: split-K slabs of the weight-gradient products; for a single-slice product with a k-major B (dX = dY W) the same
-// buffer, free between two weight-gradient products of the stream, takes the transposed weight.
-template <bool AKM, bool BKM>
-void gemm(hipStream_t st, const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C, int ldc,
-          const float *bias, int accumulate, int splits, float *slabs, SlabDefer *defer = nullptr, const float *resid = nullptr)
+// C = A B^T (+ bias) (+ C when accumulate) (+ resid), K in one slice.  resid (non-accumulating products only, same leading
+// dimension as C): C = product + resid, in the epilogue of the LDS-DMA GEMM where that kernel takes the product (the backward's
+// dh_{l} = dG W + dh_{l+1} residual path), by an add_inplace_kernel behind any other form -- the same two roundings either way.
+// A k-major B (BKM: the dX = dY W products) that the LDS-DMA GEMM cannot read in place goes through a transposed copy in `tw`:
+// NSC_EWORKSPACE when it does not fit (nothing launched).
+template <bool BKM>
+int gemm(hipStream_t st, const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C, int ldc,
+         const float *bias, int accumulate, Region tw = {}, const float *resid = nullptr)
 {
-    // resid (non-accumulating single-slice products only, same leading dimension as C): C = product + resid, in the epilogue of
-    // the LDS-DMA GEMM where that kernel takes the product (the backward's dh_{l} = dG W + dh_{l+1} residual path), by an
-    // add_inplace_kernel behind any other form -- the same two roundings either way
-    if (!AKM && splits <= 1 && (!BKM || (slabs && !(K & 15) && !(reinterpret_cast<unsigned long long>(slabs) & 15)))) {
+    if (!BKM || (tw.p && !(K & 15) && !(reinterpret_cast<unsigned long long>(tw.p) & 15))) {
         // the projections of the training forward, and the dX = dY W products of the backward through a transposed copy of
         // the weight (0.8 MB at most: a 3 us kernel): the inference forward's LDS-DMA GEMM -- same chain per output element
         // as gemm_gen_kernel, same (acc + bias) + C order; anything it cannot take (unaligned operands) falls through
+        GemmEpi ep = {};
+        ep.bias = bias;
+        if (accumulate) { ep.resid = C; ep.ldr = ldc; }
+        else if (resid) { ep.resid = resid; ep.ldr = ldc; }
         const float *Bn = B;
         int ldn = ldb;
         if (BKM) {
             // round 4: the k-major weight read element-wise from an untransposed LDS tile -- no transposed copy (a 5 us kernel per
             // product); anything that form cannot take goes through the copy as before
-            GemmEpi e0 = {};
-            e0.bias = bias;
-            if (accumulate) { e0.resid = C; e0.ldr = ldc; }
-            else if (resid) { e0.resid = resid; e0.ldr = ldc; }
-            if (launch_glds_bkm(st, A, lda, B, ldb, M, N, K, C, ldc, e0)) return;
-        }
-        if (BKM) {
-            hipLaunchKernelGGL(transpose_kernel, dim3((N + 31) / 32, (K + 31) / 32), dim3(256), 0, st, B, K, N, ldb, slabs);
-            Bn = slabs;
+            if (launch_glds_bkm(st, A, lda, B, ldb, M, N, K, C, ldc, ep)) return NSC_OK;
+            if ((size_t)K * N > tw.n) return NSC_EWORKSPACE;
+            hipLaunchKernelGGL(transpose_kernel, dim3((N + 31) / 32, (K + 31) / 32), dim3(256), 0, st, B, K, N, ldb, tw.p);
+            Bn = tw.p;
             ldn = K;
         }
-        GemmEpi ep = {};
-        ep.bias = bias;
-        if (accumulate) { ep.resid = C; ep.ldr = ldc; }
-        else if (resid) { ep.resid = resid; ep.ldr = ldc; }
-        if (launch_glds<2>(st, A, lda, Bn, ldn, nullptr, M, N, N, K, C, ldc, ep)) return;
+        if (launch_glds<2>(st, A, lda, Bn, ldn, nullptr, M, N, N, K, C, ldc, ep)) return NSC_OK;
     }
-    if (AKM && BKM && splits > 1 && !bias && ldc == N && launch_tn_glds(st, A, lda, B, ldb, M, N, K, C, accumulate, slabs, SPLITK_SLABS, defer))
-        return;
-    dim3 grid((N + 63) / 64, (M + 31) / 32, splits);
-    if (splits <= 1) {
-        hipLaunchKernelGGL((gemm_gen_kernel<AKM, BKM>), grid, dim3(256), 0, st, A, lda, B, ldb, M, N, K, K, C, ldc,
-                           0LL, bias, accumulate);
-    } else {
-        int kchunk = (K + splits - 1) / splits;
-        kchunk = (kchunk + 63) / 64 * 64;
-        const long long MN = (long long)M * N;      // requires ldc == N
-        float *own = slab_defer_take(defer, MN, splits);
-        hipLaunchKernelGGL((gemm_gen_kernel<AKM, BKM>), grid, dim3(256), 0, st, A, lda, B, ldb, M, N, K, kchunk, own ? own : slabs,
-                           N, MN, static_cast<const float *>(nullptr), 0);
-        if (own) slab_defer_push(defer, own, C, MN, splits, accumulate);
-        else hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((MN + 255) / 256)), dim3(256), 0, st, slabs, splits, MN, C, accumulate);
-    }
+    hipLaunchKernelGGL((gemm_gen_kernel<false, BKM>), dim3((N + 63) / 64, (M + 31) / 32), dim3(256), 0, st, A, lda, B, ldb, M, N, K, K,
+                       C, ldc, 0LL, bias, accumulate);
     if (resid && !accumulate && ldc == N)
         hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)(((long long)M * N + 255) / 256)), dim3(256), 0, st, C, resid, (long long)M * N);
+    return NSC_OK;
+}
+
+// A weight gradient dW[M,N] (+)= A^T B with both operands k-major (dW = dY^T X).  Over `splits` > 1 K slabs the product writes its
+// slabs to `slabs` and pushes their sum to `batch` (backward_end_finals_kernel): NSC_EWORKSPACE when they do not fit (nothing launched).
+int gemm_wgrad(hipStream_t st, const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C, int accumulate,
+               int splits, Region slabs, SlabBatch &batch)
+{
+    const dim3 grid((N + 63) / 64, (M + 31) / 32, splits);
+    if (splits <= 1) {
+        hipLaunchKernelGGL((gemm_gen_kernel<true, true>), grid, dim3(256), 0, st, A, lda, B, ldb, M, N, K, K, C, N, 0LL,
+                           static_cast<const float *>(nullptr), accumulate);
+        return NSC_OK;
+    }
+    const int s = launch_tn_glds(st, A, lda, B, ldb, M, N, K, C, accumulate, slabs, batch);
+    if (s != NSC_EUNSUPPORTED) return s;
+    int kchunk = (K + splits - 1) / splits;
+    kchunk = (kchunk + 63) / 64 * 64;
+    const long long MN = (long long)M * N;
+    if ((size_t)MN * splits > slabs.n) return NSC_EWORKSPACE;
+    hipLaunchKernelGGL((gemm_gen_kernel<true, true>), grid, dim3(256), 0, st, A, lda, B, ldb, M, N, K, kchunk, slabs.p, N, MN,
+                       static_cast<const float *>(nullptr), 0);
+    slab_push(batch, slabs.p, C, MN, splits, accumulate);
+    return NSC_OK;
 }
 
 inline int colred_rows(int N)
@@ -1612,8 +1611,8 @@ void bn_forward(hipStream_t st, const float *z, int N, int C, double *part, floa
 // kernel finishes those sums itself and stores the BatchNorm parameter gradients) + the partials of ITS column sum, returned as
 // the ColExtra the caller hands to its next final pass (or to bias_final).
 ColExtra bn_backward(hipStream_t st, const float *dh, const float *z, const float *mean, const float *invstd, const float *gamma,
-                     const float *beta, int relu, float p, SeedRef seed, unsigned stream, int N, int C, float *dv, float *s1,
-                     float *s2, float *g_bn_b, float *g_bn_w, int acc, double *part, double *part2, float *g_bias)
+                     const float *beta, int relu, float p, SeedRef seed, unsigned stream, int N, int C, float *dv,
+                     float *g_bn_b, float *g_bn_w, int acc, double *part, double *part2, float *g_bias)
 {
     const int R = colred_rows(N);
     const int rows = (N + R - 1) / R;
@@ -1621,7 +1620,6 @@ ColExtra bn_backward(hipStream_t st, const float *dh, const float *z, const floa
     hipLaunchKernelGGL(bn_bwd_colsum_kernel, grid, dim3(256), 0, st, dh, z, mean, invstd, gamma, beta, relu, p, seed, stream, N, C,
                        rows, dv, part);
     // (round 4, second step: no final launch -- the apply pass finishes s1 / s2 itself and stores the BatchNorm parameter gradients)
-    (void)s1; (void)s2;
     hipLaunchKernelGGL(bn_apply_colsum_kernel, grid, dim3(256), 0, st, dv, z, mean, invstd, gamma, part, R, g_bn_b, g_bn_w, acc, N, C,
                        rows, part2);
     return ColExtra{part2, R, acc, g_bias};
@@ -1675,7 +1673,7 @@ int nsc_graph_transpose(const NscGraph *g, int32_t *t_ptr, int32_t *t_entry, int
 size_t nsc_gat_train_workspace_bytes(const NscGatModel *m, const NscGraph *g)
 {
     if (check_train(m, g) != NSC_OK || g->n_nodes <= 0) return 0;
-    return train_ws(m, g->n_nodes, g->nnz).total;
+    return train_ws(m, g->n_nodes, g->nnz, nullptr).total;
 }
 
 int nsc_gat_forward_train(const NscGatModel *m, const NscGraph *g, const float *x, const float *edge_attr,
@@ -1686,28 +1684,22 @@ int nsc_gat_forward_train(const NscGatModel *m, const NscGraph *g, const float *
     if (!cfg || !x || !out) return NSC_EINVAL;
     const int N = g->n_nodes, H = m->hidden, L = m->n_layers;
     if (N == 0) return NSC_OK;
-    const TrainWs w = train_ws(m, N, g->nnz);
+    const TrainWs w = train_ws(m, N, g->nnz, ws);
     if (!ws || ws_bytes < w.total) return NSC_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    char *b = static_cast<char *>(ws);
-    auto F = [&](size_t off) { return reinterpret_cast<float *>(b + off); };
-    double *colpart = reinterpret_cast<double *>(b + w.colpart);
     const bool use_edge = m->edge_dim > 0 && edge_attr && g->loop_attr;
     const int upd = cfg->update_running_stats;
 
     // input_proj (bias) -> z0 ; BatchNorm(batch stats) ; ReLU                 model.py:116-118
-    gemm<false, false>(st, x, m->in_dim, m->in_w, m->in_dim, N, H, m->in_dim, F(w.z0), H, m->in_b, 0, 1, nullptr);
-    bn_forward(st, F(w.z0), N, H, colpart, m->bn_eps, cfg->bn_momentum, F(w.mean0), F(w.invstd0),
+    gemm<false>(st, x, m->in_dim, m->in_w, m->in_dim, N, H, m->in_dim, w.z0, H, m->in_b, 0);
+    bn_forward(st, w.z0, N, H, w.colpart, m->bn_eps, cfg->bn_momentum, w.mean0, w.invstd0,
                upd ? const_cast<float *>(m->in_bn_mean) : nullptr, upd ? const_cast<float *>(m->in_bn_var) : nullptr, m->in_bn_w,
-               m->in_bn_b, 1, 0.0f, SeedRef{0ull, nullptr}, 0u, nullptr, F(w.h));
+               m->in_bn_b, 1, 0.0f, SeedRef{0ull, nullptr}, 0u, nullptr, w.h(0));
 
     for (int l = 0; l < L; ++l) {
         const NscGatLayer &Ly = m->layers[l];
-        float *hin = F(w.h + w.nh * l), *hout = F(w.h + w.nh * (l + 1));
-        float *G = F(w.g + w.nh * l), *as = F(w.a_src + w.nn * l), *ad = F(w.a_dst + w.nn * l);
-        float *alpha = F(w.alpha + w.nz * l), *y = F(w.y + w.nh * l);
-        float *mean = F(w.mean + w.hh * l), *invstd = F(w.invstd + w.hh * l), *vv = F(w.vvec + 256 * l);
-        gemm<false, false>(st, hin, H, Ly.lin_w, H, N, H, H, G, H, nullptr, 0, 1, nullptr);
+        float *hin = w.h(l), *hout = w.h(l + 1), *G = w.g(l), *as = w.a_src(l), *ad = w.a_dst(l), *vv = w.vvec(l), *y = w.y(l);
+        gemm<false>(st, hin, H, Ly.lin_w, H, N, H, H, G, H, nullptr, 0);
         hipLaunchKernelGGL(att_dots_kernel, dim3((N + 3) / 4 + (use_edge ? 1 : 0)), dim3(256), 0, st, G, Ly.att_src, Ly.att_dst, N, H, as, ad,
                            use_edge ? Ly.lin_edge_w : nullptr, Ly.att_edge, m->edge_dim, vv);
         TrainAgg a;
@@ -1715,7 +1707,7 @@ int nsc_gat_forward_train(const NscGatModel *m, const NscGraph *g, const float *
         a.loop_attr = use_edge ? g->loop_attr : nullptr;
         a.edge_attr = use_edge ? edge_attr : nullptr;
         a.v = use_edge ? vv : nullptr;
-        a.a_src = as; a.a_dst = ad; a.G = G; a.bias = Ly.bias; a.alpha = alpha; a.y = y;
+        a.a_src = as; a.a_dst = ad; a.G = G; a.bias = Ly.bias; a.alpha = w.alpha(l); a.y = y;
         a.slope = m->negative_slope; a.p = cfg->dropout_p; a.seed = SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}; a.stream = 100u + l;
         a.N = N; a.H = H; a.edge_dim = m->edge_dim;
         switch ((H + 255) / 256) {
@@ -1726,7 +1718,7 @@ int nsc_gat_forward_train(const NscGatModel *m, const NscGraph *g, const float *
         }
         const int act = (l < L - 1);                                           // model.py:135-137
         const float *resid = (m->residual && l > 0 && l < L - 1) ? hin : nullptr;   // model.py:140-141
-        bn_forward(st, y, N, H, colpart, m->bn_eps, cfg->bn_momentum, mean, invstd, upd ? const_cast<float *>(Ly.bn_mean) : nullptr,
+        bn_forward(st, y, N, H, w.colpart, m->bn_eps, cfg->bn_momentum, w.mean(l), w.invstd(l), upd ? const_cast<float *>(Ly.bn_mean) : nullptr,
                    upd ? const_cast<float *>(Ly.bn_var) : nullptr, Ly.bn_w, Ly.bn_b, act, act ? cfg->dropout_p : 0.0f,
                    SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}, 200u + l, resid, hout);
     }
@@ -1738,16 +1730,15 @@ int nsc_gat_forward_train(const NscGatModel *m, const NscGraph *g, const float *
         GemmEpi ep = {};
         ep.bias = m->out_b;
         ep.resid = x; ep.ldr = m->in_dim;
-        fused_res = launch_glds<2>(st, F(w.h + w.nh * L), H, m->out_w, H, nullptr, N, m->out_dim, m->out_dim, H, out, m->out_dim, ep);
+        fused_res = launch_glds<2>(st, w.h(L), H, m->out_w, H, nullptr, N, m->out_dim, m->out_dim, H, out, m->out_dim, ep);
     }
     if (!fused_res)
-        gemm<false, false>(st, F(w.h + w.nh * L), H, m->out_w, H, N, m->out_dim, H, out, m->out_dim, m->out_b, 0, 1, nullptr);
+        gemm<false>(st, w.h(L), H, m->out_w, H, N, m->out_dim, H, out, m->out_dim, m->out_b, 0);
     if (m->residual && m->in_dim == m->out_dim) {
         const long long tot = (long long)N * m->out_dim;
         if (!fused_res) hipLaunchKernelGGL(add_inplace_kernel, dim3(blocks(tot)), dim3(256), 0, st, out, x, tot);
     } else if (m->residual) {                                                  // out += residual_proj(x)  model.py:147-149
-        gemm<false, false>(st, x, m->in_dim, m->res_w, m->in_dim, N, m->out_dim, m->in_dim, out, m->out_dim, m->res_b, 1, 1,
-                           nullptr);
+        gemm<false>(st, x, m->in_dim, m->res_w, m->in_dim, N, m->out_dim, m->in_dim, out, m->out_dim, m->res_b, 1);
     }
     return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
 }
@@ -1761,15 +1752,10 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
     if (!cfg || !x || !grad_out || !gr || !g->t_ptr || !g->t_entry || !g->tgt) return NSC_EINVAL;
     const int N = g->n_nodes, H = m->hidden, L = m->n_layers, Dout = m->out_dim, Din = m->in_dim;
     if (N == 0) return NSC_OK;
-    const TrainWs w = train_ws(m, N, g->nnz);
+    const TrainWs w = train_ws(m, N, g->nnz, ws);
     if (!ws || ws_bytes < w.total) return NSC_EWORKSPACE;
     if (m->residual && Din != Dout && (!gr->res_w || !gr->res_b)) return NSC_EINVAL;   // (before anything is enqueued)
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    char *b = static_cast<char *>(ws);
-    auto F = [&](size_t off) { return reinterpret_cast<float *>(b + off); };
-    double *colpart = reinterpret_cast<double *>(b + w.colpart);
-    auto colpart2 = [&](int slot) { return reinterpret_cast<double *>(b + w.colpart2 + w.colpart2_stride * slot); };
-    float *slabs = F(w.slabs);
     // what nothing inside the backward reads is reduced at its END, in batched launches: the final passes of every column sum
     // (in backward_end_finals_kernel), the attention-vector sums of all layers (in backward_end_partials_kernel), the edge terms,
     // the slab sums of the weight gradients
@@ -1781,12 +1767,7 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
         fin.part[k] = part; fin.R[k] = Rn; fin.C[k] = C; fin.f[k] = f; fin.x[k] = x;
     };
     const ColExtra no_extra = {nullptr, 0, 0, nullptr};
-    SlabDefer defer_ = {};
-    {
-        defer_.base = slabs + align256(slab_region0_floats(m) * 4 * SPLITK_SLABS) / 4;
-        defer_.cap = w.slab_cap;
-    }
-    SlabDefer *defer = &defer_;
+    SlabBatch slabs = {};
     EdgeVecJobs edge_jobs = {};
     bool any_edge = false;
     const bool use_edge = m->edge_dim > 0 && edge_attr && g->loop_attr;
@@ -1798,15 +1779,14 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
     // output_proj: out = h_L W_out^T + b (+ x)
     // (its column sums of dOut: with the other partial sums in the backward's second-to-last launch -- dOut is the caller's, nothing
     // overwrites it)
-    double *ob = reinterpret_cast<double *>(b + w.colpart_ob);
-    push_final(ob, Dout, ColFinal{0, N, 0.f, 0.f, gr->out_b, nullptr, nullptr, nullptr, acc, 0, nullptr, nullptr, 0}, no_extra);
-    gemm<true, true>(st, grad_out, Dout, F(w.h + w.nh * L), H, Dout, H, N, gr->out_w, H, nullptr, acc, splits, slabs, defer);
-    float *dh = F(w.dh), *dh_prev = F(w.dh2);
-    gemm<false, true>(st, grad_out, Dout, m->out_w, H, N, H, Dout, dh, H, nullptr, 0, 1, slabs);   // dh_L = dOut W_out
+    push_final(w.colpart_ob, Dout, ColFinal{0, N, 0.f, 0.f, gr->out_b, nullptr, nullptr, nullptr, acc, 0, nullptr, nullptr, 0}, no_extra);
+    if ((stt = gemm_wgrad(st, grad_out, Dout, w.h(L), H, Dout, H, N, gr->out_w, acc, splits, w.slabs.out_w, slabs))) return stt;
+    float *dh = w.dh, *dh_prev = w.dh2;
+    if ((stt = gemm<true>(st, grad_out, Dout, m->out_w, H, N, H, Dout, dh, H, nullptr, 0, w.tw))) return stt;   // dh_L = dOut W_out
     const bool res_id = m->residual && Din == Dout, res_proj = m->residual && Din != Dout;
     if (res_proj) {                // residual_proj: dW_res = dOut^T x, db_res = colsum dOut      model.py:147-149
-        colreduce(st, grad_out, nullptr, nullptr, nullptr, nullptr, N, Dout, colpart, 0, 0.f, 0.f, gr->res_b, nullptr, nullptr, nullptr, acc);
-        gemm<true, true>(st, grad_out, Dout, x, Din, Dout, Din, N, gr->res_w, Din, nullptr, acc, splits, slabs, defer);
+        colreduce(st, grad_out, nullptr, nullptr, nullptr, nullptr, N, Dout, w.colpart, 0, 0.f, 0.f, gr->res_b, nullptr, nullptr, nullptr, acc);
+        if ((stt = gemm_wgrad(st, grad_out, Dout, x, Din, Dout, Din, N, gr->res_w, acc, splits, w.slabs.res_w, slabs))) return stt;
     }
     if (gr->x) {
         // gradient wrt the input features through the residual connection: dOut itself (identity residual),
@@ -1814,7 +1794,7 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
         if (res_id) {
             hipLaunchKernelGGL(copy_kernel, dim3(blocks((long long)N * Din)), dim3(256), 0, st, gr->x, grad_out, (long long)N * Din);
         } else if (res_proj) {
-            gemm<false, true>(st, grad_out, Dout, m->res_w, Din, N, Din, Dout, gr->x, Din, nullptr, 0, 1, slabs);
+            if ((stt = gemm<true>(st, grad_out, Dout, m->res_w, Din, N, Din, Dout, gr->x, Din, nullptr, 0, w.tw))) return stt;
         } else {
             fill_zero(st, gr->x, (long long)N * Din);
         }
@@ -1823,27 +1803,22 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
     for (int l = L - 1; l >= 0; --l) {
         const NscGatLayer &Ly = m->layers[l];
         const NscGatGradLayer &Gl = gr->layers[l];
-        float *hin = F(w.h + w.nh * l);
-        float *G = F(w.g + w.nh * l), *as = F(w.a_src + w.nn * l), *ad = F(w.a_dst + w.nn * l);
-        float *alpha = F(w.alpha + w.nz * l), *y = F(w.y + w.nh * l);
-        float *mean = F(w.mean + w.hh * l), *invstd = F(w.invstd + w.hh * l), *vv = F(w.vvec + 256 * l);
-        float *dv = F(w.dv), *dG = F(w.dg), *s1 = F(w.s1), *s2 = F(w.s2);
+        float *G = w.g(l), *alpha = w.alpha(l), *dY = w.dv;
         const int act = (l < L - 1);
         const bool has_res = (m->residual && l > 0 && l < L - 1);
         // h_{l+1} = drop(relu(bn(y))) [+ h_l]  ->  dV, BatchNorm backward -> dY (in place in dv).  s1 / s2 feed the apply
         // pass AND are the BatchNorm parameter gradients (the final stores both); the conv bias gradient = column sums of dY:
         // its partials come out of the apply pass, its final rides along the attention-vector reduction below
-        const ColExtra bias_x = bn_backward(st, dh, y, mean, invstd, Ly.bn_w, Ly.bn_b, act, act ? cfg->dropout_p : 0.0f,
+        const ColExtra bias_x = bn_backward(st, dh, w.y(l), w.mean(l), w.invstd(l), Ly.bn_w, Ly.bn_b, act, act ? cfg->dropout_p : 0.0f,
                                             SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}, 200u + l,
-                                            N, H, dv, s1, s2, Gl.bn_b, Gl.bn_w, acc, colpart, colpart2(l), Gl.bias);
-        float *dY = dv;
+                                            N, H, dY, Gl.bn_b, Gl.bn_w, acc, w.colpart, w.colpart2(l), Gl.bias);
         // attention backward
         AttBwdA A;
         A.row_ptr = g->row_ptr; A.src = g->src; A.eid = g->eid;
         A.loop_attr = use_edge ? g->loop_attr : nullptr; A.edge_attr = use_edge ? edge_attr : nullptr;
-        A.v = use_edge ? vv : nullptr;
-        A.a_src = as; A.a_dst = ad; A.G = G; A.alpha = alpha; A.dY = dY;
-        A.draw = F(w.draw + w.nz * l); A.da_dst = F(w.da_dst + w.nn * l);
+        A.v = use_edge ? w.vvec(l) : nullptr;
+        A.a_src = w.a_src(l); A.a_dst = w.a_dst(l); A.G = G; A.alpha = alpha; A.dY = dY;
+        A.draw = w.draw(l); A.da_dst = w.da_dst(l);
         A.slope = m->negative_slope; A.p = cfg->dropout_p; A.seed = SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}; A.stream = 100u + l;
         A.N = N; A.H = H; A.edge_dim = m->edge_dim;
         switch ((H + 255) / 256) {
@@ -1854,8 +1829,8 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
         }
         AttBwdB Bk;
         Bk.t_ptr = g->t_ptr; Bk.t_entry = g->t_entry; Bk.tgt = g->tgt;
-        Bk.alpha = alpha; Bk.dY = dY; Bk.draw = F(w.draw + w.nz * l); Bk.da_dst = F(w.da_dst + w.nn * l);
-        Bk.att_src = Ly.att_src; Bk.att_dst = Ly.att_dst; Bk.dG = dG; Bk.da_src = F(w.da_src + w.nn * l);
+        Bk.alpha = alpha; Bk.dY = dY; Bk.draw = w.draw(l); Bk.da_dst = w.da_dst(l);
+        Bk.att_src = Ly.att_src; Bk.att_dst = Ly.att_dst; Bk.dG = w.dg; Bk.da_src = w.da_src(l);
         Bk.p = cfg->dropout_p; Bk.seed = SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}; Bk.stream = 100u + l; Bk.N = N; Bk.H = H;
         switch ((H + 255) / 256) {
         case 1: hipLaunchKernelGGL(att_bwd_source_kernel<1>, dim3((N + 3) / 4), dim3(256), 0, st, Bk); break;
@@ -1865,11 +1840,8 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
         }
         // datt_src = sum_j da_src[j] g_j ; datt_dst = sum_j da_dst[j] g_j
         // (at the end of the backward, with the other layers': the conv-bias final rides along this layer's final)
-        {
-            double *ap = reinterpret_cast<double *>(b + w.attpart + w.attpart_stride * l);
-            attp.P[l] = G; attp.w[l] = F(w.da_src + w.nn * l); attp.w2[l] = F(w.da_dst + w.nn * l); attp.part[l] = ap;
-            push_final(ap, H, ColFinal{0, N, 0.f, 0.f, Gl.att_src, Gl.att_dst, nullptr, nullptr, acc, acc, nullptr, nullptr, 0}, bias_x);
-        }
+        attp.P[l] = G; attp.w[l] = w.da_src(l); attp.w2[l] = w.da_dst(l); attp.part[l] = w.attpart(l);
+        push_final(w.attpart(l), H, ColFinal{0, N, 0.f, 0.f, Gl.att_src, Gl.att_dst, nullptr, nullptr, acc, acc, nullptr, nullptr, 0}, bias_x);
         if (m->edge_dim > 0 && Gl.lin_edge_w && Gl.att_edge) {
             if (use_edge) {                         // reduced with the other layers' at the end (backward_end_partials_kernel)
                 edge_jobs.w_edge[l] = Ly.lin_edge_w; edge_jobs.att_edge[l] = Ly.att_edge;
@@ -1881,33 +1853,30 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
             }
         }
         // g = h_l W^T :  dW = dG^T h_l ,  dh_l = dG W (+ residual path)
-        gemm<true, true>(st, dG, H, hin, H, H, H, N, Gl.lin_w, H, nullptr, acc, splits, slabs, defer);
-        gemm<false, true>(st, dG, H, Ly.lin_w, H, N, H, H, dh_prev, H, nullptr, 0, 1, slabs, nullptr, has_res ? dh : nullptr);
+        if ((stt = gemm_wgrad(st, w.dg, H, w.h(l), H, H, H, N, Gl.lin_w, acc, splits, w.slabs.lin_w[l], slabs))) return stt;
+        if ((stt = gemm<true>(st, w.dg, H, Ly.lin_w, H, N, H, H, dh_prev, H, nullptr, 0, w.tw, has_res ? dh : nullptr))) return stt;
         float *t = dh; dh = dh_prev; dh_prev = t;
     }
     // h_0 = relu(bn(z0)),  z0 = x W_in^T + b_in
-    float *dv = F(w.dv), *s1 = F(w.s1), *s2 = F(w.s2);
     push_final(nullptr, H, ColFinal{0, 0, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0},
-               bn_backward(st, dh, F(w.z0), F(w.mean0), F(w.invstd0), m->in_bn_w, m->in_bn_b, 1, 0.0f, SeedRef{0ull, nullptr}, 0u,
-                           N, H, dv, s1, s2, gr->in_bn_b, gr->in_bn_w, acc, colpart, colpart2(L), gr->in_b));
-    gemm<true, true>(st, dv, H, x, Din, H, Din, N, gr->in_w, Din, nullptr, acc, splits, slabs, defer);
-    if (gr->x) {   // + dZ0 W_in
-        gemm<false, true>(st, dv, H, m->in_w, Din, N, Din, H, gr->x, Din, nullptr, 1, 1, slabs);
-    }
+               bn_backward(st, dh, w.z0, w.mean0, w.invstd0, m->in_bn_w, m->in_bn_b, 1, 0.0f, SeedRef{0ull, nullptr}, 0u,
+                           N, H, w.dv, gr->in_bn_b, gr->in_bn_w, acc, w.colpart, w.colpart2(L), gr->in_b));
+    if ((stt = gemm_wgrad(st, w.dv, H, x, Din, H, Din, N, gr->in_w, acc, splits, w.slabs.in_w, slabs))) return stt;
+    if (gr->x && (stt = gemm<true>(st, w.dv, H, m->in_w, Din, N, Din, H, gr->x, Din, nullptr, 1, w.tw))) return stt;   // + dZ0 W_in
     {
-        double *ep = reinterpret_cast<double *>(b + w.edgepart);
         EndPartials pa = {};
         pa.att = attp; pa.N = N; pa.C = H; pa.rows = rows_n; pa.nbx = (H + 63) / 64; pa.R = Rn;
         pa.n_att = (unsigned)(pa.nbx * Rn * L);
-        pa.ob_P = grad_out; pa.ob_part = ob; pa.ob_C = Dout; pa.ob_nbx = (Dout + 63) / 64; pa.n_ob = (unsigned)(pa.ob_nbx * Rn);
-        pa.edge = EdgeTermArgs{g->row_ptr, g->eid, g->tgt, g->loop_attr, edge_attr, F(w.draw), (long long)(w.nz / 4), N, m->edge_dim, ep};
+        pa.ob_P = grad_out; pa.ob_part = w.colpart_ob; pa.ob_C = Dout; pa.ob_nbx = (Dout + 63) / 64; pa.n_ob = (unsigned)(pa.ob_nbx * Rn);
+        pa.edge = EdgeTermArgs{g->row_ptr, g->eid, g->tgt, g->loop_attr, edge_attr, w.draw(0), (long long)w.draw.stride, N, m->edge_dim,
+                               w.edgepart};
         hipLaunchKernelGGL(backward_end_partials_kernel, dim3(pa.n_att + pa.n_ob + (any_edge ? (unsigned)(EDGE_BWD_WGS * L) : 0u)), dim3(256), 0, st, pa);
         EndFinals fa = {};
         fa.fin = fin; fa.nbx = (std::max(H, Dout) + 63) / 64;
         fa.n_fin = (unsigned)(fa.nbx * fin.n); fa.n_edge = any_edge ? (unsigned)L : 0u;
-        fa.ev = edge_jobs; fa.edge_part = ep; fa.H = H; fa.edge_dim = m->edge_dim; fa.accumulate = acc;
-        fa.slabs = defer->b;                                        // (the weight gradients' slab sums: after the last product above)
-        hipLaunchKernelGGL(backward_end_finals_kernel, dim3(fa.n_fin + fa.n_edge + defer->b.blocks), dim3(256), 0, st, fa);
+        fa.ev = edge_jobs; fa.edge_part = w.edgepart; fa.H = H; fa.edge_dim = m->edge_dim; fa.accumulate = acc;
+        fa.slabs = slabs;                                           // (the weight gradients' slab sums: after the last product above)
+        hipLaunchKernelGGL(backward_end_finals_kernel, dim3(fa.n_fin + fa.n_edge + slabs.blocks), dim3(256), 0, st, fa);
     }
     return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
 }

@@ -105,6 +105,24 @@ def test_argument_validation_without_gpu(lib):
     assert lib.nsc_topk_workspace_bytes(1, 100000, 10) == 49 * 10 * 8
 
 
+@pytest.mark.parametrize("in_dim,hidden,out_dim,n_layers,n", [(800, 256, 800, 3, 4541), (64, 128, 96, 8, 700)])
+def test_train_workspace_one_byte_short(lib, in_dim, hidden, out_dim, n_layers, n):
+    """The training forward and backward take their workspace size from the layout nsc_gat_train_workspace_bytes reports: one
+    byte less is NSC_EWORKSPACE before anything is launched -- at the bench shape, and at eight layers with residual_proj and
+    hidden > max(in, out), where every weight-gradient product's split-K slabs have a region of their own."""
+    from neural_spectral_codec_amd import _lib
+    p = 256                                                          # non-null dummy pointers: nothing may be dereferenced
+    m = _lib.GatModel(in_dim=in_dim, hidden=hidden, out_dim=out_dim, n_layers=n_layers, edge_dim=2, residual=1,
+                      bn_eps=1e-5, negative_slope=0.2, res_w=p, res_b=p)
+    g = _lib.Graph(n_nodes=n, nnz=4 * n, row_ptr=p, src=p, eid=p, loop_attr=p, t_ptr=p, t_entry=p, tgt=p)
+    cfg = _lib.GatTrainCfg(dropout_p=0.1, bn_momentum=0.1)
+    gr = _lib.GatGrads(x=p, res_w=p, res_b=p)
+    need = lib.nsc_gat_train_workspace_bytes(C.byref(m), C.byref(g))
+    assert need > 0
+    assert lib.nsc_gat_forward_train(C.byref(m), C.byref(g), p, p, C.byref(cfg), p, p, need - 1, None) == -3
+    assert lib.nsc_gat_backward(C.byref(m), C.byref(g), p, p, C.byref(cfg), p, C.byref(gr), p, need - 1, None) == -3
+
+
 def test_product_refuses_cpu_tensors():
     import torch
     from neural_spectral_codec_amd import _lib

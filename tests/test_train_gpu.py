@@ -648,8 +648,8 @@ def test_captured_graphs_hold_kernel_nodes_only():
 @pytest.mark.parametrize("n_layers,in_dim,out_dim,hidden", [(1, 64, 64, 64), (2, 64, 64, 64), (5, 64, 64, 64), (8, 64, 64, 64),
                                                             (3, 64, 48, 64), (8, 48, 80, 64), (4, 64, 96, 128), (8, 64, 64, 128)])
 def test_other_depths_train_on_the_split_k_path(n_layers, in_dim, out_dim, hidden):
-    """The end-of-backward batching (round 4) is sized by NSC_GAT_MAX_LAYERS: depths 1-8 (eight layers + output + input weight
-    = ten slab jobs, two more than the batched launch holds: the last products sum their slabs at once) and residual_proj, at
+    """The end-of-backward batching (round 4) is sized by NSC_GAT_MAX_LAYERS: depths 1-8 (eight layers + output + residual_proj
+    + input weight = eleven slab jobs, each with a slab region of its own, all summed in the batched launch), at
     700 nodes -- above the 512 where the weight gradients split K over slabs.  Loss, every parameter gradient and the input
     gradient against autograd through the restatement.  hidden = 128 > max(in, out): the H x H lin gradient is then the largest
     weight-gradient product -- the slab region was sized without it until round 4 (found by tools/fuzz_train.py: a fault)."""
