@@ -403,6 +403,56 @@ int nsc_voxel_overlap(const float *points1, const int64_t *offsets1, const float
                       int32_t stride_floats, const double *transforms, double voxel_size, int32_t *counts,
                       double *iou, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Stage 2 of loop closing: batched Generalized-ICP verification (reference GeometricVerifier,
+ * src/retrieval/geometric_verification.py:48-203, after Open3D 0.18's registration_generalized_icp).
+ * The algorithm -- voxel down-sampling in first-row order, k-NN plane covariances, Gauss-Newton rounds
+ * with Open3D's convergence test, the information matrix -- is defined in
+ * neural-spectral-codec_amd/retrieval/geometric_verification.py and INTEGRATION.md section 2.
+ *
+ * Pair p registers source rows [source_offsets[p], source_offsets[p+1]) onto target rows
+ * [target_offsets[p], target_offsets[p+1]): packed float32 rows of stride_floats (3 or 4) columns, xyz first;
+ * rows with a non-finite xyz are dropped.  Offsets are (n_pairs+1) int64.  init_transforms and transforms are
+ * (n_pairs,4,4) float64 row-major and map source coordinates into the target frame (they may alias).
+ * Out: fitness_rmse (n_pairs,2) float64, corr_iterations (n_pairs,2) int64 = [n_correspondences, Gauss-Newton
+ * updates applied], information (n_pairs,6,6) float64 (rotation first).
+ * Voxel keys are 21 bits per axis from the cloud's min bound: a cloud must span fewer than 2^21 voxels per axis.
+ * Centroids are exact sums in int64 units of 2^-24 m: |coordinate| x rows per voxel must stay below 2^39 m.
+ * ------------------------------------------------------------------------------------------ */
+#define NSC_GICP_MAX_KNN 32
+
+typedef struct NscGicpParams {
+    double  voxel_size;                   /* 0.5   voxel_down_sample edge, > 0                        */
+    double  max_correspondence_distance;  /* 1.0   correspondence radius, > 0                          */
+    double  relative_fitness;             /* 1e-6  stop when |d fitness| < this ...                    */
+    double  relative_rmse;                /* 1e-6  ... and |d rmse| < this                              */
+    double  epsilon;                      /* 1e-3  plane regularisation U diag(1,1,eps) U^T, > 0        */
+    int32_t max_iteration;                /* 30    Gauss-Newton updates at most, >= 0                   */
+    int32_t covariance_knn;               /* 20    neighbours per covariance, self included, 1..32      */
+} NscGicpParams;
+
+/* Optional stage outputs (any pointer may be NULL).  points (total_source+total_target, 3) float64 and
+ * covariances (same rows, 6: xx xy xz yy yz zz) float64: the down-sampled rows of source cloud p start at row
+ * source_offsets[p], those of target cloud p at total_source_points + target_offsets[p]; counts (2*n_pairs)
+ * int64 = down-sampled rows of source 0..P-1 then target 0..P-1; system0 (n_pairs,29) float64 = the sums at
+ * init_transforms: JtWJ upper triangle row-major (21), JtW d (6), n_correspondences, Sum |d|^2.  The kernels
+ * work in these buffers in place of the workspace regions they name. */
+typedef struct NscGicpStages {
+    double  *points;
+    int64_t *counts;
+    double  *covariances;
+    double  *system0;
+} NscGicpStages;
+
+void   nsc_gicp_default_params(NscGicpParams *p);
+size_t nsc_gicp_workspace_bytes(int32_t n_pairs, int64_t total_source_points, int64_t total_target_points);
+int    nsc_gicp_register(const float *source_points, const int64_t *source_offsets, const float *target_points,
+                         const int64_t *target_offsets, int32_t n_pairs, int64_t total_source_points,
+                         int64_t total_target_points, int32_t stride_floats, const NscGicpParams *p,
+                         const double *init_transforms, double *transforms, double *fitness_rmse,
+                         int64_t *corr_iterations, double *information, const NscGicpStages *stages, void *ws,
+                         size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,21 @@ class MineParams(C.Structure):
                 ("triplets_per_anchor", C.c_int32), ("seed", C.c_uint64)]
 
 
+class GicpParams(C.Structure):
+    """struct NscGicpParams"""
+    _fields_ = [("voxel_size", C.c_double), ("max_correspondence_distance", C.c_double),
+                ("relative_fitness", C.c_double), ("relative_rmse", C.c_double), ("epsilon", C.c_double),
+                ("max_iteration", C.c_int32), ("covariance_knn", C.c_int32)]
+
+
+class GicpStages(C.Structure):
+    """struct NscGicpStages"""
+    _fields_ = [(n, C.c_void_p) for n in ("points", "counts", "covariances", "system0")]
+
+
+GICP_MAX_KNN = 32
+
+
 class GatGradLayer(C.Structure):
     """struct NscGatGradLayer"""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -142,6 +157,10 @@ SYMBOLS = {
     "nsc_voxel_overlap_workspace_bytes": (_sz, [_i64, _i64]),
     "nsc_voxel_overlap": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, C.c_double, _vp, _vp,
                                     _vp, _sz, _vp]),
+    "nsc_gicp_default_params": (None, [C.POINTER(GicpParams)]),
+    "nsc_gicp_workspace_bytes": (_sz, [_i32, _i64, _i64]),
+    "nsc_gicp_register": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, C.POINTER(GicpParams), _vp, _vp,
+                                    _vp, _vp, _vp, C.POINTER(GicpStages), _vp, _sz, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

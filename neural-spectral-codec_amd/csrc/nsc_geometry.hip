@@ -1,0 +1,687 @@
+// nsc_geometry.hip -- stage 2 of loop closing: batched Generalized-ICP verification of cloud pairs.
+//
+// Reference: GeometricVerifier (src/retrieval/geometric_verification.py:48-203), which calls Open3D 0.18's
+// voxel_down_sample, estimate covariances and registration_generalized_icp.  The definitions the kernels follow are
+// written out in retrieval/geometric_verification.py and INTEGRATION.md section 2; tests/gicp_restatement.py restates
+// them in float64 numpy.
+//
+// Clouds: cloud c < n_pairs is the source (query) of pair c, cloud n_pairs + c its target.  Rows of a cloud are
+// addressed through int64 offsets, so a packed input may hold more than 2^31 floats.
+//
+// Launch sequence (all on the caller's stream, nothing allocated, copied or synchronised):
+//   ds_prepare    (G, C)   clear the cloud's hash slots, per-block min over finite rows, reset pair state
+//   ds_insert     (G, C)   voxel key per finite row; insert (64-bit CAS), first row (atomicMin), count and int64
+//                          fixed-point coordinate sums -- exact, so independent of arrival order
+//   ds_compact    (C)      voxels in first-row order (block scan of "row is its voxel's first"), centroids
+//   covariance    (G, C)   exact k-NN over the voxel hash (one point per voxel: rings of voxels with a stopping
+//                          bound), covariance, plane regularisation
+//   max_iteration + 1 rounds of
+//     linearize   (G, P)   nearest target within the radius, per-block float64 slab of the normal equations,
+//                          Sum|d|^2, n_corr and the information matrix
+//     finalize    (P)      slabs summed in a fixed order, evaluation, convergence test, 6x6 Cholesky, T <- dT T
+//
+// No float atomics anywhere: results are bitwise reproducible and independent of what else shares the batch.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/nsc.h"
+
+namespace {
+
+constexpr int GEO_BLOCKS = 64;          // blocks per cloud (down-sampling, covariances) and per pair (linearize)
+constexpr int GEO_THREADS = 256;
+constexpr int COMPACT_THREADS = 1024;
+constexpr int KEY_BITS = 21;            // voxel key per axis: 0 .. 2^21-1 voxels from the cloud's min bound
+constexpr long long KEY_MAX = (1LL << KEY_BITS) - 1;
+constexpr double FIX_SCALE = 16777216.0;        // coordinate sums in int64 units of 2^-24 m
+constexpr int SLAB = 50;                // 21 JtWJ + 6 JtWd + n_corr + Sum|d|^2 + 21 information terms
+constexpr int SYS = 29;                 // the first 29 terms: the system of stage output system0
+
+struct Slot {                           // one voxel of a cloud's open-addressing table (2 slots per input row)
+    unsigned long long key;             // packed key + 1; 0 = empty
+    unsigned long long first;           // smallest input row in the voxel
+    unsigned long long count;
+    long long sum[3];
+    long long ds;                       // row of the voxel in the down-sampled cloud
+    long long pad;
+};
+
+struct PairState {
+    double prev_fitness, prev_rmse;
+    int round, done, pad0, pad1;
+};
+
+struct Layout {
+    size_t partial, bound, count, slots, points, cov, slab, state, total;
+};
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+Layout layout(int n_pairs, long long total_src, long long total_tgt)
+{
+    const size_t C = 2 * (size_t)n_pairs, N = (size_t)(total_src + total_tgt);
+    Layout L;
+    size_t o = 0;
+    L.partial = o; o = align256(o + C * GEO_BLOCKS * 3 * sizeof(double));
+    L.bound = o;   o = align256(o + C * 4 * sizeof(double));
+    L.count = o;   o = align256(o + C * sizeof(long long));
+    L.slots = o;   o = align256(o + 2 * N * sizeof(Slot));
+    L.points = o;  o = align256(o + N * 3 * sizeof(double));
+    L.cov = o;     o = align256(o + N * 6 * sizeof(double));
+    L.slab = o;    o = align256(o + (size_t)n_pairs * GEO_BLOCKS * SLAB * sizeof(double));
+    L.state = o;   o = align256(o + (size_t)n_pairs * sizeof(PairState));
+    L.total = o;
+    return L;
+}
+
+struct Clouds {                         // the 2P clouds of a batch and where each one's data lives
+    const float *src, *tgt;
+    const long long *src_off, *tgt_off;
+    long long total_src;
+    int stride, n_pairs;
+    // first row of cloud c, its row count, and its position in the combined (source | target) row space that
+    // indexes the workspace regions
+    __device__ void rows(int c, const float *&first, long long &n, long long &start) const
+    {
+        if (c < n_pairs) {
+            start = src_off[c]; n = src_off[c + 1] - start; first = src + start * stride;
+        } else {
+            const long long b = tgt_off[c - n_pairs];
+            n = tgt_off[c - n_pairs + 1] - b; first = tgt + b * stride; start = total_src + b;
+        }
+    }
+};
+
+__device__ __forceinline__ bool finite3(const float *q) { return isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]); }
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x)
+{
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
+    return x;
+}
+
+__device__ __forceinline__ long long voxel_coord(double p, double lo, double v)
+{
+    const double k = floor((p - lo) / v);
+    return k < 0.0 ? 0 : (k > (double)KEY_MAX ? KEY_MAX : (long long)k);
+}
+
+__device__ __forceinline__ unsigned long long pack_key(long long x, long long y, long long z)
+{
+    return (unsigned long long)x | ((unsigned long long)y << KEY_BITS) | ((unsigned long long)z << (2 * KEY_BITS));
+}
+
+// Slot of a voxel key in a table of `cap` slots, or -1.
+__device__ __forceinline__ long long find_slot(const Slot *tab, long long cap, unsigned long long key)
+{
+    if (cap == 0) return -1;
+    long long h = (long long)(mix64(key) % (unsigned long long)cap);
+    for (long long probe = 0; probe < cap; ++probe) {
+        const unsigned long long e = tab[h].key;
+        if (e == 0) return -1;
+        if (e == key + 1) return h;
+        h = h + 1 == cap ? 0 : h + 1;
+    }
+    return -1;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// down-sampling
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(GEO_THREADS) void ds_prepare_kernel(Clouds cl, Slot *slots, double *partial,
+                                                                 const double *init, double *transforms,
+                                                                 PairState *state)
+{
+    const int c = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
+    const float *base; long long n, start;
+    cl.rows(c, base, n, start);
+    Slot *tab = slots + 2 * start;
+    for (long long i = (long long)g * GEO_THREADS + tid; i < 2 * n; i += (long long)GEO_BLOCKS * GEO_THREADS)
+        tab[i] = Slot{0ULL, ~0ULL, 0ULL, {0, 0, 0}, -1, 0};
+    double mn[3] = {INFINITY, INFINITY, INFINITY};
+    for (long long i = (long long)g * GEO_THREADS + tid; i < n; i += (long long)GEO_BLOCKS * GEO_THREADS) {
+        const float *q = base + i * cl.stride;
+        if (!finite3(q)) continue;
+        for (int a = 0; a < 3; ++a) mn[a] = fmin(mn[a], (double)q[a]);
+    }
+    __shared__ double red[3][GEO_THREADS];
+    for (int a = 0; a < 3; ++a) red[a][tid] = mn[a];
+    __syncthreads();
+    for (int s = GEO_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int a = 0; a < 3; ++a) red[a][tid] = fmin(red[a][tid], red[a][tid + s]);
+        __syncthreads();
+    }
+    if (tid < 3) partial[((long long)c * GEO_BLOCKS + g) * 3 + tid] = red[tid][0];
+    if (g == 0 && c < cl.n_pairs) {
+        if (tid < 16) transforms[16 * (long long)c + tid] = init[16 * (long long)c + tid];
+        if (tid == 0) state[c] = PairState{0.0, 0.0, 0, 0, 0, 0};
+    }
+}
+
+// min bound of cloud c: min over finite rows minus voxel / 2 (+inf when the cloud has no finite row)
+__device__ __forceinline__ void min_bound(const double *partial, int c, double half, double lo[3])
+{
+    for (int a = 0; a < 3; ++a) {
+        double m = INFINITY;
+        for (int g = 0; g < GEO_BLOCKS; ++g) m = fmin(m, partial[((long long)c * GEO_BLOCKS + g) * 3 + a]);
+        lo[a] = m - half;
+    }
+}
+
+__global__ __launch_bounds__(GEO_THREADS) void ds_insert_kernel(Clouds cl, Slot *slots, const double *partial,
+                                                                double *bound, double voxel)
+{
+    const int c = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
+    const float *base; long long n, start;
+    cl.rows(c, base, n, start);
+    double lo[3];
+    min_bound(partial, c, 0.5 * voxel, lo);
+    if (g == 0 && tid < 3) bound[4 * c + tid] = lo[tid];
+    Slot *tab = slots + 2 * start;
+    const long long cap = 2 * n;
+    for (long long i = (long long)g * GEO_THREADS + tid; i < n; i += (long long)GEO_BLOCKS * GEO_THREADS) {
+        const float *q = base + i * cl.stride;
+        if (!finite3(q)) continue;
+        const double p[3] = {q[0], q[1], q[2]};
+        const unsigned long long key = pack_key(voxel_coord(p[0], lo[0], voxel), voxel_coord(p[1], lo[1], voxel),
+                                                voxel_coord(p[2], lo[2], voxel));
+        long long h = (long long)(mix64(key) % (unsigned long long)cap);
+        for (;;) {                       // at most n distinct keys in 2n slots: an empty slot always exists
+            unsigned long long e = tab[h].key;
+            if (e == 0) {
+                e = atomicCAS(&tab[h].key, 0ULL, key + 1);
+                if (e == 0) e = key + 1;
+            }
+            if (e == key + 1) break;
+            h = h + 1 == cap ? 0 : h + 1;
+        }
+        Slot &s = tab[h];
+        atomicMin(&s.first, (unsigned long long)i);
+        atomicAdd(&s.count, 1ULL);
+        for (int a = 0; a < 3; ++a)      // float32 -> 2^-24 m: exact for |p| >= 0.5 m
+            atomicAdd(reinterpret_cast<unsigned long long *>(&s.sum[a]),
+                      (unsigned long long)__double2ll_rn(p[a] * FIX_SCALE));
+    }
+}
+
+__global__ __launch_bounds__(COMPACT_THREADS) void ds_compact_kernel(Clouds cl, Slot *slots, const double *bound,
+                                                                     double voxel, double *points, long long *count)
+{
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *base; long long n, start;
+    cl.rows(c, base, n, start);
+    const double lo[3] = {bound[4 * c], bound[4 * c + 1], bound[4 * c + 2]};
+    Slot *tab = slots + 2 * start;
+    double *out = points + 3 * start;
+    __shared__ long long wsum[COMPACT_THREADS / 64];
+    long long written = 0;
+    for (long long b = 0; b < n; b += COMPACT_THREADS) {
+        const long long i = b + tid;
+        long long h = -1;
+        if (i < n) {
+            const float *q = base + i * cl.stride;
+            if (finite3(q)) {
+                h = find_slot(tab, 2 * n, pack_key(voxel_coord(q[0], lo[0], voxel), voxel_coord(q[1], lo[1], voxel),
+                                                    voxel_coord(q[2], lo[2], voxel)));
+                if (h >= 0 && tab[h].first != (unsigned long long)i) h = -1;
+            }
+        }
+        const unsigned long long m = __ballot(h >= 0);
+        if (lane == 0) wsum[wave] = __popcll(m);
+        __syncthreads();
+        long long before = written;
+        for (int w = 0; w < wave; ++w) before += wsum[w];
+        long long total = 0;
+        for (int w = 0; w < COMPACT_THREADS / 64; ++w) total += wsum[w];
+        if (h >= 0) {
+            const long long pos = before + __popcll(m & ((1ULL << lane) - 1ULL));
+            Slot &s = tab[h];
+            const double cnt = (double)s.count;
+            for (int a = 0; a < 3; ++a) out[3 * pos + a] = ((double)s.sum[a] / FIX_SCALE) / cnt;
+            s.ds = pos;
+        }
+        written += total;
+        __syncthreads();
+    }
+    if (tid == 0) count[c] = written;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// covariances
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int MAX_KNN = NSC_GICP_MAX_KNN;
+
+struct TopK {                            // k smallest (d2, index), ascending; ties to the smaller index
+    double d[MAX_KNN];
+    long long j[MAX_KNN];
+    int n, k;
+    __device__ void insert(double d2, long long idx)
+    {
+        if (n == k && !(d2 < d[k - 1] || (d2 == d[k - 1] && idx < j[k - 1]))) return;
+        int p = n < k ? n++ : k - 1;
+        while (p > 0 && (d2 < d[p - 1] || (d2 == d[p - 1] && idx < j[p - 1]))) { d[p] = d[p - 1]; j[p] = j[p - 1]; --p; }
+        d[p] = d2; j[p] = idx;
+    }
+};
+
+__device__ __forceinline__ double dist2(const double *a, const double *b)
+{
+    const double x = a[0] - b[0], y = a[1] - b[1], z = a[2] - b[2];
+    return x * x + y * y + z * z;
+}
+
+// eigenvector of the smallest eigenvalue of a symmetric 3x3 (cyclic Jacobi)
+__device__ void smallest_eigvec(const double C[6], double u[3])
+{
+    double A[3][3] = {{C[0], C[1], C[2]}, {C[1], C[3], C[4]}, {C[2], C[4], C[5]}};
+    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    for (int sweep = 0; sweep < 32; ++sweep) {
+        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+        const double diag = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+        if (!(off > 1e-30 * diag)) break;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                if (A[p][q] == 0.0) continue;
+                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+                for (int r = 0; r < 3; ++r) {            // A <- A J
+                    const double arp = A[r][p], arq = A[r][q];
+                    A[r][p] = cs * arp - sn * arq; A[r][q] = sn * arp + cs * arq;
+                }
+                for (int r = 0; r < 3; ++r) {            // A <- J^T A
+                    const double apr = A[p][r], aqr = A[q][r];
+                    A[p][r] = cs * apr - sn * aqr; A[q][r] = sn * apr + cs * aqr;
+                }
+                for (int r = 0; r < 3; ++r) {
+                    const double vrp = V[r][p], vrq = V[r][q];
+                    V[r][p] = cs * vrp - sn * vrq; V[r][q] = sn * vrp + cs * vrq;
+                }
+            }
+    }
+    int m = 0;
+    for (int a = 1; a < 3; ++a) if (A[a][a] < A[m][m]) m = a;
+    for (int a = 0; a < 3; ++a) u[a] = V[a][m];
+}
+
+__global__ __launch_bounds__(GEO_THREADS) void covariance_kernel(Clouds cl, const Slot *slots, const double *bound,
+                                                                 const long long *count, const double *points,
+                                                                 double *cov, double voxel, int knn, double eps)
+{
+    const int c = blockIdx.y;
+    const float *base; long long n, start;
+    cl.rows(c, base, n, start);
+    const long long m = count[c];
+    const Slot *tab = slots + 2 * start;
+    const double *P = points + 3 * start;
+    const double lo[3] = {bound[4 * c], bound[4 * c + 1], bound[4 * c + 2]};
+    const int k = (int)(m < knn ? m : knn);
+    for (long long i = (long long)blockIdx.x * GEO_THREADS + threadIdx.x; i < m;
+         i += (long long)GEO_BLOCKS * GEO_THREADS) {
+        const double *q = P + 3 * i;
+        TopK top;
+        top.n = 0; top.k = k;
+        bool brute = m <= knn;
+        if (!brute) {
+            long long kc[3];
+            for (int a = 0; a < 3; ++a) kc[a] = voxel_coord(q[a], lo[a], voxel);
+            for (int r = 0;; ++r) {
+                const long long side = 2LL * r + 1;
+                if (side * side * side > 2 * m) { brute = true; break; }     // rings cost more than a scan
+                for (long long dz = -r; dz <= r; ++dz)
+                    for (long long dy = -r; dy <= r; ++dy)
+                        for (long long dx = -r; dx <= r; ++dx) {
+                            if (llabs(dx) != r && llabs(dy) != r && llabs(dz) != r) continue;   // shell only
+                            const long long x = kc[0] + dx, y = kc[1] + dy, z = kc[2] + dz;
+                            if (x < 0 || y < 0 || z < 0 || x > KEY_MAX || y > KEY_MAX || z > KEY_MAX) continue;
+                            const long long h = find_slot(tab, 2 * n, pack_key(x, y, z));
+                            if (h < 0) continue;
+                            const long long j = tab[h].ds;
+                            top.insert(dist2(q, P + 3 * j), j);
+                        }
+                // every row not yet seen lies in a voxel >= r+1 rings out: farther than r * voxel (minus rounding)
+                const double reach = r * voxel * (1.0 - 1e-9) - 1e-6;
+                if (top.n == k && reach > 0.0 && top.d[k - 1] < reach * reach) break;
+            }
+            if (brute) top.n = 0;
+        }
+        if (brute)
+            for (long long j = 0; j < m; ++j) top.insert(dist2(q, P + 3 * j), j);
+        double C[6] = {1, 0, 0, 1, 0, 1};
+        if (top.n >= 3) {
+            double mu[3] = {0, 0, 0};
+            for (int t = 0; t < top.n; ++t)
+                for (int a = 0; a < 3; ++a) mu[a] += P[3 * top.j[t] + a];
+            for (int a = 0; a < 3; ++a) mu[a] /= top.n;
+            for (int e = 0; e < 6; ++e) C[e] = 0.0;
+            for (int t = 0; t < top.n; ++t) {
+                const double *pt = P + 3 * top.j[t];
+                const double x = pt[0] - mu[0], y = pt[1] - mu[1], z = pt[2] - mu[2];
+                C[0] += x * x; C[1] += x * y; C[2] += x * z; C[3] += y * y; C[4] += y * z; C[5] += z * z;
+            }
+            for (int e = 0; e < 6; ++e) C[e] /= top.n;
+        }
+        double u[3];
+        smallest_eigvec(C, u);            // U diag(1,1,eps) U^T = I - (1 - eps) u u^T
+        const double f = 1.0 - eps;
+        double *o = cov + 6 * (start + i);
+        o[0] = 1.0 - f * u[0] * u[0]; o[1] = -f * u[0] * u[1]; o[2] = -f * u[0] * u[2];
+        o[3] = 1.0 - f * u[1] * u[1]; o[4] = -f * u[1] * u[2]; o[5] = 1.0 - f * u[2] * u[2];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Gauss-Newton rounds
+// ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void sym_from6(const double *s, double M[3][3])
+{
+    M[0][0] = s[0]; M[0][1] = M[1][0] = s[1]; M[0][2] = M[2][0] = s[2];
+    M[1][1] = s[3]; M[1][2] = M[2][1] = s[4]; M[2][2] = s[5];
+}
+
+// acc[0..20] += upper triangle of [[A^T W A, A^T W], [W A, W]], acc[21..26] += [A^T W d; W d] for J = [A | I]
+__device__ __forceinline__ void accumulate_jtwj(double *acc, const double A[3][3], const double W[3][3],
+                                                const double *d)
+{
+    double J[3][6];
+    for (int r = 0; r < 3; ++r) {
+        for (int a = 0; a < 3; ++a) J[r][a] = A[r][a];
+        for (int a = 0; a < 3; ++a) J[r][3 + a] = r == a ? 1.0 : 0.0;
+    }
+    double WJ[3][6];
+    for (int r = 0; r < 3; ++r)
+        for (int a = 0; a < 6; ++a) WJ[r][a] = W[r][0] * J[0][a] + W[r][1] * J[1][a] + W[r][2] * J[2][a];
+    int t = 0;
+    for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b) acc[t++] += J[0][a] * WJ[0][b] + J[1][a] * WJ[1][b] + J[2][a] * WJ[2][b];
+    for (int a = 0; a < 6; ++a) acc[21 + a] += WJ[0][a] * d[0] + WJ[1][a] * d[1] + WJ[2][a] * d[2];
+}
+
+__global__ __launch_bounds__(GEO_THREADS) void linearize_kernel(Clouds cl, const Slot *slots, const double *bound,
+                                                                const long long *count, const double *points,
+                                                                const double *cov, const double *transforms,
+                                                                const PairState *state, double *slab, double voxel,
+                                                                double radius)
+{
+    const int p = blockIdx.y, tid = threadIdx.x;
+    if (state[p].done) return;
+    const int cs = p, ct = cl.n_pairs + p;
+    const float *base; long long ns, ss, nt, st;
+    cl.rows(cs, base, ns, ss);
+    cl.rows(ct, base, nt, st);
+    const long long ms = count[cs], mt = count[ct];
+    const Slot *tab = slots + 2 * st;
+    const double *S = points + 3 * ss, *Tp = points + 3 * st;
+    const double *CS = cov + 6 * ss, *CT = cov + 6 * st;
+    const double lo[3] = {bound[4 * ct], bound[4 * ct + 1], bound[4 * ct + 2]};
+    const double *T = transforms + 16 * (long long)p;
+    double R[3][3], tr[3];
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) R[a][b] = T[4 * a + b];
+        tr[a] = T[4 * a + 3];
+    }
+    const double r2 = radius * radius;
+    long long span = 1;                  // cells per axis the radius can reach
+    if (mt > 0) span = (long long)floor(2.0 * radius / voxel) + 2;
+    const bool brute = span * span * span > mt;
+    double acc[SLAB];
+    for (int e = 0; e < SLAB; ++e) acc[e] = 0.0;
+    for (long long i = (long long)blockIdx.x * GEO_THREADS + tid; i < ms; i += (long long)GEO_BLOCKS * GEO_THREADS) {
+        const double *s = S + 3 * i;
+        double q[3];
+        for (int a = 0; a < 3; ++a) q[a] = R[a][0] * s[0] + R[a][1] * s[1] + R[a][2] * s[2] + tr[a];
+        double best = INFINITY;
+        long long bj = -1;
+        auto consider = [&](long long j) {
+            const double d2 = dist2(q, Tp + 3 * j);
+            if (d2 <= r2 && (d2 < best || (d2 == best && j < bj))) { best = d2; bj = j; }
+        };
+        if (brute) {
+            for (long long j = 0; j < mt; ++j) consider(j);
+        } else if (mt > 0) {
+            long long klo[3], khi[3];
+            bool any = true;
+            for (int a = 0; a < 3; ++a) {
+                const double fl = floor((q[a] - radius - lo[a]) / voxel), fh = floor((q[a] + radius - lo[a]) / voxel);
+                if (!(fh >= 0.0) || !(fl <= (double)KEY_MAX)) { any = false; break; }
+                klo[a] = fl < 0.0 ? 0 : (long long)fl;
+                khi[a] = fh > (double)KEY_MAX ? KEY_MAX : (long long)fh;
+            }
+            if (any)
+                for (long long z = klo[2]; z <= khi[2]; ++z)
+                    for (long long y = klo[1]; y <= khi[1]; ++y)
+                        for (long long x = klo[0]; x <= khi[0]; ++x) {
+                            const long long kk[3] = {x, y, z};
+                            double gap = 0.0;                  // distance from q to the cell's box
+                            for (int a = 0; a < 3; ++a) {
+                                const double c0 = lo[a] + kk[a] * voxel, c1 = c0 + voxel;
+                                const double g = q[a] < c0 ? c0 - q[a] : (q[a] > c1 ? q[a] - c1 : 0.0);
+                                gap += g * g;
+                            }
+                            if (gap > r2 * (1.0 + 1e-9) + 1e-12) continue;
+                            const long long h = find_slot(tab, 2 * nt, pack_key(x, y, z));
+                            if (h >= 0) consider(tab[h].ds);
+                        }
+        }
+        if (bj < 0) continue;
+        const double *t = Tp + 3 * bj;
+        const double d[3] = {q[0] - t[0], q[1] - t[1], q[2] - t[2]};
+        double Cs[3][3], Ct[3][3], M[3][3], RC[3][3];
+        sym_from6(CS + 6 * i, Cs);
+        sym_from6(CT + 6 * bj, Ct);
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) RC[a][b] = R[a][0] * Cs[0][b] + R[a][1] * Cs[1][b] + R[a][2] * Cs[2][b];
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) M[a][b] = Ct[a][b] + (RC[a][0] * R[b][0] + RC[a][1] * R[b][1] + RC[a][2] * R[b][2]);
+        double W[3][3];                  // M^-1 by cofactors
+        W[0][0] = M[1][1] * M[2][2] - M[1][2] * M[2][1];
+        W[0][1] = M[0][2] * M[2][1] - M[0][1] * M[2][2];
+        W[0][2] = M[0][1] * M[1][2] - M[0][2] * M[1][1];
+        W[1][0] = M[1][2] * M[2][0] - M[1][0] * M[2][2];
+        W[1][1] = M[0][0] * M[2][2] - M[0][2] * M[2][0];
+        W[1][2] = M[0][2] * M[1][0] - M[0][0] * M[1][2];
+        W[2][0] = M[1][0] * M[2][1] - M[1][1] * M[2][0];
+        W[2][1] = M[0][1] * M[2][0] - M[0][0] * M[2][1];
+        W[2][2] = M[0][0] * M[1][1] - M[0][1] * M[1][0];
+        const double det = M[0][0] * W[0][0] + M[0][1] * W[1][0] + M[0][2] * W[2][0];
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) W[a][b] /= det;
+        const double A[3][3] = {{0.0, q[2], -q[1]}, {-q[2], 0.0, q[0]}, {q[1], -q[0], 0.0}};     // -[q]x
+        accumulate_jtwj(acc, A, W, d);
+        acc[27] += 1.0;
+        acc[28] += d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        const double B[3][3] = {{0.0, t[2], -t[1]}, {-t[2], 0.0, t[0]}, {t[1], -t[0], 0.0}};     // -[t]x, W = I
+        const double I3[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+        double info[27];
+        for (int e = 0; e < 27; ++e) info[e] = 0.0;
+        accumulate_jtwj(info, B, I3, d);
+        for (int e = 0; e < 21; ++e) acc[SYS + e] += info[e];
+    }
+    // fixed-shape reduction: wave butterfly, then the 4 waves in order
+    __shared__ double part[GEO_THREADS / 64][SLAB];
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int e = 0; e < SLAB; ++e) {
+        double v = acc[e];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) part[wave][e] = v;
+    }
+    __syncthreads();
+    if (tid < SLAB) {
+        double v = part[0][tid];
+        for (int w = 1; w < GEO_THREADS / 64; ++w) v += part[w][tid];
+        slab[((long long)p * GEO_BLOCKS + blockIdx.x) * SLAB + tid] = v;
+    }
+}
+
+__device__ void rot_zyx(double a, double b, double g, double R[3][3])
+{
+    const double ca = cos(a), sa = sin(a), cb = cos(b), sb = sin(b), cg = cos(g), sg = sin(g);
+    // Rz(g) Ry(b) Rx(a)
+    R[0][0] = cg * cb; R[0][1] = cg * sb * sa - sg * ca; R[0][2] = cg * sb * ca + sg * sa;
+    R[1][0] = sg * cb; R[1][1] = sg * sb * sa + cg * ca; R[1][2] = sg * sb * ca - cg * sa;
+    R[2][0] = -sb;     R[2][1] = cb * sa;                R[2][2] = cb * ca;
+}
+
+__global__ __launch_bounds__(64) void finalize_kernel(const long long *count, const double *slab, PairState *state,
+                                                      double *transforms, double *fit_rmse, long long *corr_iters,
+                                                      double *information, double *system0, int n_pairs,
+                                                      int max_iteration, double rel_fitness, double rel_rmse)
+{
+    const int p = blockIdx.x, tid = threadIdx.x;
+    PairState &stt = state[p];
+    if (stt.done) return;
+    __shared__ double sum[SLAB];
+    if (tid < SLAB) {
+        double v = 0.0;
+        for (int g = 0; g < GEO_BLOCKS; ++g) v += slab[((long long)p * GEO_BLOCKS + g) * SLAB + tid];
+        sum[tid] = v;
+    }
+    __syncthreads();
+    const int round = stt.round;
+    if (system0 && round == 0 && tid < SYS) system0[(long long)p * SYS + tid] = sum[tid];
+    if (tid != 0) return;
+    const double nc = sum[27];
+    const long long ms = count[p];
+    const double fitness = ms > 0 ? nc / (double)ms : 0.0;
+    const double rmse = nc > 0.0 ? sqrt(sum[28] / nc) : 0.0;
+    bool done = round == max_iteration;
+    if (round > 0 && fabs(stt.prev_fitness - fitness) < rel_fitness && fabs(stt.prev_rmse - rmse) < rel_rmse)
+        done = true;
+    if (done) {
+        stt.done = 1;
+        fit_rmse[2 * p] = fitness;
+        fit_rmse[2 * p + 1] = rmse;
+        corr_iters[2 * p] = (long long)nc;
+        corr_iters[2 * p + 1] = round;
+        double *info = information + 36 * (long long)p;
+        int t = 0;
+        for (int a = 0; a < 6; ++a)
+            for (int b = a; b < 6; ++b) { info[6 * a + b] = info[6 * b + a] = sum[SYS + t]; ++t; }
+        return;
+    }
+    stt.prev_fitness = fitness;
+    stt.prev_rmse = rmse;
+    stt.round = round + 1;
+    // (sum JtWJ) x = -sum JtWd by Cholesky; dT = I without correspondences or a positive-definite system
+    double L[6][6], x[6];
+    bool ok = nc > 0.0;
+    {
+        int t = 0;
+        for (int a = 0; a < 6; ++a)
+            for (int b = a; b < 6; ++b) { L[b][a] = sum[t]; ++t; }         // lower triangle of the symmetric H
+    }
+    for (int j = 0; j < 6 && ok; ++j) {
+        double dj = L[j][j];
+        for (int k = 0; k < j; ++k) dj -= L[j][k] * L[j][k];
+        if (!(dj > 0.0) || !isfinite(dj)) { ok = false; break; }
+        L[j][j] = sqrt(dj);
+        for (int i = j + 1; i < 6; ++i) {
+            double v = L[i][j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    if (!ok) return;
+    for (int i = 0; i < 6; ++i) {                                         // L y = -g
+        double v = -sum[21 + i];
+        for (int k = 0; k < i; ++k) v -= L[i][k] * x[k];
+        x[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {                                        // L^T x = y
+        double v = x[i];
+        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
+        x[i] = v / L[i][i];
+    }
+    double dR[3][3];
+    rot_zyx(x[0], x[1], x[2], dR);
+    double *T = transforms + 16 * (long long)p, N[12];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 4; ++b)
+            N[4 * a + b] = dR[a][0] * T[b] + dR[a][1] * T[4 + b] + dR[a][2] * T[8 + b] + (b == 3 ? x[3 + a] : 0.0);
+    for (int e = 0; e < 12; ++e) T[e] = N[e];
+}
+
+inline int launch_status() { return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH; }
+
+}  // namespace
+
+extern "C" {
+
+void nsc_gicp_default_params(NscGicpParams *p)
+{
+    if (!p) return;
+    p->voxel_size = 0.5;
+    p->max_correspondence_distance = 1.0;
+    p->relative_fitness = 1e-6;
+    p->relative_rmse = 1e-6;
+    p->epsilon = 1e-3;
+    p->max_iteration = 30;
+    p->covariance_knn = 20;
+}
+
+size_t nsc_gicp_workspace_bytes(int32_t n_pairs, int64_t total_source_points, int64_t total_target_points)
+{
+    if (n_pairs < 0 || total_source_points < 0 || total_target_points < 0) return 0;
+    return layout(n_pairs, total_source_points, total_target_points).total;
+}
+
+int nsc_gicp_register(const float *source_points, const int64_t *source_offsets, const float *target_points,
+                      const int64_t *target_offsets, int32_t n_pairs, int64_t total_source_points,
+                      int64_t total_target_points, int32_t stride_floats, const NscGicpParams *p,
+                      const double *init_transforms, double *transforms, double *fitness_rmse,
+                      int64_t *corr_iterations, double *information, const NscGicpStages *stages, void *ws,
+                      size_t ws_bytes, void *stream)
+{
+    if (n_pairs < 0 || total_source_points < 0 || total_target_points < 0 || !p) return NSC_EINVAL;
+    if (stride_floats != 3 && stride_floats != 4) return NSC_EINVAL;
+    if (!(p->voxel_size > 0.0) || !(p->max_correspondence_distance > 0.0) || !(p->epsilon > 0.0) ||
+        !(p->relative_fitness >= 0.0) || !(p->relative_rmse >= 0.0) || p->max_iteration < 0 ||
+        !isfinite(p->voxel_size) || !isfinite(p->max_correspondence_distance))
+        return NSC_EINVAL;
+    if (p->covariance_knn < 1 || p->covariance_knn > NSC_GICP_MAX_KNN) return NSC_EUNSUPPORTED;
+    if (n_pairs == 0) return NSC_OK;
+    if (!source_offsets || !target_offsets || !init_transforms || !transforms || !fitness_rmse || !corr_iterations ||
+        !information)
+        return NSC_EINVAL;
+    if ((total_source_points > 0 && !source_points) || (total_target_points > 0 && !target_points)) return NSC_EINVAL;
+    const Layout L = layout(n_pairs, total_source_points, total_target_points);
+    if (!ws || ws_bytes < L.total) return NSC_EWORKSPACE;
+    char *w = static_cast<char *>(ws);
+    double *partial = reinterpret_cast<double *>(w + L.partial), *bound = reinterpret_cast<double *>(w + L.bound);
+    long long *count = reinterpret_cast<long long *>(w + L.count);
+    Slot *slots = reinterpret_cast<Slot *>(w + L.slots);
+    double *points = reinterpret_cast<double *>(w + L.points), *cov = reinterpret_cast<double *>(w + L.cov);
+    double *slab = reinterpret_cast<double *>(w + L.slab);
+    PairState *state = reinterpret_cast<PairState *>(w + L.state);
+    double *system0 = nullptr;
+    if (stages) {                        // stage outputs replace the workspace regions they name
+        if (stages->points) points = stages->points;
+        if (stages->covariances) cov = stages->covariances;
+        if (stages->counts) count = reinterpret_cast<long long *>(stages->counts);
+        system0 = stages->system0;
+    }
+    Clouds cl{source_points, target_points, reinterpret_cast<const long long *>(source_offsets),
+              reinterpret_cast<const long long *>(target_offsets), (long long)total_source_points, stride_floats,
+              n_pairs};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 per_cloud(GEO_BLOCKS, 2 * n_pairs), per_pair(GEO_BLOCKS, n_pairs);
+    hipLaunchKernelGGL(ds_prepare_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, partial, init_transforms,
+                       transforms, state);
+    hipLaunchKernelGGL(ds_insert_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, partial, bound, p->voxel_size);
+    hipLaunchKernelGGL(ds_compact_kernel, dim3(2 * n_pairs), dim3(COMPACT_THREADS), 0, s, cl, slots, bound,
+                       p->voxel_size, points, count);
+    hipLaunchKernelGGL(covariance_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, bound, count, points, cov,
+                       p->voxel_size, p->covariance_knn, p->epsilon);
+    for (int r = 0; r <= p->max_iteration; ++r) {
+        hipLaunchKernelGGL(linearize_kernel, per_pair, dim3(GEO_THREADS), 0, s, cl, slots, bound, count, points, cov,
+                           transforms, state, slab, p->voxel_size, p->max_correspondence_distance);
+        hipLaunchKernelGGL(finalize_kernel, dim3(n_pairs), dim3(64), 0, s, count, slab, state, transforms,
+                           fitness_rmse, reinterpret_cast<long long *>(corr_iterations), information, system0, n_pairs,
+                           p->max_iteration, p->relative_fitness, p->relative_rmse);
+    }
+    return launch_status();
+}
+
+}  // extern "C"

@@ -11,10 +11,11 @@ What runs where
     ``dist < spatial_filter_distance`` test of :160-170 fused in (nsc_w1_distances_cdf) and a device top-k
     (nsc_topk_smallest).  The reference ranks ALL rows, then walks the sorted list skipping filtered rows until it
     has top_k (:182-200): that is the top_k of the unfiltered rows, which is what the fused form returns.
-  * stage 2 (Open3D GICP, src/retrieval/geometric_verification.py) is NOT part of the data-parallel descriptor path
-    (SURVEY section 2 #9): pass ``verifier=`` (an object with the reference's ``verify(query_points,
-    candidate_points) -> (verified, transform, info)``) and, for g2o edges, ``edge_fn=`` (the reference's
-    ``compute_pose_graph_edge``).  Without them ``query(verify=True)`` / ``get_loop_closures`` raise.
+  * stage 2 (GICP, src/retrieval/geometric_verification.py) is injected: pass ``verifier=`` (an object with the
+    reference's ``verify(query_points, candidate_points) -> (verified, transform, info)``; ``GeometricVerifier()``
+    of geometric_verification.py runs it on the device) and, for g2o edges, ``edge_fn=`` (the reference's
+    ``compute_pose_graph_edge``).  Without them ``query(verify=True)`` / ``get_loop_closures`` raise.  A verifier
+    with ``verify_batch(query_points, candidate_points_list)`` checks all candidates of a query in one call.
 
 ``ShardedTwoStageRetrieval`` is the multi-GPU form (BASELINE configs[3]): the database rows
 stay sharded over the ranks in the layout of ``distributed.shard_range``; every rank scores its own rows, the
@@ -136,9 +137,12 @@ class TwoStageRetrieval:
                                 "with verifier=<object with the reference's GeometricVerifier.verify> or call "
                                 "query(..., verify=False)")
         verified_candidates = []
-        for candidate in candidates:
-            candidate_points = self.keyframes[candidate.database_idx].points
-            verified, transform, info = self.verifier.verify(query_points, candidate_points)
+        if hasattr(self.verifier, "verify_batch"):
+            results = self.verifier.verify_batch(query_points,
+                                                 [self.keyframes[c.database_idx].points for c in candidates])
+        else:
+            results = (self.verifier.verify(query_points, self.keyframes[c.database_idx].points) for c in candidates)
+        for candidate, (verified, transform, info) in zip(candidates, results):
             candidate.verified = verified
             candidate.transform = transform
             candidate.fitness = info['fitness']

@@ -5,7 +5,8 @@ produces (src/data/kitti_loader.py:113, nclt_loader.py:230-253, helipr_loader.py
 """
 import numpy as np
 
-__all__ = ["make_cloud", "make_clouds_packed", "make_clouds_device", "make_pose_chain", "randomize_bn_stats"]
+__all__ = ["make_cloud", "make_clouds_packed", "make_clouds_device", "make_pose_chain", "randomize_bn_stats", "make_world",
+           "scan_world", "pose_xyz_yaw"]
 
 
 def _sph_to_xyz(az, el, r):
@@ -181,3 +182,70 @@ def randomize_bn_stats(model, seed=1):
                 m.running_var.copy_((torch.rand(m.num_features, generator=g) * 1.5 + 0.25).to(m.running_var.device))
                 m.weight.copy_((torch.rand(m.num_features, generator=g) + 0.5).to(m.weight.device))
                 m.bias.copy_((torch.randn(m.num_features, generator=g) * 0.1).to(m.bias.device))
+
+
+# ------------------------------------------------------------------------------------------------
+# analytic worlds and ray-cast LiDAR scans (stage-2 verification tests)
+# ------------------------------------------------------------------------------------------------
+def make_world(seed, ground_z=-1.8, extent=60.0, n_boxes=40, n_poles=30):
+    """A seeded analytic world: the ground plane z = ground_z, axis-aligned boxes (buildings, cars) standing on it and
+    vertical poles (radius 0.1-0.3 m).  Returned as a dict of arrays for scan_world."""
+    rng = np.random.default_rng(seed)
+    lo = rng.uniform(-extent, extent, (n_boxes, 2))
+    size = rng.uniform(1.5, 12.0, (n_boxes, 2))
+    height = rng.uniform(1.0, 10.0, n_boxes)
+    keep = np.all((np.abs(lo + size / 2) > 4.0) | (np.abs(lo) > 4.0), 1)      # keep the sensor's start area free
+    boxes = np.concatenate([lo, np.full((n_boxes, 1), ground_z), lo + size, ground_z + height[:, None]], 1)[keep]
+    poles = np.stack([rng.uniform(-extent, extent, n_poles), rng.uniform(-extent, extent, n_poles),
+                      rng.uniform(0.1, 0.3, n_poles), ground_z + rng.uniform(3.0, 8.0, n_poles)], 1)
+    poles = poles[np.hypot(poles[:, 0], poles[:, 1]) > 3.0]
+    return {"ground_z": float(ground_z), "boxes": boxes, "poles": poles}
+
+
+def pose_xyz_yaw(x, y, z=0.0, yaw_deg=0.0):
+    """(4,4) float64 sensor-to-world pose: translation (x, y, z), rotation about z."""
+    c, s = np.cos(np.deg2rad(yaw_deg)), np.sin(np.deg2rad(yaw_deg))
+    T = np.eye(4)
+    T[:2, :2] = [[c, -s], [s, c]]
+    T[:3, 3] = (x, y, z)
+    return T
+
+
+def scan_world(world, pose, seed=0, n_rings=64, n_azimuth=2048, range_noise=0.01, max_range=80.0):
+    """Ray-cast ``world`` like a 64-ring LiDAR (elevation -24.8..2 deg) mounted at ``pose`` (sensor-to-world 4x4):
+    the nearest hit of every ray within max_range, range noise N(0, range_noise) m, a random azimuth phase per scan.
+    Returns (N,4) float32 [x, y, z, intensity] in the sensor frame."""
+    rng = np.random.default_rng(seed)
+    pose = np.asarray(pose, np.float64)
+    el = np.deg2rad(np.linspace(-24.8, 2.0, n_rings))
+    az = np.linspace(-np.pi, np.pi, n_azimuth, endpoint=False) + rng.uniform(0, 2 * np.pi / n_azimuth)
+    el, az = np.repeat(el, n_azimuth), np.tile(az, n_rings)
+    d = pose[:3, :3] @ np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)])   # (3, M) world
+    o = pose[:3, 3]
+    t = np.full(d.shape[1], np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tg = (world["ground_z"] - o[2]) / d[2]
+        t = np.where((tg > 0) & (tg < t), tg, t)
+        for b in world["boxes"]:                                      # slab test
+            t0 = (b[:3, None] - o[:, None]) / d
+            t1 = (b[3:, None] - o[:, None]) / d
+            tn = np.nanmax(np.minimum(t0, t1), 0)
+            tf = np.nanmin(np.maximum(t0, t1), 0)
+            hit = (tn <= tf) & (tn > 0)
+            t = np.where(hit & (tn < t), tn, t)
+        for px, py, r, top in world["poles"]:                         # vertical cylinder
+            ox, oy = o[0] - px, o[1] - py
+            a = d[0] ** 2 + d[1] ** 2
+            bq = 2 * (ox * d[0] + oy * d[1])
+            cq = ox * ox + oy * oy - r * r
+            disc = bq * bq - 4 * a * cq
+            th = (-bq - np.sqrt(np.maximum(disc, 0))) / (2 * a)
+            z = o[2] + th * d[2]
+            hit = (disc >= 0) & (th > 0) & (z >= world["ground_z"]) & (z <= top)
+            t = np.where(hit & (th < t), th, t)
+    ok = t < max_range
+    r = t[ok] + rng.normal(0.0, range_noise, int(ok.sum()))
+    el, az = el[ok], az[ok]
+    pts = np.stack([r * np.cos(el) * np.cos(az), r * np.cos(el) * np.sin(az), r * np.sin(el),
+                    rng.uniform(0, 1, r.size)], 1)
+    return pts.astype(np.float32)

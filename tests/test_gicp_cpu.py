@@ -1,0 +1,97 @@
+"""Stage-2 verification without a GPU: the float64 restatement (tests/gicp_restatement.py) recovers known relative
+poses of ray-cast revisits and rejects scans of another world; the nsc_gicp_* C ABI validates its arguments on the
+host."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import gicp_restatement as G
+from neural_spectral_codec_amd import synth
+
+# GICP is local: from the identity it converges for ~1 m of offset or ~10 deg of yaw alone (calibrated on the
+# restatement); the 2 m / 10 deg revisits start from an odometry-like guess within 0.6 m / 4 deg.
+REVISITS = [((0.5, 0.3, 2.0), None), ((1.0, -0.5, 5.0), None), ((0.0, 0.0, 10.0), None),
+            ((2.0, 0.0, 0.0), (1.4, 0.0, 0.0)), ((1.4, 1.4, 10.0), (1.0, 1.0, 6.0))]
+T_BAR, R_BAR = 0.05, np.deg2rad(0.25)
+
+
+def revisit(offset, guess, world_seed=3):
+    w = synth.make_world(world_seed)
+    PA = synth.pose_xyz_yaw(0, 0)
+    PB = synth.pose_xyz_yaw(offset[0], offset[1], 0.0, offset[2])
+    A, B = synth.scan_world(w, PA, seed=1), synth.scan_world(w, PB, seed=2)
+    init = None if guess is None else np.linalg.inv(synth.pose_xyz_yaw(guess[0], guess[1], 0.0, guess[2])) @ PA
+    return A, B, np.linalg.inv(PB) @ PA, init
+
+
+@pytest.mark.parametrize("offset,guess", REVISITS)
+def test_restatement_recovers_revisit(offset, guess):
+    A, B, T_true, init = revisit(offset, guess)
+    r = G.register(A, B, init=init)
+    te, re = G.pose_error(r["transform"], T_true)
+    assert te <= T_BAR and re <= R_BAR, (te, np.rad2deg(re))
+    assert r["fitness"] >= 0.3 and r["rmse"] <= 0.5
+
+
+def test_restatement_rejects_other_world():
+    A = synth.scan_world(synth.make_world(3), synth.pose_xyz_yaw(0, 0), seed=1)
+    B = synth.scan_world(synth.make_world(11, ground_z=-4.0), synth.pose_xyz_yaw(0, 0), seed=5)
+    r = G.register(A, B)
+    assert r["n_corr"] == 0 or r["fitness"] < 0.3 or r["rmse"] > 0.5
+
+
+def test_restatement_down_sampling_order():
+    p = np.array([[0.1, 0.1, 0.1], [5.0, 5.0, 5.0], [0.2, 0.2, 0.2], [np.nan, 0, 0], [5.1, 5.1, 5.1]], np.float32)
+    d = G.voxel_down_sample(p, 1.0)
+    np.testing.assert_allclose(d, [[0.15, 0.15, 0.15], [5.05, 5.05, 5.05]], rtol=1e-6)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from neural_spectral_codec_amd import _lib, build
+    build.build_hip()
+    return _lib.lib()
+
+
+def test_gicp_abi_validates_on_host(lib):
+    from neural_spectral_codec_amd import _lib
+    EINVAL, EUNSUP, EWS = -1, -2, -3
+    p = _lib.GicpParams()
+    lib.nsc_gicp_default_params(p)
+    assert (p.voxel_size, p.max_correspondence_distance, p.max_iteration, p.covariance_knn) == (0.5, 1.0, 30, 20)
+    P, Ns, Nt = 3, 1000, 2000
+    need = lib.nsc_gicp_workspace_bytes(P, Ns, Nt)
+    assert need > 0 and lib.nsc_gicp_workspace_bytes(-1, Ns, Nt) == 0 and lib.nsc_gicp_workspace_bytes(P, -1, Nt) == 0
+    fake = C.c_void_p(4096)                      # never dereferenced: every check runs before a launch
+
+    def call(**kw):
+        a = dict(sp=fake, so=fake, tp=fake, to=fake, P=P, Ns=Ns, Nt=Nt, stride=4, params=p, init=fake, out=fake,
+                 fr=fake, ci=fake, info=fake, ws=fake, nbytes=need)
+        a.update(kw)
+        return lib.nsc_gicp_register(a["sp"], a["so"], a["tp"], a["to"], a["P"], a["Ns"], a["Nt"], a["stride"],
+                                     C.byref(a["params"]) if a["params"] is not None else None, a["init"], a["out"],
+                                     a["fr"], a["ci"], a["info"], None, a["ws"], a["nbytes"], None)
+
+    for k in ("sp", "so", "tp", "to", "init", "out", "fr", "ci", "info"):
+        assert call(**{k: None}) == EINVAL, k
+    assert call(params=None) == EINVAL
+    for k in ("P", "Ns", "Nt"):
+        assert call(**{k: -1}) == EINVAL, k
+    assert call(stride=5) == EINVAL
+    for bad in (0.0, -0.5, float("nan")):
+        q = _lib.GicpParams()
+        lib.nsc_gicp_default_params(q)
+        q.voxel_size = bad
+        assert call(params=q) == EINVAL
+    q = _lib.GicpParams()
+    lib.nsc_gicp_default_params(q)
+    q.max_correspondence_distance = 0.0
+    assert call(params=q) == EINVAL
+    q.max_correspondence_distance, q.max_iteration = 1.0, -1
+    assert call(params=q) == EINVAL
+    q.max_iteration, q.covariance_knn = 30, _lib.GICP_MAX_KNN + 1
+    assert call(params=q) == EUNSUP
+    assert call(nbytes=need - 1) == EWS
+    assert call(ws=None) == EWS
+    assert call(P=0) == 0                        # nothing to do, nothing launched
