@@ -453,6 +453,47 @@ int    nsc_gicp_register(const float *source_points, const int64_t *source_offse
                          int64_t *corr_iterations, double *information, const NscGicpStages *stages, void *ws,
                          size_t ws_bytes, void *stream);
 
+/* A store of prepared clouds.  A cloud's down-sampled points, covariances, min bound and voxel index depend only
+ * on the cloud and on voxel_size, covariance_knn and epsilon: nsc_gicp_prepare computes them once per cloud and
+ * appends them to a store, nsc_gicp_register_prepared registers pairs given as cloud indices into stores.  Its
+ * results are bitwise those of nsc_gicp_register on the same raw clouds with the same parameters.
+ * The struct is a host struct of device pointers; the caller owns the memory and the host counts.  Cloud c owns
+ * rows [row_offsets[c], row_offsets[c+1]) of points / covariances (rows as in NscGicpStages) and index slots
+ * [slot_offsets[c], slot_offsets[c+1]) (2 per row: packed voxel key + 1, 0 = empty; row within the cloud);
+ * bounds[c] = the cloud's min bound (x, y, z, 0).  After nsc_gicp_prepare of B clouds the caller reads
+ * row_offsets[n_clouds + B] and slot_offsets[n_clouds + B] back into n_rows and n_slots and adds B to n_clouds. */
+typedef struct NscGicpCloudSet {
+    double   voxel_size, epsilon;         /* parameters the clouds were prepared with                        */
+    int32_t  covariance_knn, n_clouds;    /* ... and the clouds present                                      */
+    int64_t  n_rows, n_slots;             /* rows / index slots present                                      */
+    int64_t  cap_clouds, cap_rows, cap_slots;
+    int64_t  *row_offsets, *slot_offsets; /* (cap_clouds + 1) int64                                          */
+    double   *bounds;                     /* (cap_clouds, 4) float64                                         */
+    double   *points, *covariances;       /* (cap_rows, 3), (cap_rows, 6) float64                            */
+    uint64_t *slots;                      /* (cap_slots, 2)                                                  */
+} NscGicpCloudSet;
+
+/* Prepare clouds [offsets[c], offsets[c+1]) of points (as nsc_gicp_register's) and append them to set as clouds
+ * set->n_clouds .. + n_clouds - 1.  p's voxel_size, covariance_knn and epsilon must equal the set's (NSC_EINVAL);
+ * the set must have room for every input row being a voxel of its own: n_clouds + n_clouds(batch) <= cap_clouds,
+ * n_rows + total_points <= cap_rows, n_slots + 2 total_points <= cap_slots (else NSC_EWORKSPACE). */
+size_t nsc_gicp_prepare_workspace_bytes(int32_t n_clouds, int64_t total_points);
+int    nsc_gicp_prepare(const float *points, const int64_t *offsets, int32_t n_clouds, int64_t total_points,
+                        int32_t stride_floats, const NscGicpParams *p, const NscGicpCloudSet *set, void *ws,
+                        size_t ws_bytes, void *stream);
+/* Register cloud source_ids[i] of sources onto cloud target_ids[i] of targets (device int64 ids; the two sets may be
+ * one).  p's voxel_size, covariance_knn and epsilon must equal both sets'; the correspondence radius and the
+ * iteration and convergence parameters are free.  Outputs as nsc_gicp_register's; system0 (optional) as
+ * NscGicpStages.system0.  A pair with an id outside [0, n_clouds) of its set gets NaN transform, fitness, rmse,
+ * information and system0, n_correspondences -1 and 0 iterations; nothing of the sets is read for it.
+ * Launches 1 + 2 (max_iteration + 1) kernels and nothing else. */
+size_t nsc_gicp_register_prepared_workspace_bytes(int32_t n_pairs);
+int    nsc_gicp_register_prepared(const NscGicpCloudSet *sources, const NscGicpCloudSet *targets,
+                                  const int64_t *source_ids, const int64_t *target_ids, int32_t n_pairs,
+                                  const NscGicpParams *p, const double *init_transforms, double *transforms,
+                                  double *fitness_rmse, int64_t *corr_iterations, double *information,
+                                  double *system0, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

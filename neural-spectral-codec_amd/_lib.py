@@ -85,6 +85,14 @@ class GicpStages(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("points", "counts", "covariances", "system0")]
 
 
+class GicpCloudSet(C.Structure):
+    """struct NscGicpCloudSet"""
+    _fields_ = [("voxel_size", C.c_double), ("epsilon", C.c_double), ("covariance_knn", C.c_int32),
+                ("n_clouds", C.c_int32), ("n_rows", C.c_int64), ("n_slots", C.c_int64), ("cap_clouds", C.c_int64),
+                ("cap_rows", C.c_int64), ("cap_slots", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("row_offsets", "slot_offsets", "bounds", "points", "covariances", "slots")]
+
+
 GICP_MAX_KNN = 32
 
 
@@ -161,6 +169,12 @@ SYMBOLS = {
     "nsc_gicp_workspace_bytes": (_sz, [_i32, _i64, _i64]),
     "nsc_gicp_register": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, C.POINTER(GicpParams), _vp, _vp,
                                     _vp, _vp, _vp, C.POINTER(GicpStages), _vp, _sz, _vp]),
+    "nsc_gicp_prepare_workspace_bytes": (_sz, [_i32, _i64]),
+    "nsc_gicp_prepare": (C.c_int, [_vp, _vp, _i32, _i64, _i32, C.POINTER(GicpParams), C.POINTER(GicpCloudSet), _vp,
+                                   _sz, _vp]),
+    "nsc_gicp_register_prepared_workspace_bytes": (_sz, [_i32]),
+    "nsc_gicp_register_prepared": (C.c_int, [C.POINTER(GicpCloudSet), C.POINTER(GicpCloudSet), _vp, _vp, _i32,
+                                             C.POINTER(GicpParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

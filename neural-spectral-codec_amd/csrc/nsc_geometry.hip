@@ -20,6 +20,16 @@
 //                          Sum|d|^2, n_corr and the information matrix
 //     finalize    (P)      slabs summed in a fixed order, evaluation, convergence test, 6x6 Cholesky, T <- dT T
 //
+// The store of prepared clouds (NscGicpCloudSet): a cloud's down-sampled points, covariances, min bound and voxel
+// index depend on the cloud and on voxel_size, covariance_knn and epsilon only, so nsc_gicp_prepare computes them once
+// per cloud and nsc_gicp_register_prepared registers pairs given as indices into one or two stores:
+//   prepare:             ds_prepare, ds_insert, ds_compact, covariance as above over a batch of clouds (no pairs),
+//                        then store  (C)  offsets after the store's end, rows, covariances, bound, compact index
+//   register_prepared:   prepared_setup  (P / 256)  ids -> row ranges and counts, initial transform, pair state
+//                        then the max_iteration + 1 rounds of linearize + finalize above
+// The results equal nsc_gicp_register's bit for bit: the stored rows are the same values, and a voxel lookup gives the
+// same row whatever the capacity of the table it is made in.
+//
 // No float atomics anywhere: results are bitwise reproducible and independent of what else shares the batch.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -112,8 +122,17 @@ __device__ __forceinline__ unsigned long long pack_key(long long x, long long y,
     return (unsigned long long)x | ((unsigned long long)y << KEY_BITS) | ((unsigned long long)z << (2 * KEY_BITS));
 }
 
+struct IndexSlot {                      // one voxel of a stored cloud's index (2 slots per down-sampled row)
+    unsigned long long key;             // packed key + 1; 0 = empty
+    unsigned long long row;             // row of the voxel in the down-sampled cloud
+};
+
+__device__ __forceinline__ long long ds_row(const Slot &s) { return s.ds; }
+__device__ __forceinline__ long long ds_row(const IndexSlot &s) { return (long long)s.row; }
+
 // Slot of a voxel key in a table of `cap` slots, or -1.
-__device__ __forceinline__ long long find_slot(const Slot *tab, long long cap, unsigned long long key)
+template <class S>
+__device__ __forceinline__ long long find_slot(const S *tab, long long cap, unsigned long long key)
 {
     if (cap == 0) return -1;
     long long h = (long long)(mix64(key) % (unsigned long long)cap);
@@ -399,23 +418,81 @@ __device__ __forceinline__ void accumulate_jtwj(double *acc, const double A[3][3
     for (int a = 0; a < 6; ++a) acc[21 + a] += WJ[0][a] * d[0] + WJ[1][a] * d[1] + WJ[2][a] * d[2];
 }
 
-__global__ __launch_bounds__(GEO_THREADS) void linearize_kernel(Clouds cl, const Slot *slots, const double *bound,
-                                                                const long long *count, const double *points,
-                                                                const double *cov, const double *transforms,
+// What linearize reads of pair p: the down-sampled source and target rows with their covariances, the target's min
+// bound and its voxel table (`cap` slots of type S).
+template <class S>
+struct PairView {
+    const double *S_pts, *S_cov, *T_pts, *T_cov;
+    long long ms, mt, cap;
+    double lo[3];
+    const S *tab;
+};
+
+// nsc_gicp_register: both clouds of pair p were prepared in this call's workspace
+struct BatchPairs {
+    Clouds cl;
+    const Slot *slots;
+    const double *bound, *points, *cov;
+    const long long *count;
+    __device__ PairView<Slot> view(int p) const
+    {
+        const int cs = p, ct = cl.n_pairs + p;
+        const float *base; long long ns, ss, nt, st;
+        cl.rows(cs, base, ns, ss);
+        cl.rows(ct, base, nt, st);
+        PairView<Slot> v;
+        v.ms = count[cs]; v.mt = count[ct];
+        v.tab = slots + 2 * st; v.cap = 2 * nt;
+        v.S_pts = points + 3 * ss; v.T_pts = points + 3 * st;
+        v.S_cov = cov + 6 * ss; v.T_cov = cov + 6 * st;
+        for (int a = 0; a < 3; ++a) v.lo[a] = bound[4 * ct + a];
+        return v;
+    }
+};
+
+// A NscGicpCloudSet as the kernels read it
+struct StoreView {
+    long long *row_off, *slot_off;
+    double *bounds, *points, *cov;
+    IndexSlot *slots;
+    long long n_clouds;
+};
+
+struct PairRows {                       // pair p of nsc_gicp_register_prepared, resolved by prepared_setup_kernel
+    long long s_row, t_row, t_slot, t_cap, t_cloud, pad[3];
+};
+
+// nsc_gicp_register_prepared: pair p reads two clouds of (possibly different) stores
+struct StoredPairs {
+    StoreView src, tgt;
+    const PairRows *rows;
+    const long long *count;
+    int n_pairs;
+    __device__ PairView<IndexSlot> view(int p) const
+    {
+        const PairRows r = rows[p];
+        PairView<IndexSlot> v;
+        v.ms = count[p]; v.mt = count[n_pairs + p];
+        v.tab = tgt.slots + r.t_slot; v.cap = r.t_cap;
+        v.S_pts = src.points + 3 * r.s_row; v.T_pts = tgt.points + 3 * r.t_row;
+        v.S_cov = src.cov + 6 * r.s_row; v.T_cov = tgt.cov + 6 * r.t_row;
+        for (int a = 0; a < 3; ++a) v.lo[a] = tgt.bounds[4 * r.t_cloud + a];
+        return v;
+    }
+};
+
+// One body for both entry points: Pairs (BatchPairs or StoredPairs) only says where a pair's clouds live.
+template <class Pairs>
+__global__ __launch_bounds__(GEO_THREADS) void linearize_kernel(Pairs pairs, const double *transforms,
                                                                 const PairState *state, double *slab, double voxel,
                                                                 double radius)
 {
     const int p = blockIdx.y, tid = threadIdx.x;
     if (state[p].done) return;
-    const int cs = p, ct = cl.n_pairs + p;
-    const float *base; long long ns, ss, nt, st;
-    cl.rows(cs, base, ns, ss);
-    cl.rows(ct, base, nt, st);
-    const long long ms = count[cs], mt = count[ct];
-    const Slot *tab = slots + 2 * st;
-    const double *S = points + 3 * ss, *Tp = points + 3 * st;
-    const double *CS = cov + 6 * ss, *CT = cov + 6 * st;
-    const double lo[3] = {bound[4 * ct], bound[4 * ct + 1], bound[4 * ct + 2]};
+    const auto v = pairs.view(p);
+    const long long ms = v.ms, mt = v.mt;
+    const double *S = v.S_pts, *Tp = v.T_pts, *CS = v.S_cov, *CT = v.T_cov;
+    const double lo[3] = {v.lo[0], v.lo[1], v.lo[2]};
     const double *T = transforms + 16 * (long long)p;
     double R[3][3], tr[3];
     for (int a = 0; a < 3; ++a) {
@@ -461,8 +538,8 @@ __global__ __launch_bounds__(GEO_THREADS) void linearize_kernel(Clouds cl, const
                                 gap += g * g;
                             }
                             if (gap > r2 * (1.0 + 1e-9) + 1e-12) continue;
-                            const long long h = find_slot(tab, 2 * nt, pack_key(x, y, z));
-                            if (h >= 0) consider(tab[h].ds);
+                            const long long h = find_slot(v.tab, v.cap, pack_key(x, y, z));
+                            if (h >= 0) consider(ds_row(v.tab[h]));
                         }
         }
         if (bj < 0) continue;
@@ -603,6 +680,158 @@ __global__ __launch_bounds__(64) void finalize_kernel(const long long *count, co
     for (int e = 0; e < 12; ++e) T[e] = N[e];
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// the store of prepared clouds
+// ------------------------------------------------------------------------------------------------------------------
+// One block per cloud c of a prepare batch, after ds_compact and covariance: the cloud's store rows and index slots
+// follow the store's end (rows0, slots0) and the batch's earlier clouds (fixed-order sum of count[0..c)).  Writes
+// the offsets, the min bound, the down-sampled points and covariances, and the index: 2m slots keyed on the voxel
+// keys of the workspace table (the input keys, not keys recomputed from the centroids, which may round into a
+// neighbouring voxel).
+__global__ __launch_bounds__(COMPACT_THREADS) void store_kernel(Clouds cl, const Slot *slots, const double *bound,
+                                                                const long long *count, const double *points,
+                                                                const double *cov, StoreView set, long long n0,
+                                                                long long rows0, long long slots0)
+{
+    const int c = blockIdx.x, tid = threadIdx.x;
+    __shared__ long long red[COMPACT_THREADS];
+    long long acc = 0;
+    for (int b = tid; b < c; b += COMPACT_THREADS) acc += count[b];
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = COMPACT_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    const long long m = count[c], row = rows0 + red[0], slot = slots0 + 2 * red[0], cap = 2 * m;
+    if (tid == 0) {
+        set.row_off[n0 + c + 1] = row + m;
+        set.slot_off[n0 + c + 1] = slot + cap;
+        if (c == 0) { set.row_off[n0] = rows0; set.slot_off[n0] = slots0; }
+    }
+    if (tid < 4) set.bounds[4 * (n0 + c) + tid] = tid < 3 ? bound[4 * c + tid] : 0.0;
+    const float *base; long long n, start;
+    cl.rows(c, base, n, start);
+    for (long long i = tid; i < 3 * m; i += COMPACT_THREADS) set.points[3 * row + i] = points[3 * start + i];
+    for (long long i = tid; i < 6 * m; i += COMPACT_THREADS) set.cov[6 * row + i] = cov[6 * start + i];
+    IndexSlot *tab = set.slots + slot;
+    for (long long i = tid; i < cap; i += COMPACT_THREADS) tab[i] = IndexSlot{0ULL, 0ULL};
+    __threadfence();                     // the cleared slots are in memory before any block-mate's CAS below
+    __syncthreads();
+    const Slot *ws = slots + 2 * start;
+    for (long long i = tid; i < 2 * n; i += COMPACT_THREADS) {
+        const unsigned long long e = ws[i].key;
+        if (e == 0) continue;
+        long long h = (long long)(mix64(e - 1) % (unsigned long long)cap);
+        while (atomicCAS(&tab[h].key, 0ULL, e) != 0ULL)      // m distinct keys in 2m slots
+            h = h + 1 == cap ? 0 : h + 1;
+        tab[h].row = (unsigned long long)ws[i].ds;
+    }
+}
+
+// One thread per pair of nsc_gicp_register_prepared: resolve the ids into row ranges and counts, copy the initial
+// transform, reset the pair state.  A pair with an id outside its store is finished here with NaN outputs,
+// n_correspondences -1 and 0 iterations; nothing of either store is read for it.
+__global__ __launch_bounds__(GEO_THREADS) void prepared_setup_kernel(StoreView src, StoreView tgt,
+                                                                     const long long *source_ids,
+                                                                     const long long *target_ids, int n_pairs,
+                                                                     const double *init, double *transforms,
+                                                                     PairState *state, long long *count,
+                                                                     PairRows *rows, double *fit_rmse,
+                                                                     long long *corr_iters, double *information,
+                                                                     double *system0)
+{
+    const int p = blockIdx.x * GEO_THREADS + threadIdx.x;
+    if (p >= n_pairs) return;
+    const long long a = source_ids[p], b = target_ids[p];
+    double *T = transforms + 16 * (long long)p;
+    if (a < 0 || a >= src.n_clouds || b < 0 || b >= tgt.n_clouds) {
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        for (int e = 0; e < 16; ++e) T[e] = nan;
+        for (int e = 0; e < 36; ++e) information[36 * (long long)p + e] = nan;
+        if (system0)
+            for (int e = 0; e < SYS; ++e) system0[(long long)p * SYS + e] = nan;
+        fit_rmse[2 * p] = fit_rmse[2 * p + 1] = nan;
+        corr_iters[2 * p] = -1;
+        corr_iters[2 * p + 1] = 0;
+        count[p] = count[n_pairs + p] = 0;
+        rows[p] = PairRows{0, 0, 0, 0, 0, {0, 0, 0}};
+        state[p] = PairState{0.0, 0.0, 0, 1, 0, 0};
+        return;
+    }
+    const long long s0 = src.row_off[a], t0 = tgt.row_off[b], ts0 = tgt.slot_off[b];
+    count[p] = src.row_off[a + 1] - s0;
+    count[n_pairs + p] = tgt.row_off[b + 1] - t0;
+    rows[p] = PairRows{s0, t0, ts0, tgt.slot_off[b + 1] - ts0, b, {0, 0, 0}};
+    for (int e = 0; e < 16; ++e) T[e] = init[16 * (long long)p + e];
+    state[p] = PairState{0.0, 0.0, 0, 0, 0, 0};
+}
+
+struct PreparedLayout {
+    size_t count, rows, slab, state, total;
+};
+
+PreparedLayout prepared_layout(int n_pairs)
+{
+    const size_t P = (size_t)n_pairs;
+    PreparedLayout L;
+    size_t o = 0;
+    L.count = o; o = align256(o + 2 * P * sizeof(long long));
+    L.rows = o;  o = align256(o + P * sizeof(PairRows));
+    L.slab = o;  o = align256(o + P * GEO_BLOCKS * SLAB * sizeof(double));
+    L.state = o; o = align256(o + P * sizeof(PairState));
+    L.total = o;
+    return L;
+}
+
+// nsc_gicp_prepare's workspace: the per-cloud regions of layout() for n_clouds clouds of total_points rows
+struct PrepLayout {
+    size_t partial, bound, count, slots, points, cov, total;
+};
+
+PrepLayout prep_layout(int n_clouds, long long total_points)
+{
+    const size_t C = (size_t)n_clouds, N = (size_t)total_points;
+    PrepLayout L;
+    size_t o = 0;
+    L.partial = o; o = align256(o + C * GEO_BLOCKS * 3 * sizeof(double));
+    L.bound = o;   o = align256(o + C * 4 * sizeof(double));
+    L.count = o;   o = align256(o + C * sizeof(long long));
+    L.slots = o;   o = align256(o + 2 * N * sizeof(Slot));
+    L.points = o;  o = align256(o + N * 3 * sizeof(double));
+    L.cov = o;     o = align256(o + N * 6 * sizeof(double));
+    L.total = o;
+    return L;
+}
+
+int check_params(const NscGicpParams *p)
+{
+    if (!(p->voxel_size > 0.0) || !(p->max_correspondence_distance > 0.0) || !(p->epsilon > 0.0) ||
+        !(p->relative_fitness >= 0.0) || !(p->relative_rmse >= 0.0) || p->max_iteration < 0 ||
+        !isfinite(p->voxel_size) || !isfinite(p->max_correspondence_distance))
+        return NSC_EINVAL;
+    if (p->covariance_knn < 1 || p->covariance_knn > NSC_GICP_MAX_KNN) return NSC_EUNSUPPORTED;
+    return NSC_OK;
+}
+
+// a set is usable: its arrays are there, its counts fit its capacities and it was prepared with p's down-sampling
+// and covariance parameters
+bool set_ok(const NscGicpCloudSet *s, const NscGicpParams *p)
+{
+    if (!s->row_offsets || !s->slot_offsets || !s->bounds || !s->points || !s->covariances || !s->slots) return false;
+    if (s->n_clouds < 0 || s->n_rows < 0 || s->n_slots < 0 || s->n_clouds > s->cap_clouds ||
+        s->n_rows > s->cap_rows || s->n_slots > s->cap_slots)
+        return false;
+    return s->voxel_size == p->voxel_size && s->covariance_knn == p->covariance_knn && s->epsilon == p->epsilon;
+}
+
+StoreView store_view(const NscGicpCloudSet *s)
+{
+    return StoreView{reinterpret_cast<long long *>(s->row_offsets), reinterpret_cast<long long *>(s->slot_offsets),
+                     s->bounds, s->points, s->covariances, reinterpret_cast<IndexSlot *>(s->slots),
+                     (long long)s->n_clouds};
+}
+
 inline int launch_status() { return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH; }
 
 }  // namespace
@@ -636,11 +865,7 @@ int nsc_gicp_register(const float *source_points, const int64_t *source_offsets,
 {
     if (n_pairs < 0 || total_source_points < 0 || total_target_points < 0 || !p) return NSC_EINVAL;
     if (stride_floats != 3 && stride_floats != 4) return NSC_EINVAL;
-    if (!(p->voxel_size > 0.0) || !(p->max_correspondence_distance > 0.0) || !(p->epsilon > 0.0) ||
-        !(p->relative_fitness >= 0.0) || !(p->relative_rmse >= 0.0) || p->max_iteration < 0 ||
-        !isfinite(p->voxel_size) || !isfinite(p->max_correspondence_distance))
-        return NSC_EINVAL;
-    if (p->covariance_knn < 1 || p->covariance_knn > NSC_GICP_MAX_KNN) return NSC_EUNSUPPORTED;
+    if (const int st = check_params(p)) return st;
     if (n_pairs == 0) return NSC_OK;
     if (!source_offsets || !target_offsets || !init_transforms || !transforms || !fitness_rmse || !corr_iterations ||
         !information)
@@ -674,12 +899,101 @@ int nsc_gicp_register(const float *source_points, const int64_t *source_offsets,
                        p->voxel_size, points, count);
     hipLaunchKernelGGL(covariance_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, bound, count, points, cov,
                        p->voxel_size, p->covariance_knn, p->epsilon);
+    const BatchPairs pairs{cl, slots, bound, points, cov, count};
     for (int r = 0; r <= p->max_iteration; ++r) {
-        hipLaunchKernelGGL(linearize_kernel, per_pair, dim3(GEO_THREADS), 0, s, cl, slots, bound, count, points, cov,
-                           transforms, state, slab, p->voxel_size, p->max_correspondence_distance);
+        hipLaunchKernelGGL(linearize_kernel<BatchPairs>, per_pair, dim3(GEO_THREADS), 0, s, pairs, transforms, state,
+                           slab, p->voxel_size, p->max_correspondence_distance);
         hipLaunchKernelGGL(finalize_kernel, dim3(n_pairs), dim3(64), 0, s, count, slab, state, transforms,
                            fitness_rmse, reinterpret_cast<long long *>(corr_iterations), information, system0, n_pairs,
                            p->max_iteration, p->relative_fitness, p->relative_rmse);
+    }
+    return launch_status();
+}
+
+size_t nsc_gicp_prepare_workspace_bytes(int32_t n_clouds, int64_t total_points)
+{
+    if (n_clouds < 0 || total_points < 0) return 0;
+    return prep_layout(n_clouds, total_points).total;
+}
+
+int nsc_gicp_prepare(const float *points, const int64_t *offsets, int32_t n_clouds, int64_t total_points,
+                     int32_t stride_floats, const NscGicpParams *p, const NscGicpCloudSet *set, void *ws,
+                     size_t ws_bytes, void *stream)
+{
+    if (n_clouds < 0 || total_points < 0 || !p || !set) return NSC_EINVAL;
+    if (stride_floats != 3 && stride_floats != 4) return NSC_EINVAL;
+    if (const int st = check_params(p)) return st;
+    if (!set_ok(set, p)) return NSC_EINVAL;
+    if (n_clouds == 0) return NSC_OK;
+    if (!offsets || (total_points > 0 && !points)) return NSC_EINVAL;
+    // room for the batch's upper bound: every input row a voxel of its own
+    if ((int64_t)set->n_clouds + n_clouds > set->cap_clouds || set->n_rows > set->cap_rows - total_points ||
+        set->n_slots > set->cap_slots - 2 * total_points)
+        return NSC_EWORKSPACE;
+    const PrepLayout L = prep_layout(n_clouds, total_points);
+    if (!ws || ws_bytes < L.total) return NSC_EWORKSPACE;
+    char *w = static_cast<char *>(ws);
+    double *partial = reinterpret_cast<double *>(w + L.partial), *bound = reinterpret_cast<double *>(w + L.bound);
+    long long *count = reinterpret_cast<long long *>(w + L.count);
+    Slot *slots = reinterpret_cast<Slot *>(w + L.slots);
+    double *pts = reinterpret_cast<double *>(w + L.points), *cov = reinterpret_cast<double *>(w + L.cov);
+    // every cloud of the batch is a "target" of a batch without pairs: Clouds::rows addresses it at offsets[c], and
+    // ds_prepare has no pair state to reset
+    const long long *off = reinterpret_cast<const long long *>(offsets);
+    const Clouds cl{points, points, off, off, 0, stride_floats, 0};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 per_cloud(GEO_BLOCKS, n_clouds);
+    hipLaunchKernelGGL(ds_prepare_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, partial, nullptr, nullptr,
+                       nullptr);
+    hipLaunchKernelGGL(ds_insert_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, partial, bound, p->voxel_size);
+    hipLaunchKernelGGL(ds_compact_kernel, dim3(n_clouds), dim3(COMPACT_THREADS), 0, s, cl, slots, bound,
+                       p->voxel_size, pts, count);
+    hipLaunchKernelGGL(covariance_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, bound, count, pts, cov,
+                       p->voxel_size, p->covariance_knn, p->epsilon);
+    hipLaunchKernelGGL(store_kernel, dim3(n_clouds), dim3(COMPACT_THREADS), 0, s, cl, slots, bound, count, pts, cov,
+                       store_view(set), (long long)set->n_clouds, (long long)set->n_rows, (long long)set->n_slots);
+    return launch_status();
+}
+
+size_t nsc_gicp_register_prepared_workspace_bytes(int32_t n_pairs)
+{
+    if (n_pairs < 0) return 0;
+    return prepared_layout(n_pairs).total;
+}
+
+int nsc_gicp_register_prepared(const NscGicpCloudSet *sources, const NscGicpCloudSet *targets,
+                               const int64_t *source_ids, const int64_t *target_ids, int32_t n_pairs,
+                               const NscGicpParams *p, const double *init_transforms, double *transforms,
+                               double *fitness_rmse, int64_t *corr_iterations, double *information, double *system0,
+                               void *ws, size_t ws_bytes, void *stream)
+{
+    if (n_pairs < 0 || !p || !sources || !targets) return NSC_EINVAL;
+    if (const int st = check_params(p)) return st;
+    if (!set_ok(sources, p) || !set_ok(targets, p)) return NSC_EINVAL;
+    if (n_pairs == 0) return NSC_OK;
+    if (!source_ids || !target_ids || !init_transforms || !transforms || !fitness_rmse || !corr_iterations ||
+        !information)
+        return NSC_EINVAL;
+    const PreparedLayout L = prepared_layout(n_pairs);
+    if (!ws || ws_bytes < L.total) return NSC_EWORKSPACE;
+    char *w = static_cast<char *>(ws);
+    long long *count = reinterpret_cast<long long *>(w + L.count);
+    PairRows *rows = reinterpret_cast<PairRows *>(w + L.rows);
+    double *slab = reinterpret_cast<double *>(w + L.slab);
+    PairState *state = reinterpret_cast<PairState *>(w + L.state);
+    long long *ci = reinterpret_cast<long long *>(corr_iterations);
+    const StoredPairs pairs{store_view(sources), store_view(targets), rows, count, n_pairs};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(prepared_setup_kernel, dim3((n_pairs + GEO_THREADS - 1) / GEO_THREADS), dim3(GEO_THREADS), 0, s,
+                       pairs.src, pairs.tgt, reinterpret_cast<const long long *>(source_ids),
+                       reinterpret_cast<const long long *>(target_ids), n_pairs, init_transforms, transforms, state,
+                       count, rows, fitness_rmse, ci, information, system0);
+    for (int r = 0; r <= p->max_iteration; ++r) {
+        hipLaunchKernelGGL(linearize_kernel<StoredPairs>, dim3(GEO_BLOCKS, n_pairs), dim3(GEO_THREADS), 0, s, pairs,
+                           transforms, state, slab, p->voxel_size, p->max_correspondence_distance);
+        hipLaunchKernelGGL(finalize_kernel, dim3(n_pairs), dim3(64), 0, s, count, slab, state, transforms,
+                           fitness_rmse, ci, information, system0, n_pairs, p->max_iteration, p->relative_fitness,
+                           p->relative_rmse);
     }
     return launch_status();
 }

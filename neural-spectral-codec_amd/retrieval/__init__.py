@@ -1,12 +1,12 @@
 """Mirror of the reference's ``retrieval`` package: stage-1 (Wasserstein) retrieval and stage-2 (GICP) verification."""
-from .geometric_verification import GeometricVerifier, register_batch
+from .geometric_verification import GeometricVerifier, PreparedClouds, register_batch, register_prepared
 from .two_stage_retrieval import (LoopClosureCandidate, ShardedTwoStageRetrieval, TwoStageRetrieval,
                                   batch_loop_closing, create_two_stage_retrieval)
 from .wasserstein import (WassersteinRetriever, wasserstein_distance_1d_numpy, wasserstein_distance_1d_torch,
                           wasserstein_distance_batch_numpy, wasserstein_distance_batch_torch,
                           wasserstein_distance_matrix_numpy, wasserstein_distance_matrix_torch)
 
-__all__ = ["GeometricVerifier", "register_batch", "LoopClosureCandidate", "ShardedTwoStageRetrieval", "TwoStageRetrieval", "batch_loop_closing",
+__all__ = ["GeometricVerifier", "PreparedClouds", "register_batch", "register_prepared", "LoopClosureCandidate", "ShardedTwoStageRetrieval", "TwoStageRetrieval", "batch_loop_closing",
            "create_two_stage_retrieval", "WassersteinRetriever", "wasserstein_distance_1d_numpy", "wasserstein_distance_1d_torch",
            "wasserstein_distance_batch_numpy", "wasserstein_distance_batch_torch",
            "wasserstein_distance_matrix_numpy", "wasserstein_distance_matrix_torch"]

@@ -114,6 +114,165 @@ def _pack(clouds, device):
     return pts, torch.from_numpy(off).to(device)
 
 
+def _device(device):
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+class PreparedClouds:
+    """A device-resident store of prepared clouds (include/nsc.h NscGicpCloudSet): each cloud's down-sampled points,
+    covariances, min bound and voxel index, computed once by nsc_gicp_prepare when the cloud is added.
+    ``register_prepared`` then registers pairs given as cloud ids, bit for bit as ``register_packed`` on the raw
+    clouds.  The buffers grow by amortised doubling; a cloud takes about 104 bytes per down-sampled row
+    (points 24, covariances 48, index 32) plus 48 bytes.  Adding needs room for every input row being a voxel
+    of its own, so the buffers are sized for the raw rows of the largest batch added."""
+
+    def __init__(self, voxel_size: float = 0.5, covariance_knn: int = 20, epsilon: float = 1e-3, device="cuda"):
+        self.params = dict(voxel_size=float(voxel_size), covariance_knn=int(covariance_knn), epsilon=float(epsilon))
+        _params(**self.params)
+        self.device = _device(device)
+        self._row_host = np.zeros(1, np.int64)          # row offsets of the clouds present (host copy)
+        self._n_slots = 0
+        self._buf = None
+
+    def __len__(self):
+        return len(self._row_host) - 1
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._row_host[-1])
+
+    @property
+    def nbytes(self) -> int:
+        """device bytes the store holds (its capacity)"""
+        return 0 if self._buf is None else sum(t.numel() * t.element_size() for t in self._buf.values())
+
+    def clear(self):
+        """Forget every cloud; the buffers are kept for the next adds."""
+        self._row_host = np.zeros(1, np.int64)
+        self._n_slots = 0
+
+    def _reserve(self, clouds, rows, slots):
+        b = self._buf
+        caps = (0, 0, 0) if b is None else (b["bounds"].shape[0], b["points"].shape[0], b["slots"].shape[0])
+        if b is not None and clouds <= caps[0] and rows <= caps[1] and slots <= caps[2]:
+            return
+        nc, nr, ns = (max(need, 2 * cap, least) for need, cap, least in
+                      zip((clouds, rows, slots), caps, (64, 1 << 16, 1 << 17)))
+        i64 = dict(dtype=torch.int64, device=self.device)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        nb = dict(row_offsets=torch.zeros(nc + 1, **i64), slot_offsets=torch.zeros(nc + 1, **i64),
+                  bounds=torch.zeros((nc, 4), **f64), points=torch.empty((nr, 3), **f64),
+                  covariances=torch.empty((nr, 6), **f64), slots=torch.zeros((ns, 2), **i64))
+        if b is not None:
+            n, r, s = len(self), self.n_rows, self._n_slots
+            for k, m in (("row_offsets", n + 1), ("slot_offsets", n + 1), ("bounds", n), ("points", r),
+                         ("covariances", r), ("slots", s)):
+                nb[k][:m].copy_(b[k][:m])
+        self._buf = nb
+
+    def _set(self):
+        """the NscGicpCloudSet of the store as it stands"""
+        if self._buf is None:
+            self._reserve(0, 0, 0)
+        b = self._buf
+        return _lib.GicpCloudSet(voxel_size=self.params["voxel_size"], epsilon=self.params["epsilon"],
+                                 covariance_knn=self.params["covariance_knn"], n_clouds=len(self),
+                                 n_rows=self.n_rows, n_slots=self._n_slots, cap_clouds=b["bounds"].shape[0],
+                                 cap_rows=b["points"].shape[0], cap_slots=b["slots"].shape[0],
+                                 **{k: v.data_ptr() for k, v in b.items()})
+
+    def add_packed(self, points, offsets) -> List[int]:
+        """Prepare packed clouds -- ``points`` (N, 3|4) float32 device tensor, ``offsets`` (B+1,) int64 device tensor
+        -- in one nsc_gicp_prepare call; one sync to learn the new row and slot totals.  Returns the new ids."""
+        _lib.require_cuda(points, "points")
+        _lib.require_cuda(offsets, "offsets")
+        if points.dtype != torch.float32 or points.ndim != 2 or int(points.shape[1]) not in (3, 4):
+            raise _lib.NscError("points must be an (N,3) or (N,4) float32 tensor")
+        pts, off = points.contiguous(), offsets.contiguous().to(torch.int64)
+        B, N, n = int(off.numel()) - 1, int(pts.shape[0]), len(self)
+        if B <= 0:
+            return []
+        self._reserve(n + B, self.n_rows + N, self._n_slots + 2 * N)
+        st = self._set()
+        p = _params(**self.params)
+        L = _lib.lib()
+        nbytes = L.nsc_gicp_prepare_workspace_bytes(B, N)
+        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            status = L.nsc_gicp_prepare(_lib.ptr(pts), _lib.ptr(off), B, N, int(pts.shape[1]), C.byref(p),
+                                        C.byref(st), _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(self.device))
+        _lib.check(status, "nsc_gicp_prepare")
+        b = self._buf
+        new = torch.cat([b["row_offsets"][n + 1:n + B + 1], b["slot_offsets"][n + B:n + B + 1]]).cpu().numpy()
+        self._row_host = np.concatenate([self._row_host, new[:B]])
+        self._n_slots = int(new[B])
+        return list(range(n, n + B))
+
+    def add(self, clouds: Sequence) -> List[int]:
+        """Prepare a list of (N,3|4) host arrays or device tensors in one nsc_gicp_prepare call -> their ids."""
+        pts, off = _pack(list(clouds), self.device)
+        return self.add_packed(pts, off)
+
+    def cloud(self, i: int):
+        """-> {points (m,3), covariances (m,6)}: float64 device views of stored cloud i"""
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        r0, r1 = int(self._row_host[i]), int(self._row_host[i + 1])
+        return dict(points=self._buf["points"][r0:r1], covariances=self._buf["covariances"][r0:r1])
+
+
+def _ids(ids, device):
+    t = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids, np.int64).reshape(-1))
+    return t.to(device=device, dtype=torch.int64).contiguous().reshape(-1)
+
+
+def register_prepared(sources: PreparedClouds, source_ids, targets: PreparedClouds, target_ids, init_transforms=None,
+                      stages=False, **params):
+    """Register cloud ``source_ids[i]`` of store ``sources`` onto cloud ``target_ids[i]`` of ``targets`` (ids: device
+    int64 tensors or host sequences; the stores may be one).  Returns register_packed's dict of device tensors, bit
+    for bit what register_packed gives on the raw clouds; with ``stages=True`` also system0 (P,29).  Nothing is
+    synchronised, so a call with device ids and ``init_transforms`` can be captured.  The down-sampling and
+    covariance parameters are the stores'; the others default as in register_packed.  A pair whose id is outside
+    its store gets NaN transform, fitness, rmse and information, n_correspondences -1 and iterations 0."""
+    dev = sources.device
+    if targets.device != dev:
+        raise _lib.NscError("register_prepared: the source and target stores are on different devices")
+    p = _params(**{**sources.params, **params})
+    sid, tid = _ids(source_ids, dev), _ids(target_ids, dev)
+    P = int(sid.numel())
+    if int(tid.numel()) != P:
+        raise _lib.NscError("register_prepared needs as many target ids as source ids")
+    if init_transforms is None:
+        init = torch.eye(4, dtype=torch.float64, device=dev).repeat(P, 1, 1)
+    else:
+        init = init_transforms if isinstance(init_transforms, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(np.asarray(init_transforms, np.float64)))
+        init = init.to(device=dev, dtype=torch.float64).reshape(P, 4, 4).contiguous()
+    L = _lib.lib()
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = dict(transform=torch.empty((P, 4, 4), **f64), fit_rmse=torch.empty((P, 2), **f64),
+               corr_iters=torch.empty((P, 2), dtype=torch.int64, device=dev),
+               information=torch.empty((P, 6, 6), **f64))
+    if stages:
+        out["system0"] = torch.empty((P, 29), **f64)
+    ss, ts = sources._set(), targets._set()
+    nbytes = L.nsc_gicp_register_prepared_workspace_bytes(P)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        status = L.nsc_gicp_register_prepared(C.byref(ss), C.byref(ts), _lib.ptr(sid), _lib.ptr(tid), P, C.byref(p),
+                                              _lib.ptr(init), _lib.ptr(out["transform"]), _lib.ptr(out["fit_rmse"]),
+                                              _lib.ptr(out["corr_iters"]), _lib.ptr(out["information"]),
+                                              _lib.ptr(out["system0"]) if stages else None, _lib.ptr(ws),
+                                              int(ws.numel()), _lib.stream_ptr(dev))
+    _lib.check(status, "nsc_gicp_register_prepared")
+    fr, ci = out.pop("fit_rmse"), out.pop("corr_iters")
+    out.update(fitness=fr[:, 0], rmse=fr[:, 1], n_correspondences=ci[:, 0], iterations=ci[:, 1])
+    return out
+
+
 def register_batch(sources: Sequence, targets: Sequence, init_transforms=None, device="cuda", **params):
     """Register sources[i] onto targets[i] for every i in one batch.  Clouds are host arrays or device tensors,
     (N,3) or (N,4); ``init_transforms`` (P,4,4) maps source into target coordinates (identity by default).
@@ -188,7 +347,35 @@ class GeometricVerifier:
         else:
             init = torch.from_numpy(np.ascontiguousarray(np.asarray(init_transforms, np.float64).reshape(k, 4, 4)))
             init = init.to(dev)
-        out = register_packed(sp, so, tp, to, init, **self.params)
+        return self._decide(register_packed(sp, so, tp, to, init, **self.params), k)
+
+    def prepare(self, clouds: Sequence = ()) -> PreparedClouds:
+        """A PreparedClouds store with this verifier's down-sampling and covariance parameters, holding ``clouds``."""
+        store = PreparedClouds(voxel_size=self.params["voxel_size"], covariance_knn=self.params["covariance_knn"],
+                               epsilon=self.params["epsilon"], device=self.device)
+        if len(clouds):
+            store.add(clouds)
+        return store
+
+    def verify_prepared(self, query_store: PreparedClouds, query_id: int, store: PreparedClouds, candidate_ids,
+                        init_transforms: Optional[np.ndarray] = None):
+        """verify_batch() of stored cloud ``query_id`` against stored clouds ``candidate_ids``: the same list, bit for
+        bit, without touching raw points."""
+        k = len(candidate_ids)
+        return self.verify_pairs(query_store, [int(query_id)] * k, store, candidate_ids, init_transforms)
+
+    def verify_pairs(self, query_store: PreparedClouds, query_ids, store: PreparedClouds, candidate_ids,
+                     init_transforms: Optional[np.ndarray] = None):
+        """verify() of stored pairs (query_ids[i], candidate_ids[i]) in one register_prepared call and one sync.  The
+        stores must have been prepared with this verifier's parameters (else NscError)."""
+        k = len(candidate_ids)
+        if k == 0:
+            return []
+        init = None if init_transforms is None else np.asarray(init_transforms, np.float64).reshape(k, 4, 4)
+        return self._decide(register_prepared(query_store, query_ids, store, candidate_ids, init, **self.params), k)
+
+    def _decide(self, out, k):
+        """register_* outputs of k pairs -> [(verified, transform, info)]"""
         flat = torch.cat([out["transform"].reshape(k, 16), out["fitness"][:, None], out["rmse"][:, None],
                           out["n_correspondences"][:, None].double(), out["iterations"][:, None].double(),
                           out["information"].reshape(k, 36)], 1).cpu().numpy()      # the one sync

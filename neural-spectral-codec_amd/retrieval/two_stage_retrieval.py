@@ -16,6 +16,10 @@ What runs where
     of geometric_verification.py runs it on the device) and, for g2o edges, ``edge_fn=`` (the reference's
     ``compute_pose_graph_edge``).  Without them ``query(verify=True)`` / ``get_loop_closures`` raise.  A verifier
     with ``verify_batch(query_points, candidate_points_list)`` checks all candidates of a query in one call.
+    With ``prepare_geometry=True`` (and a ``GeometricVerifier``) every keyframe's cloud is prepared once, when it is
+    inserted, into a device store (PreparedClouds) whose ids are the database indices; a query prepares its own
+    cloud once and is registered against its candidates by id.  The results are bitwise those of the default
+    mode; the store costs about 100 B of HBM per down-sampled row and moves the cost to insert time.
 
 ``ShardedTwoStageRetrieval`` is the multi-GPU form (BASELINE configs[3]): the database rows
 stay sharded over the ranks in the layout of ``distributed.shard_range``; every rank scores its own rows, the
@@ -31,9 +35,11 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib
+from . import geometric_verification as _gv
 from .wasserstein import WassersteinRetriever, _topk
 
 _NO_POSE = np.full(3, np.inf, np.float32)     # a keyframe without a pose is never filtered out (:163)
+_PREPARE_ROWS = 1 << 22                       # raw rows per prepare call: bounds its workspace (~200 B per row)
 
 
 @dataclass
@@ -59,7 +65,8 @@ class TwoStageRetrieval:
 
     def __init__(self, top_k: int = 10, spatial_filter_distance: float = 50.0, context_window: int = 10,
                  fitness_threshold: float = 0.3, rmse_threshold: float = 0.5, verification_method: str = "gicp",
-                 use_torch: bool = True, device: str = 'cuda', verifier=None, edge_fn=None):
+                 use_torch: bool = True, device: str = 'cuda', verifier=None, edge_fn=None,
+                 prepare_geometry: bool = False):
         self.top_k = top_k
         self.spatial_filter_distance = spatial_filter_distance
         self.context_window = context_window
@@ -69,12 +76,28 @@ class TwoStageRetrieval:
         self.verifier = verifier                                                      # :82-86 (Open3D: injected)
         self.edge_fn = edge_fn
         self.keyframes: list = []                                                     # :89
+        self.geometry = None             # prepare_geometry: PreparedClouds of the keyframes, id = database index
+        self._query_geometry = None
+        if prepare_geometry:
+            if not isinstance(verifier, _gv.GeometricVerifier):
+                raise _lib.NscError("prepare_geometry=True needs verifier=GeometricVerifier(...)")
+            self.geometry = verifier.prepare()
+            self._query_geometry = verifier.prepare()
+
+    def _check_points(self, keyframes):
+        if self.geometry is not None:
+            for kf in keyframes:
+                if getattr(kf, "points", None) is None:
+                    raise ValueError("Keyframe must have points before adding to a database with prepare_geometry")
 
     # -- database --------------------------------------------------------------------------------
     def add_keyframe(self, keyframe):
         """:91-105"""
         if keyframe.descriptor is None:
             raise ValueError("Keyframe must have descriptor before adding to database")
+        self._check_points([keyframe])
+        if self.geometry is not None:
+            self.geometry.add([keyframe.points])
         self.keyframes.append(keyframe)
         descriptor = np.asarray(keyframe.descriptor, dtype=np.float32).reshape(1, -1)
         self.retriever.add_to_database(descriptor, positions=_position(keyframe.pose).reshape(1, 3))
@@ -88,6 +111,9 @@ class TwoStageRetrieval:
         for kf in keyframes:
             if kf.descriptor is None:
                 raise ValueError("Keyframe must have descriptor before adding to database")
+        self._check_points(keyframes)
+        if self.geometry is not None:
+            prepare_chunked(self.geometry, [kf.points for kf in keyframes])
         self.keyframes.extend(keyframes)
         desc = np.stack([np.asarray(kf.descriptor, dtype=np.float32).reshape(-1) for kf in keyframes])
         self.retriever.add_to_database(desc, positions=np.stack([_position(kf.pose) for kf in keyframes]))
@@ -96,6 +122,8 @@ class TwoStageRetrieval:
         """:292-295"""
         self.keyframes.clear()
         self.retriever.clear_database()
+        if self.geometry is not None:
+            self.geometry.clear()
 
     # -- stage 1 ---------------------------------------------------------------------------------
     def _retrieve(self, descriptors: np.ndarray, poses) -> tuple:
@@ -136,21 +164,17 @@ class TwoStageRetrieval:
             raise _lib.NscError("stage 2 (GICP) is outside the MI355X descriptor path: construct TwoStageRetrieval "
                                 "with verifier=<object with the reference's GeometricVerifier.verify> or call "
                                 "query(..., verify=False)")
-        verified_candidates = []
-        if hasattr(self.verifier, "verify_batch"):
+        if self.geometry is not None:
+            self._query_geometry.clear()
+            self._query_geometry.add([query_points])
+            results = self.verifier.verify_prepared(self._query_geometry, 0, self.geometry,
+                                                    [c.database_idx for c in candidates])
+        elif hasattr(self.verifier, "verify_batch"):
             results = self.verifier.verify_batch(query_points,
                                                  [self.keyframes[c.database_idx].points for c in candidates])
         else:
             results = (self.verifier.verify(query_points, self.keyframes[c.database_idx].points) for c in candidates)
-        for candidate, (verified, transform, info) in zip(candidates, results):
-            candidate.verified = verified
-            candidate.transform = transform
-            candidate.fitness = info['fitness']
-            candidate.rmse = info['rmse']
-            candidate.information_matrix = info.get('information_matrix', None)
-            if verified:
-                verified_candidates.append(candidate)
-        return verified_candidates
+        return _apply(candidates, results)
 
     def query(self, query_keyframe, query_points: Optional[np.ndarray] = None, verify: bool = True
               ) -> List[LoopClosureCandidate]:
@@ -172,6 +196,10 @@ class TwoStageRetrieval:
             raise _lib.NscError("get_loop_closures needs edge_fn=<the reference's compute_pose_graph_edge> "
                                 "(geometric_verification.py, outside the MI355X descriptor path)")
         candidates = self.query(query_keyframe, query_points=query_points, verify=True)
+        return self._edges(query_keyframe, candidates)
+
+    def _edges(self, query_keyframe, candidates) -> List[Dict]:
+        """The loop-closure edges of a query's verified candidates (:260-288)."""
         loop_closures = []
         for candidate in candidates:
             if not candidate.verified:
@@ -189,6 +217,35 @@ class TwoStageRetrieval:
         return loop_closures
 
 
+def _apply(candidates, results):
+    """Write the stage-2 results onto the candidates; -> the verified ones (:204-242)."""
+    verified_candidates = []
+    for candidate, (verified, transform, info) in zip(candidates, results):
+        candidate.verified = verified
+        candidate.transform = transform
+        candidate.fitness = info['fitness']
+        candidate.rmse = info['rmse']
+        candidate.information_matrix = info.get('information_matrix', None)
+        if verified:
+            verified_candidates.append(candidate)
+    return verified_candidates
+
+
+def prepare_chunked(store, clouds, max_rows: int = _PREPARE_ROWS):
+    """store.add(clouds) in calls of at most ``max_rows`` raw rows (one cloud at least) -> ids"""
+    ids, chunk, rows = [], [], 0
+    for c in clouds:
+        n = len(c)
+        if chunk and rows + n > max_rows:
+            ids += store.add(chunk)
+            chunk, rows = [], 0
+        chunk.append(c)
+        rows += n
+    if chunk:
+        ids += store.add(chunk)
+    return ids
+
+
 def create_two_stage_retrieval(top_k: int = 10, spatial_filter_distance: float = 50.0, use_gpu: bool = True,
                                **kwargs) -> TwoStageRetrieval:
     """:298-320 (``use_gpu`` is accepted for signature compatibility: stage 1 always runs on the HIP device)."""
@@ -197,15 +254,38 @@ def create_two_stage_retrieval(top_k: int = 10, spatial_filter_distance: float =
 
 
 def batch_loop_closing(query_keyframes, database_keyframes, top_k: int = 10, spatial_filter_distance: float = 50.0,
-                       verify: bool = True, verifier=None, edge_fn=None) -> Dict[int, list]:
+                       verify: bool = True, verifier=None, edge_fn=None, prepare_geometry: bool = False
+                       ) -> Dict[int, list]:
     """:322-359.  With ``verify=False`` the values are the stage-1 candidate lists (one database pass for all
-    queries); with ``verify=True`` the injected stage 2 runs per query as in the reference."""
+    queries); with ``verify=True`` the injected stage 2 runs per query as in the reference.  With
+    ``prepare_geometry=True`` (a GeometricVerifier) every database and query cloud is prepared once, stage 1 runs
+    for all queries in one pass and stage 2 registers all queries' candidate pairs in one register_prepared call;
+    the result equals the per-query one."""
     retrieval = create_two_stage_retrieval(top_k=top_k, spatial_filter_distance=spatial_filter_distance,
-                                           verifier=verifier, edge_fn=edge_fn)
+                                           verifier=verifier, edge_fn=edge_fn, prepare_geometry=prepare_geometry)
     retrieval.add_keyframes(database_keyframes)
     if not verify:
         return dict(enumerate(retrieval.global_retrieval_batch(query_keyframes)))
-    return {i: retrieval.get_loop_closures(kf) for i, kf in enumerate(query_keyframes)}
+    if not prepare_geometry:
+        return {i: retrieval.get_loop_closures(kf) for i, kf in enumerate(query_keyframes)}
+    query_keyframes = list(query_keyframes)
+    if retrieval.edge_fn is None and query_keyframes:
+        retrieval.get_loop_closures(query_keyframes[0])          # raises, as the per-query path does
+    for kf in query_keyframes:
+        if kf.descriptor is None:
+            raise ValueError("Query keyframe must have descriptor")
+    retrieval._check_points(query_keyframes)
+    candidates = retrieval.global_retrieval_batch(query_keyframes)
+    queries = verifier.prepare()
+    prepare_chunked(queries, [kf.points for kf in query_keyframes])
+    qids = [i for i, cl in enumerate(candidates) for _ in cl]
+    results = verifier.verify_pairs(queries, qids, retrieval.geometry,
+                                    [c.database_idx for cl in candidates for c in cl])
+    out, at = {}, 0
+    for i, (kf, cl) in enumerate(zip(query_keyframes, candidates)):
+        out[i] = retrieval._edges(kf, _apply(cl, results[at:at + len(cl)]))
+        at += len(cl)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
