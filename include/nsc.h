@@ -420,6 +420,12 @@ int nsc_voxel_overlap(const float *points1, const int64_t *offsets1, const float
  * Centroids are exact sums in int64 units of 2^-24 m: |coordinate| x rows per voxel must stay below 2^39 m.
  * ------------------------------------------------------------------------------------------ */
 #define NSC_GICP_MAX_KNN 32
+/* Largest batch of one call (the launches index clouds or pairs by gridDim.y <= 65 535): a larger count returns
+ * NSC_EUNSUPPORTED before anything is launched and the caller splits the batch -- pairs and clouds are independent
+ * of the rest of their batch, so splitting changes no result.  The *_workspace_bytes queries accept any count. */
+#define NSC_GICP_MAX_PAIRS          32767   /* nsc_gicp_register: 2 clouds per pair                  */
+#define NSC_GICP_MAX_CLOUDS         65535   /* nsc_gicp_prepare                                       */
+#define NSC_GICP_MAX_PREPARED_PAIRS 65535   /* nsc_gicp_register_prepared                             */
 
 typedef struct NscGicpParams {
     double  voxel_size;                   /* 0.5   voxel_down_sample edge, > 0                        */

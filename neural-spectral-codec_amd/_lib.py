@@ -94,6 +94,8 @@ class GicpCloudSet(C.Structure):
 
 
 GICP_MAX_KNN = 32
+# include/nsc.h NSC_GICP_MAX_PAIRS, NSC_GICP_MAX_CLOUDS, NSC_GICP_MAX_PREPARED_PAIRS: the largest batch of one call
+GICP_MAX_PAIRS, GICP_MAX_CLOUDS, GICP_MAX_PREPARED_PAIRS = 32767, 65535, 65535
 
 
 class GatGradLayer(C.Structure):

@@ -41,6 +41,14 @@ namespace {
 
 constexpr int GEO_BLOCKS = 64;          // blocks per cloud (down-sampling, covariances) and per pair (linearize)
 constexpr int GEO_THREADS = 256;
+// gridDim.y is at most 65 535.  The per-cloud launches put the cloud in y (2 clouds per pair in nsc_gicp_register),
+// the per-pair launches the pair; a larger count is NSC_EUNSUPPORTED before anything is launched, callers chunk.
+constexpr int GRID_Y_MAX = 65535;
+constexpr int MAX_PAIRS = NSC_GICP_MAX_PAIRS;                       // nsc_gicp_register
+constexpr int MAX_CLOUDS = NSC_GICP_MAX_CLOUDS;                     // nsc_gicp_prepare
+constexpr int MAX_PREPARED_PAIRS = NSC_GICP_MAX_PREPARED_PAIRS;     // nsc_gicp_register_prepared
+static_assert(2 * MAX_PAIRS <= GRID_Y_MAX && MAX_CLOUDS <= GRID_Y_MAX && MAX_PREPARED_PAIRS <= GRID_Y_MAX,
+              "the batch limits of include/nsc.h must fit gridDim.y");
 constexpr int COMPACT_THREADS = 1024;
 constexpr int KEY_BITS = 21;            // voxel key per axis: 0 .. 2^21-1 voxels from the cloud's min bound
 constexpr long long KEY_MAX = (1LL << KEY_BITS) - 1;
@@ -866,6 +874,7 @@ int nsc_gicp_register(const float *source_points, const int64_t *source_offsets,
     if (n_pairs < 0 || total_source_points < 0 || total_target_points < 0 || !p) return NSC_EINVAL;
     if (stride_floats != 3 && stride_floats != 4) return NSC_EINVAL;
     if (const int st = check_params(p)) return st;
+    if (n_pairs > MAX_PAIRS) return NSC_EUNSUPPORTED;
     if (n_pairs == 0) return NSC_OK;
     if (!source_offsets || !target_offsets || !init_transforms || !transforms || !fitness_rmse || !corr_iterations ||
         !information)
@@ -924,6 +933,7 @@ int nsc_gicp_prepare(const float *points, const int64_t *offsets, int32_t n_clou
     if (stride_floats != 3 && stride_floats != 4) return NSC_EINVAL;
     if (const int st = check_params(p)) return st;
     if (!set_ok(set, p)) return NSC_EINVAL;
+    if (n_clouds > MAX_CLOUDS) return NSC_EUNSUPPORTED;
     if (n_clouds == 0) return NSC_OK;
     if (!offsets || (total_points > 0 && !points)) return NSC_EINVAL;
     // room for the batch's upper bound: every input row a voxel of its own
@@ -970,6 +980,7 @@ int nsc_gicp_register_prepared(const NscGicpCloudSet *sources, const NscGicpClou
     if (n_pairs < 0 || !p || !sources || !targets) return NSC_EINVAL;
     if (const int st = check_params(p)) return st;
     if (!set_ok(sources, p) || !set_ok(targets, p)) return NSC_EINVAL;
+    if (n_pairs > MAX_PREPARED_PAIRS) return NSC_EUNSUPPORTED;
     if (n_pairs == 0) return NSC_OK;
     if (!source_ids || !target_ids || !init_transforms || !transforms || !fitness_rmse || !corr_iterations ||
         !information)

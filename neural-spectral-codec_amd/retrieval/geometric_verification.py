@@ -14,7 +14,8 @@ used and rows with a non-finite coordinate are dropped.
    2^-24 m, so they do not depend on summation order.
 2. Covariances (source and target): the ``covariance_knn`` nearest down-sampled neighbours of each down-sampled
    point, the point itself included, ties to the smaller index; ``C = (1/n) sum (p - mean)(p - mean)^T``, the
-   identity if n < 3; then ``C <- U diag(1, 1, epsilon) U^T`` with U the eigenvectors by descending eigenvalue.
+   identity if n < 3; then ``C <- U diag(1, 1, epsilon) U^T`` with U the eigenvectors by descending eigenvalue
+   (of the identity the axes in order, so the normal is the x axis and the result diag(epsilon, 1, 1)).
 3. Evaluation of T (float64): each transformed source point takes the nearest target point at distance
    ``<= max_correspondence_distance`` (ties to the smaller target index); ``fitness = n_corr / n_source``
    (down-sampled), ``rmse = sqrt(sum |d|^2 / n_corr)``, 0 without correspondences.
@@ -29,6 +30,15 @@ used and rows with a non-finite coordinate are dropped.
    ``sum G^T G`` with ``G = [-[t]x | I]`` over the correspondences (t the target point), rotation first.
 7. Decision: ``verified = n_corr > 0 and fitness >= fitness_threshold and rmse <= rmse_threshold``.
 
+Supported range (include/nsc.h): voxel keys are 21 bits per axis counted from the cloud's min bound and the centroid
+sums are int64 in units of 2^-24 m, so a cloud must satisfy ``(max - min) / voxel_size < 2^21`` on every axis over
+its finite rows and ``|coordinate| * rows-per-voxel < 2^39`` m.  Outside that range the result is unspecified (voxel
+coordinates clamp to 2^21 - 1, so distant rows merge into one voxel; nothing is read or written out of bounds):
+one finite stray row at, say, -1e7 m moves the min bound so far that at voxel 0.5 every other row clamps into one
+voxel.  Callers drop such rows, or mark them non-finite, before registering.  One call takes at most
+MAX_PAIRS_PER_CALL raw pairs, MAX_CLOUDS_PER_CALL clouds to prepare or MAX_PREPARED_PAIRS_PER_CALL stored pairs;
+the functions below split larger requests.
+
 GICP is a local method: from the identity it converges for offsets of about the correspondence radius (1 m) or
 about 10 degrees of yaw alone; pass ``init_transforms`` (odometry) for larger offsets.
 """
@@ -39,6 +49,20 @@ import numpy as np
 import torch
 
 from .. import _lib
+
+# Largest batch handed to one library call (include/nsc.h NSC_GICP_MAX_*: the launches index clouds and pairs by
+# gridDim.y).  register_packed, register_prepared and PreparedClouds.add_packed split a larger request into several
+# calls; a pair or cloud is independent of the rest of its batch, so the results are bit for bit the same.  Module
+# constants, so a test can lower them.
+MAX_PAIRS_PER_CALL = _lib.GICP_MAX_PAIRS
+MAX_CLOUDS_PER_CALL = _lib.GICP_MAX_CLOUDS
+MAX_PREPARED_PAIRS_PER_CALL = _lib.GICP_MAX_PREPARED_PAIRS
+
+
+def _cat_outputs(parts):
+    """dicts of per-pair / per-row tensors of consecutive chunks -> one dict"""
+    return {k: torch.cat([q[k] for q in parts], 0) for k in parts[0]}
+
 
 def _params(voxel_size=0.5, max_correspondence_distance=1.0, max_iteration=30, relative_fitness=1e-6,
             relative_rmse=1e-6, covariance_knn=20, epsilon=1e-3):
@@ -54,7 +78,10 @@ def register_packed(source_points, source_offsets, target_points, target_offsets
     can be captured.  ``*_points`` (N, 3|4) float32 device tensors of one stride, ``*_offsets`` (P+1,) int64 device
     tensors, ``init_transforms`` (P,4,4) float64 device tensor.  Returns a dict of device tensors: transform (P,4,4),
     fitness, rmse (P,), n_correspondences, iterations (P,) int64, information (P,6,6); with ``stages=True`` also
-    points (Ns+Nt,3), counts (2P,), covariances (Ns+Nt,6) and system0 (P,29) (include/nsc.h NscGicpStages)."""
+    points (Ns+Nt,3), counts (2P,), covariances (Ns+Nt,6) and system0 (P,29) (include/nsc.h NscGicpStages).
+    More than MAX_PAIRS_PER_CALL pairs go to the library in several calls (the offsets are then read on the host, so
+    such a call cannot be captured, and they must start at 0 and end at the last row); the outputs are those of
+    one call, bit for bit."""
     dev = source_points.device
     for t, name in ((source_points, "source_points"), (target_points, "target_points"),
                     (source_offsets, "source_offsets"), (target_offsets, "target_offsets"),
@@ -67,6 +94,9 @@ def register_packed(source_points, source_offsets, target_points, target_offsets
     P = int(source_offsets.numel()) - 1
     if int(target_offsets.numel()) - 1 != P or tuple(init_transforms.shape) != (P, 4, 4):
         raise _lib.NscError("offsets and init_transforms must describe the same number of pairs")
+    if P > MAX_PAIRS_PER_CALL:
+        return _register_packed_chunked(source_points, source_offsets, target_points, target_offsets,
+                                        init_transforms, stages, params)
     src, tgt = source_points.contiguous(), target_points.contiguous()
     so, to = source_offsets.contiguous().to(torch.int64), target_offsets.contiguous().to(torch.int64)
     init = init_transforms.contiguous().to(torch.float64)
@@ -93,6 +123,32 @@ def register_packed(source_points, source_offsets, target_points, target_offsets
     _lib.check(status, "nsc_gicp_register")
     fr, ci = out.pop("fit_rmse"), out.pop("corr_iters")
     out.update(fitness=fr[:, 0], rmse=fr[:, 1], n_correspondences=ci[:, 0], iterations=ci[:, 1])
+    return out
+
+
+def _register_packed_chunked(source_points, source_offsets, target_points, target_offsets, init_transforms, stages,
+                             params):
+    """register_packed of more than MAX_PAIRS_PER_CALL pairs: consecutive chunks of pairs, each on the rows its
+    offsets name (one read of the offsets to the host), outputs concatenated in the order of the unsplit call."""
+    so, to = source_offsets.cpu().tolist(), target_offsets.cpu().tolist()
+    P = len(so) - 1
+    parts = []
+    for a in range(0, P, MAX_PAIRS_PER_CALL):
+        b = min(a + MAX_PAIRS_PER_CALL, P)
+        parts.append(register_packed(source_points[so[a]:so[b]], source_offsets[a:b + 1] - so[a],
+                                     target_points[to[a]:to[b]], target_offsets[a:b + 1] - to[a],
+                                     init_transforms[a:b], stages=stages, **params))
+    if not stages:
+        return _cat_outputs(parts)
+    # stage rows: every chunk's source rows, then every chunk's target rows; counts likewise
+    rows = [(so[min(a + MAX_PAIRS_PER_CALL, P)] - so[a], min(a + MAX_PAIRS_PER_CALL, P) - a)
+            for a in range(0, P, MAX_PAIRS_PER_CALL)]
+    out = _cat_outputs([{k: v for k, v in q.items() if k not in ("points", "covariances", "counts")} for q in parts])
+    for k in ("points", "covariances"):
+        out[k] = torch.cat([q[k][:ns] for q, (ns, _) in zip(parts, rows)] +
+                           [q[k][ns:] for q, (ns, _) in zip(parts, rows)], 0)
+    out["counts"] = torch.cat([q["counts"][:n] for q, (_, n) in zip(parts, rows)] +
+                              [q["counts"][n:] for q, (_, n) in zip(parts, rows)], 0)
     return out
 
 
@@ -195,6 +251,12 @@ class PreparedClouds:
         B, N, n = int(off.numel()) - 1, int(pts.shape[0]), len(self)
         if B <= 0:
             return []
+        if B > MAX_CLOUDS_PER_CALL:                      # several calls; one read of the offsets to the host
+            host, ids = off.cpu().tolist(), []
+            for a in range(0, B, MAX_CLOUDS_PER_CALL):
+                b = min(a + MAX_CLOUDS_PER_CALL, B)
+                ids += self.add_packed(pts[host[a]:host[b]], off[a:b + 1] - host[a])
+            return ids
         self._reserve(n + B, self.n_rows + N, self._n_slots + 2 * N)
         st = self._set()
         p = _params(**self.params)
@@ -236,7 +298,8 @@ def register_prepared(sources: PreparedClouds, source_ids, targets: PreparedClou
     for bit what register_packed gives on the raw clouds; with ``stages=True`` also system0 (P,29).  Nothing is
     synchronised, so a call with device ids and ``init_transforms`` can be captured.  The down-sampling and
     covariance parameters are the stores'; the others default as in register_packed.  A pair whose id is outside
-    its store gets NaN transform, fitness, rmse and information, n_correspondences -1 and iterations 0."""
+    its store gets NaN transform, fitness, rmse and information, n_correspondences -1 and iterations 0.  More than
+    MAX_PREPARED_PAIRS_PER_CALL pairs go to the library in several calls, with the same results."""
     dev = sources.device
     if targets.device != dev:
         raise _lib.NscError("register_prepared: the source and target stores are on different devices")
@@ -251,6 +314,10 @@ def register_prepared(sources: PreparedClouds, source_ids, targets: PreparedClou
         init = init_transforms if isinstance(init_transforms, torch.Tensor) else \
             torch.from_numpy(np.ascontiguousarray(np.asarray(init_transforms, np.float64)))
         init = init.to(device=dev, dtype=torch.float64).reshape(P, 4, 4).contiguous()
+    if P > MAX_PREPARED_PAIRS_PER_CALL:
+        step = MAX_PREPARED_PAIRS_PER_CALL
+        return _cat_outputs([register_prepared(sources, sid[a:a + step], targets, tid[a:a + step], init[a:a + step],
+                                               stages=stages, **params) for a in range(0, P, step)])
     L = _lib.lib()
     f64 = dict(dtype=torch.float64, device=dev)
     out = dict(transform=torch.empty((P, 4, 4), **f64), fit_rmse=torch.empty((P, 2), **f64),

@@ -95,3 +95,52 @@ def test_gicp_abi_validates_on_host(lib):
     assert call(nbytes=need - 1) == EWS
     assert call(ws=None) == EWS
     assert call(P=0) == 0                        # nothing to do, nothing launched
+
+
+def test_gicp_batch_limits_on_host(lib):
+    """A pair or cloud count over what the launches can index (include/nsc.h NSC_GICP_MAX_*) is NSC_EUNSUPPORTED; a
+    count at the limit is not (the workspace, declared one byte short, is what stops that call).  Either way the
+    call returns before its first launch, so the fake pointers are never read."""
+    import os
+    import re
+    from neural_spectral_codec_amd import _lib
+    EUNSUP, EWS = -2, -3
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "nsc.h")).read()
+    limits = {k: int(v) for k, v in re.findall(r"#define (NSC_GICP_MAX_[A-Z_]+)\s+(\d+)", hdr)}
+    assert (limits["NSC_GICP_MAX_PAIRS"], limits["NSC_GICP_MAX_CLOUDS"], limits["NSC_GICP_MAX_PREPARED_PAIRS"]) == \
+        (_lib.GICP_MAX_PAIRS, _lib.GICP_MAX_CLOUDS, _lib.GICP_MAX_PREPARED_PAIRS)
+    assert 2 * _lib.GICP_MAX_PAIRS <= 65535 and _lib.GICP_MAX_CLOUDS <= 65535 and \
+        _lib.GICP_MAX_PREPARED_PAIRS <= 65535                    # gridDim.y
+    p = _lib.GicpParams()
+    lib.nsc_gicp_default_params(p)
+    fake = C.c_void_p(4096)
+    rows = 1 << 20
+
+    def register(P):
+        need = lib.nsc_gicp_workspace_bytes(P, rows, rows)
+        assert need > 0                                          # the size query works for any count
+        return lib.nsc_gicp_register(fake, fake, fake, fake, P, rows, rows, 4, C.byref(p), fake, fake, fake, fake,
+                                     fake, None, fake, need - 1, None)
+    assert register(_lib.GICP_MAX_PAIRS + 1) == EUNSUP and register(2 ** 31 - 1) == EUNSUP
+    assert register(_lib.GICP_MAX_PAIRS) == EWS
+
+    big = 1 << 40
+    store = _lib.GicpCloudSet(voxel_size=p.voxel_size, epsilon=p.epsilon, covariance_knn=p.covariance_knn, n_clouds=0,
+                              n_rows=0, n_slots=0, cap_clouds=big, cap_rows=big, cap_slots=big,
+                              **{k: 4096 for k in ("row_offsets", "slot_offsets", "bounds", "points", "covariances",
+                                                   "slots")})
+
+    def prepare(B):
+        need = lib.nsc_gicp_prepare_workspace_bytes(B, rows)
+        assert need > 0
+        return lib.nsc_gicp_prepare(fake, fake, B, rows, 4, C.byref(p), C.byref(store), fake, need - 1, None)
+    assert prepare(_lib.GICP_MAX_CLOUDS + 1) == EUNSUP and prepare(2 ** 31 - 1) == EUNSUP
+    assert prepare(_lib.GICP_MAX_CLOUDS) == EWS
+
+    def register_prepared(P):
+        need = lib.nsc_gicp_register_prepared_workspace_bytes(P)
+        assert need > 0
+        return lib.nsc_gicp_register_prepared(C.byref(store), C.byref(store), fake, fake, P, C.byref(p), fake, fake,
+                                              fake, fake, fake, None, fake, need - 1, None)
+    assert register_prepared(_lib.GICP_MAX_PREPARED_PAIRS + 1) == EUNSUP and register_prepared(2 ** 31 - 1) == EUNSUP
+    assert register_prepared(_lib.GICP_MAX_PREPARED_PAIRS) == EWS

@@ -25,9 +25,9 @@ def dev_pack(clouds, stride=4):
     return (torch.from_numpy(np.concatenate(pts, 0)).cuda(), torch.from_numpy(off).cuda())
 
 
-def run(sources, targets, inits=None, stages=False, **params):
-    sp, so = dev_pack(sources)
-    tp, to = dev_pack(targets)
+def run(sources, targets, inits=None, stages=False, stride=4, **params):
+    sp, so = dev_pack(sources, stride)
+    tp, to = dev_pack(targets, stride)
     P = len(sources)
     init = np.tile(np.eye(4), (P, 1, 1)) if inits is None else np.asarray(inits, np.float64)
     out = _gv().register_packed(sp, so, tp, to, torch.from_numpy(init).cuda(), stages=stages, **params)
