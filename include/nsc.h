@@ -500,6 +500,30 @@ int    nsc_gicp_register_prepared(const NscGicpCloudSet *sources, const NscGicpC
                                   double *fitness_rmse, int64_t *corr_iterations, double *information,
                                   double *system0, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Yaw initial guess for stage 2: the circular column shift that best aligns two interpolated range images
+ * (the encoder's `interpolated` output, (rows, 360) float32, 1 <= rows <= 64, the same rows for both).
+ * In float64: a = Iq - its row means, b = Ic - its row means,
+ *   score[s] = sum_r sum_c a[r,c] * b[r,(c - s) mod 360],  s = 0 .. 359;
+ * shift = the s of the largest score, ties to the smaller s, 0 when that score is not > 0 (flat or empty images);
+ * peak = score[shift]; runner_up = the largest score among shifts more than NSC_YAW_GUARD_BINS bins from shift
+ * (circularly).  The guess is the rotation Rz(-shift degrees, wrapped to (-180, 180]) with zero translation,
+ * mapping query into candidate coordinates: exactly the identity for shift 0.
+ *
+ * Pair i aligns image ids_q[i] of images_q (n_q, rows, 360) with image ids_c[i] of images_c (n_c, rows, 360); the
+ * two arrays may be one.  Out: shift (n_pairs) int32, scores (n_pairs, 2) float64 = [peak, runner_up],
+ * init_transforms (n_pairs, 4, 4) float64 row-major.  A pair with an id outside its array gets shift -1, NaN scores
+ * and the identity; nothing of the images is read for it.  One kernel launch and nothing else, no workspace; a
+ * pair's outputs depend on its two images alone.
+ * A launch holds at most 2^32 - 1 threads, 768 per pair: more than NSC_YAW_MAX_PAIRS pairs return
+ * NSC_EUNSUPPORTED before anything is launched and the caller splits the batch.
+ * ------------------------------------------------------------------------------------------ */
+#define NSC_YAW_GUARD_BINS 10
+#define NSC_YAW_MAX_PAIRS  4194304
+int nsc_yaw_align(const float *images_q, int32_t n_q, const float *images_c, int32_t n_c, const int64_t *ids_q,
+                  const int64_t *ids_c, int32_t n_pairs, int32_t rows, int32_t *shift, double *scores,
+                  double *init_transforms, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

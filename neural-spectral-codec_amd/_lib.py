@@ -96,6 +96,8 @@ class GicpCloudSet(C.Structure):
 GICP_MAX_KNN = 32
 # include/nsc.h NSC_GICP_MAX_PAIRS, NSC_GICP_MAX_CLOUDS, NSC_GICP_MAX_PREPARED_PAIRS: the largest batch of one call
 GICP_MAX_PAIRS, GICP_MAX_CLOUDS, GICP_MAX_PREPARED_PAIRS = 32767, 65535, 65535
+# include/nsc.h NSC_YAW_GUARD_BINS, NSC_YAW_MAX_PAIRS
+YAW_GUARD_BINS, YAW_MAX_PAIRS = 10, 4194304
 
 
 class GatGradLayer(C.Structure):
@@ -177,6 +179,7 @@ SYMBOLS = {
     "nsc_gicp_register_prepared_workspace_bytes": (_sz, [_i32]),
     "nsc_gicp_register_prepared": (C.c_int, [C.POINTER(GicpCloudSet), C.POINTER(GicpCloudSet), _vp, _vp, _i32,
                                              C.POINTER(GicpParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nsc_yaw_align": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

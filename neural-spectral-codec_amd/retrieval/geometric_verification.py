@@ -40,7 +40,11 @@ MAX_PAIRS_PER_CALL raw pairs, MAX_CLOUDS_PER_CALL clouds to prepare or MAX_PREPA
 the functions below split larger requests.
 
 GICP is a local method: from the identity it converges for offsets of about the correspondence radius (1 m) or
-about 10 degrees of yaw alone; pass ``init_transforms`` (odometry) for larger offsets.
+about 10 degrees of yaw alone, and from further away it can end on the ground plane alone with a fitness that passes
+the default thresholds and a transform that is wrong by the whole yaw.  ``TwoStageRetrieval(yaw_init=True)`` covers
+any yaw about the vertical axis: it starts every pair from the rotation ``estimate_yaw`` (yaw_alignment.py) reads
+off the two range images, good to a few degrees.  It does not cover a translation beyond about 1 m, or roll and
+pitch: pass ``init_transforms`` (odometry; host arrays or device tensors) for those.
 """
 import ctypes as C
 from typing import List, Optional, Sequence
@@ -168,6 +172,14 @@ def _pack(clouds, device):
     off[1:] = np.cumsum([int(t.shape[0]) for t in ts])
     pts = torch.cat(ts, 0) if ts else torch.zeros((0, 3), dtype=torch.float32, device=device)
     return pts, torch.from_numpy(off).to(device)
+
+
+def _init_tensor(init_transforms, k, device):
+    """(k,4,4) initial transforms, a host array or a tensor (a device tensor is used in place: no host visit) ->
+    (k,4,4) float64 tensor on ``device``"""
+    t = init_transforms if isinstance(init_transforms, torch.Tensor) else \
+        torch.from_numpy(np.ascontiguousarray(np.asarray(init_transforms, np.float64).reshape(k, 4, 4)))
+    return t.to(device=device, dtype=torch.float64).reshape(k, 4, 4).contiguous()
 
 
 def _device(device):
@@ -397,7 +409,8 @@ class GeometricVerifier:
         return self.verify_batch(query_points, [candidate_points], init)[0]
 
     def verify_batch(self, query_points, candidate_points_list: List, init_transforms: Optional[np.ndarray] = None):
-        """verify() for every candidate of one query in one batch; one host sync when the results come back."""
+        """verify() for every candidate of one query in one batch; one host sync when the results come back.
+        ``init_transforms`` (k,4,4): a host array or a device tensor (here and in verify_prepared / verify_pairs)."""
         k = len(candidate_points_list)
         if k == 0:
             return []
@@ -412,8 +425,7 @@ class GeometricVerifier:
         if init_transforms is None:
             init = torch.eye(4, dtype=torch.float64, device=dev).repeat(k, 1, 1)
         else:
-            init = torch.from_numpy(np.ascontiguousarray(np.asarray(init_transforms, np.float64).reshape(k, 4, 4)))
-            init = init.to(dev)
+            init = _init_tensor(init_transforms, k, dev)
         return self._decide(register_packed(sp, so, tp, to, init, **self.params), k)
 
     def prepare(self, clouds: Sequence = ()) -> PreparedClouds:
@@ -438,7 +450,7 @@ class GeometricVerifier:
         k = len(candidate_ids)
         if k == 0:
             return []
-        init = None if init_transforms is None else np.asarray(init_transforms, np.float64).reshape(k, 4, 4)
+        init = None if init_transforms is None else _init_tensor(init_transforms, k, query_store.device)
         return self._decide(register_prepared(query_store, query_ids, store, candidate_ids, init, **self.params), k)
 
     def _decide(self, out, k):

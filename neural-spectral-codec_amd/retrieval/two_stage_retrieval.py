@@ -20,6 +20,11 @@ What runs where
     inserted, into a device store (PreparedClouds) whose ids are the database indices; a query prepares its own
     cloud once and is registered against its candidates by id.  The results are bitwise those of the default
     mode; the store costs about 100 B of HBM per down-sampled row and moves the cost to insert time.
+    With ``yaw_init=True`` every pair starts from the yaw read off the two keyframes' range images (yaw_alignment.py,
+    nsc_yaw_align) instead of the identity, so a revisit under another heading verifies: every keyframe's
+    interpolated range image (``keyframe.range_image``, else ``yaw_encoder`` on its points) goes into a device store
+    (YawImages, 23 KB per keyframe at 16 rows) when it is inserted, a query's candidates are estimated in one launch
+    and the guesses reach the registration as a device tensor.  Off (the default) nothing of this runs.
 
 ``ShardedTwoStageRetrieval`` is the multi-GPU form (BASELINE configs[3]): the database rows
 stay sharded over the ranks in the layout of ``distributed.shard_range``; every rank scores its own rows, the
@@ -27,6 +32,7 @@ k best (distance, global index) pairs of every rank are exchanged with ONE all-g
 query, and merged -- identical on every rank, and identical to the single-GPU result (ties resolve to the smaller
 global index in both).
 """
+import inspect
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
@@ -36,6 +42,7 @@ import torch.distributed as dist
 
 from .. import _lib
 from . import geometric_verification as _gv
+from . import yaw_alignment as _yaw
 from .wasserstein import WassersteinRetriever, _topk
 
 _NO_POSE = np.full(3, np.inf, np.float32)     # a keyframe without a pose is never filtered out (:163)
@@ -52,6 +59,7 @@ class LoopClosureCandidate:
     fitness: Optional[float] = None
     rmse: Optional[float] = None
     information_matrix: Optional[np.ndarray] = None
+    info: Optional[dict] = None          # the verifier's info dict (with yaw_init: + init_yaw_deg, yaw_peak_ratio)
 
 
 def _position(pose) -> np.ndarray:
@@ -66,7 +74,7 @@ class TwoStageRetrieval:
     def __init__(self, top_k: int = 10, spatial_filter_distance: float = 50.0, context_window: int = 10,
                  fitness_threshold: float = 0.3, rmse_threshold: float = 0.5, verification_method: str = "gicp",
                  use_torch: bool = True, device: str = 'cuda', verifier=None, edge_fn=None,
-                 prepare_geometry: bool = False):
+                 prepare_geometry: bool = False, yaw_init: bool = False, yaw_encoder=None):
         self.top_k = top_k
         self.spatial_filter_distance = spatial_filter_distance
         self.context_window = context_window
@@ -83,6 +91,19 @@ class TwoStageRetrieval:
                 raise _lib.NscError("prepare_geometry=True needs verifier=GeometricVerifier(...)")
             self.geometry = verifier.prepare()
             self._query_geometry = verifier.prepare()
+        self.yaw_images = None           # yaw_init: YawImages of the keyframes, id = database index
+        self.yaw_encoder = None
+        if yaw_init:
+            method = "verify_prepared" if prepare_geometry else "verify_batch"
+            fn = getattr(verifier, method, None)
+            if fn is None or "init_transforms" not in inspect.signature(fn).parameters:
+                raise _lib.NscError(f"yaw_init=True needs a verifier whose {method} takes init_transforms "
+                                    "(GeometricVerifier does)")
+            self.yaw_images = _yaw.YawImages(device=device)
+            if yaw_encoder is None:
+                from ..encoding import SpectralEncoder
+                yaw_encoder = SpectralEncoder(n_elevation=16, device=device).to(device)
+            self.yaw_encoder = yaw_encoder
 
     def _check_points(self, keyframes):
         if self.geometry is not None:
@@ -90,14 +111,32 @@ class TwoStageRetrieval:
                 if getattr(kf, "points", None) is None:
                     raise ValueError("Keyframe must have points before adding to a database with prepare_geometry")
 
+    def _range_images(self, keyframes, points=None) -> torch.Tensor:
+        """(B, R, 360) float32 device tensor: each keyframe's ``range_image`` if it has one, else the interpolated
+        image of its points (``points[i]`` in place of ``keyframes[i].points`` if given) by ``yaw_encoder``, all
+        clouds in one encoder call."""
+        dev = self.yaw_images.device
+        given = [None if points is not None and points[i] is not None else getattr(kf, "range_image", None)
+                 for i, kf in enumerate(keyframes)]
+        clouds = [(points[i] if points is not None and points[i] is not None else kf.points)
+                  for i, kf in enumerate(keyframes) if given[i] is None]
+        if any(c is None for c in clouds):
+            raise ValueError("Keyframe must have a range_image or points with yaw_init")
+        made = iter(self.yaw_encoder.encode_points_batch(clouds, return_images=True)[2]) if clouds else iter(())
+        out = [_yaw._images(g, dev)[0] if g is not None else next(made) for g in given]
+        return torch.stack(out) if out else torch.empty((0, 1, _yaw.N_AZIMUTH), dtype=torch.float32, device=dev)
+
     # -- database --------------------------------------------------------------------------------
     def add_keyframe(self, keyframe):
         """:91-105"""
         if keyframe.descriptor is None:
             raise ValueError("Keyframe must have descriptor before adding to database")
         self._check_points([keyframe])
+        image = self._range_images([keyframe]) if self.yaw_images is not None else None
         if self.geometry is not None:
             self.geometry.add([keyframe.points])
+        if image is not None:
+            self.yaw_images.add(image)
         self.keyframes.append(keyframe)
         descriptor = np.asarray(keyframe.descriptor, dtype=np.float32).reshape(1, -1)
         self.retriever.add_to_database(descriptor, positions=_position(keyframe.pose).reshape(1, 3))
@@ -112,8 +151,11 @@ class TwoStageRetrieval:
             if kf.descriptor is None:
                 raise ValueError("Keyframe must have descriptor before adding to database")
         self._check_points(keyframes)
+        images = self._range_images(keyframes) if self.yaw_images is not None else None
         if self.geometry is not None:
             prepare_chunked(self.geometry, [kf.points for kf in keyframes])
+        if images is not None:
+            self.yaw_images.add(images)
         self.keyframes.extend(keyframes)
         desc = np.stack([np.asarray(kf.descriptor, dtype=np.float32).reshape(-1) for kf in keyframes])
         self.retriever.add_to_database(desc, positions=np.stack([_position(kf.pose) for kf in keyframes]))
@@ -124,6 +166,8 @@ class TwoStageRetrieval:
         self.retriever.clear_database()
         if self.geometry is not None:
             self.geometry.clear()
+        if self.yaw_images is not None:
+            self.yaw_images.clear()
 
     # -- stage 1 ---------------------------------------------------------------------------------
     def _retrieve(self, descriptors: np.ndarray, poses) -> tuple:
@@ -158,13 +202,25 @@ class TwoStageRetrieval:
                 for ri, rv in zip(idx, val)]
 
     # -- stage 2 (injected) ----------------------------------------------------------------------
-    def _geometric_verification(self, query_points, candidates):
-        """:204-242 with the injected verifier."""
+    def _geometric_verification(self, query_points, candidates, query_image=None):
+        """:204-242 with the injected verifier.  ``query_image``: the query's range image with yaw_init."""
         if self.verifier is None:
             raise _lib.NscError("stage 2 (GICP) is outside the MI355X descriptor path: construct TwoStageRetrieval "
                                 "with verifier=<object with the reference's GeometricVerifier.verify> or call "
                                 "query(..., verify=False)")
-        if self.geometry is not None:
+        if self.yaw_images is not None:
+            ids = [c.database_idx for c in candidates]
+            yaw = _yaw.estimate_yaw(query_image, [0] * len(ids), self.yaw_images, ids)      # one launch, no sync
+            if self.geometry is not None:
+                self._query_geometry.clear()
+                self._query_geometry.add([query_points])
+                results = self.verifier.verify_prepared(self._query_geometry, 0, self.geometry, ids,
+                                                        init_transforms=yaw["init_transforms"])
+            else:
+                results = self.verifier.verify_batch(query_points, [self.keyframes[i].points for i in ids],
+                                                     init_transforms=yaw["init_transforms"])
+            results = _with_yaw_info(results, yaw)
+        elif self.geometry is not None:
             self._query_geometry.clear()
             self._query_geometry.add([query_points])
             results = self.verifier.verify_prepared(self._query_geometry, 0, self.geometry,
@@ -185,9 +241,12 @@ class TwoStageRetrieval:
         if len(candidates) == 0:
             return []
         if verify:
+            image = None
+            if self.yaw_images is not None:
+                image = self._range_images([query_keyframe], [query_points])
             if query_points is None:
                 query_points = query_keyframe.points
-            candidates = self._geometric_verification(query_points, candidates)
+            candidates = self._geometric_verification(query_points, candidates, query_image=image)
         return candidates
 
     def get_loop_closures(self, query_keyframe, query_points: Optional[np.ndarray] = None) -> List[Dict]:
@@ -226,9 +285,20 @@ def _apply(candidates, results):
         candidate.fitness = info['fitness']
         candidate.rmse = info['rmse']
         candidate.information_matrix = info.get('information_matrix', None)
+        candidate.info = info
         if verified:
             verified_candidates.append(candidate)
     return verified_candidates
+
+
+def _with_yaw_info(results, yaw):
+    """Add init_yaw_deg and yaw_peak_ratio of estimate_yaw's outputs to the info dicts of the pairs' results (read
+    after the verifier's sync)."""
+    host = torch.stack([yaw["shift"].double(), yaw["peak"], yaw["runner_up"]], 1).cpu().numpy()
+    results = list(results)
+    for (_, _, info), (shift, peak, runner_up) in zip(results, host):
+        info.update(_yaw.yaw_info(shift, peak, runner_up))
+    return results
 
 
 def prepare_chunked(store, clouds, max_rows: int = _PREPARE_ROWS):
@@ -254,15 +324,18 @@ def create_two_stage_retrieval(top_k: int = 10, spatial_filter_distance: float =
 
 
 def batch_loop_closing(query_keyframes, database_keyframes, top_k: int = 10, spatial_filter_distance: float = 50.0,
-                       verify: bool = True, verifier=None, edge_fn=None, prepare_geometry: bool = False
-                       ) -> Dict[int, list]:
+                       verify: bool = True, verifier=None, edge_fn=None, prepare_geometry: bool = False,
+                       yaw_init: bool = False) -> Dict[int, list]:
     """:322-359.  With ``verify=False`` the values are the stage-1 candidate lists (one database pass for all
     queries); with ``verify=True`` the injected stage 2 runs per query as in the reference.  With
     ``prepare_geometry=True`` (a GeometricVerifier) every database and query cloud is prepared once, stage 1 runs
     for all queries in one pass and stage 2 registers all queries' candidate pairs in one register_prepared call;
-    the result equals the per-query one."""
+    the result equals the per-query one.  ``yaw_init=True`` starts every pair from its yaw guess (TwoStageRetrieval);
+    with ``prepare_geometry=True`` all queries' pairs are estimated in one estimate_yaw call before the one
+    registration."""
     retrieval = create_two_stage_retrieval(top_k=top_k, spatial_filter_distance=spatial_filter_distance,
-                                           verifier=verifier, edge_fn=edge_fn, prepare_geometry=prepare_geometry)
+                                           verifier=verifier, edge_fn=edge_fn, prepare_geometry=prepare_geometry,
+                                           yaw_init=yaw_init)
     retrieval.add_keyframes(database_keyframes)
     if not verify:
         return dict(enumerate(retrieval.global_retrieval_batch(query_keyframes)))
@@ -279,8 +352,13 @@ def batch_loop_closing(query_keyframes, database_keyframes, top_k: int = 10, spa
     queries = verifier.prepare()
     prepare_chunked(queries, [kf.points for kf in query_keyframes])
     qids = [i for i, cl in enumerate(candidates) for _ in cl]
-    results = verifier.verify_pairs(queries, qids, retrieval.geometry,
-                                    [c.database_idx for cl in candidates for c in cl])
+    cids = [c.database_idx for cl in candidates for c in cl]
+    if yaw_init and qids:
+        yaw = _yaw.estimate_yaw(retrieval._range_images(query_keyframes), qids, retrieval.yaw_images, cids)
+        results = _with_yaw_info(verifier.verify_pairs(queries, qids, retrieval.geometry, cids,
+                                                       init_transforms=yaw["init_transforms"]), yaw)
+    else:
+        results = verifier.verify_pairs(queries, qids, retrieval.geometry, cids)
     out, at = {}, 0
     for i, (kf, cl) in enumerate(zip(query_keyframes, candidates)):
         out[i] = retrieval._edges(kf, _apply(cl, results[at:at + len(cl)]))
