@@ -81,7 +81,11 @@ def _topk(dist: torch.Tensor, k: int):
         # beyond the selection kernel's range (k > 256: the reference's callers ask for 10-50, but `query(top_k=n)` is legal there,
         # wasserstein.py:380): a stable device sort gives the same (value, index) order -- still on the device, no host copy
         val, idx = torch.sort(dist, dim=1, stable=True)
-        return idx[:, :k].contiguous(), val[:, :k].contiguous()
+        idx, val = idx[:, :k].contiguous(), val[:, :k].contiguous()
+        # the selection kernel never picks a NaN (a NaN histogram row): the slots a row cannot fill hold -1 / +inf.
+        # torch.sort puts NaN last, so the same answer is the sorted one with its NaN tail rewritten
+        nan = torch.isnan(val)
+        return idx.masked_fill_(nan, -1), val.masked_fill_(nan, float("inf"))
     _lib.check(st, "nsc_topk_smallest")
     return idx, val
 
