@@ -19,7 +19,7 @@ int nsc_debug_point_bins(const float *pts, int64_t n_points, int32_t stride_floa
                          void *stream);
 
 /* Development builds only (NSC_DEV_BUILD=1 python neural-spectral-codec_amd/build.py -> -DNSC_DEV_TUNING); the product
- * library does not export it. */
+ * library does not export it.  This function and its kernel (nsc_gat.hip) are all that -DNSC_DEV_TUNING compiles in. */
 /* Diagnostic co-runner (bench.py --gnn-burn): `workgroups` x 4 waves of the co-resident GNN kernels' footprint (0 B of LDS,
  * < 56 VGPRs), each wave issuing `per_wave` operations of ONE kind -- mode 0: v_mfma_f32_16x16x4_f32 on register operands
  * (4 independent accumulators), 1: v_fma_f32 (64 lanes), 2: 16-byte loads from a 1 MB L2-resident buffer (`scratch`, >= 1 MB),

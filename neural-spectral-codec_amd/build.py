@@ -37,7 +37,7 @@ FLAGS_FILE = LIB + ".flags"        # the flags the library in place was built wi
 
 def _flags():
     flags = list(HIPCC_FLAGS)
-    if os.environ.get("NSC_DEV_BUILD") == "1":       # enables the NSC_TUNE_* development knobs
+    if os.environ.get("NSC_DEV_BUILD") == "1":       # compiles in nsc_debug_burn (nsc_gat.hip), nothing else
         flags.append("-DNSC_DEV_TUNING")
     for d in os.environ.get("NSC_DEV_DEFINES", "").split():      # development A/B builds
         flags.append("-D" + d)

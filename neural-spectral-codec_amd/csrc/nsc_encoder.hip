@@ -19,7 +19,6 @@
 // Built with -ffp-contract=off: float32/float64 expressions round exactly as written; FMAs appear
 // only where fma()/__builtin_fmaf is spelled out.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
@@ -45,19 +44,7 @@ struct EncDev {
     int E, R, B;
     float eps;
     int interp;
-#ifdef NSC_DEV_TUNING
-    int dev_skip;          // development builds only (NSC_TUNE_SKIP_FINISH): phase masks for tools/ab_enc.py
-#endif
 };
-
-// Phase masks exist only in development builds (NSC_DEV_BUILD=1); the shipped kernels carry none of it.
-#ifdef NSC_DEV_TUNING
-#define NSC_DEV_SKIP(d, bit) (((d).dev_skip & (bit)) != 0)
-#define NSC_DEV_MODE(d) ((d).dev_skip)
-#else
-#define NSC_DEV_SKIP(d, bit) false
-#define NSC_DEV_MODE(d) 0
-#endif
 
 // exp(-2 pi i j / 360) = (cos, -sin): table holds (cos, sin)
 __device__ const double2 g_tw360[A] = {
@@ -705,27 +692,15 @@ template <int N, class F> __device__ __forceinline__ void static_for(F &&f)
 // loads and counts its waits down to vmcnt(0), so nothing is in flight when the registers are reused.
 template <int NT, int U>
 __device__ __forceinline__ void stream_fast(const f32x4 *__restrict__ P, int n, int tid, const NscBinParams &bp,
-                                            unsigned *img, f32x4 *queue, unsigned *qcount, int dev_mode = 0)
+                                            unsigned *img, f32x4 *queue, unsigned *qcount)
 {
-#ifdef NSC_DEV_TUNING
-    float dev_acc = 0.f;
-#endif
     auto park = [&](const f32x4 &v, float s) {                       // ~2e-4 of the points
         const unsigned slot = atomicAdd(qcount, 1u);                 // counts past FQ_CAP: the kernel then re-streams
         if (slot < (unsigned)FQ_CAP) queue[slot] = f32x4{v.x, v.y, v.z, s};
     };
     // two slots at a time: the lean estimate of both points in packed float32 instructions (nsc_point_lean_pair)
     auto process2 = [&](const f32x4 &va, const f32x4 &vb) {
-#ifdef NSC_DEV_TUNING
-        if (dev_mode & 64) { dev_acc += (va.x + va.y + va.z) + (vb.x + vb.y + vb.z); return; }   // loads only
-#endif
         const NscLeanPair p = nsc_point_lean_pair(va.x, va.y, va.z, vb.x, vb.y, vb.z, bp);
-#ifdef NSC_DEV_TUNING
-        if (dev_mode & 128) {                                                    // loads + binning, no LDS atomics
-            dev_acc += (float)(p.pix[0] + (int)p.ok[0] + p.pix[1] + (int)p.ok[1]) + p.s[0] + p.s[1] + (float)(p.park[0] | p.park[1]);
-            return;
-        }
-#endif
         if (p.ok[0]) atomicMin(&img[p.pix[0]], __float_as_uint(p.s[0]));   // ds_min_u32 (s >= 0: uint order == float order)
         if (p.ok[1]) atomicMin(&img[p.pix[1]], __float_as_uint(p.s[1]));
         if (p.park[0] | p.park[1]) {
@@ -809,9 +784,6 @@ __device__ __forceinline__ void stream_fast(const f32x4 *__restrict__ P, int n, 
     });
 #undef NSC_SLOT_WAIT2
 #undef NSC_SLOT_LOAD
-#ifdef NSC_DEV_TUNING
-    if (dev_mode & (64 | 128)) atomicMin(&img[tid & 63], __float_as_uint(fabsf(dev_acc)));
-#endif
 }
 
 // Cold path of encode_fast_kernel: the whole cloud through the lean estimate, one point per thread and iteration,
@@ -871,13 +843,6 @@ __device__ __forceinline__ void finish_fast(unsigned char *lds, const EncDev &d,
     int lut_cur = ft.lut_cur;
     const int lut_prev = ft.lut_prev;
 
-#ifdef NSC_DEV_TUNING
-    unsigned long long st[7];
-#define NSC_STAMP(i) st[i] = wall_clock64()
-#else
-#define NSC_STAMP(i)
-#endif
-    NSC_STAMP(0);
     const int r0 = 4 * wave;                                      // this wave owns rows r0 .. r0 + 3
     {
         float v[4][6];                                            // the four rows' square roots are independent
@@ -906,7 +871,6 @@ __device__ __forceinline__ void finish_fast(unsigned char *lds, const EncDev &d,
             if (lane == 0) rowflag[r0 + q] = (nv > 0);
         }
     }
-    NSC_STAMP(1);
     if (tid < TW_N) tw[tid] = twv;
     if (tid < F) {
         lut_cur = min(lut_cur, B - 1);
@@ -915,7 +879,6 @@ __device__ __forceinline__ void finish_fast(unsigned char *lds, const EncDev &d,
             for (int b = lut_cur; b < B; ++b) { seg[B + b] = F; if (b > lut_cur) seg[b] = F; }
     }
     __syncthreads();
-    NSC_STAMP(2);
     if (d.interp) {                                               // range_image.py:77-87
         unsigned ne = 0u;
         for (int r = 0; r < E; ++r) ne |= (unsigned)(rowflag[r] != 0) << r;
@@ -943,13 +906,11 @@ __device__ __forceinline__ void finish_fast(unsigned char *lds, const EncDev &d,
     if (out_interp)
         for (int r = r0; r < r0 + 4; ++r)
             for (int c = lane; c < A; c += 64) out_interp[r * A + c] = img[r * A + c];
-    if (NSC_DEV_SKIP(d, 16)) return;
 
     // spectrum + histogram.  All four rows' stage-1 operands go to registers first; from then on the wave's 5 760
     // image bytes are two FFT scratch buffers (180 double2 each) and the rows run as two PAIRS, the two FFTs of a pair
     // interleaved instruction by instruction.  The magnitudes of a row land on its own scratch once the unpack has
     // read it, the histogram value of bin `lane` of each of the four rows stays in a register until the normalisation.
-    NSC_STAMP(3);
     f32x2 in[4][4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) fft_load_row(img + (r0 + q) * A, lane, in[q]);
@@ -961,10 +922,8 @@ __device__ __forceinline__ void finish_fast(unsigned char *lds, const EncDev &d,
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
         float mg[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-        if (!NSC_DEV_SKIP(d, 4)) {            // pair 0 carries pair 1's stage-1 operands: the lean form (see fft_rows)
-            if (pr == 0) fft_rows<2, true>(in, bufs, tw, mg, lane);
-            else fft_rows<2, false>(in + 2, bufs, tw, mg, lane);
-        }
+        if (pr == 0) fft_rows<2, true>(in, bufs, tw, mg, lane);   // pair 0 carries pair 1's stage-1 operands: the lean
+        else fft_rows<2, false>(in + 2, bufs, tw, mg, lane);      // form (see fft_rows)
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             float *mags = reinterpret_cast<float *>(bufs[p]);
@@ -975,29 +934,25 @@ __device__ __forceinline__ void finish_fast(unsigned char *lds, const EncDev &d,
             }
         }
         wave_sync();
-        if (!NSC_DEV_SKIP(d, 8)) {
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const float *mags = reinterpret_cast<const float *>(bufs[p]);
-                float acc = 0.0f;
-                for (int k = k0; k < k1; k += 8) {               // scatter_add_, ascending k (:152-155)
-                    float v[8];
+        for (int p = 0; p < 2; ++p) {
+            const float *mags = reinterpret_cast<const float *>(bufs[p]);
+            float acc = 0.0f;
+            for (int k = k0; k < k1; k += 8) {                   // scatter_add_, ascending k (:152-155)
+                float v[8];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = (k + u < k1) ? mags[k + u] : 0.0f;
+                for (int u = 0; u < 8; ++u) v[u] = (k + u < k1) ? mags[k + u] : 0.0f;
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) acc += v[u];      // acc + 0.0f == acc: order and rounding unchanged
-                }
-                h[2 * pr + p] = acc;
-                part += (double)acc;
+                for (int u = 0; u < 8; ++u) acc += v[u];          // acc + 0.0f == acc: order and rounding unchanged
             }
+            h[2 * pr + p] = acc;
+            part += (double)acc;
         }
         wave_sync();                                              // the magnitudes are overwritten by the next pair
     }
-    NSC_STAMP(4);
     part = wave_sum(part);
     if (lane == 0) rowsum[wave] = part;
     __syncthreads();
-    NSC_STAMP(5);
 
     const double tot = (rowsum[0] + rowsum[1]) + (rowsum[2] + rowsum[3]);
     const float s = (float)tot;                                   // :197
@@ -1012,15 +967,6 @@ __device__ __forceinline__ void finish_fast(unsigned char *lds, const EncDev &d,
             for (int q = 0; q < 4; ++q) out_desc[(r0 + q) * B + lane] = u;
         }
     }
-#ifdef NSC_DEV_TUNING
-    if (NSC_DEV_SKIP(d, 512)) {
-        NSC_STAMP(6);
-        __syncthreads();
-        if (tid == 0)
-            for (int i = 0; i < 7; ++i) out_desc[3 + i] = __uint_as_float((unsigned)st[i]);
-    }
-#endif
-#undef NSC_STAMP
 }
 
 template <int U>
@@ -1049,11 +995,7 @@ __global__ __launch_bounds__(256, 6) void encode_fast_kernel(
     // cloud beyond it takes the cold loop, the rest of the batch is unaffected
     const bool streamable = n64 > 0 && n64 < FAST_MAX_POINTS;
     const int n = streamable ? (int)n64 : 0;
-#ifdef NSC_DEV_TUNING
-    const unsigned long long dev_t0 = wall_clock64();
-    unsigned long long dev_t1 = 0;
-#endif
-    if (n > 0 && !NSC_DEV_SKIP(d, 2)) stream_fast<NT, U>(P, n, tid, d.bp, img, queue, qcount, NSC_DEV_MODE(d));
+    if (n > 0) stream_fast<NT, U>(P, n, tid, d.bp, img, queue, qcount);
     __syncthreads();
     {   // drain the uncertain-point queue with the exact chain (the definition of the pixel), compacted
         const unsigned qn = *qcount;
@@ -1068,26 +1010,7 @@ __global__ __launch_bounds__(256, 6) void encode_fast_kernel(
         }
     }
     __syncthreads();
-#ifdef NSC_DEV_TUNING
-    dev_t1 = wall_clock64();
-#endif
-    if (NSC_DEV_SKIP(d, 1)) {
-        if (tid == 0) out_desc[(long long)c * 16 * d.B] = __uint_as_float(img[0]);
-        return;
-    }
     const long long D = 16LL * d.B;
-#ifdef NSC_DEV_TUNING
-    if (NSC_DEV_SKIP(d, 512)) {         // per-workgroup timeline probe (tools/wg_timeline.py): 100 MHz wall clock
-        finish_fast(lds, d, load_finish_tables(lut, tid), out_desc + c * D, nullptr, nullptr);
-        __syncthreads();
-        if (tid == 0) {
-            out_desc[c * D + 0] = __uint_as_float((unsigned)dev_t0);
-            out_desc[c * D + 1] = __uint_as_float((unsigned)dev_t1);
-            out_desc[c * D + 2] = __uint_as_float((unsigned)wall_clock64());
-        }
-        return;
-    }
-#endif
     finish_fast(lds, d, load_finish_tables(lut, tid), out_desc + c * D, out_raw ? out_raw + (long long)c * 16 * A : nullptr,
                 out_interp ? out_interp + (long long)c * 16 * A : nullptr);
 }
@@ -1229,19 +1152,6 @@ constexpr int FUSED_U = 4;           // float4 loads in flight per thread (split
 constexpr int SPLIT_MIN_PTS = 16384; // a part must amortise its 5 760-pixel LDS init + flush
 constexpr int SPLIT_TARGET_WGS = 512;
 
-// Development knobs (tools/ab_enc.py, tools/sweep_enc.py) exist only in builds made with
-// NSC_DEV_BUILD=1 (-DNSC_DEV_TUNING); the shipped library reads no environment variables.
-int tune_env(const char *name, int def)
-{
-#ifdef NSC_DEV_TUNING
-    const char *v = getenv(name);
-    return v ? atoi(v) : def;
-#else
-    (void)name;
-    return def;
-#endif
-}
-
 int check_params(const NscEncParams *p)
 {
     if (!p) return NSC_EINVAL;
@@ -1263,37 +1173,30 @@ EncDev make_dev(const NscEncParams *p, int rows_in)
     d.B = p->n_bins;
     d.eps = p->epsilon;
     d.interp = p->interpolate;
-#ifdef NSC_DEV_TUNING
-    d.dev_skip = tune_env("NSC_TUNE_SKIP_FINISH", 0);
-#endif
     return d;
-}
-
-int split_parts(int32_t n_clouds, int64_t total_points);
-
-// Which kernel set nsc_encode_clouds launches for a batch: the one decision function the launcher and
-// nsc_encode_clouds_path() share.
-int encode_path(const EncDev &d, int32_t n_clouds, int64_t total_points, int32_t stride, int variant)
-{
-    if (split_parts(n_clouds, total_points) > 1) return NSC_ENC_PATH_SPLIT;
-    // the configuration of every reference caller: the lean streaming kernel.  No limit on the batch: the kernel's
-    // 32-bit byte offsets are relative to each cloud's own base, and a single cloud of >= 2^27 points takes its cold
-    // loop (round 2 tested total_points here and sent batches of more than 1 118 x 120 000 points to the generic kernel).
-    if (variant <= 0 && stride == 4 && d.E == 16 && d.R == 16 && d.B <= FAST_HSTRIDE && nsc_lean_ok(d.bp))
-        return NSC_ENC_PATH_FAST;
-    return NSC_ENC_PATH_FUSED;
 }
 
 int split_parts(int32_t n_clouds, int64_t total_points)
 {
-    const int force = tune_env("NSC_TUNE_SPLIT", 0);
-    if (force > 0) return force;
     if (n_clouds <= 0 || n_clouds >= SPLIT_TARGET_WGS) return 1;
     const int64_t avg = total_points / n_clouds;
     int64_t by_size = avg / SPLIT_MIN_PTS;
     int64_t want = (SPLIT_TARGET_WGS + n_clouds - 1) / n_clouds;
     int64_t s = want < by_size ? want : by_size;
     return s < 2 ? 1 : (int)s;
+}
+
+// Which kernel set nsc_encode_clouds launches for a batch: the one decision function the launcher and
+// nsc_encode_clouds_path() share.
+int encode_path(const EncDev &d, int32_t n_clouds, int64_t total_points, int32_t stride)
+{
+    if (split_parts(n_clouds, total_points) > 1) return NSC_ENC_PATH_SPLIT;
+    // the configuration of every reference caller: the lean streaming kernel.  No limit on the batch: the kernel's
+    // 32-bit byte offsets are relative to each cloud's own base, and a single cloud of >= 2^27 points takes its cold
+    // loop (round 2 tested total_points here and sent batches of more than 1 118 x 120 000 points to the generic kernel).
+    if (stride == 4 && d.E == 16 && d.R == 16 && d.B <= FAST_HSTRIDE && nsc_lean_ok(d.bp))
+        return NSC_ENC_PATH_FAST;
+    return NSC_ENC_PATH_FUSED;
 }
 
 // Dynamic LDS above 64 KiB (E = 64 images) must be opted into once per kernel; the call is
@@ -1304,6 +1207,47 @@ template <class K> int set_lds(K kernel, int bytes)
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess
                ? NSC_OK : NSC_ELAUNCH;
+}
+
+// One launcher per kernel.  Each returns set_lds()'s status; the entry point asks hipGetLastError() once, after its
+// last launch.
+template <int NW, int U, int MINW>
+int launch_fused(hipStream_t stream, const EncDev &d, int n_clouds, const float *pts, const long long *off, int stride,
+                 const int *lut, float *out_desc, float *out_raw, float *out_interp)
+{
+    auto k = encode_fused_kernel<NW, U, MINW>;
+    const LdsPlan lp = lds_plan(d.E, d.R, d.B, NW);
+    const int st = set_lds(k, lp.total);
+    if (st != NSC_OK) return st;
+    hipLaunchKernelGGL(k, dim3(n_clouds), dim3(NW * 64), lp.total, stream, pts, off, stride, d, lut, out_desc, out_raw,
+                       out_interp);
+    return NSC_OK;
+}
+
+// `grid` workgroups, `parts` of them per cloud, each with an LDS image of `img_bytes`
+template <int NW, int U>
+int launch_scatter(hipStream_t stream, const EncDev &d, int img_bytes, int grid, int parts, const float *pts,
+                   const long long *off, int stride, unsigned *out_sqr)
+{
+    auto k = scatter_split_kernel<NW, U>;
+    const int st = set_lds(k, img_bytes);
+    if (st != NSC_OK) return st;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(NW * 64), img_bytes, stream, pts, off, stride, parts, d, out_sqr);
+    return NSC_OK;
+}
+
+// mode as finish_image(): 0 reads the squared-range images `sqr`, 1 and 2 the caller's range images `imgs`
+template <int NW>
+int launch_finish(hipStream_t stream, const EncDev &d, int n_images, const unsigned *sqr, const float *imgs, int mode,
+                  const int *lut, float *out_desc, float *out_raw, float *out_interp)
+{
+    auto k = finish_kernel<NW>;
+    const LdsPlan lp = lds_plan(d.E, d.R, d.B, NW);
+    const int st = set_lds(k, lp.total);
+    if (st != NSC_OK) return st;
+    hipLaunchKernelGGL(k, dim3(n_images), dim3(NW * 64), lp.total, stream, sqr, imgs, (int)(mode == 2), d, lut,
+                       out_desc, out_raw, out_interp);
+    return NSC_OK;
 }
 
 }  // namespace
@@ -1352,7 +1296,7 @@ int nsc_encode_clouds_path(int32_t n_clouds, int64_t total_points, int32_t strid
     int st = check_params(p);
     if (st != NSC_OK) return st;
     if (n_clouds < 0 || total_points < 0 || (stride != 3 && stride != 4)) return NSC_EINVAL;
-    return encode_path(make_dev(p, p->n_elevation), n_clouds, total_points, stride, tune_env("NSC_TUNE_VARIANT", 0));
+    return encode_path(make_dev(p, p->n_elevation), n_clouds, total_points, stride);
 }
 
 int nsc_encode_clouds(const float *pts, const int64_t *cloud_offsets, int32_t n_clouds,
@@ -1368,53 +1312,41 @@ int nsc_encode_clouds(const float *pts, const int64_t *cloud_offsets, int32_t n_
     if (stride == 4 && (reinterpret_cast<uintptr_t>(pts) & 15u)) return NSC_EINVAL;   // 16-B loads
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const EncDev d = make_dev(p, p->n_elevation);
-    const LdsPlan lp = lds_plan(d.E, d.R, d.B, FUSED_NW);
-    const int parts = split_parts(n_clouds, total_points);
     const long long *off = reinterpret_cast<const long long *>(cloud_offsets);
-    const int variant = tune_env("NSC_TUNE_VARIANT", 0);
-    const int path = encode_path(d, n_clouds, total_points, stride, variant);
+    const int path = encode_path(d, n_clouds, total_points, stride);
 
-    if (path != NSC_ENC_PATH_SPLIT) {
-        if (path == NSC_ENC_PATH_FAST) {
-            const FastLds fl = fast_lds(d.B);
-                // two loads per lane: measured against 4, 6, 8 and 12, alone 1-2 % faster on uniform and 3-4 % on
-                // ring-ordered clouds, identical in the two-stream step (round 2, interleaved A/B)
-                hipLaunchKernelGGL(encode_fast_kernel<2>, dim3(n_clouds), dim3(256), fl.total, stream, pts, off, d, lut,
-                                   out_desc, out_raw, out_interp);
-            return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
-        }
-#define NSC_LAUNCH_FUSED(NW_, U_, MINW_)                                                              \
-    {                                                                                                 \
-        auto k = encode_fused_kernel<NW_, U_, MINW_>;                                                 \
-        const LdsPlan lpv = lds_plan(d.E, d.R, d.B, NW_);                                             \
-        if ((st = set_lds(k, lpv.total)) != NSC_OK) return st;                                        \
-        hipLaunchKernelGGL(k, dim3(n_clouds), dim3(NW_ * 64), lpv.total, stream, pts, off, stride, d, \
-                           lut, out_desc, out_raw, out_interp);                                       \
-    }
+    if (path == NSC_ENC_PATH_FAST) {
+        const FastLds fl = fast_lds(d.B);
+        // two loads per lane: measured against 4, 6, 8 and 12, alone 1-2 % faster on uniform and 3-4 % on
+        // ring-ordered clouds, identical in the two-stream step (round 2, interleaved A/B)
+        hipLaunchKernelGGL(encode_fast_kernel<2>, dim3(n_clouds), dim3(256), fl.total, stream, pts, off, d, lut,
+                           out_desc, out_raw, out_interp);
+    } else if (path == NSC_ENC_PATH_FUSED) {
         // 16 waves per CU in every shape: the LDS image decides how many workgroups share a CU, the workgroup
         // brings the waves (E <= 16: 4 x 4 waves, <= 32 rows: 2 x 8, up to 64 rows: 1 x 16)
         // (the wave / load-depth shapes measured against these in rounds 1-2 -- 8 loads per lane, 8 or 16 waves on 16 rows --
         // are DESIGN.md section 7, experiments 1-12; the library instantiates only what it launches)
-        if (d.E > 32) NSC_LAUNCH_FUSED(16, 4, 1)
-        else if (d.E > 16) NSC_LAUNCH_FUSED(8, 4, 2)
+        if (d.E > 32)
+            st = launch_fused<16, 4, 1>(stream, d, n_clouds, pts, off, stride, lut, out_desc, out_raw, out_interp);
+        else if (d.E > 16)
+            st = launch_fused<8, 4, 2>(stream, d, n_clouds, pts, off, stride, lut, out_desc, out_raw, out_interp);
         // 4 waves x 4 float4 loads in flight per lane (92 VGPRs), 39.4 KB LDS -> 4 workgroups per CU: a 1 024-cloud batch is
         // exactly one resident round.  Interleaved A/B on three boxes: 1-1.5 % faster than 8 loads per lane (108 VGPRs), and
         // it leaves 128 VGPRs per SIMD lane to co-resident kernels.
-        else NSC_LAUNCH_FUSED(4, 4, 4)
+        else
+            st = launch_fused<4, 4, 4>(stream, d, n_clouds, pts, off, stride, lut, out_desc, out_raw, out_interp);
+        if (st != NSC_OK) return st;
     } else {
-        const size_t need = (size_t)n_clouds * d.E * A * sizeof(unsigned);
-        if (!ws || ws_bytes < need) return NSC_EWORKSPACE;
-        nsc_fill_u32(stream, ws, 0xffffffffu, (long long)(need / 4));
-        auto ks = scatter_split_kernel<FUSED_NW, FUSED_U>;
         const int img_bytes = d.E * A * 4;
-        if ((st = set_lds(ks, img_bytes)) != NSC_OK) return st;
-        hipLaunchKernelGGL(ks, dim3(n_clouds * parts), dim3(FUSED_NW * 64), img_bytes, stream, pts, off,
-                           stride, parts, d, static_cast<unsigned *>(ws));
-        auto kf = finish_kernel<FUSED_NW>;
-        if ((st = set_lds(kf, lp.total)) != NSC_OK) return st;
-        hipLaunchKernelGGL(kf, dim3(n_clouds), dim3(FUSED_NW * 64), lp.total, stream,
-                           static_cast<const unsigned *>(ws), static_cast<const float *>(nullptr), 0, d, lut,
-                           out_desc, out_raw, out_interp);
+        const size_t need = (size_t)n_clouds * img_bytes;
+        if (!ws || ws_bytes < need) return NSC_EWORKSPACE;
+        unsigned *sqr = static_cast<unsigned *>(ws);
+        const int parts = split_parts(n_clouds, total_points);
+        nsc_fill_u32(stream, sqr, 0xffffffffu, (long long)(need / 4));
+        st = launch_scatter<FUSED_NW, FUSED_U>(stream, d, img_bytes, n_clouds * parts, parts, pts, off, stride, sqr);
+        if (st != NSC_OK) return st;
+        st = launch_finish<FUSED_NW>(stream, d, n_clouds, sqr, nullptr, 0, lut, out_desc, out_raw, out_interp);
+        if (st != NSC_OK) return st;
     }
     return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
 }
@@ -1461,15 +1393,13 @@ int nsc_scatter_clouds(const float *pts, const int64_t *cloud_offsets, int32_t n
     const int img_bytes = d.E * A * 4;
     if (parts > 1) {
         nsc_fill_u32(stream, out_sqr, 0xffffffffu, (long long)n_clouds * (img_bytes / 4));
-        auto ks = scatter_split_kernel<FUSED_NW, FUSED_U>;
-        if ((st = set_lds(ks, img_bytes)) != NSC_OK) return st;
-        hipLaunchKernelGGL(ks, dim3(n_clouds * parts), dim3(FUSED_NW * 64), img_bytes, stream, pts, off, stride, parts,
-                           d, out_sqr);
+        st = launch_scatter<FUSED_NW, FUSED_U>(stream, d, img_bytes, n_clouds * parts, parts, pts, off, stride,
+                                               out_sqr);
     } else {
-        auto ks = scatter_split_kernel<4, 8>;          // one 4-wave workgroup per cloud, 23 KB LDS
-        if ((st = set_lds(ks, img_bytes)) != NSC_OK) return st;
-        hipLaunchKernelGGL(ks, dim3(n_clouds), dim3(256), img_bytes, stream, pts, off, stride, 1, d, out_sqr);
+        // one 4-wave workgroup per cloud, 23 KB LDS
+        st = launch_scatter<4, 8>(stream, d, img_bytes, n_clouds, 1, pts, off, stride, out_sqr);
     }
+    if (st != NSC_OK) return st;
     return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
 }
 
@@ -1483,11 +1413,8 @@ int nsc_finish_images(const uint32_t *sqr, int32_t n_images, const NscEncParams 
     if (!sqr || !lut || !out_desc) return NSC_EINVAL;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const EncDev d = make_dev(p, p->n_elevation);
-    const LdsPlan lp = lds_plan(d.E, d.R, d.B, FUSED_NW);
-    auto kf = finish_kernel<FUSED_NW>;
-    if ((st = set_lds(kf, lp.total)) != NSC_OK) return st;
-    hipLaunchKernelGGL(kf, dim3(n_images), dim3(FUSED_NW * 64), lp.total, stream, sqr,
-                       static_cast<const float *>(nullptr), 0, d, lut, out_desc, out_raw, out_interp);
+    st = launch_finish<FUSED_NW>(stream, d, n_images, sqr, nullptr, 0, lut, out_desc, out_raw, out_interp);
+    if (st != NSC_OK) return st;
     return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
 }
 
@@ -1502,12 +1429,8 @@ int nsc_encode_range_images(const float *imgs, int32_t n_images, int32_t rows, c
     if (!imgs || !lut || !out_desc) return NSC_EINVAL;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const EncDev d = make_dev(p, rows);
-    const LdsPlan lp = lds_plan(d.E, d.R, d.B, FUSED_NW);
-    auto kf = finish_kernel<FUSED_NW>;
-    if ((st = set_lds(kf, lp.total)) != NSC_OK) return st;
-    hipLaunchKernelGGL(kf, dim3(n_images), dim3(FUSED_NW * 64), lp.total, stream,
-                       static_cast<const unsigned *>(nullptr), imgs, 0, d, lut, out_desc,
-                       static_cast<float *>(nullptr), static_cast<float *>(nullptr));
+    st = launch_finish<FUSED_NW>(stream, d, n_images, nullptr, imgs, 1, lut, out_desc, nullptr, nullptr);
+    if (st != NSC_OK) return st;
     return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
 }
 
@@ -1530,15 +1453,10 @@ int nsc_interpolate_range_images_ex(const float *imgs, int32_t n_images, int32_t
     p.n_elevation = rows;
     p.target_rows = rows < MAXR ? rows : MAXR;
     p.interpolate = method;
-    int st;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const EncDev d = make_dev(&p, rows);
-    const LdsPlan lp = lds_plan(d.E, d.R, d.B, FUSED_NW);
-    auto kf = finish_kernel<FUSED_NW>;
-    if ((st = set_lds(kf, lp.total)) != NSC_OK) return st;
-    hipLaunchKernelGGL(kf, dim3(n_images), dim3(FUSED_NW * 64), lp.total, stream,
-                       static_cast<const unsigned *>(nullptr), imgs, 1, d, lut, static_cast<float *>(nullptr),
-                       static_cast<float *>(nullptr), out);
+    const int st = launch_finish<FUSED_NW>(stream, d, n_images, nullptr, imgs, 2, lut, nullptr, nullptr, out);
+    if (st != NSC_OK) return st;
     return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
 }
 

@@ -309,26 +309,36 @@ def test_projector_project_matches_reference(golden_dir):
 
 
 def test_scatter_and_finish_as_separate_launches():
-    """nsc_scatter_clouds + nsc_finish_images == nsc_encode_clouds (bit for bit)."""
-    import ctypes as C
+    """nsc_scatter_clouds + nsc_finish_images == nsc_encode_clouds (bit for bit) where nsc_encode_clouds runs other
+    kernels; where it would run the same split kernels, both launches are held to the C oracle."""
     from neural_spectral_codec_amd import _lib
     enc = _enc()
-    pts, off = synth.make_clouds_packed(range(50, 60), 20000, "ring")
-    tp, to = torch.from_numpy(pts).cuda(), torch.from_numpy(off).cuda()
-    ref = enc.encode_points_batch((tp, to))
-    L, p, lut = _lib.lib(), enc._params(), enc._lut(tp.device)
-    for n in (10, 600):                                   # split path and one-workgroup-per-cloud path
-        if n == 600:
-            pts2, off2 = synth.make_clouds_packed(range(600), 1000, "uniform")
-            tp, to = torch.from_numpy(pts2).cuda(), torch.from_numpy(off2).cuda()
-            ref = enc.encode_points_batch((tp, to))
+    L, p = _lib.lib(), enc._params()
+    # split_parts() gives 1 for the first two batches (20000 / 16384 = 1 part by size; 600 clouds >= 512): nsc_scatter_clouds
+    # takes its one-workgroup-per-cloud branch, nsc_encode_clouds the fast kernel, which is the reference.  The third is the
+    # smallest batch that splits (32768 / 16384 = 2 parts per cloud): nsc_scatter_clouds takes its parts > 1 branch,
+    # nsc_encode_clouds would run the same two kernels, so the reference is the C oracle.
+    for seeds, npts, kind in ((range(50, 60), 20000, "ring"), (range(600), 1000, "uniform"), (range(2), 32768, "uniform")):
+        n = len(seeds)
+        pts, off = synth.make_clouds_packed(seeds, npts, kind)
+        tp, to = torch.from_numpy(pts).cuda(), torch.from_numpy(off).cuda()
+        split = L.nsc_encode_clouds_path(n, n * npts, 4, p) == 3            # NSC_ENC_PATH_SPLIT
+        assert split == (npts == 32768)
         sq = torch.empty((n, 16, 360), dtype=torch.int32, device="cuda")
         out = torch.empty((n, 800), device="cuda")
-        st = _lib.stream_ptr(tp.device)
+        lut, st = enc._lut(tp.device), _lib.stream_ptr(tp.device)
         assert L.nsc_scatter_clouds(_lib.ptr(tp), _lib.ptr(to), n, int(tp.shape[0]), 4, p, _lib.ptr(sq), st) == 0
         assert L.nsc_finish_images(_lib.ptr(sq), n, p, _lib.ptr(lut), _lib.ptr(out), None, None, st) == 0
         torch.cuda.synchronize()
-        assert torch.equal(out, ref)
+        if not split:
+            assert torch.equal(out, enc.encode_points_batch((tp, to)))
+            continue
+        od, oraw, _ = orc.encode_clouds(pts, off, want_images=True)
+        bits = sq.cpu().numpy().view(np.uint32)
+        empty = bits == 0xffffffff                                          # NSC_EMPTY_BITS: no point in the pixel -> range 0
+        rng = np.where(empty, np.float32(0), np.sqrt(np.where(empty, 0, bits).astype(np.uint32).view(np.float32)))
+        assert np.array_equal(rng.view(np.uint32), oraw.view(np.uint32)), "scatter image differs from oracle"
+        assert _close(out.cpu().numpy(), od, 1e-6, 1e-9)
 
 
 def test_full_bench_size_properties():

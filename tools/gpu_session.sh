@@ -5,7 +5,6 @@
 #   suite [pytest args]      GPU test suite (-m gpu) into $O/pytest.log
 #   bench [bench args]       the driver's command (--steps 20 --warmup 5) + the long run; both JSON lines kept
 #   one NAME [bench args]    one bench.py invocation -> $O/NAME.json, one summary line
-#   ab CFG...                development build, interleaved A/B of encoder variants (tools/ab_enc.py); AB_ORDER honoured
 #   gat                      GAT parity tests, forward timings, per-kernel trace at N = 4541 / 1024
 #   build [DEFINE ...]       rebuild csrc/libnsc_hip.so with -DDEFINE ... (no argument: the product build)
 #   py SCRIPT [args]         python SCRIPT args  -> $O/<script>.log
@@ -45,10 +44,6 @@ run_step() {
         local name=$1; shift; cd /tmp
         timeout -k 10 600 python $R/bench.py --gpus 1 "$@" > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; return 1; }
         python3 $R/tools/bench_line.py $O/$name.json ;;
-    ab)
-        cd $R; NSC_DEV_BUILD=1 python neural-spectral-codec_amd/build.py > $O/devbuild.log 2>&1 || { tail -20 $O/devbuild.log; return 1; }
-        NSC_DEV_BUILD=1 timeout -k 10 900 python tools/ab_enc.py "$@" >> $O/ab.log 2>&1; rc=$?
-        cat $O/ab.log; return $rc ;;
     gat)
         cd $R; timeout -k 10 900 python -m pytest tests/test_gat_gpu.py -x -q -m gpu > $O/pytest_gat.log 2>&1; rc=$?
         tail -3 $O/pytest_gat.log; [ $rc -eq 0 ] || return 1
