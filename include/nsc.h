@@ -325,6 +325,21 @@ size_t nsc_topk_workspace_bytes(int32_t Q, int32_t N, int32_t k);
 int nsc_topk_smallest(const float *dist, int32_t Q, int32_t N, int32_t k, int64_t *idx, float *val,
                       void *ws, size_t ws_bytes, void *stream);
 
+/* Stage 1 over QUANTISED descriptors.  quantized (n, dim) uint16, 1 <= dim <= 1024.  A row is
+ * canonical iff its bins sum to exactly 65535 (summed in 32 bits; what nsc_quantize_descriptors emits for every
+ * histogram with a positive sum).  cdf[i][k] = sum_{j <= k} quantized[i][j] as uint16 for canonical rows, a row of
+ * zeros otherwise; canonical[i] = 1 / 0.  One launch, no workspace. */
+int nsc_w1q_cdf(const uint16_t *quantized, int32_t n, int32_t dim, uint16_t *cdf, uint8_t *canonical, void *stream);
+/* dist (Q, N) = float(sum_k |db_cdf[i][k] - q_cdf[q][k]|) / 65535.0f: the integer sum is exact in uint32, so a
+ * distance does not depend on the kernel or the batch; it is W1 between the dequantised histograms.  +inf where the
+ * database row or the query row is not canonical, or (both position arrays given) the pair is closer than min_dist,
+ * as in nsc_w1_distances.  dim % 8 == 0 and both CDF matrices 16-byte aligned: Q <= 4 HBM-streaming kernel (2 dim
+ * bytes per row, read once), Q > 4 register-tiled kernel; any other dim or alignment: a wave-per-row kernel with
+ * scalar loads.  One launch, no workspace.  Feed dist to nsc_topk_smallest. */
+int nsc_w1q_distances(const uint16_t *db_cdf, const uint8_t *db_canonical, int32_t N, int32_t dim,
+                      const uint16_t *q_cdf, const uint8_t *q_canonical, int32_t Q,
+                      const float *db_pos, const float *q_pos, float min_dist, float *dist, void *stream);
+
 /* Hard-negative triplet mining inside ONE sequence: replaces
  * TripletMiner._mine_sequence_triplets / _select_hard_negative (reference src/gnn/triplet_miner.py
  * :141-229, :314-359).  Members of the sequence are rows 0..n-1 in temporal order. */

@@ -25,6 +25,10 @@ What runs where
     interpolated range image (``keyframe.range_image``, else ``yaw_encoder`` on its points) goes into a device store
     (YawImages, 23 KB per keyframe at 16 rows) when it is inserted, a query's candidates are estimated in one launch
     and the guesses reach the registration as a device tensor.  Off (the default) nothing of this runs.
+  * With ``compressed=True`` stage 1 runs over 16-bit rows: ``retriever`` is a ``CompressedRetriever`` (compressed.py),
+    descriptors and queries are quantised as the wire format quantises them and ranked by the integer W1 of their
+    CDFs -- a quarter of the HBM per keyframe, distances that are those of the dequantised descriptors.  Off (the
+    default) nothing of this runs.
 
 ``ShardedTwoStageRetrieval`` is the multi-GPU form (BASELINE configs[3]): the database rows
 stay sharded over the ranks in the layout of ``distributed.shard_range``; every rank scores its own rows, the
@@ -43,6 +47,7 @@ import torch.distributed as dist
 from .. import _lib
 from . import geometric_verification as _gv
 from . import yaw_alignment as _yaw
+from .compressed import CompressedRetriever
 from .wasserstein import WassersteinRetriever, _topk
 
 _NO_POSE = np.full(3, np.inf, np.float32)     # a keyframe without a pose is never filtered out (:163)
@@ -74,13 +79,16 @@ class TwoStageRetrieval:
     def __init__(self, top_k: int = 10, spatial_filter_distance: float = 50.0, context_window: int = 10,
                  fitness_threshold: float = 0.3, rmse_threshold: float = 0.5, verification_method: str = "gicp",
                  use_torch: bool = True, device: str = 'cuda', verifier=None, edge_fn=None,
-                 prepare_geometry: bool = False, yaw_init: bool = False, yaw_encoder=None):
+                 prepare_geometry: bool = False, yaw_init: bool = False, yaw_encoder=None, compressed: bool = False):
         self.top_k = top_k
         self.spatial_filter_distance = spatial_filter_distance
         self.context_window = context_window
         self.fitness_threshold, self.rmse_threshold = fitness_threshold, rmse_threshold
         self.verification_method = verification_method
-        self.retriever = WassersteinRetriever(use_torch=True, device=device)          # :76-79
+        if compressed:                   # 16-bit database (compressed.py): descriptors are quantised at insert
+            self.retriever = CompressedRetriever(device=device)
+        else:
+            self.retriever = WassersteinRetriever(use_torch=True, device=device)      # :76-79
         self.verifier = verifier                                                      # :82-86 (Open3D: injected)
         self.edge_fn = edge_fn
         self.keyframes: list = []                                                     # :89
