@@ -35,11 +35,34 @@ def add_self_loops_mean(edge_index, edge_attr, n):
     return ei, ea
 
 
+def csr_order(edge_index, n):
+    """The entry order of the kernels' CSR-by-target (nsc_graph_build_csr) as a permutation of add_self_loops_mean's edge list:
+    targets ascending, a target's entries in edge-list order, its own loop last (a stable sort by target of a list whose loops
+    come last).  Returns (perm, row_ptr): CSR entry e is edge perm[e] of that list."""
+    ei, _ = add_self_loops_mean(edge_index, None, n)
+    perm = torch.sort(ei[1], stable=True)[1]
+    row_ptr = torch.zeros(n + 1, dtype=torch.int64)
+    row_ptr[1:] = torch.cumsum(torch.bincount(ei[1], minlength=n), 0)
+    return perm, row_ptr
+
+
+def _tap(taps, name, t):
+    """Record an intermediate in `taps`; a tensor of the autograd graph keeps its gradient (retain_grad), so that the
+    gradient that reaches it (dZ0, dG_l, dOut ...) is readable after backward()."""
+    if taps is not None:
+        if t.requires_grad:
+            t.retain_grad()
+        taps[name] = t
+
+
 def gatconv_reference(x, edge_index, edge_attr, lin_w, att_src, att_dst, lin_edge_w, att_edge, bias,
-                      negative_slope=0.2, return_alpha=False):
-    """GATConv 2.4.0 forward, heads=1.  edge_index[0]=source j, [1]=target i."""
+                      negative_slope=0.2, return_alpha=False, taps=None, tap_prefix="", att_mask=None):
+    """GATConv 2.4.0 forward, heads=1.  edge_index[0]=source j, [1]=target i.
+    att_mask: multiplicative attention-dropout mask (keep / (1 - p) or 0) per entry of the kernels' CSR (csr_order),
+    applied to alpha after the softmax."""
     n = x.shape[0]
     h = x @ lin_w.t()
+    _tap(taps, tap_prefix + "G", h)
     a_src = (h * att_src.view(1, -1)).sum(-1)
     a_dst = (h * att_dst.view(1, -1)).sum(-1)
     ei, ea = add_self_loops_mean(edge_index, edge_attr if lin_edge_w is not None else None, n)
@@ -47,12 +70,18 @@ def gatconv_reference(x, edge_index, edge_attr, lin_w, att_src, att_dst, lin_edg
     logit = a_src[j] + a_dst[i]
     if ea is not None and lin_edge_w is not None:
         logit = logit + ((ea @ lin_edge_w.t()) * att_edge.view(1, -1)).sum(-1)
+    _tap(taps, tap_prefix + "logit", logit)
     logit = F.leaky_relu(logit, negative_slope)
     m = torch.full((n,), float("-inf"), dtype=x.dtype).scatter_reduce(0, i, logit.detach(), "amax",
                                                                       include_self=True)
     p = torch.exp(logit - m[i])                       # the max shift carries no gradient (softmax identity)
     den = torch.zeros(n, dtype=x.dtype).index_add_(0, i, p)
     alpha = p / (den[i] + 1e-16)
+    _tap(taps, tap_prefix + "alpha", alpha)
+    if att_mask is not None:
+        by_edge = torch.empty_like(att_mask)
+        by_edge[csr_order(edge_index, n)[0]] = att_mask
+        alpha = alpha * by_edge.to(alpha.dtype)
     out = torch.zeros_like(h).index_add_(0, i, alpha.unsqueeze(1) * h[j])
     out = out + bias
     return (out, ei, alpha) if return_alpha else out
@@ -98,18 +127,27 @@ def gatconv_dense(x, edge_index, edge_attr, lin_w, att_src, att_dst, lin_edge_w,
     return (alpha @ h + bias.double()).float()
 
 
-def _bn(x, bn, training):
+def _bn(x, bn, training, taps=None, tap_prefix=""):
     if training:
         mean = x.mean(0)
         var = x.var(0, unbiased=False)
+        if taps is not None:
+            taps[tap_prefix + "mean"], taps[tap_prefix + "var"] = mean.detach(), var.detach()
     else:
         mean, var = bn.running_mean, bn.running_var
     return (x - mean) / torch.sqrt(var + bn.eps) * bn.weight + bn.bias
 
 
-def forward_from_state(sd, gnn_cfg, x, ei, ea, training=False):
+def forward_from_state(sd, gnn_cfg, x, ei, ea, training=False, taps=None, masks=None):
     """src/gnn/model.py:96-153 from a state dict (tensors may require grad -> torch autograd gives
-    the reference gradients).  gnn_cfg = (n_layers, residual, edge_dim)."""
+    the reference gradients).  gnn_cfg = (n_layers, residual, edge_dim).
+
+    taps: a dict that collects the intermediates -- "z0" / "y{l}" (pre-BatchNorm activations), "relu0" / "relu{l+1}" (ReLU
+    inputs), "bn0.mean" / "bn0.var" / "bn{l+1}.mean" / ".var" (batch statistics, biased variance), per layer "l{l}.G" = h W^T,
+    "l{l}.logit" (pre-leaky-ReLU), "l{l}.alpha" (pre-dropout), "h{l}" (layer inputs, h{L} feeds output_proj) and "out"; with
+    gradients taken, each keeps its .grad.
+    masks: {"att": [L tensors (nnz,) in CSR entry order], "feat": [L - 1 tensors (N, H)]} -- explicit dropout masks (values
+    0 or 1 / (1 - p)); with them this restatement is the reference for dropout > 0."""
     n_layers, residual, edge_dim = gnn_cfg
     use_edge = ea is not None and edge_dim is not None                   # :126
 
@@ -121,29 +159,40 @@ def forward_from_state(sd, gnn_cfg, x, ei, ea, training=False):
 
     x_input = x
     h = x @ sd["input_proj.weight"].t() + sd["input_proj.bias"]          # :116
-    h = F.relu(_bn(h, _B("input_norm"), training))                       # :117-118
+    _tap(taps, "z0", h)
+    h = _bn(h, _B("input_norm"), training, taps, "bn0.")
+    _tap(taps, "relu0", h)
+    h = F.relu(h)                                                        # :117-118
     for l in range(n_layers):
+        _tap(taps, f"h{l}", h)
         h_prev = h
         pre = f"convs.{l}."
         h = gatconv_reference(
             h, ei, ea if use_edge else None, sd[pre + "lin_src.weight"], sd[pre + "att_src"],
             sd[pre + "att_dst"], sd.get(pre + "lin_edge.weight") if use_edge else None,
-            sd.get(pre + "att_edge") if use_edge else None, sd[pre + "bias"])          # :126-129
-        h = _bn(h, _B(f"batch_norms.{l}"), training)                     # :132
+            sd.get(pre + "att_edge") if use_edge else None, sd[pre + "bias"], taps=taps, tap_prefix=f"l{l}.",
+            att_mask=masks["att"][l] if masks is not None else None)                   # :126-129
+        _tap(taps, f"y{l}", h)
+        h = _bn(h, _B(f"batch_norms.{l}"), training, taps, f"bn{l + 1}.")  # :132
         if l < n_layers - 1:
-            h = F.relu(h)                                                # :135-137 (dropout off)
+            _tap(taps, f"relu{l + 1}", h)
+            h = F.relu(h)                                                # :135-137 (dropout: only through `masks`)
+            if masks is not None:
+                h = h * masks["feat"][l].to(h.dtype)
         if residual and 0 < l < n_layers - 1:
             h = h + h_prev                                               # :140-141
+    _tap(taps, f"h{n_layers}", h)
     out = h @ sd["output_proj.weight"].t() + sd["output_proj.bias"]      # :144
     if residual:
         if "residual_proj.weight" in sd:
             out = out + x_input @ sd["residual_proj.weight"].t() + sd["residual_proj.bias"]
         else:
             out = out + x_input                                          # :147-151
+    _tap(taps, "out", out)
     return out
 
 
-def forward_reference(model, data, training=False, dtype=torch.float32):
+def forward_reference(model, data, training=False, dtype=torch.float32, taps=None, masks=None):
     """src/gnn/model.py:96-153 with the module's own parameters, on the CPU in float32 (the reference's
     arithmetic) or, with dtype=torch.float64, the same restatement evaluated in double precision (the
     checker for element-wise bounds: its own rounding error is negligible against the 1e-4 bar).
@@ -156,7 +205,7 @@ def forward_reference(model, data, training=False, dtype=torch.float32):
     ei = data.edge_index.detach().cpu()
     ea = getattr(data, "edge_attr", None)
     ea = ea.detach().cpu().to(dtype) if ea is not None else None
-    return forward_from_state(sd, (gnn.n_layers, gnn.residual, gnn.edge_dim), x, ei, ea, training)
+    return forward_from_state(sd, (gnn.n_layers, gnn.residual, gnn.edge_dim), x, ei, ea, training, taps=taps, masks=masks)
 
 
 def assert_within_bar(out, ref, rtol=1e-4, atol=1e-6, what="GAT output"):
@@ -171,11 +220,11 @@ def assert_within_bar(out, ref, rtol=1e-4, atol=1e-6, what="GAT output"):
     return worst
 
 
-def reference_gradients(model, data, loss_fn, dtype=torch.float32):
+def reference_gradients(model, data, loss_fn, dtype=torch.float32, taps=None, masks=None):
     """Reference gradients by torch autograd through the restatement (train-mode BatchNorm, no
     dropout).  loss_fn(embeddings) -> scalar.  Returns (embeddings, {state-dict key: grad}, grad_x, loss).
     dtype=torch.float64 evaluates the same restatement in double precision (used to measure how far float32
-    arithmetic itself sits from the exact result on ill-conditioned inputs)."""
+    arithmetic itself sits from the exact result on ill-conditioned inputs).  taps / masks: see forward_from_state."""
     gnn = getattr(model, "gnn", model)
     sd = {}
     for k, v in gnn.state_dict().items():
@@ -189,7 +238,7 @@ def reference_gradients(model, data, loss_fn, dtype=torch.float32):
     ei = data.edge_index.detach().cpu()
     ea = getattr(data, "edge_attr", None)
     ea = ea.detach().cpu().to(dtype) if ea is not None else None
-    emb = forward_from_state(sd, (gnn.n_layers, gnn.residual, gnn.edge_dim), x, ei, ea, training=True)
+    emb = forward_from_state(sd, (gnn.n_layers, gnn.residual, gnn.edge_dim), x, ei, ea, training=True, taps=taps, masks=masks)
     loss = loss_fn(emb)
     loss.backward()
     grads = {k: v.grad for k, v in sd.items() if v.requires_grad and "lin_dst" not in k and v.grad is not None}

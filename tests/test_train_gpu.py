@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import gat_oracle as go
+import train_families
 from neural_spectral_codec_amd.gnn.model import create_spectral_gnn
 from neural_spectral_codec_amd.gnn.trainer import TripletLoss, GNNTrainer
 from neural_spectral_codec_amd.keyframe import graph_manager as gm
@@ -87,7 +88,8 @@ def test_forward_train_and_gradients(n, edge_dim):
     loss = crit.forward_indexed(emb, trip[:, 0], trip[:, 1], trip[:, 2]) + (emb * R.cuda()).sum()
     loss.backward()
     # north_star bar, element-wise (|gpu - ref| <= 1e-4 |ref| + 1e-6), against the float64 evaluation of the restatement
-    emb64 = go.reference_gradients(m, g, lambda e: (e * 0).sum(), dtype=torch.float64)[0]
+    taps64 = {}
+    emb64 = go.reference_gradients(m, g, lambda e: (e * 0).sum(), dtype=torch.float64, taps=taps64)[0]
     _assert_train_forward(emb, emb_ref, emb64, f"train-mode forward, {n} nodes")
     assert abs(loss.item() - loss_ref.item()) <= 1e-4 * abs(loss_ref.item()) + 1e-6
     params = dict(m.gnn.named_parameters())
@@ -110,6 +112,8 @@ def test_forward_train_and_gradients(n, edge_dim):
     assert torch.allclose(m.gnn.input_norm.running_mean.cpu(), rm, rtol=1e-4, atol=1e-5)
     assert torch.allclose(m.gnn.input_norm.running_var.cpu(), rv, rtol=1e-4, atol=1e-5)
     assert int(m.gnn.input_norm.num_batches_tracked) == 1
+    # ... and so did every layer's BatchNorm (batch statistics from the float64 restatement's taps)
+    train_families.check_bn_running_stats(m, ref_model_state, taps64, n)
 
 
 def test_gradients_on_hub_graph():
