@@ -14,7 +14,6 @@
 // (c) a per-source kernel (transposed CSR, no atomics) for the feature gradient, (d) f32-MFMA GEMMs in
 // NT / NN / TN form with split-K slabs for the weight gradients (deterministic reduce).
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <algorithm>
 #include <atomic>
 #include <type_traits>
@@ -60,16 +59,16 @@ __device__ __forceinline__ float keep_scale(float p, unsigned long long seed, un
 //   AKM = false: A(m,k) = A[m*lda + k] (k contiguous);  AKM = true: A(m,k) = A[k*lda + m] (m contiguous)
 //   same for B.  blockIdx.z = split-K slice; slices write their own (M,N) slab.
 // ---------------------------------------------------------------------------------------------
-// (BM = 64 -- four accumulators per wave sharing every B operand -- was measured in round 4 on the split-K weight gradients:
-// 34.2 us against 25.8 us per product at 4 541 keyframes for the 32-row form, which stays.)
-template <bool AKM, bool BKM, int BM = 32>
+// (A 64-row tile -- four accumulators per wave sharing every B operand -- was measured in round 4 on the split-K weight gradients:
+// 34.2 us against 25.8 us per product at 4 541 keyframes for the 32-row tile, which stays.)
+template <bool AKM, bool BKM>
 __global__ __launch_bounds__(256) void gemm_gen_kernel(const float *__restrict__ A, int lda,
                                                        const float *__restrict__ B, int ldb, int M, int N,
                                                        int K, int kchunk, float *__restrict__ C, int ldc,
                                                        long long slab, const float *__restrict__ bias,
                                                        int accumulate)
 {
-    constexpr int BN = 64, BK = 64, LD = BK + 4, NH = BM / 16;
+    constexpr int BM = 32, BN = 64, BK = 64, LD = BK + 4, NH = BM / 16;
     __shared__ __attribute__((aligned(16))) float As[BM * LD];
     __shared__ __attribute__((aligned(16))) float Bs[BN * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -408,70 +407,26 @@ int launch_tn_glds(hipStream_t st, const float *A, int lda, const float *B, int 
 
 // ---------------------------------------------------------------------------------------------
 // column reductions over the N rows of an (N, C) matrix, float64 partials, two passes:
-//   out_a[c] = sum_n P[n][c] * (w ? w[n] : 1)
-//   out_b[c] = sum_n P[n][c] * Q'[n][c],  Q' = Q or (Q - qm[c]) * qs[c]        (Q nullable)
+//   a[c] = sum_n P[n][c] * (w ? w[n] : 1)
+//   b[c] = sum_n P[n][c] * Q[n][c]   or, with Q null,   sum_n P[n][c] * w2[n]        (Q, w2 nullable)
 // ---------------------------------------------------------------------------------------------
-// mode 0: out_a = A, out_b = B (plain sums, nullable outputs)
-// mode 1: BatchNorm statistics of P (Q = P): mean = A/N, var = B/N - mean^2 -> out_a = mean,
-//         out_b = 1/sqrt(var+eps); optional running-stat update (momentum, unbiased variance)
+// Where a final pass stores the two sums (backward_end_finals_kernel): all destinations nullable
 struct ColFinal {
-    int mode, N;
-    float eps, momentum;
-    float *out_a, *out_b, *run_mean, *run_var;
-    int acc_a, acc_b;          // mode 0: add to what out_a / out_b hold (gradient accumulation) instead of overwriting
-    float *copy_a, *copy_b;    // mode 0, nullable: the same sums also stored to (acc_copy: added into) a second vector -- the
-    int acc_copy;              // BatchNorm gradients are both an input of the next kernel and a parameter gradient
+    float *out_a, *out_b;
+    int acc_a, acc_b;          // add to what out_a / out_b hold (gradient accumulation) instead of overwriting
+    float *copy_a;             // a second vector that takes a, under acc_a (res_b beside out_b: both are the column sums of dOut)
 };
 
-__device__ __forceinline__ void colreduce_finish(const double *__restrict__ part, int R, int C, int c, int cx, int ry,
-                                                 double *sa, double *sb, const ColFinal &f)
-{
-    // 64 columns per workgroup, the R partial rows split over the 4 waves (fixed order -> deterministic)
-    // (loads in groups of 8 ahead of the adds: one partial per L2 round trip was a 5 us latency chain; the order of the
-    // additions is unchanged)
-    double a = 0.0, b = 0.0;
-    if (c < C) {
-        int r = ry;
-        for (; r + 28 < R; r += 32) {
-            double2 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const double2 *>(&part[((long long)(r + 4 * u) * C + c) * 2]);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { a += v[u].x; b += v[u].y; }
-        }
-        for (; r < R; r += 4) { a += part[((long long)r * C + c) * 2]; b += part[((long long)r * C + c) * 2 + 1]; }
-    }
-    sa[threadIdx.x] = a; sb[threadIdx.x] = b;
-    __syncthreads();
-    if (ry != 0 || c >= C) return;
-    a = (sa[cx] + sa[64 + cx]) + (sa[128 + cx] + sa[192 + cx]);
-    b = (sb[cx] + sb[64 + cx]) + (sb[128 + cx] + sb[192 + cx]);
-    if (f.mode == 0) {
-        if (f.out_a) f.out_a[c] = f.acc_a ? f.out_a[c] + (float)a : (float)a;
-        if (f.out_b) f.out_b[c] = f.acc_b ? f.out_b[c] + (float)b : (float)b;
-        if (f.copy_a) f.copy_a[c] = f.acc_copy ? f.copy_a[c] + (float)a : (float)a;
-        if (f.copy_b) f.copy_b[c] = f.acc_copy ? f.copy_b[c] + (float)b : (float)b;
-    } else {
-        const double mean = a / f.N;
-        double var = b / f.N - mean * mean;
-        if (var < 0.0) var = 0.0;
-        f.out_a[c] = (float)mean;
-        f.out_b[c] = (float)(1.0 / sqrt(var + (double)f.eps));
-        if (f.run_mean) {                                 // nn.BatchNorm1d: momentum 0.1, unbiased running_var
-            const double unb = f.N > 1 ? var * f.N / (f.N - 1) : var;
-            f.run_mean[c] = (1.0f - f.momentum) * f.run_mean[c] + f.momentum * (float)mean;
-            f.run_var[c] = (1.0f - f.momentum) * f.run_var[c] + f.momentum * (float)unb;
-        }
-    }
-}
-
-// The sum of the R partial rows for the 64 columns of a column block, by the workgroup that CONSUMES it (round 4: the forward's
-// BatchNorm apply and the backward's apply pass finish the reduction of the pass before them themselves -- 64 x 64 x 16 bytes of
-// L2 hits per workgroup instead of a 5 us launch per reduction).  Same order of additions as colreduce_finish: wave ry sums rows
-// ry, ry + 4, ..., then (w0 + w1) + (w2 + w3).  All 256 threads call it; the sums of column cx are returned to every thread.
+// The sum of the R partial rows for the 64 columns of a column block: wave ry sums rows ry, ry + 4, ... (fixed order ->
+// deterministic), then (w0 + w1) + (w2 + w3).  All 256 threads call it; the sums of column cx are returned to every thread.
+// Also called by the workgroup that CONSUMES the sums (round 4: the forward's BatchNorm apply and the backward's apply pass
+// finish the reduction of the pass before them themselves -- 64 x 64 x 16 bytes of L2 hits per workgroup instead of a 5 us
+// launch per reduction).
 __device__ __forceinline__ void colreduce_local(const double *__restrict__ part, int R, int C, int c, int cx, int ry,
                                                 double *sa, double *sb, double &a_out, double &b_out)
 {
+    // (loads in groups of 8 ahead of the adds: one partial per L2 round trip was a 5 us latency chain; the order of the
+    // additions is unchanged)
     double a = 0.0, b = 0.0;
     if (c < C) {
         int r = ry;
@@ -491,51 +446,27 @@ __device__ __forceinline__ void colreduce_local(const double *__restrict__ part,
     __syncthreads();
 }
 
-// Pass 1: every workgroup reduces its rows of a 64-column block to float64 partials.
-// (Round 3 measured both passes fused into ONE launch -- the last workgroup of a column block to arrive, by a device-scope
-// ticket, finishing the sum: the release / acquire fences it needs are an L2 write-back + invalidate on an 8-XCD part, and the
-// fused kernel took 26.5 us where the two launches take 8 + 5.5 -- the whole training step got slower by a third of its kernel
-// time.  Two launches it stays; inside a captured hipGraph the second launch costs about a microsecond.)
-__device__ __forceinline__ void colreduce_partial_body(const float *__restrict__ P, const float *__restrict__ w,
-                                                       const float *__restrict__ Q, const float *__restrict__ qm,
-                                                       const float *__restrict__ qs, int N, int C,
-                                                       int rows_per_block, double *__restrict__ part,
-                                                       const float *__restrict__ w2, int bx, int by)
+// The row walk of the column kernels' pass over an (N, C) matrix: thread (cx, ry) of a workgroup takes rows n0 + ry, n0 + ry + 4,
+// ... below n1 of its column.  load(n) fetches what row n contributes, step(n, v) consumes it.  8 rows' loads go out before the
+// first step (one row per round trip was an 8 us latency chain for 16 rows per thread); the steps keep their row order.
+template <class Load, class Step>
+__device__ __forceinline__ void colwalk(int n0, int n1, int ry, Load load, Step step)
 {
-    // w2 (with Q null): out_b[c] = sum_n P[n][c] * w2[n] -- the two attention-vector gradients of a layer read the same
-    // matrix with two weight vectors: one pass instead of two.  (bx, by): column block and row block of this workgroup
-    __shared__ double sa[256], sb[256];
-    const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-    const int c = bx * 64 + cx;
-    const int n0 = by * rows_per_block, n1 = min(N, n0 + rows_per_block);
-    double a = 0.0, b = 0.0;
-    if (c < C) {
-        const float m = qm ? qm[c] : 0.0f, s = qs ? qs[c] : 1.0f;
-        auto step = [&](float p, float wv, float qv) {
-            a += (double)(w ? p * wv : p);
-            if (Q) {
-                if (qm) qv = (qv - m) * s;
-                b += (double)p * (double)qv;
-            } else if (w2) {
-                b += (double)(p * qv);                          // qv carries w2[n] here
-            }
-        };
-        // 8 rows' loads go out before the first add (one row per round trip was an 8 us latency chain for 16 rows per
-        // thread); the additions keep their order
-        int n = n0 + ry;
-        for (; n + 28 < n1; n += 32) {
-            float pv[8], wv[8], qv[8];
+    int n = n0 + ry;
+    for (; n + 28 < n1; n += 32) {
+        decltype(load(n)) v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                pv[u] = P[(long long)(n + 4 * u) * C + c];
-                wv[u] = w ? w[n + 4 * u] : 1.0f;
-                qv[u] = Q ? Q[(long long)(n + 4 * u) * C + c] : (w2 ? w2[n + 4 * u] : 0.0f);
-            }
+        for (int u = 0; u < 8; ++u) v[u] = load(n + 4 * u);
 #pragma unroll
-            for (int u = 0; u < 8; ++u) step(pv[u], wv[u], qv[u]);
-        }
-        for (; n < n1; n += 4) step(P[(long long)n * C + c], w ? w[n] : 1.0f, Q ? Q[(long long)n * C + c] : (w2 ? w2[n] : 0.0f));
+        for (int u = 0; u < 8; ++u) step(n + 4 * u, v[u]);
     }
+    for (; n < n1; n += 4) step(n, load(n));
+}
+
+// The end of such a pass: the four waves' sums of column c, added left to right, as row `by` of the (R, C, 2) float64 partials
+__device__ __forceinline__ void colwalk_store(double a, double b, double *sa, double *sb, double *__restrict__ part, int by,
+                                              int C, int c, int cx, int ry)
+{
     sa[threadIdx.x] = a; sb[threadIdx.x] = b;
     __syncthreads();
     if (ry == 0 && c < C) {
@@ -546,13 +477,48 @@ __device__ __forceinline__ void colreduce_partial_body(const float *__restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void colreduce_partial_kernel(const float *__restrict__ P, const float *__restrict__ w,
-                                                                const float *__restrict__ Q, const float *__restrict__ qm,
-                                                                const float *__restrict__ qs, int N, int C,
-                                                                int rows_per_block, double *__restrict__ part,
-                                                                const float *__restrict__ w2)
+// Pass 1: every workgroup reduces its rows of a 64-column block to float64 partials.
+// (Round 3 measured both passes fused into ONE launch -- the last workgroup of a column block to arrive, by a device-scope
+// ticket, finishing the sum: the release / acquire fences it needs are an L2 write-back + invalidate on an 8-XCD part, and the
+// fused kernel took 26.5 us where the two launches take 8 + 5.5 -- the whole training step got slower by a third of its kernel
+// time.  Two launches it stays; inside a captured hipGraph the second launch costs about a microsecond.)
+struct ColRow { float p, w, q; };                                   // what a row gives colreduce_partial_body: P, w, Q (or w2)
+__device__ __forceinline__ void colreduce_partial_body(const float *__restrict__ P, const float *__restrict__ w,
+                                                       const float *__restrict__ Q, int N, int C, int rows_per_block,
+                                                       double *__restrict__ part, const float *__restrict__ w2, int bx, int by)
 {
-    colreduce_partial_body(P, w, Q, qm, qs, N, C, rows_per_block, part, w2, blockIdx.x, blockIdx.y);
+    // w2 (with Q null): b[c] = sum_n P[n][c] * w2[n] -- the two attention-vector gradients of a layer read the same
+    // matrix with two weight vectors: one pass instead of two.  (bx, by): column block and row block of this workgroup
+    __shared__ double sa[256], sb[256];
+    const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+    const int c = bx * 64 + cx;
+    const int n0 = by * rows_per_block, n1 = min(N, n0 + rows_per_block);
+    double a = 0.0, b = 0.0;
+    if (c < C) {
+        auto load = [&](int n) {
+            return ColRow{P[(long long)n * C + c], w ? w[n] : 1.0f, Q ? Q[(long long)n * C + c] : (w2 ? w2[n] : 0.0f)};
+        };
+        auto step = [&](int, ColRow r) {
+            const float p = r.p, wv = r.w, qv = r.q;
+            a += (double)(w ? p * wv : p);
+            if (Q) {
+                b += (double)p * (double)qv;
+            } else if (w2) {
+                b += (double)(p * qv);                          // qv carries w2[n] here
+            }
+        };
+        colwalk(n0, n1, ry, load, step);
+    }
+    colwalk_store(a, b, sa, sb, part, by, C, c, cx, ry);
+}
+
+// (The forward's BatchNorm statistics, P = Q = z, are its one caller, and w / w2 stay run-time arguments all the same: with them
+// compiled out the compiler put a vmcnt(0) wait behind every row's Q load -- 7.2 us against 4.9 us per launch at 4 541 keyframes.)
+__global__ __launch_bounds__(256) void colreduce_partial_kernel(const float *__restrict__ P, const float *__restrict__ w,
+                                                                const float *__restrict__ Q, int N, int C, int rows_per_block,
+                                                                double *__restrict__ part, const float *__restrict__ w2)
+{
+    colreduce_partial_body(P, w, Q, N, C, rows_per_block, part, w2, blockIdx.x, blockIdx.y);
 }
 
 // The attention-vector gradients of ALL layers (datt_src = sum_j da_src[j] g_j, datt_dst likewise: two weighted column sums of
@@ -572,16 +538,23 @@ struct ColExtra {
     float *out;
 };
 
-// Pass 2: the R partial rows of a 64-column block, summed in fixed order (deterministic), then the finish (ColFinal).
+// Pass 2: the R partial rows of a 64-column block, summed in fixed order (deterministic) and stored (ColFinal).
 __device__ __forceinline__ void colreduce_final_body(const double *__restrict__ part, int R, int C, const ColFinal &f,
                                                      const ColExtra &x, int bx)
 {
     __shared__ double sa[256], sb[256];
     const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
     const int c = bx * 64 + cx;
-    if (part) colreduce_finish(part, R, C, c, cx, ry, sa, sb, f);
+    if (part) {
+        double a, b;
+        colreduce_local(part, R, C, c, cx, ry, sa, sb, a, b);
+        if (ry == 0 && c < C) {
+            if (f.out_a) f.out_a[c] = f.acc_a ? f.out_a[c] + (float)a : (float)a;
+            if (f.out_b) f.out_b[c] = f.acc_b ? f.out_b[c] + (float)b : (float)b;
+            if (f.copy_a) f.copy_a[c] = f.acc_a ? f.copy_a[c] + (float)a : (float)a;
+        }
+    }
     if (x.part) {
-        __syncthreads();                                   // (sa is reused; the threads that left colreduce_finish early are back)
         double a = 0.0;
         if (c < C)
             for (int r = ry; r < x.R; r += 4) a += x.part[(long long)r * C + c];
@@ -592,12 +565,6 @@ __device__ __forceinline__ void colreduce_final_body(const double *__restrict__ 
             x.out[c] = x.acc ? x.out[c] + (float)a : (float)a;
         }
     }
-}
-
-__global__ __launch_bounds__(256) void colreduce_final_kernel(const double *__restrict__ part, int R, int C, ColFinal f,
-                                                              ColExtra x)
-{
-    colreduce_final_body(part, R, C, f, x, blockIdx.x);
 }
 
 // Every final pass a backward has left for its end (backward_end_finals_kernel): the attention-vector gradients of the layers
@@ -631,7 +598,9 @@ __global__ __launch_bounds__(256) void bn_bwd_colsum_kernel(const float *__restr
     if (c < C) {
         const float m = mean[c], s = invstd[c], ga = gamma[c], be = beta[c];
         const unsigned long long sd = p > 0.0f ? seed.get() : 0ull;
-        auto step = [&](int n, float dhv, float zv) {
+        auto load = [&](int n) { return float2{dh[(long long)n * C + c], z[(long long)n * C + c]}; };
+        auto step = [&](int n, float2 r) {
+            const float dhv = r.x, zv = r.y;
             const long long i = (long long)n * C + c;
             float g = dhv * keep_scale(p, sd, stream, (unsigned long long)i);
             if (relu) {
@@ -642,27 +611,9 @@ __global__ __launch_bounds__(256) void bn_bwd_colsum_kernel(const float *__restr
             a += (double)g;
             b += (double)g * (double)((zv - m) * s);
         };
-        int n = n0 + ry;
-        for (; n + 28 < n1; n += 32) {
-            float dv8[8], zv8[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                dv8[u] = dh[(long long)(n + 4 * u) * C + c];
-                zv8[u] = z[(long long)(n + 4 * u) * C + c];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) step(n + 4 * u, dv8[u], zv8[u]);
-        }
-        for (; n < n1; n += 4) step(n, dh[(long long)n * C + c], z[(long long)n * C + c]);
+        colwalk(n0, n1, ry, load, step);
     }
-    sa[threadIdx.x] = a; sb[threadIdx.x] = b;
-    __syncthreads();
-    if (ry == 0 && c < C) {
-        a = sa[cx] + sa[64 + cx] + sa[128 + cx] + sa[192 + cx];
-        b = sb[cx] + sb[64 + cx] + sb[128 + cx] + sb[192 + cx];
-        part[((long long)blockIdx.y * C + c) * 2] = a;
-        part[((long long)blockIdx.y * C + c) * 2 + 1] = b;
-    }
+    colwalk_store(a, b, sa, sb, part, blockIdx.y, C, c, cx, ry);
 }
 
 // BatchNorm backward, apply pass, with pass 1 of the bias gradient fused in (round 4: bn_bwd_apply_kernel +
@@ -692,24 +643,15 @@ __global__ __launch_bounds__(256) void bn_apply_colsum_kernel(float *__restrict_
     if (c < C) {
         const float m = mean[c], s = invstd[c], ga = gamma[c];
         const float invn = 1.0f / (float)N;
-        auto step = [&](int n, float dvv, float zv) {
+        auto load = [&](int n) { return float2{dv[(long long)n * C + c], z[(long long)n * C + c]}; };
+        auto step = [&](int n, float2 r) {
+            const float dvv = r.x, zv = r.y;
             const float xhat = (zv - m) * s;
             const float dz = ga * s * (dvv - t1 * invn - xhat * t2 * invn);
             dv[(long long)n * C + c] = dz;
             a += (double)dz;
         };
-        int n = n0 + ry;
-        for (; n + 28 < n1; n += 32) {
-            float dv8[8], zv8[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                dv8[u] = dv[(long long)(n + 4 * u) * C + c];
-                zv8[u] = z[(long long)(n + 4 * u) * C + c];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) step(n + 4 * u, dv8[u], zv8[u]);
-        }
-        for (; n < n1; n += 4) step(n, dv[(long long)n * C + c], z[(long long)n * C + c]);
+        colwalk(n0, n1, ry, load, step);
     }
     sa[threadIdx.x] = a;
     __syncthreads();
@@ -720,7 +662,7 @@ __global__ __launch_bounds__(256) void bn_apply_colsum_kernel(float *__restrict_
 // BatchNorm(train) apply + ReLU + dropout + residual:  h = drop(relu(gamma*xhat + beta)) + resid
 // ---------------------------------------------------------------------------------------------
 // (round 4: column-blocked, and it finishes the batch statistics of the reduction before it itself -- mean = A / N,
-// var = B / N - mean^2, invstd = 1 / sqrt(var + eps) in float64 from the float64 partials, exactly colreduce_finish's mode 1;
+// var = B / N - mean^2, invstd = 1 / sqrt(var + eps) in float64 from the float64 partials, as the separate final pass did;
 // the first row block stores mean / invstd for the backward and updates the running statistics)
 __global__ __launch_bounds__(256) void bn_act_kernel(const float *__restrict__ z, const double *__restrict__ part_in, int R,
                                                      float eps, float momentum, float *__restrict__ mean_out,
@@ -752,7 +694,9 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const float *__restrict__ z
     }
     const float ga = gamma[c], be = beta[c];
     const unsigned long long sd = p > 0.0f ? seed.get() : 0ull;
-    auto step = [&](int n, float zv, float rv) {
+    auto load = [&](int n) { return float2{z[(long long)n * C + c], resid ? resid[(long long)n * C + c] : 0.0f}; };
+    auto step = [&](int n, float2 r) {
+        const float zv = r.x, rv = r.y;
         const long long i = (long long)n * C + c;
         float v = (zv - m) * s * ga + be;
         if (relu) v = fmaxf(v, 0.0f);
@@ -760,18 +704,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const float *__restrict__ z
         if (resid) v += rv;
         out[i] = v;
     };
-    int n = n0 + ry;
-    for (; n + 28 < n1; n += 32) {
-        float z8[8], r8[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            z8[u] = z[(long long)(n + 4 * u) * C + c];
-            r8[u] = resid ? resid[(long long)(n + 4 * u) * C + c] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) step(n + 4 * u, z8[u], r8[u]);
-    }
-    for (; n < n1; n += 4) step(n, z[(long long)n * C + c], resid ? resid[(long long)n * C + c] : 0.0f);
+    colwalk(n0, n1, ry, load, step);
 }
 
 // Zero fill / copy as KERNELS (round 4).  The training step is replayed as a captured hipGraph, and a hipMemsetAsync captured into
@@ -851,19 +784,27 @@ __global__ __launch_bounds__(256) void att_dots_kernel(const float *__restrict__
     if (lane == 0) { a_src[i] = s; a_dst[i] = d; }
 }
 
-struct TrainAgg {
-    const int *row_ptr, *src, *eid;
+// What the raw attention logit of a CSR entry is computed from, forward and backward alike (edge_logit() fills it per layer)
+struct EdgeLogit {
+    const int *src, *eid;
     const float *loop_attr, *edge_attr, *v;   // v = W_edge^T att_edge (edge_dim), nullable
-    const float *a_src, *a_dst, *G, *bias;
+    const float *a_src, *a_dst;
+    int edge_dim;
+};
+
+struct TrainAgg {
+    const int *row_ptr;
+    EdgeLogit lg;
+    const float *G, *bias;
     float *alpha;                             // (nnz) softmax weights BEFORE dropout (saved)
     float *y;                                 // (N,H) aggregate + bias (pre-BatchNorm)
     float slope, p;
     SeedRef seed;
     unsigned stream;
-    int N, H, edge_dim;
+    int N, H;
 };
 
-__device__ __forceinline__ float edge_raw(const TrainAgg &a, int i, int e, int &j)
+__device__ __forceinline__ float edge_raw(const EdgeLogit &a, int i, int e, int &j)
 {
     j = a.src[e];
     float l = a.a_src[j] + a.a_dst[i];
@@ -891,7 +832,7 @@ __global__ __launch_bounds__(256) void agg_train_kernel(TrainAgg a)
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         int j = i;
         float l = -INFINITY;
-        if (e < end) { l = edge_raw(a, i, e, j); l = l > 0.f ? l : a.slope * l; }
+        if (e < end) { l = edge_raw(a.lg, i, e, j); l = l > 0.f ? l : a.slope * l; }
         const float m = wave_maxf(l);
         const float pe = (e < end) ? expf(l - m) : 0.0f;
         const float s = wave_sumf(pe) + 1e-16f;                      // PyG softmax
@@ -942,10 +883,10 @@ __global__ __launch_bounds__(256) void agg_train_kernel(TrainAgg a)
         return;
     }
     float m = -INFINITY;
-    for (int e = beg + lane; e < end; e += 64) { int j; float l = edge_raw(a, i, e, j); l = l > 0.f ? l : a.slope * l; m = fmaxf(m, l); }
+    for (int e = beg + lane; e < end; e += 64) { int j; float l = edge_raw(a.lg, i, e, j); l = l > 0.f ? l : a.slope * l; m = fmaxf(m, l); }
     m = wave_maxf(m);
     float s = 0.0f;
-    for (int e = beg + lane; e < end; e += 64) { int j; float l = edge_raw(a, i, e, j); l = l > 0.f ? l : a.slope * l; s += expf(l - m); }
+    for (int e = beg + lane; e < end; e += 64) { int j; float l = edge_raw(a.lg, i, e, j); l = l > 0.f ? l : a.slope * l; s += expf(l - m); }
     s = wave_sumf(s) + 1e-16f;                                   // PyG softmax
     // H <= 1024: up to 16 columns per lane; softmax weights travel between lanes by shuffle only
     float acc[16];
@@ -956,7 +897,7 @@ __global__ __launch_bounds__(256) void agg_train_kernel(TrainAgg a)
         int j = 0;
         float al = 0.0f, ald = 0.0f;
         if (e < end) {
-            float l = edge_raw(a, i, e, j); l = l > 0.f ? l : a.slope * l;
+            float l = edge_raw(a.lg, i, e, j); l = l > 0.f ? l : a.slope * l;
             al = expf(l - m) / s;
             a.alpha[e] = al;                                      // saved for the backward (pre-dropout)
             ald = al * keep_scale(a.p, a.seed.get(), a.stream, (unsigned long long)e);   // attention dropout
@@ -982,15 +923,15 @@ __global__ __launch_bounds__(256) void agg_train_kernel(TrainAgg a)
 
 // backward, per target i: dalpha'_e = <dY_i, g_j>; softmax + leaky-relu backward -> draw[e]; da_dst[i]
 struct AttBwdA {
-    const int *row_ptr, *src, *eid;
-    const float *loop_attr, *edge_attr, *v;
-    const float *a_src, *a_dst, *G, *alpha, *dY;
+    const int *row_ptr;
+    EdgeLogit lg;
+    const float *G, *alpha, *dY;
     float *draw;        // (nnz) gradient of the pre-leaky-relu logit
     float *da_dst;      // (N)
     float slope, p;
     SeedRef seed;
     unsigned stream;
-    int N, H, edge_dim;
+    int N, H;
 };
 
 // CH = ceil(H / 256): float4 chunks per lane.  Round 3: the common case (in-degree <= 64) keeps dY_i in registers, fetches
@@ -1003,9 +944,6 @@ __global__ __launch_bounds__(256) void att_bwd_target_kernel(AttBwdA a)
     const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= a.N) return;
     const int beg = a.row_ptr[i], end = a.row_ptr[i + 1], deg = end - beg;
-    TrainAgg t;   // view for edge_raw()
-    t.src = a.src; t.eid = a.eid; t.a_src = a.a_src; t.a_dst = a.a_dst; t.edge_attr = a.edge_attr;
-    t.loop_attr = a.loop_attr; t.v = a.v; t.edge_dim = a.edge_dim;
     if (deg <= 64) {
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         f32x4 dy[CH];
@@ -1016,7 +954,7 @@ __global__ __launch_bounds__(256) void att_bwd_target_kernel(AttBwdA a)
         }
         const int e_l = beg + lane;
         const bool have = e_l < end;
-        const int j_l = have ? a.src[e_l] : 0;
+        const int j_l = have ? a.lg.src[e_l] : 0;
         const float al_l = have ? a.alpha[e_l] : 0.0f;
         const unsigned long long seed = a.seed.get();
         float da = 0.0f;                                          // <dY_i, g_j> of entry `lane`, through the dropout mask
@@ -1052,7 +990,7 @@ __global__ __launch_bounds__(256) void att_bwd_target_kernel(AttBwdA a)
         float dr = 0.0f;
         if (have) {
             int j;
-            const float raw = edge_raw(t, i, e_l, j);
+            const float raw = edge_raw(a.lg, i, e_l, j);
             const float dl = al_l * (da - inner);                 // softmax backward
             dr = raw > 0.0f ? dl : a.slope * dl;                  // leaky-relu backward
             a.draw[e_l] = dr;
@@ -1063,7 +1001,7 @@ __global__ __launch_bounds__(256) void att_bwd_target_kernel(AttBwdA a)
         return;
     }
     auto dalpha = [&](int e) -> float {                       // <dY_i, g_j> through the dropout mask
-        const int j = a.src[e];
+        const int j = a.lg.src[e];
         float d = 0.0f;
         for (int c = lane; c < a.H; c += 64)
             d = __builtin_fmaf(a.dY[(long long)i * a.H + c], a.G[(long long)j * a.H + c], d);
@@ -1074,7 +1012,7 @@ __global__ __launch_bounds__(256) void att_bwd_target_kernel(AttBwdA a)
     float dd = 0.0f;
     for (int e = beg; e < end; ++e) {
         int j;
-        const float raw = edge_raw(t, i, e, j);
+        const float raw = edge_raw(a.lg, i, e, j);
         const float dl = a.alpha[e] * (dalpha(e) - inner);    // softmax backward
         const float dr = raw > 0.0f ? dl : a.slope * dl;      // leaky-relu backward
         if (lane == 0) a.draw[e] = dr;
@@ -1269,10 +1207,10 @@ __global__ __launch_bounds__(256) void backward_end_partials_kernel(EndPartials 
     unsigned b = blockIdx.x;
     if (b < p.n_att) {
         const int bx = (int)(b % (unsigned)p.nbx), t = (int)(b / (unsigned)p.nbx), by = t % p.R, l = t / p.R;
-        colreduce_partial_body(p.att.P[l], p.att.w[l], nullptr, nullptr, nullptr, p.N, p.C, p.rows, p.att.part[l], p.att.w2[l], bx, by);
+        colreduce_partial_body(p.att.P[l], p.att.w[l], nullptr, p.N, p.C, p.rows, p.att.part[l], p.att.w2[l], bx, by);
     } else if (b < p.n_att + p.n_ob) {
         b -= p.n_att;
-        colreduce_partial_body(p.ob_P, nullptr, nullptr, nullptr, nullptr, p.N, p.ob_C, p.rows, p.ob_part, nullptr,
+        colreduce_partial_body(p.ob_P, nullptr, nullptr, p.N, p.ob_C, p.rows, p.ob_part, nullptr,
                                (int)(b % (unsigned)p.ob_nbx), (int)(b / (unsigned)p.ob_nbx));
     } else {
         b -= p.n_att + p.n_ob;
@@ -1509,8 +1447,9 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float *__restrict_
 }
 
 // C = A B^T (+ bias) (+ C when accumulate) (+ resid), K in one slice.  resid (non-accumulating products only, same leading
-// dimension as C): C = product + resid, in the epilogue of the LDS-DMA GEMM where that kernel takes the product (the backward's
-// dh_{l} = dG W + dh_{l+1} residual path), by an add_inplace_kernel behind any other form -- the same two roundings either way.
+// dimension as C): C = product + resid, in the epilogue of the LDS-DMA GEMM where that kernel takes the product (the forward's
+// out = h_L W_out^T + b + x, the backward's dh_{l} = dG W + dh_{l+1} residual path), by an add_inplace_kernel behind any other
+// form -- the same two roundings either way.
 // A k-major B (BKM: the dX = dY W products) that the LDS-DMA GEMM cannot read in place goes through a transposed copy in `tw`:
 // NSC_EWORKSPACE when it does not fit (nothing launched).
 template <bool BKM>
@@ -1579,29 +1518,12 @@ inline int colred_rows(int N)
 // kernel, which finishes them itself (bn_act_kernel).
 void bn_forward(hipStream_t st, const float *z, int N, int C, double *part, float eps, float momentum, float *mean, float *invstd,
                 float *run_mean, float *run_var, const float *gamma, const float *beta, int relu, float p, SeedRef seed,
-                unsigned stream, const float *resid, float *out);
-
-void colreduce(hipStream_t st, const float *P, const float *w, const float *Q, const float *qm, const float *qs,
-               int N, int C, double *part, int mode, float eps, float momentum, float *out_a,
-               float *out_b, float *run_mean, float *run_var, int acc_a = 0, int acc_b = 0, float *copy_a = nullptr,
-               float *copy_b = nullptr, int acc_copy = 0, const float *w2 = nullptr, ColExtra extra = ColExtra{nullptr, 0, 0, nullptr})
-{
-    const int R = colred_rows(N);
-    const int rows = (N + R - 1) / R;
-    const ColFinal f = {mode, N, eps, momentum, out_a, out_b, run_mean, run_var, acc_a, acc_b, copy_a, copy_b, acc_copy};
-    hipLaunchKernelGGL(colreduce_partial_kernel, dim3((C + 63) / 64, R), dim3(256), 0, st, P, w, Q, qm, qs, N, C, rows, part, w2);
-    hipLaunchKernelGGL(colreduce_final_kernel, dim3((C + 63) / 64), dim3(256), 0, st, part, R, C, f, extra);
-}
-
-void bn_forward(hipStream_t st, const float *z, int N, int C, double *part, float eps, float momentum, float *mean, float *invstd,
-                float *run_mean, float *run_var, const float *gamma, const float *beta, int relu, float p, SeedRef seed,
                 unsigned stream, const float *resid, float *out)
 {
     const int R = colred_rows(N);
     const int rows = (N + R - 1) / R;
     const dim3 grid((C + 63) / 64, R);
-    hipLaunchKernelGGL(colreduce_partial_kernel, grid, dim3(256), 0, st, z, static_cast<const float *>(nullptr), z,
-                       static_cast<const float *>(nullptr), static_cast<const float *>(nullptr), N, C, rows, part,
+    hipLaunchKernelGGL(colreduce_partial_kernel, grid, dim3(256), 0, st, z, static_cast<const float *>(nullptr), z, N, C, rows, part,
                        static_cast<const float *>(nullptr));
     hipLaunchKernelGGL(bn_act_kernel, grid, dim3(256), 0, st, z, part, R, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta,
                        relu, p, seed, stream, resid, N, C, rows, out);
@@ -1609,7 +1531,7 @@ void bn_forward(hipStream_t st, const float *z, int N, int C, double *part, floa
 
 // BatchNorm backward of one layer in TWO launches (round 3: five): dV + the partials of its two column sums; then dZ in place (the
 // kernel finishes those sums itself and stores the BatchNorm parameter gradients) + the partials of ITS column sum, returned as
-// the ColExtra the caller hands to its next final pass (or to bias_final).
+// the ColExtra the caller hands to its next final pass.
 ColExtra bn_backward(hipStream_t st, const float *dh, const float *z, const float *mean, const float *invstd, const float *gamma,
                      const float *beta, int relu, float p, SeedRef seed, unsigned stream, int N, int C, float *dv,
                      float *g_bn_b, float *g_bn_w, int acc, double *part, double *part2, float *g_bias)
@@ -1625,13 +1547,25 @@ ColExtra bn_backward(hipStream_t st, const float *dh, const float *z, const floa
     return ColExtra{part2, R, acc, g_bias};
 }
 
-void bias_final(hipStream_t st, int C, const ColExtra &x)
+// CH = ceil(H / 256) of the attention kernels (H <= 1024: check_train) as a compile-time constant: f(std::integral_constant<int, CH>)
+template <class F> void dispatch_ch(int H, F f)
 {
-    const ColFinal none = {0, 0, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0};
-    hipLaunchKernelGGL(colreduce_final_kernel, dim3((C + 63) / 64), dim3(256), 0, st, static_cast<const double *>(nullptr), 0, C, none, x);
+    switch ((H + 255) / 256) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+    }
 }
 
 inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
+
+// Layer l's logit operands; use_edge: the forward had edge attributes and an edge projection (else the logit has no edge term)
+EdgeLogit edge_logit(const NscGraph *g, const float *edge_attr, bool use_edge, const TrainWs &w, int l, int edge_dim)
+{
+    return {g->src, g->eid, use_edge ? g->loop_attr : nullptr, use_edge ? edge_attr : nullptr, use_edge ? w.vvec(l) : nullptr,
+            w.a_src(l), w.a_dst(l), edge_dim};
+}
 
 int check_train(const NscGatModel *m, const NscGraph *g)
 {
@@ -1689,12 +1623,13 @@ int nsc_gat_forward_train(const NscGatModel *m, const NscGraph *g, const float *
     hipStream_t st = static_cast<hipStream_t>(stream_);
     const bool use_edge = m->edge_dim > 0 && edge_attr && g->loop_attr;
     const int upd = cfg->update_running_stats;
+    const SeedRef seed = {cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)};
 
     // input_proj (bias) -> z0 ; BatchNorm(batch stats) ; ReLU                 model.py:116-118
     gemm<false>(st, x, m->in_dim, m->in_w, m->in_dim, N, H, m->in_dim, w.z0, H, m->in_b, 0);
     bn_forward(st, w.z0, N, H, w.colpart, m->bn_eps, cfg->bn_momentum, w.mean0, w.invstd0,
                upd ? const_cast<float *>(m->in_bn_mean) : nullptr, upd ? const_cast<float *>(m->in_bn_var) : nullptr, m->in_bn_w,
-               m->in_bn_b, 1, 0.0f, SeedRef{0ull, nullptr}, 0u, nullptr, w.h(0));
+               m->in_bn_b, 1, 0.0f, seed, 0u, nullptr, w.h(0));                // (p = 0: no dropout, the seed is not read)
 
     for (int l = 0; l < L; ++l) {
         const NscGatLayer &Ly = m->layers[l];
@@ -1703,43 +1638,26 @@ int nsc_gat_forward_train(const NscGatModel *m, const NscGraph *g, const float *
         hipLaunchKernelGGL(att_dots_kernel, dim3((N + 3) / 4 + (use_edge ? 1 : 0)), dim3(256), 0, st, G, Ly.att_src, Ly.att_dst, N, H, as, ad,
                            use_edge ? Ly.lin_edge_w : nullptr, Ly.att_edge, m->edge_dim, vv);
         TrainAgg a;
-        a.row_ptr = g->row_ptr; a.src = g->src; a.eid = g->eid;
-        a.loop_attr = use_edge ? g->loop_attr : nullptr;
-        a.edge_attr = use_edge ? edge_attr : nullptr;
-        a.v = use_edge ? vv : nullptr;
-        a.a_src = as; a.a_dst = ad; a.G = G; a.bias = Ly.bias; a.alpha = w.alpha(l); a.y = y;
-        a.slope = m->negative_slope; a.p = cfg->dropout_p; a.seed = SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}; a.stream = 100u + l;
-        a.N = N; a.H = H; a.edge_dim = m->edge_dim;
-        switch ((H + 255) / 256) {
-        case 1: hipLaunchKernelGGL(agg_train_kernel<1>, dim3((N + 3) / 4), dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(agg_train_kernel<2>, dim3((N + 3) / 4), dim3(256), 0, st, a); break;
-        case 3: hipLaunchKernelGGL(agg_train_kernel<3>, dim3((N + 3) / 4), dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL(agg_train_kernel<4>, dim3((N + 3) / 4), dim3(256), 0, st, a); break;
-        }
+        a.row_ptr = g->row_ptr; a.lg = edge_logit(g, edge_attr, use_edge, w, l, m->edge_dim);
+        a.G = G; a.bias = Ly.bias; a.alpha = w.alpha(l); a.y = y;
+        a.slope = m->negative_slope; a.p = cfg->dropout_p; a.seed = seed; a.stream = 100u + l;
+        a.N = N; a.H = H;
+        dispatch_ch(H, [&](auto ch) {
+            hipLaunchKernelGGL(agg_train_kernel<decltype(ch)::value>, dim3((N + 3) / 4), dim3(256), 0, st, a);
+        });
         const int act = (l < L - 1);                                           // model.py:135-137
         const float *resid = (m->residual && l > 0 && l < L - 1) ? hin : nullptr;   // model.py:140-141
         bn_forward(st, y, N, H, w.colpart, m->bn_eps, cfg->bn_momentum, w.mean(l), w.invstd(l), upd ? const_cast<float *>(Ly.bn_mean) : nullptr,
-                   upd ? const_cast<float *>(Ly.bn_var) : nullptr, Ly.bn_w, Ly.bn_b, act, act ? cfg->dropout_p : 0.0f,
-                   SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}, 200u + l, resid, hout);
+                   upd ? const_cast<float *>(Ly.bn_var) : nullptr, Ly.bn_w, Ly.bn_b, act, act ? cfg->dropout_p : 0.0f, seed, 200u + l,
+                   resid, hout);
     }
     // output_proj + input residual                                             model.py:144-151
-    bool fused_res = false;
-    if (m->residual && m->in_dim == m->out_dim) {
-        // (acc + bias) + x in the GEMM's epilogue: the order of the GEMM followed by out += x, one launch and one pass over the
-        // (N, 800) output less (round 4)
-        GemmEpi ep = {};
-        ep.bias = m->out_b;
-        ep.resid = x; ep.ldr = m->in_dim;
-        fused_res = launch_glds<2>(st, w.h(L), H, m->out_w, H, nullptr, N, m->out_dim, m->out_dim, H, out, m->out_dim, ep);
-    }
-    if (!fused_res)
-        gemm<false>(st, w.h(L), H, m->out_w, H, N, m->out_dim, H, out, m->out_dim, m->out_b, 0);
-    if (m->residual && m->in_dim == m->out_dim) {
-        const long long tot = (long long)N * m->out_dim;
-        if (!fused_res) hipLaunchKernelGGL(add_inplace_kernel, dim3(blocks(tot)), dim3(256), 0, st, out, x, tot);
-    } else if (m->residual) {                                                  // out += residual_proj(x)  model.py:147-149
+    // identity residual: (acc + bias) + x in the GEMM's epilogue -- the order of the GEMM followed by out += x, one launch and one
+    // pass over the (N, 800) output less (round 4)
+    const bool res_id = m->residual && m->in_dim == m->out_dim;
+    gemm<false>(st, w.h(L), H, m->out_w, H, N, m->out_dim, H, out, m->out_dim, m->out_b, 0, {}, res_id ? x : nullptr);
+    if (m->residual && !res_id)                                                // out += residual_proj(x)  model.py:147-149
         gemm<false>(st, x, m->in_dim, m->res_w, m->in_dim, N, m->out_dim, m->in_dim, out, m->out_dim, m->res_b, 1);
-    }
     return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
 }
 
@@ -1756,6 +1674,7 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
     if (!ws || ws_bytes < w.total) return NSC_EWORKSPACE;
     if (m->residual && Din != Dout && (!gr->res_w || !gr->res_b)) return NSC_EINVAL;   // (before anything is enqueued)
     hipStream_t st = static_cast<hipStream_t>(stream_);
+    const SeedRef seed = {cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)};
     // what nothing inside the backward reads is reduced at its END, in batched launches: the final passes of every column sum
     // (in backward_end_finals_kernel), the attention-vector sums of all layers (in backward_end_partials_kernel), the edge terms,
     // the slab sums of the weight gradients
@@ -1776,16 +1695,15 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
     // over the batches of an optimizer step without a pass of axpy kernels behind the backward); gr->x is always overwritten
     const int acc = cfg->accumulate_grads ? 1 : 0;
 
+    const bool res_id = m->residual && Din == Dout, res_proj = m->residual && Din != Dout;
     // output_proj: out = h_L W_out^T + b (+ x)
     // (its column sums of dOut: with the other partial sums in the backward's second-to-last launch -- dOut is the caller's, nothing
-    // overwrites it)
-    push_final(w.colpart_ob, Dout, ColFinal{0, N, 0.f, 0.f, gr->out_b, nullptr, nullptr, nullptr, acc, 0, nullptr, nullptr, 0}, no_extra);
+    // overwrites it; they are db_res of a residual_proj as well, model.py:147-149: the same final stores both)
+    push_final(w.colpart_ob, Dout, ColFinal{gr->out_b, nullptr, acc, 0, res_proj ? gr->res_b : nullptr}, no_extra);
     if ((stt = gemm_wgrad(st, grad_out, Dout, w.h(L), H, Dout, H, N, gr->out_w, acc, splits, w.slabs.out_w, slabs))) return stt;
     float *dh = w.dh, *dh_prev = w.dh2;
     if ((stt = gemm<true>(st, grad_out, Dout, m->out_w, H, N, H, Dout, dh, H, nullptr, 0, w.tw))) return stt;   // dh_L = dOut W_out
-    const bool res_id = m->residual && Din == Dout, res_proj = m->residual && Din != Dout;
-    if (res_proj) {                // residual_proj: dW_res = dOut^T x, db_res = colsum dOut      model.py:147-149
-        colreduce(st, grad_out, nullptr, nullptr, nullptr, nullptr, N, Dout, w.colpart, 0, 0.f, 0.f, gr->res_b, nullptr, nullptr, nullptr, acc);
+    if (res_proj) {                // residual_proj: dW_res = dOut^T x                            model.py:147-149
         if ((stt = gemm_wgrad(st, grad_out, Dout, x, Din, Dout, Din, N, gr->res_w, acc, splits, w.slabs.res_w, slabs))) return stt;
     }
     if (gr->x) {
@@ -1810,38 +1728,27 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
         // pass AND are the BatchNorm parameter gradients (the final stores both); the conv bias gradient = column sums of dY:
         // its partials come out of the apply pass, its final rides along the attention-vector reduction below
         const ColExtra bias_x = bn_backward(st, dh, w.y(l), w.mean(l), w.invstd(l), Ly.bn_w, Ly.bn_b, act, act ? cfg->dropout_p : 0.0f,
-                                            SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}, 200u + l,
-                                            N, H, dY, Gl.bn_b, Gl.bn_w, acc, w.colpart, w.colpart2(l), Gl.bias);
+                                            seed, 200u + l, N, H, dY, Gl.bn_b, Gl.bn_w, acc, w.colpart, w.colpart2(l), Gl.bias);
         // attention backward
         AttBwdA A;
-        A.row_ptr = g->row_ptr; A.src = g->src; A.eid = g->eid;
-        A.loop_attr = use_edge ? g->loop_attr : nullptr; A.edge_attr = use_edge ? edge_attr : nullptr;
-        A.v = use_edge ? w.vvec(l) : nullptr;
-        A.a_src = w.a_src(l); A.a_dst = w.a_dst(l); A.G = G; A.alpha = alpha; A.dY = dY;
+        A.row_ptr = g->row_ptr; A.lg = edge_logit(g, edge_attr, use_edge, w, l, m->edge_dim);
+        A.G = G; A.alpha = alpha; A.dY = dY;
         A.draw = w.draw(l); A.da_dst = w.da_dst(l);
-        A.slope = m->negative_slope; A.p = cfg->dropout_p; A.seed = SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}; A.stream = 100u + l;
-        A.N = N; A.H = H; A.edge_dim = m->edge_dim;
-        switch ((H + 255) / 256) {
-        case 1: hipLaunchKernelGGL(att_bwd_target_kernel<1>, dim3((N + 3) / 4), dim3(256), 0, st, A); break;
-        case 2: hipLaunchKernelGGL(att_bwd_target_kernel<2>, dim3((N + 3) / 4), dim3(256), 0, st, A); break;
-        case 3: hipLaunchKernelGGL(att_bwd_target_kernel<3>, dim3((N + 3) / 4), dim3(256), 0, st, A); break;
-        default: hipLaunchKernelGGL(att_bwd_target_kernel<4>, dim3((N + 3) / 4), dim3(256), 0, st, A); break;
-        }
+        A.slope = m->negative_slope; A.p = cfg->dropout_p; A.seed = seed; A.stream = 100u + l;
+        A.N = N; A.H = H;
         AttBwdB Bk;
         Bk.t_ptr = g->t_ptr; Bk.t_entry = g->t_entry; Bk.tgt = g->tgt;
         Bk.alpha = alpha; Bk.dY = dY; Bk.draw = w.draw(l); Bk.da_dst = w.da_dst(l);
         Bk.att_src = Ly.att_src; Bk.att_dst = Ly.att_dst; Bk.dG = w.dg; Bk.da_src = w.da_src(l);
-        Bk.p = cfg->dropout_p; Bk.seed = SeedRef{cfg->seed, reinterpret_cast<const unsigned long long *>(cfg->seed_dev)}; Bk.stream = 100u + l; Bk.N = N; Bk.H = H;
-        switch ((H + 255) / 256) {
-        case 1: hipLaunchKernelGGL(att_bwd_source_kernel<1>, dim3((N + 3) / 4), dim3(256), 0, st, Bk); break;
-        case 2: hipLaunchKernelGGL(att_bwd_source_kernel<2>, dim3((N + 3) / 4), dim3(256), 0, st, Bk); break;
-        case 3: hipLaunchKernelGGL(att_bwd_source_kernel<3>, dim3((N + 3) / 4), dim3(256), 0, st, Bk); break;
-        default: hipLaunchKernelGGL(att_bwd_source_kernel<4>, dim3((N + 3) / 4), dim3(256), 0, st, Bk); break;
-        }
+        Bk.p = cfg->dropout_p; Bk.seed = seed; Bk.stream = 100u + l; Bk.N = N; Bk.H = H;
+        dispatch_ch(H, [&](auto ch) {
+            hipLaunchKernelGGL(att_bwd_target_kernel<decltype(ch)::value>, dim3((N + 3) / 4), dim3(256), 0, st, A);
+            hipLaunchKernelGGL(att_bwd_source_kernel<decltype(ch)::value>, dim3((N + 3) / 4), dim3(256), 0, st, Bk);
+        });
         // datt_src = sum_j da_src[j] g_j ; datt_dst = sum_j da_dst[j] g_j
         // (at the end of the backward, with the other layers': the conv-bias final rides along this layer's final)
         attp.P[l] = G; attp.w[l] = w.da_src(l); attp.w2[l] = w.da_dst(l); attp.part[l] = w.attpart(l);
-        push_final(w.attpart(l), H, ColFinal{0, N, 0.f, 0.f, Gl.att_src, Gl.att_dst, nullptr, nullptr, acc, acc, nullptr, nullptr, 0}, bias_x);
+        push_final(w.attpart(l), H, ColFinal{Gl.att_src, Gl.att_dst, acc, acc, nullptr}, bias_x);
         if (m->edge_dim > 0 && Gl.lin_edge_w && Gl.att_edge) {
             if (use_edge) {                         // reduced with the other layers' at the end (backward_end_partials_kernel)
                 edge_jobs.w_edge[l] = Ly.lin_edge_w; edge_jobs.att_edge[l] = Ly.att_edge;
@@ -1858,8 +1765,8 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
         float *t = dh; dh = dh_prev; dh_prev = t;
     }
     // h_0 = relu(bn(z0)),  z0 = x W_in^T + b_in
-    push_final(nullptr, H, ColFinal{0, 0, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0},
-               bn_backward(st, dh, w.z0, w.mean0, w.invstd0, m->in_bn_w, m->in_bn_b, 1, 0.0f, SeedRef{0ull, nullptr}, 0u,
+    push_final(nullptr, H, ColFinal{},
+               bn_backward(st, dh, w.z0, w.mean0, w.invstd0, m->in_bn_w, m->in_bn_b, 1, 0.0f, seed, 0u,    // (p = 0: the seed is not read)
                            N, H, w.dv, gr->in_bn_b, gr->in_bn_w, acc, w.colpart, w.colpart2(L), gr->in_b));
     if ((stt = gemm_wgrad(st, w.dv, H, x, Din, H, Din, N, gr->in_w, acc, splits, w.slabs.in_w, slabs))) return stt;
     if (gr->x && (stt = gemm<true>(st, w.dv, H, m->in_w, Din, N, Din, H, gr->x, Din, nullptr, 1, w.tw))) return stt;   // + dZ0 W_in
