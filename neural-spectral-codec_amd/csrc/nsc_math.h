@@ -83,12 +83,27 @@ NSC_HD int nsc_row_exact(float z, float sxy, const NscBinParams &bp)
 
 // ---- fast estimate --------------------------------------------------------------------------
 
+// v_rcp_f32, v_sqrt_f32 and v_rsq_f32 take a denormal input as zero, whatever the denormal mode of the wave: an estimate
+// fed with one (sxy below FLT_MIN) is never accepted, see nsc_row_fast / nsc_row_fast_narrow.
+#define NSC_F32_MIN_NORMAL 1.17549435e-38f
+
+#if defined(NSC_TEST_APPROX_BIAS) && !defined(__HIP_DEVICE_COMPILE__)
+/* host margin tests: the device instruction as a model -- denormal inputs flushed, the 1-ULP error pushed to either side
+ * (an infinite or zero result stays what it is) */
+inline float nsc_test_flush(float x) { return fabsf(x) < NSC_F32_MIN_NORMAL ? copysignf(0.0f, x) : x; }
+inline float nsc_test_push(float exact, bool up)      /* exact >= 0 at every caller: up = larger, !up = towards zero */
+{
+    if (!(fabsf(exact) < INFINITY) || exact == 0.0f) return exact;
+    return nextafterf(exact, up ? INFINITY : 0.0f);
+}
+#endif
+
 NSC_HD float nsc_rcp_approx(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_rcpf(x);    // v_rcp_f32, 1 ULP
-#elif defined(NSC_TEST_APPROX_BIAS)  /* host margin tests: push the 1-ULP error to either side */
-    return nextafterf(1.0f / x, NSC_TEST_APPROX_BIAS > 0 ? INFINITY : 0.0f);
+#elif defined(NSC_TEST_APPROX_BIAS)
+    return nsc_test_push(1.0f / nsc_test_flush(x), NSC_TEST_APPROX_BIAS > 0);
 #else
     return 1.0f / x;
 #endif
@@ -99,7 +114,7 @@ NSC_HD float nsc_sqrt_approx(float x)
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_sqrtf(x);   // v_sqrt_f32, 1 ULP
 #elif defined(NSC_TEST_APPROX_BIAS)
-    return nextafterf(sqrtf(x), NSC_TEST_APPROX_BIAS > 0 ? 0.0f : INFINITY);
+    return nsc_test_push(sqrtf(nsc_test_flush(x)), NSC_TEST_APPROX_BIAS < 0);
 #else
     return sqrtf(x);
 #endif
@@ -110,7 +125,7 @@ NSC_HD float nsc_rsq_approx(float x)
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_rsqf(x);    // v_rsq_f32, 1 ULP
 #elif defined(NSC_TEST_APPROX_BIAS)
-    return nextafterf(1.0f / sqrtf(x), NSC_TEST_APPROX_BIAS > 0 ? INFINITY : 0.0f);
+    return nsc_test_push(1.0f / sqrtf(nsc_test_flush(x)), NSC_TEST_APPROX_BIAS > 0);
 #else
     return 1.0f / sqrtf(x);
 #endif
@@ -178,7 +193,8 @@ NSC_HD bool nsc_row_fast(float z, float sxy, const NscBinParams &bp, int &row)
     int r = (int)fminf(fmaxf(fi, 0.0f), (float)(bp.E - 1));
     row = r;
     const float d = bp.el_delta;
-    return ((f > d) && (f < 1.0f - d)) || (u < -d) || (u > (float)bp.E + d);
+    // a denormal sxy reaches v_sqrt_f32 as 0: the estimate would call every such point vertical (min_range = 0 only)
+    return (((f > d) && (f < 1.0f - d)) || (u < -d) || (u > (float)bp.E + d)) && (sxy >= NSC_F32_MIN_NORMAL);
 }
 
 // Row estimate for sensors whose FOV edges lie within |tan(elevation)| < 0.58 (about +-30 deg, every
@@ -187,13 +203,15 @@ NSC_HD bool nsc_row_fast(float z, float sxy, const NscBinParams &bp, int &row)
 NSC_HD bool nsc_row_fast_narrow(float z, float sxy, const NscBinParams &bp, int &row)
 {
     float t = z * nsc_rsq_approx(sxy);
-    t = fminf(fmaxf(t, -0.62f), 0.62f);       // z = 0 and sxy = 0 gives NaN: ruled uncertain below
+    t = fminf(fmaxf(t, -0.62f), 0.62f);       // z = 0 and sxy = 0 (to v_rsq_f32: any sxy below FLT_MIN) gives NaN, which
+                                              // fmaxf turns into -0.62: ruled uncertain below
     const float u = __builtin_fmaf(nsc_atan_small(t), bp.el_u_scale, bp.el_u_bias);
     const float fi = floorf(u);
     const float f = u - fi;
     row = (int)fminf(fmaxf(fi, 0.0f), (float)(bp.E - 1));
     const float d = bp.el_delta;
-    return (((f > d) && (f < 1.0f - d)) || (u < -d) || (u > (float)bp.E + d)) && (sxy > 0.0f);
+    const bool clear = ((f > d) && (f < 1.0f - d)) || (u < -d) || (u > (float)bp.E + d);
+    return clear && (sxy >= NSC_F32_MIN_NORMAL);      // sxy = 0 or denormal: t above was NaN or +-inf, not an estimate
 }
 
 // One point -> (pixel, squared range).  Returns 0 if the point is dropped, else 1 | 2*(exact path
@@ -503,8 +521,8 @@ inline float nsc_az_edge_slack()
     return slack;
 }
 
-// Error budget of the float32 estimates (validated by tests/test_binning_margins.py on 1e8 points
-// and by the -m gpu debug-bin tests): v_rcp 1 ULP + polynomial + roundings, in bin units.
+// Error budget of the float32 estimates (validated by tests/test_abi_cpu.py::test_binning_margins_host, by the host
+// restatement of tests/test_point_families_cpu.py and by the -m gpu debug-bin tests): v_rcp 1 ULP + polynomial + roundings, in bin units.
 #define NSC_AZ_EST_ERR 4.0e-5f
 #define NSC_EL_EST_ERR 3.0e-5f
 

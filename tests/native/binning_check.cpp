@@ -1,5 +1,5 @@
 // Host-side validation of the fast binning estimate's acceptance margins (test tool, built by
-// tests/test_binning_margins.py with g++).  For random points it compares the fast estimate,
+// tests/test_abi_cpu.py::test_binning_margins_host with g++).  For random points it compares the fast estimate,
 // when it claims certainty, with the exact chain of csrc/nsc_math.h.
 //   usage: binning_check N seed emin_deg emax_deg E elev_f64 [lean [generator]]
 //   prints: n az_uncertain el_uncertain az_wrong el_wrong az_slack s_lo s_hi

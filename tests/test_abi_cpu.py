@@ -156,6 +156,17 @@ def test_binning_margins_host(tmp_path, bias):
         out = subprocess.check_output([exe] + args).decode().split()
         n, azu, elu, azw, elw = map(int, out[:5])
         assert azw == 0 and elw == 0, out
+    # the parameter sets of tests/point_families.py whose bins are narrower or whose rows are float32: 64 rows at the
+    # default field of view (the class default) in both row modes, 1.1 mrad bins, a symmetric and a lopsided narrow field
+    # of view, 32 float32 rows -- each on edge-parked points alone (generator 2) and on the mixed generator
+    for i, fov in enumerate((["-24.8", "2.0", "64", "1"], ["-24.8", "2.0", "64", "0"], ["-2", "2", "64", "1"],
+                             ["-11.25", "11.25", "64", "1"], ["-30", "10", "64", "1"], ["-25", "15", "32", "0"])):
+        for gen in ("2", "-1"):
+            out = subprocess.check_output([exe, "1000000", str(30 + i)] + fov + ["0", gen]).decode().split()
+            n, azu, elu, azw, elw = map(int, out[:5])
+            assert azw == 0 and elw == 0, (fov, gen, out)
+    out = subprocess.check_output([exe, "1000000", "40", "-24.8", "2.0", "16", "0", "1", "2"]).decode().split()
+    assert int(out[3]) == 0 and int(out[4]) == 0, out          # the lean estimate, float32 rows, edge-parked points only
     # on bench-like points (generator 0) all but a few 1e-4 are certain: the uncertain queue stays short
     out = subprocess.check_output([exe, "4000000", "23", "-24.8", "2.0", "16", "1", "1", "0"]).decode().split()
     n, azu, elu, azw, elw = map(int, out[:5])
