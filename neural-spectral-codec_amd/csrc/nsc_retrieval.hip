@@ -8,16 +8,18 @@
 //
 // 1-D W1 between histograms = L1 distance of their CDFs.  One wavefront per database row: the row is
 // streamed once from HBM (3 200 B for 800 bins), normalised and prefix-summed in registers (16 bins per
-// lane + a wave scan of the lane totals), and compared with every query CDF of the batch.
+// lane + a wave scan of the lane totals), and compared with every query CDF of the batch.  Against a database of
+// pre-normalised CDF rows: a stream kernel here for up to 4 queries, the tile kernel of nsc_w1_rows.h for batches.  That
+// header holds what this file shares with the 16-bit kernels of nsc_retrieval_q.hip: the spatial filter, the float32 row
+// form F32Rows, the tile kernel and the dispatch rules.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "../../include/nsc.h"
+#include "nsc_w1_rows.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float wave_sumf(float v)
 {
@@ -99,8 +101,8 @@ __global__ __launch_bounds__(256) void w1_dist_kernel(const float *__restrict__ 
     float v[PER];
     load_row<PER>(db + (long long)i * D, D, lane, v);
     row_cdf<PER>(v, lane, eps, 0);
-    float px = 0.f, py = 0.f, pz = 0.f;
-    if (db_pos) { px = db_pos[i * 3]; py = db_pos[i * 3 + 1]; pz = db_pos[i * 3 + 2]; }
+    float p[3] = {0.f, 0.f, 0.f};                                // the row's position, loaded once
+    if (db_pos) { p[0] = db_pos[i * 3]; p[1] = db_pos[i * 3 + 1]; p[2] = db_pos[i * 3 + 2]; }
     for (int q = 0; q < Q; ++q) {
         float w[PER];
         load_row<PER>(qcdf + (long long)q * D, D, lane, w);
@@ -111,10 +113,7 @@ __global__ __launch_bounds__(256) void w1_dist_kernel(const float *__restrict__ 
             if (c < D) s += fabsf(v[k] - w[k]);
         }
         s = wave_sumf(s);
-        if (db_pos && q_pos) {       // two_stage_retrieval.py:160-170: skip database frames that are too close
-            const float dx = px - q_pos[q * 3], dy = py - q_pos[q * 3 + 1], dz = pz - q_pos[q * 3 + 2];
-            if (sqrtf(dx * dx + dy * dy + dz * dz) < min_dist) s = INFINITY;
-        }
+        if (db_pos && q_pos && w1_too_close(p, q_pos + q * 3, min_dist)) s = INFINITY;
         if (lane == 0) dist[(long long)q * N + i] = s;
     }
 }
@@ -125,10 +124,7 @@ __global__ __launch_bounds__(256) void w1_dist_kernel(const float *__restrict__ 
 //
 // w1_stream_kernel<QT>: 1..4 queries.  HBM-bound: the query CDFs sit in registers, every wave walks its
 //   share of the rows with the next row's loads in flight (3 200 B per row, read once).
-// w1_tile_kernel: query batches.  VALU-bound (2 ops per |a - b| element): a 64-row x 64-query tile per
-//   workgroup, 4 x 4 results per thread, k in chunks of 32 staged k-major through LDS -- the structure of a
-//   register-tiled SGEMM with |a - b| in place of a * b.  Each (row, query) sum is accumulated by ONE thread in
-//   ascending k, so it does not depend on the tiling.
+// w1_tile_kernel<F32Rows, NQ> (nsc_w1_rows.h): query batches.
 // ---------------------------------------------------------------------------------------------
 template <int QT>
 __global__ __launch_bounds__(256) void w1_stream_kernel(const float *__restrict__ dbc, int N, int D,
@@ -181,121 +177,11 @@ __global__ __launch_bounds__(256) void w1_stream_kernel(const float *__restrict_
 #pragma unroll
             for (int t = 0; t < QT; ++t) {
                 if (t >= Q) break;
-                float r = s[t];
-                if (db_pos && q_pos) {                          // two_stage_retrieval.py:160-170
-                    const float dx = db_pos[i * 3] - q_pos[t * 3], dy = db_pos[i * 3 + 1] - q_pos[t * 3 + 1],
-                                dz = db_pos[i * 3 + 2] - q_pos[t * 3 + 2];
-                    if (sqrtf(dx * dx + dy * dy + dz * dz) < min_dist) r = INFINITY;
-                }
-                dist[(long long)t * N + i] = r;
+                dist[(long long)t * N + i] = w1_filter(s[t], db_pos, i, q_pos, t, min_dist);
             }
         }
 #pragma unroll
         for (int j = 0; j < NV; ++j) cur[j] = nxt[j];
-    }
-}
-
-constexpr int TL_I = 64, TL_K = 32, TL_LD = 68;               // LDS rows padded to 68 floats
-
-template <int NQ>   // queries per thread: the tile is 64 rows x 16 NQ queries
-__global__ __launch_bounds__(256) void w1_tile_kernel(const float *__restrict__ dbc, int N, int D,
-                                                      const float *__restrict__ qc, int Q,
-                                                      const float *__restrict__ db_pos,
-                                                      const float *__restrict__ q_pos, float min_dist,
-                                                      float *__restrict__ dist)
-{
-    __shared__ __attribute__((aligned(16))) float As[2][TL_K * TL_LD];   // [k][row]
-    __shared__ __attribute__((aligned(16))) float Bs[2][TL_K * TL_LD];   // [k][query]
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    constexpr int TL_Q = 16 * NQ;
-    constexpr int HB = (TL_Q + 31) / 32;                            // staging passes for the query tile
-    const int i0 = blockIdx.x * TL_I, q0 = blockIdx.y * TL_Q;
-    // staging: thread -> (tile row sr / sr + 32, k offset 4 sk): 128 contiguous bytes per 8 threads
-    const int sr = tid >> 3, sk = (tid & 7) * 4;
-    const float *ga[2], *gb[HB];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int ri = i0 + sr + 32 * h;
-        ga[h] = dbc + (long long)(ri < N ? ri : N - 1) * D + sk;
-    }
-#pragma unroll
-    for (int h = 0; h < HB; ++h) {
-        const int rq = q0 + sr + 32 * h;
-        gb[h] = qc + (long long)(rq < Q ? rq : Q - 1) * D + sk;
-    }
-    const int nchunks = (D + TL_K - 1) / TL_K;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    auto gload = [&](int ch, f32x4 (&ra)[2], f32x4 (&rb)[HB]) {
-        const int k = ch * TL_K + sk;                                // past D: zeros on both sides add |0 - 0|
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            ra[h] = (k + 4 <= D) ? *reinterpret_cast<const f32x4 *>(ga[h] + ch * TL_K) : zero;
-#pragma unroll
-        for (int h = 0; h < HB; ++h)
-            rb[h] = (k + 4 <= D && sr + 32 * h < TL_Q) ? *reinterpret_cast<const f32x4 *>(gb[h] + ch * TL_K) : zero;
-    };
-    auto stage = [&](int buf, const f32x4 (&ra)[2], const f32x4 (&rb)[HB]) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) As[buf][(sk + j) * TL_LD + sr + 32 * h] = ra[h][j];
-#pragma unroll
-        for (int h = 0; h < HB; ++h)
-            if (sr + 32 * h < TL_Q)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) Bs[buf][(sk + j) * TL_LD + sr + 32 * h] = rb[h][j];
-    };
-    float acc[4][NQ];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < NQ; ++b) acc[a][b] = 0.0f;
-
-    f32x4 ra[2], rb[HB];
-    gload(0, ra, rb);
-    stage(0, ra, rb);
-    __syncthreads();
-    for (int ch = 0; ch < nchunks; ++ch) {
-        const int cur = ch & 1;
-        if (ch + 1 < nchunks) gload(ch + 1, ra, rb);
-        const float *as = As[cur], *bs = Bs[cur];
-#pragma unroll 8
-        for (int k = 0; k < TL_K; ++k) {
-            const f32x4 av = *reinterpret_cast<const f32x4 *>(&as[k * TL_LD + 4 * tx]);
-            float bv[NQ];
-#pragma unroll
-            for (int b = 0; b < NQ; ++b) bv[b] = bs[k * TL_LD + NQ * ty + b];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < NQ; ++b) acc[a][b] += fabsf(av[a] - bv[b]);
-        }
-        if (ch + 1 < nchunks) stage(cur ^ 1, ra, rb);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int b = 0; b < NQ; ++b) {
-        const int q = q0 + NQ * ty + b;
-        if (q >= Q) continue;
-        float r[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int i = i0 + 4 * tx + a;
-            r[a] = acc[a][b];
-            if (db_pos && q_pos && i < N) {
-                const float dx = db_pos[i * 3] - q_pos[q * 3], dy = db_pos[i * 3 + 1] - q_pos[q * 3 + 1],
-                            dz = db_pos[i * 3 + 2] - q_pos[q * 3 + 2];
-                if (sqrtf(dx * dx + dy * dy + dz * dz) < min_dist) r[a] = INFINITY;
-            }
-        }
-        float *o = dist + (long long)q * N + i0 + 4 * tx;
-        if (i0 + 4 * tx + 3 < N && ((reinterpret_cast<uintptr_t>(o) & 15u) == 0)) {
-            *reinterpret_cast<f32x4 *>(o) = f32x4{r[0], r[1], r[2], r[3]};
-        } else {
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-                if (i0 + 4 * tx + a < N) o[a] = r[a];
-        }
     }
 }
 
@@ -646,22 +532,14 @@ int nsc_w1_distances_cdf(const float *db_cdf, int32_t N, int32_t D, const float 
     if (!db_cdf || !q_cdf || !dist) return NSC_EINVAL;
     if ((reinterpret_cast<uintptr_t>(db_cdf) | reinterpret_cast<uintptr_t>(q_cdf)) & 15u) return NSC_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    if (Q <= 4) {
-        int wgs = (N + 3) / 4;
-        if (wgs > 256 * 8) wgs = 256 * 8;                      // 8 resident workgroups per CU walk the rows
-        const dim3 grid(wgs), block(256);
+    if (Q <= W1_STREAM_MAX_Q) {
+        const dim3 grid(w1_stream_workgroups(N)), block(256);
         if (Q == 1) hipLaunchKernelGGL(w1_stream_kernel<1>, grid, block, 0, st, db_cdf, N, D, q_cdf, Q, db_pos, q_pos, min_dist, dist);
         else if (Q == 2) hipLaunchKernelGGL(w1_stream_kernel<2>, grid, block, 0, st, db_cdf, N, D, q_cdf, Q, db_pos, q_pos, min_dist, dist);
         else hipLaunchKernelGGL(w1_stream_kernel<4>, grid, block, 0, st, db_cdf, N, D, q_cdf, Q, db_pos, q_pos, min_dist, dist);
-    } else {
-        // tile of 64 rows x 16 / 32 / 64 queries: the smallest one that covers Q in as few column tiles as 64 does
-        const int nq = Q <= 16 ? 1 : (Q <= 32 || (Q > 64 && Q <= 96) ? 2 : 4);
-        const dim3 grid((N + TL_I - 1) / TL_I, (Q + 16 * nq - 1) / (16 * nq)), block(256);
-        if (nq == 1) hipLaunchKernelGGL(w1_tile_kernel<1>, grid, block, 0, st, db_cdf, N, D, q_cdf, Q, db_pos, q_pos, min_dist, dist);
-        else if (nq == 2) hipLaunchKernelGGL(w1_tile_kernel<2>, grid, block, 0, st, db_cdf, N, D, q_cdf, Q, db_pos, q_pos, min_dist, dist);
-        else hipLaunchKernelGGL(w1_tile_kernel<4>, grid, block, 0, st, db_cdf, N, D, q_cdf, Q, db_pos, q_pos, min_dist, dist);
+        return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
     }
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_w1_tile(st, F32Rows{db_cdf, q_cdf}, N, D, Q, db_pos, q_pos, min_dist, dist);
 }
 
 int nsc_revisit_queries(const double *positions, int32_t n, int32_t skip_frames, double distance_threshold,

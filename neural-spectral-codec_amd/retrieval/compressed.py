@@ -17,7 +17,7 @@ import torch
 
 from .. import _lib
 from ..encoding import quantization as _qz
-from .wasserstein import _dev_f32, _pos_f32, _topk
+from .wasserstein import _dev_f32, _grow_rows, _pos_f32, _topk
 
 
 def _dev_u16(q, device=None, name="quantized") -> torch.Tensor:
@@ -105,17 +105,13 @@ class CompressedRetriever:
     def _grow(self, need: int, d: int):
         if self._cdf is not None and int(self._cdf.shape[1]) != d:
             raise _lib.NscError(f"the database holds {self.n_bins}-bin rows (got {d})")
-        if self._cdf is not None and need <= self._cdf.shape[0]:
-            return
-        cap = max(need, 2 * (0 if self._cdf is None else self._cdf.shape[0]), self.INITIAL_CAPACITY)
-        # int16 storage: the uint16 bits, in a dtype every torch copy supports
-        nc = torch.empty((cap, d), dtype=torch.int16, device=self.device)
-        nk = torch.zeros((cap,), dtype=torch.uint8, device=self.device)
-        npos = torch.zeros((cap, 3), dtype=torch.float32, device=self.device)
-        if self._cdf is not None:
-            n = self.database_size
-            nc[:n], nk[:n], npos[:n] = self._cdf[:n], self._ok[:n], self._pos[:n]
-        self._cdf, self._ok, self._pos = nc, nk, npos
+        if self._cdf is None:
+            # int16 storage: the uint16 bits, in a dtype every torch copy supports
+            self._cdf, self._ok, self._pos = (torch.empty(s, dtype=t, device=self.device) for s, t in
+                                              (((0, d), torch.int16), ((0,), torch.uint8), ((0, 3), torch.float32)))
+        if need > self._cdf.shape[0]:
+            bufs = (self._cdf, self._ok, self._pos)
+            self._cdf, self._ok, self._pos = _grow_rows(bufs, self.database_size, need, self.INITIAL_CAPACITY)
 
     def add_quantized(self, quantized, positions=None):
         """(n, D) uint16 rows as the quantiser emits them; ``positions`` (n, 3) optional keyframe translations for

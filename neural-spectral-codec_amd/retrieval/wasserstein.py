@@ -33,6 +33,16 @@ def _pos_f32(p, device):
     return p.detach().to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
 
 
+def _grow_rows(bufs, live: int, need: int, first: int = 1024):
+    """Amortised doubling: zeroed (max(need, 2 * cap, first), ...) buffers holding the ``live`` rows; a None stays None."""
+    cap = max(need, 2 * int(bufs[0].shape[0]), first)
+    out = [None if b is None else b.new_zeros((cap,) + tuple(b.shape[1:])) for b in bufs]
+    for nb, b in zip(out, bufs):
+        if b is not None:
+            nb[:live] = b[:live]
+    return out
+
+
 def _cdf(h: torch.Tensor, eps: float, divide_plain: bool) -> torch.Tensor:
     out = torch.empty_like(h)
     with torch.cuda.device(h.device):
@@ -172,17 +182,11 @@ class WassersteinRetriever:
             h = h.unsqueeze(0)
         n, d = int(h.shape[0]), int(h.shape[1])
         need = self.database_size + n
-        if self._buf is None or need > self._buf.shape[0]:
-            cap = max(need, 2 * (0 if self._buf is None else self._buf.shape[0]), 1024)
-            nb = torch.empty((cap, d), dtype=torch.float32, device=self.device)
-            nc = torch.empty((cap, d), dtype=torch.float32, device=self.device) if d % 4 == 0 else None
-            npos = torch.zeros((cap, 3), dtype=torch.float32, device=self.device)
-            if self._buf is not None:
-                nb[:self.database_size] = self._buf[:self.database_size]
-                npos[:self.database_size] = self._pos[:self.database_size]
-                if nc is not None:
-                    nc[:self.database_size] = self._cdf_buf[:self.database_size]
-            self._buf, self._pos, self._cdf_buf = nb, npos, nc
+        if self._buf is None:
+            self._buf, self._pos = h.new_empty((0, d)), h.new_empty((0, 3))
+            self._cdf_buf = h.new_empty((0, d)) if d % 4 == 0 else None
+        if need > self._buf.shape[0]:
+            self._buf, self._pos, self._cdf_buf = _grow_rows((self._buf, self._pos, self._cdf_buf), self.database_size, need)
         self._buf[self.database_size:need] = h
         if self._cdf_buf is not None:
             # the database form of the normalisation (wasserstein.py:158-163), done once per inserted row

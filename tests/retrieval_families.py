@@ -18,7 +18,8 @@ import numpy as np
 
 import miner_oracle as mo
 
-# ---- the dispatch constants of csrc/nsc_retrieval.hip, restated (test_retrieval_families_cpu.py parses the source) ----
+# ---- the dispatch constants of csrc/nsc_retrieval.hip and csrc/nsc_w1_rows.h, restated (test_retrieval_families_cpu.py
+# parses the sources) ----
 TK_CHUNK = 2048            # distances per top-k stage-1 workgroup
 TK_MAX_K = 256             # k beyond this: stable device sort
 TK_MAX_CAND = 4096         # chunks * k beyond this: stable device sort
@@ -73,22 +74,26 @@ def topk_path(N, k):
     return SimpleNamespace(path="kernel" if kern else "sort", chunks=chunks, last=N - (chunks - 1) * TK_CHUNK)
 
 
-def parse_constants(src):
-    """the same constants read out of the .hip text"""
-    def one(pat):
-        m = re.search(pat, src)
+def parse_constants(src, shared):
+    """the same constants read out of the .hip text and, for what both W1 files share, csrc/nsc_w1_rows.h"""
+    def one(pat, text=src):
+        m = re.search(pat, text)
         assert m, pat
         return m
     out = {"TK_CHUNK": int(one(r"constexpr int TK_CHUNK = (\d+)").group(1)),
-           "TL_I": int(one(r"constexpr int TL_I = (\d+)").group(1)),
+           "TL_I": int(one(r"constexpr int TL_I = (\d+)", shared).group(1)),
            "per_of": one(r"int per_of\(int D\) \{(.*?)\}").group(1).strip()}
-    m = one(r"if \(wgs > (\d+) \* (\d+)\) wgs = (\d+) \* (\d+);")
-    assert m.group(1, 2) == m.group(3, 4)
+    m = one(r"constexpr int W1_STREAM_WG_CAP = (\d+) \* (\d+);", shared)
+    one(r"int w1_stream_workgroups\(int N\) \{ const int wgs = \(N \+ 3\) / 4; "
+        r"return wgs < W1_STREAM_WG_CAP \? wgs : W1_STREAM_WG_CAP; \}", shared)
+    one(r"const dim3 grid\(w1_stream_workgroups\(N\)\)")
     out["STREAM_WG_CAP"] = int(m.group(1)) * int(m.group(2))
     m = one(r"if \(k > (\d+) \|\| \(long long\)chunks \* k > (\d+)\) return NSC_EUNSUPPORTED;")
     out["TK_MAX_K"], out["TK_MAX_CAND"] = int(m.group(1)), int(m.group(2))
-    out["nq"] = one(r"const int nq = (.*?);").group(1).strip()
-    out["stream_split"] = one(r"if \(Q <= (\d+)\) \{\s*int wgs = \(N \+ 3\) / 4;").group(1)
+    out["nq"] = one(r"int w1_tile_nq\(int Q\) \{ return (.*?); \}", shared).group(1).strip()
+    one(r"const int nq = w1_tile_nq\(Q\);", shared)
+    one(r"if \(Q <= W1_STREAM_MAX_Q\) \{\s*const dim3 grid\(w1_stream_workgroups\(N\)\)")
+    out["stream_split"] = one(r"constexpr int W1_STREAM_MAX_Q = (\d+);", shared).group(1)
     return out
 
 

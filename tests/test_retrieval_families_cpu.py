@@ -1,6 +1,6 @@
 """The retrieval input families (tests/retrieval_families.py) without a GPU: the exact integer W1 equals the float32
-oracle bit for bit on every dyadic family, ``path_of`` agrees with the constants of csrc/nsc_retrieval.hip (a change
-there fails here, loudly), and every (N, Q, D) the GPU tests use reaches the kernel instance it is named after."""
+oracle bit for bit on every dyadic family, ``path_of`` agrees with the constants of csrc/nsc_retrieval.hip and
+csrc/nsc_w1_rows.h (a change there fails here, loudly), and every (N, Q, D) the GPU tests use reaches the kernel instance it is named after."""
 import os
 
 import numpy as np
@@ -11,11 +11,12 @@ import retrieval_families as F
 import retrieval_oracle as ro
 from retrieval_families import CDF_D, STREAM_D, STREAM_N, STREAM_Q, TILE_D, TILE_INST, TILE_N, TILE_Q, TOPK_K, TOPK_N, k_of
 
-HIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "neural-spectral-codec_amd", "csrc",
-                   "nsc_retrieval.hip")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "neural-spectral-codec_amd", "csrc")
+HIP, SHARED = os.path.join(CSRC, "nsc_retrieval.hip"), os.path.join(CSRC, "nsc_w1_rows.h")
+
 
 def hip_constants():
-    return F.parse_constants(open(HIP).read())
+    return F.parse_constants(open(HIP).read(), open(SHARED).read())
 
 
 def test_path_of_agrees_with_the_hip_source():
@@ -25,11 +26,13 @@ def test_path_of_agrees_with_the_hip_source():
     assert c["per_of"] == "int p = ((D + 63) / 64 + 3) / 4 * 4; return p < 4 ? 4 : p;"
     assert c["nq"] == "Q <= 16 ? 1 : (Q <= 32 || (Q > 64 && Q <= 96) ? 2 : 4)"
     assert c["stream_split"] == "4"
-    src = open(HIP).read()
+    src, shared = open(HIP).read(), open(SHARED).read()
     for inst in ("w1_cdf_kernel<4>", "w1_cdf_kernel<8>", "w1_cdf_kernel<12>", "w1_cdf_kernel<16>", "w1_dist_kernel<8>",
                  "w1_dist_kernel<12>", "w1_stream_kernel<1>", "w1_stream_kernel<2>", "w1_stream_kernel<4>",
-                 "w1_tile_kernel<1>", "w1_tile_kernel<2>", "w1_tile_kernel<4>"):
+                 "launch_w1_tile(st, F32Rows{"):
         assert inst in src, inst
+    for inst in ("w1_tile_kernel<Rows, 1>", "w1_tile_kernel<Rows, 2>", "w1_tile_kernel<Rows, 4>"):
+        assert inst in shared, inst
 
 
 def test_per_of_and_the_d_set_reach_all_four_instances():

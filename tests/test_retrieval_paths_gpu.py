@@ -92,6 +92,7 @@ def test_dist_kernel_exact(D):
 def _free_big():
     yield
     big.cache_clear()
+    cubed.cache_clear()
 
 
 @functools.lru_cache(maxsize=1)
@@ -137,22 +138,64 @@ def test_tile_kernel_exact(D):
             assert_bits(_w()._distances_cdf(dbc[:N], qc[:Q]), want[:Q, :N], f"tile D={D} N={N} Q={Q}")
 
 
+@functools.lru_cache(maxsize=1)
+def cubed():
+    """257 database rows and 97 queries on which float32 sums do round, as device CDF rows and read back"""
+    D, N = 800, 257
+    dbc = _w()._cdf(dev(F.rounding_rows("cubed", N, D, 11)), EPS, False)
+    qc = _w()._cdf(dev(F.rounding_rows("cubed", 97, D, 12)), EPS, True)
+    return dbc, qc, dbc.cpu().numpy(), qc.cpu().numpy()
+
+
 def test_tile_kernel_batch_independence():
     """One query's row of distances is bitwise the same at Q = 5, 17, 33, 65, 97 and at any position in the batch (each
-    (row, query) sum is accumulated by one thread in ascending k), on rows where rounding does happen."""
+    (row, query) sum is accumulated by one thread in ascending k), on rows where rounding does happen -- and it IS the
+    sequential float32 sum in ascending k of the CDF rows the kernel read (np.cumsum in float32 is sequential; a pairwise
+    or a descending sum of these rows changes bits in more than 230 of the 257)."""
     D, N = 800, 257
     assert [F.path_of(N, Q, D).inst for Q in (5, 17, 33, 65, 97)] == [1, 2, 4, 2, 4]
-    db = F.rounding_rows("cubed", N, D, 11)
-    qs = F.rounding_rows("cubed", 97, D, 12)
-    dbc, qc = _w()._cdf(dev(db), EPS, False), _w()._cdf(dev(qs), EPS, True)
+    dbc, qc, dbc_h, qc_h = cubed()
     base = _w()._distances_cdf(dbc, qc[:5])[0].cpu().numpy()
     assert np.isfinite(base).all() and len(np.unique(base)) > 200
+    diff = np.abs(dbc_h - qc_h[0])
+    assert diff.dtype == np.float32
+    assert_bits(base, np.cumsum(diff, axis=1, dtype=np.float32)[:, -1], "tile kernel vs the ascending-k float32 sum")
     for Q in (5, 17, 33, 65, 97):
         for at in sorted({0, 1, Q // 2, Q - 1}):
             order = list(range(1, Q))
             order.insert(at, 0)                                  # query 0 moved to position `at`
             got = _w()._distances_cdf(dbc, qc[torch.tensor(order).cuda()].contiguous())[at]
             assert_bits(got, base, f"batch independence Q={Q} at={at}")
+
+
+def stream_sum(diff):
+    """w1_stream_kernel's sum of each row of |a - b| (N, D) in float32: lane l adds its float4 chunks c = l + 64 j, j
+    ascending, components x, y, z, w (a lane past the row adds zeros), then v += v[lane ^ o] for o = 32, 16, .., 1"""
+    N, D = diff.shape
+    assert diff.dtype == np.float32 and D % 4 == 0 and D <= 1024
+    chunks = np.zeros((N, 4 * 64 * 4), np.float32)
+    chunks[:, :D] = diff
+    chunks = chunks.reshape(N, 4, 64, 4)                         # [row][j][lane][component]
+    v = np.zeros((N, 64), np.float32)
+    for j in range(4):
+        for comp in range(4):
+            v = v + chunks[:, j, :, comp]
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, np.arange(64) ^ o]
+    assert v.dtype == np.float32
+    return v[:, 0]
+
+
+def test_stream_kernel_accumulation_order():
+    """The float stream kernel at Q = 1 on the rounding rows equals its restated lane-strided sum and butterfly bit for
+    bit; that order is not the ascending-k one (the restatement itself differs from it in most of the 257 rows)."""
+    D, N = 800, 257
+    assert F.path_of(N, 1, D).kernel == "stream" and F.path_of(N, 1, D).inst == 1
+    dbc, qc, dbc_h, qc_h = cubed()
+    diff = np.abs(dbc_h - qc_h[0])
+    want = stream_sum(diff)
+    assert (want.view(np.uint32) != np.cumsum(diff, axis=1, dtype=np.float32)[:, -1].view(np.uint32)).sum() > 200
+    assert_bits(_w()._distances_cdf(dbc, qc[:1])[0], want, "stream kernel vs its restated order")
 
 
 # ---------------------------------------------------------------------------------------------------------------------

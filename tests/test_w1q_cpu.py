@@ -1,6 +1,7 @@
 """Stage 1 over quantised descriptors without a GPU: the restatement (tests/w1q_restatement.py) against the float32
 retrieval oracle on dequantised rows, the canonical-row property of the quantiser, the argument checks of the two
-entry points, and ``path_of`` against the constants of csrc/nsc_retrieval_q.hip (a change there fails here)."""
+entry points, and ``path_of`` against the constants of csrc/nsc_retrieval_q.hip and csrc/nsc_w1_rows.h (a change there
+fails here)."""
 import functools
 import glob
 import os
@@ -15,6 +16,7 @@ import w1q_restatement as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIP = os.path.join(ROOT, "neural-spectral-codec_amd", "csrc", "nsc_retrieval_q.hip")
+SHARED = os.path.join(ROOT, "neural-spectral-codec_amd", "csrc", "nsc_w1_rows.h")
 
 
 @functools.lru_cache(maxsize=1)
@@ -133,17 +135,19 @@ def test_abi_argument_checks_without_gpu(lib):
 
 
 def test_path_of_agrees_with_the_hip_source():
-    src = open(HIP).read()
-    c = R.parse_constants(src)
+    src, shared = open(HIP).read(), open(SHARED).read()
+    c = R.parse_constants(src, shared)
     assert c["QTL_I"] == R.QTL_I and c["QTL_KP"] == R.QTL_KP and c["STREAM_WG_CAP"] == R.STREAM_WG_CAP
     assert c["qnq"] == "Q <= 16 ? 1 : (Q <= 32 || (Q > 64 && Q <= 96) ? 2 : 4)"
     assert c["stream_split"] == "4"
     assert c["packed"] == ("D % 8 == 0 && !((reinterpret_cast<uintptr_t>(db_cdf) | "
                            "reinterpret_cast<uintptr_t>(q_cdf)) & 15u)")
-    for inst in ("w1q_stream_kernel<1>", "w1q_stream_kernel<2>", "w1q_stream_kernel<4>", "w1q_tile_kernel<1>",
-                 "w1q_tile_kernel<2>", "w1q_tile_kernel<4>", "w1q_generic_kernel", "w1q_cdf_kernel",
-                 "__builtin_amdgcn_sad_u16"):
+    for inst in ("w1q_stream_kernel<1>", "w1q_stream_kernel<2>", "w1q_stream_kernel<4>", "launch_w1_tile(st, U16Rows{",
+                 "w1q_generic_kernel", "w1q_cdf_kernel", "U16Rows::add("):
         assert inst in src, inst
+    for inst in ("w1_tile_kernel<Rows, 1>", "w1_tile_kernel<Rows, 2>", "w1_tile_kernel<Rows, 4>",
+                 "__builtin_amdgcn_sad_u16"):
+        assert inst in shared, inst
 
 
 def test_the_gpu_shapes_reach_the_paths_they_are_named_after():

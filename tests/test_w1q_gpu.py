@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import keyframe_oracle as ko
+import retrieval_families as F
 import w1q_restatement as R
 
 pytestmark = pytest.mark.gpu
@@ -154,7 +155,7 @@ def mid(D):
 
 @pytest.mark.parametrize("D", R.TILE_D)
 def test_tile_kernel(D):
-    """w1q_tile_kernel<1|2|4>: every NQ choice on both sides of its Q boundaries, partial row and query tiles, a last chunk
+    """w1_tile_kernel<U16Rows, 1|2|4>: every NQ choice on both sides of its Q boundaries, partial row and query tiles, a last chunk
     of k-pairs that is full or not, N % 4 != 0 (the scalar store path)."""
     ns = R.tile_n()
     assert {R.path_of(257, Q, D).inst for Q in R.TILE_Q} == {1, 2, 4} and any(N % 4 for N in ns)
@@ -256,6 +257,29 @@ def test_a_pair_does_not_depend_on_its_kernel_or_batch():
     assert_bits(one, want[9:10], "stream")
     assert_bits(tile[9:10], one, "tile vs stream")
     assert_bits(gen, one, "generic vs stream")
+
+
+def test_tile_grid_limit_on_both_entries():
+    """Q = 64 x 65 535 + 1 queries need 65 536 column tiles, one more than a grid's y extent holds: nsc_w1q_distances and
+    nsc_w1_distances_cdf both answer NSC_EUNSUPPORTED before launching anything, and ``dist`` keeps its sentinel."""
+    from neural_spectral_codec_amd import _lib
+    N, Q = 1, 64 * 65535 + 1
+    assert R.path_of(N, Q, 8).kernel == "tile" and R.path_of(N, Q, 8).grid == (1, 65536)
+    assert F.path_of(N, Q, 4).kernel == "tile" and F.path_of(N, Q, 4).grid == (1, 65536)
+    L, st = _lib.lib(), _lib.stream_ptr(torch.device("cuda", torch.cuda.current_device()))
+    dist = torch.full((Q, N), -7.0, dtype=torch.float32, device="cuda")
+    qc = torch.zeros((Q, 8), dtype=torch.int16, device="cuda")                            # 67 MB, either way read
+    ok = torch.ones((Q,), dtype=torch.uint8, device="cuda")
+    p = _lib.ptr
+    assert L.nsc_w1q_distances(p(qc[:1]), p(ok), N, 8, p(qc), p(ok), Q, None, None, 0.0, p(dist), st) == -2
+    qf = qc.view(torch.float32)
+    assert qf.shape == (Q, 4)
+    assert L.nsc_w1_distances_cdf(p(qf[:1]), N, 4, p(qf), Q, None, None, 0.0, p(dist), st) == -2
+    torch.cuda.synchronize()
+    assert bool((dist == -7.0).all())
+    assert L.nsc_w1_distances_cdf(p(qf[:1]), N, 4, p(qf), Q - 1, None, None, 0.0, p(dist), st) == 0    # 65 535 tiles: served
+    torch.cuda.synchronize()
+    assert bool((dist[:Q - 1] == 0.0).all()) and float(dist[Q - 1, 0]) == -7.0
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -15,9 +15,10 @@ import numpy as np
 
 TOTAL = 65535
 
-# ---- the dispatch constants of csrc/nsc_retrieval_q.hip, restated (tests/test_w1q_cpu.py parses the source) ----------
-QTL_I = 64                 # database rows per tile-kernel workgroup
-QTL_KP = 32                # k-pairs (64 bins) per staged chunk
+# ---- the dispatch constants of csrc/nsc_retrieval_q.hip and csrc/nsc_w1_rows.h, restated (tests/test_w1q_cpu.py parses
+# the sources) ----
+QTL_I = 64                 # database rows per tile-kernel workgroup (TL_I)
+QTL_KP = 32                # k-pairs (64 bins) per staged chunk (TL_K words of two bins)
 STREAM_WG_CAP = 256 * 8    # workgroups of the stream kernel; 4 waves each
 WAVES_PER_WG = 4
 PACK = 8                   # the packed kernels need D % 8 == 0 (16-byte chunks) and 16-byte aligned bases
@@ -65,19 +66,23 @@ def tile_n():
     return (1, QTL_I - 1, QTL_I, QTL_I + 1, 257)
 
 
-def parse_constants(src):
-    """the same constants read out of the .hip text"""
-    def one(pat):
-        m = re.search(pat, src)
+def parse_constants(src, shared):
+    """the same constants read out of the .hip text and, for what both W1 files share, csrc/nsc_w1_rows.h"""
+    def one(pat, text=src):
+        m = re.search(pat, text)
         assert m, pat
         return m
-    m = one(r"constexpr int QTL_I = (\d+), QTL_KP = (\d+)")
+    m = one(r"constexpr int TL_I = (\d+), TL_K = (\d+)", shared)
     out = {"QTL_I": int(m.group(1)), "QTL_KP": int(m.group(2))}
-    m = one(r"if \(qwgs > (\d+) \* (\d+)\) qwgs = (\d+) \* (\d+);")
-    assert m.group(1, 2) == m.group(3, 4)
+    one(r"static __device__ __forceinline__ int words\(int D\) \{ return D >> 1; \}", shared)     # a word is a k-pair
+    m = one(r"constexpr int W1_STREAM_WG_CAP = (\d+) \* (\d+);", shared)
+    one(r"int w1_stream_workgroups\(int N\) \{ const int wgs = \(N \+ 3\) / 4; "
+        r"return wgs < W1_STREAM_WG_CAP \? wgs : W1_STREAM_WG_CAP; \}", shared)
     out["STREAM_WG_CAP"] = int(m.group(1)) * int(m.group(2))
-    out["qnq"] = one(r"const int qnq = (.*?);").group(1).strip()
-    out["stream_split"] = one(r"else if \(Q <= (\d+)\) \{\s*int qwgs = \(N \+ 3\) / 4;").group(1)
+    out["qnq"] = one(r"int w1_tile_nq\(int Q\) \{ return (.*?); \}", shared).group(1).strip()
+    one(r"const int nq = w1_tile_nq\(Q\);", shared)
+    one(r"else if \(Q <= W1_STREAM_MAX_Q\) \{\s*const dim3 grid\(w1_stream_workgroups\(N\)\)")
+    out["stream_split"] = one(r"constexpr int W1_STREAM_MAX_Q = (\d+);", shared).group(1)
     out["packed"] = one(r"const bool packed = (.*?);").group(1).strip()
     return out
 
