@@ -44,10 +44,8 @@ constexpr int GEO_THREADS = 256;
 // gridDim.y is at most 65 535.  The per-cloud launches put the cloud in y (2 clouds per pair in nsc_gicp_register),
 // the per-pair launches the pair; a larger count is NSC_EUNSUPPORTED before anything is launched, callers chunk.
 constexpr int GRID_Y_MAX = 65535;
-constexpr int MAX_PAIRS = NSC_GICP_MAX_PAIRS;                       // nsc_gicp_register
-constexpr int MAX_CLOUDS = NSC_GICP_MAX_CLOUDS;                     // nsc_gicp_prepare
-constexpr int MAX_PREPARED_PAIRS = NSC_GICP_MAX_PREPARED_PAIRS;     // nsc_gicp_register_prepared
-static_assert(2 * MAX_PAIRS <= GRID_Y_MAX && MAX_CLOUDS <= GRID_Y_MAX && MAX_PREPARED_PAIRS <= GRID_Y_MAX,
+static_assert(2 * NSC_GICP_MAX_PAIRS <= GRID_Y_MAX && NSC_GICP_MAX_CLOUDS <= GRID_Y_MAX &&
+                  NSC_GICP_MAX_PREPARED_PAIRS <= GRID_Y_MAX,
               "the batch limits of include/nsc.h must fit gridDim.y");
 constexpr int COMPACT_THREADS = 1024;
 constexpr int KEY_BITS = 21;            // voxel key per axis: 0 .. 2^21-1 voxels from the cloud's min bound
@@ -69,29 +67,6 @@ struct PairState {
     double prev_fitness, prev_rmse;
     int round, done, pad0, pad1;
 };
-
-struct Layout {
-    size_t partial, bound, count, slots, points, cov, slab, state, total;
-};
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-Layout layout(int n_pairs, long long total_src, long long total_tgt)
-{
-    const size_t C = 2 * (size_t)n_pairs, N = (size_t)(total_src + total_tgt);
-    Layout L;
-    size_t o = 0;
-    L.partial = o; o = align256(o + C * GEO_BLOCKS * 3 * sizeof(double));
-    L.bound = o;   o = align256(o + C * 4 * sizeof(double));
-    L.count = o;   o = align256(o + C * sizeof(long long));
-    L.slots = o;   o = align256(o + 2 * N * sizeof(Slot));
-    L.points = o;  o = align256(o + N * 3 * sizeof(double));
-    L.cov = o;     o = align256(o + N * 6 * sizeof(double));
-    L.slab = o;    o = align256(o + (size_t)n_pairs * GEO_BLOCKS * SLAB * sizeof(double));
-    L.state = o;   o = align256(o + (size_t)n_pairs * sizeof(PairState));
-    L.total = o;
-    return L;
-}
 
 struct Clouds {                         // the 2P clouds of a batch and where each one's data lives
     const float *src, *tgt;
@@ -130,6 +105,12 @@ __device__ __forceinline__ unsigned long long pack_key(long long x, long long y,
     return (unsigned long long)x | ((unsigned long long)y << KEY_BITS) | ((unsigned long long)z << (2 * KEY_BITS));
 }
 
+template <class T>
+__device__ __forceinline__ unsigned long long voxel_key(const T *p, const double *lo, double voxel)
+{
+    return pack_key(voxel_coord(p[0], lo[0], voxel), voxel_coord(p[1], lo[1], voxel), voxel_coord(p[2], lo[2], voxel));
+}
+
 struct IndexSlot {                      // one voxel of a stored cloud's index (2 slots per down-sampled row)
     unsigned long long key;             // packed key + 1; 0 = empty
     unsigned long long row;             // row of the voxel in the down-sampled cloud
@@ -137,6 +118,9 @@ struct IndexSlot {                      // one voxel of a stored cloud's index (
 
 __device__ __forceinline__ long long ds_row(const Slot &s) { return s.ds; }
 __device__ __forceinline__ long long ds_row(const IndexSlot &s) { return (long long)s.row; }
+
+// the slot a linear probe visits after h, wrapping at the table's end
+__device__ __forceinline__ long long next_slot(long long h, long long cap) { return h + 1 == cap ? 0 : h + 1; }
 
 // Slot of a voxel key in a table of `cap` slots, or -1.
 template <class S>
@@ -148,7 +132,7 @@ __device__ __forceinline__ long long find_slot(const S *tab, long long cap, unsi
         const unsigned long long e = tab[h].key;
         if (e == 0) return -1;
         if (e == key + 1) return h;
-        h = h + 1 == cap ? 0 : h + 1;
+        h = next_slot(h, cap);
     }
     return -1;
 }
@@ -212,8 +196,7 @@ __global__ __launch_bounds__(GEO_THREADS) void ds_insert_kernel(Clouds cl, Slot 
         const float *q = base + i * cl.stride;
         if (!finite3(q)) continue;
         const double p[3] = {q[0], q[1], q[2]};
-        const unsigned long long key = pack_key(voxel_coord(p[0], lo[0], voxel), voxel_coord(p[1], lo[1], voxel),
-                                                voxel_coord(p[2], lo[2], voxel));
+        const unsigned long long key = voxel_key(p, lo, voxel);
         long long h = (long long)(mix64(key) % (unsigned long long)cap);
         for (;;) {                       // at most n distinct keys in 2n slots: an empty slot always exists
             unsigned long long e = tab[h].key;
@@ -222,7 +205,7 @@ __global__ __launch_bounds__(GEO_THREADS) void ds_insert_kernel(Clouds cl, Slot 
                 if (e == 0) e = key + 1;
             }
             if (e == key + 1) break;
-            h = h + 1 == cap ? 0 : h + 1;
+            h = next_slot(h, cap);
         }
         Slot &s = tab[h];
         atomicMin(&s.first, (unsigned long long)i);
@@ -250,8 +233,7 @@ __global__ __launch_bounds__(COMPACT_THREADS) void ds_compact_kernel(Clouds cl, 
         if (i < n) {
             const float *q = base + i * cl.stride;
             if (finite3(q)) {
-                h = find_slot(tab, 2 * n, pack_key(voxel_coord(q[0], lo[0], voxel), voxel_coord(q[1], lo[1], voxel),
-                                                    voxel_coord(q[2], lo[2], voxel)));
+                h = find_slot(tab, 2 * n, voxel_key(q, lo, voxel));
                 if (h >= 0 && tab[h].first != (unsigned long long)i) h = -1;
             }
         }
@@ -732,7 +714,7 @@ __global__ __launch_bounds__(COMPACT_THREADS) void store_kernel(Clouds cl, const
         if (e == 0) continue;
         long long h = (long long)(mix64(e - 1) % (unsigned long long)cap);
         while (atomicCAS(&tab[h].key, 0ULL, e) != 0ULL)      // m distinct keys in 2m slots
-            h = h + 1 == cap ? 0 : h + 1;
+            h = next_slot(h, cap);
         tab[h].row = (unsigned long long)ws[i].ds;
     }
 }
@@ -775,51 +757,71 @@ __global__ __launch_bounds__(GEO_THREADS) void prepared_setup_kernel(StoreView s
     state[p] = PairState{0.0, 0.0, 0, 0, 0, 0};
 }
 
-struct PreparedLayout {
-    size_t count, rows, slab, state, total;
+// The workspaces are regions carved in order, each rounded up to 256 bytes: the offset of the next one, `bytes` long.
+inline size_t carve(size_t &o, size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; }
+
+// Byte `offset` of a workspace as a T*.  Integer arithmetic: a size query lays out a null workspace.
+template <class T>
+inline T *at(void *ws, size_t offset) { return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(ws) + offset); }
+
+// Per-cloud regions for n_clouds clouds of total_rows input rows in all, and the bytes they take: nsc_gicp_prepare's
+// workspace, and the head of nsc_gicp_register's (2 clouds per pair; source rows, then target rows).
+struct CloudRegions {
+    double *partial, *bound, *points, *cov;
+    long long *count;
+    Slot *slots;
+    size_t total;
 };
 
-PreparedLayout prepared_layout(int n_pairs)
+CloudRegions cloud_regions(void *ws, size_t n_clouds, size_t total_rows)
 {
-    const size_t P = (size_t)n_pairs;
-    PreparedLayout L;
-    size_t o = 0;
-    L.count = o; o = align256(o + 2 * P * sizeof(long long));
-    L.rows = o;  o = align256(o + P * sizeof(PairRows));
-    L.slab = o;  o = align256(o + P * GEO_BLOCKS * SLAB * sizeof(double));
-    L.state = o; o = align256(o + P * sizeof(PairState));
-    L.total = o;
-    return L;
+    CloudRegions r;
+    r.total = 0;
+    r.partial = at<double>(ws, carve(r.total, n_clouds * GEO_BLOCKS * 3 * sizeof(double)));
+    r.bound = at<double>(ws, carve(r.total, n_clouds * 4 * sizeof(double)));
+    r.count = at<long long>(ws, carve(r.total, n_clouds * sizeof(long long)));
+    r.slots = at<Slot>(ws, carve(r.total, 2 * total_rows * sizeof(Slot)));
+    r.points = at<double>(ws, carve(r.total, total_rows * 3 * sizeof(double)));
+    r.cov = at<double>(ws, carve(r.total, total_rows * 6 * sizeof(double)));
+    return r;
 }
 
-// nsc_gicp_prepare's workspace: the per-cloud regions of layout() for n_clouds clouds of total_points rows
-struct PrepLayout {
-    size_t partial, bound, count, slots, points, cov, total;
+// Per-pair regions from byte `base` on, and where they end: the tail of nsc_gicp_register's workspace, after its
+// cloud regions, and, with count[2P] and rows in front (`stored`), nsc_gicp_register_prepared's workspace.
+struct PairRegions {
+    long long *count; PairRows *rows;   // of stored pairs only
+    double *slab; PairState *state;
+    size_t total;
 };
 
-PrepLayout prep_layout(int n_clouds, long long total_points)
+PairRegions pair_regions(void *ws, size_t n_pairs, bool stored, size_t base)
 {
-    const size_t C = (size_t)n_clouds, N = (size_t)total_points;
-    PrepLayout L;
-    size_t o = 0;
-    L.partial = o; o = align256(o + C * GEO_BLOCKS * 3 * sizeof(double));
-    L.bound = o;   o = align256(o + C * 4 * sizeof(double));
-    L.count = o;   o = align256(o + C * sizeof(long long));
-    L.slots = o;   o = align256(o + 2 * N * sizeof(Slot));
-    L.points = o;  o = align256(o + N * 3 * sizeof(double));
-    L.cov = o;     o = align256(o + N * 6 * sizeof(double));
-    L.total = o;
-    return L;
+    PairRegions r;
+    r.total = base;
+    r.count = at<long long>(ws, carve(r.total, stored ? 2 * n_pairs * sizeof(long long) : 0));
+    r.rows = at<PairRows>(ws, carve(r.total, stored ? n_pairs * sizeof(PairRows) : 0));
+    r.slab = at<double>(ws, carve(r.total, n_pairs * GEO_BLOCKS * SLAB * sizeof(double)));
+    r.state = at<PairState>(ws, carve(r.total, n_pairs * sizeof(PairState)));
+    return r;
 }
 
 int check_params(const NscGicpParams *p)
 {
+    if (!p) return NSC_EINVAL;
     if (!(p->voxel_size > 0.0) || !(p->max_correspondence_distance > 0.0) || !(p->epsilon > 0.0) ||
         !(p->relative_fitness >= 0.0) || !(p->relative_rmse >= 0.0) || p->max_iteration < 0 ||
         !isfinite(p->voxel_size) || !isfinite(p->max_correspondence_distance))
         return NSC_EINVAL;
     if (p->covariance_knn < 1 || p->covariance_knn > NSC_GICP_MAX_KNN) return NSC_EUNSUPPORTED;
     return NSC_OK;
+}
+
+inline bool stride_ok(int stride_floats) { return stride_floats == 3 || stride_floats == 4; }
+
+inline bool outputs_ok(const double *init_transforms, const double *transforms, const double *fitness_rmse,
+                       const int64_t *corr_iterations, const double *information)
+{
+    return init_transforms && transforms && fitness_rmse && corr_iterations && information;
 }
 
 // a set is usable: its arrays are there, its counts fit its capacities and it was prepared with p's down-sampling
@@ -838,6 +840,43 @@ StoreView store_view(const NscGicpCloudSet *s)
     return StoreView{reinterpret_cast<long long *>(s->row_offsets), reinterpret_cast<long long *>(s->slot_offsets),
                      s->bounds, s->points, s->covariances, reinterpret_cast<IndexSlot *>(s->slots),
                      (long long)s->n_clouds};
+}
+
+// nsc_gicp_prepare's clouds: every cloud of the batch is a "target" of a batch without pairs: Clouds::rows addresses it
+// at offsets[c], and ds_prepare has no pair state to reset
+Clouds unpaired_clouds(const float *points, const int64_t *offsets, int stride_floats)
+{
+    const long long *off = reinterpret_cast<const long long *>(offsets);
+    return Clouds{points, points, off, off, 0, stride_floats, 0};
+}
+
+// ds_prepare, ds_insert, ds_compact and covariance over n_clouds clouds.  init, transforms and state are the pairs'
+// (nsc_gicp_register), or null for clouds without pairs.
+void launch_prepare(const Clouds &cl, int n_clouds, const CloudRegions &r, const NscGicpParams *p, const double *init,
+                    double *transforms, PairState *state, hipStream_t s)
+{
+    const dim3 per_cloud(GEO_BLOCKS, n_clouds), threads(GEO_THREADS);
+    hipLaunchKernelGGL(ds_prepare_kernel, per_cloud, threads, 0, s, cl, r.slots, r.partial, init, transforms, state);
+    hipLaunchKernelGGL(ds_insert_kernel, per_cloud, threads, 0, s, cl, r.slots, r.partial, r.bound, p->voxel_size);
+    hipLaunchKernelGGL(ds_compact_kernel, dim3(n_clouds), dim3(COMPACT_THREADS), 0, s, cl, r.slots, r.bound,
+                       p->voxel_size, r.points, r.count);
+    hipLaunchKernelGGL(covariance_kernel, per_cloud, threads, 0, s, cl, r.slots, r.bound, r.count, r.points, r.cov,
+                       p->voxel_size, p->covariance_knn, p->epsilon);
+}
+
+// The max_iteration + 1 rounds of linearize + finalize over n_pairs pairs; count[p] is pair p's source row count.
+template <class Pairs>
+void launch_rounds(const Pairs &pairs, int n_pairs, const long long *count, double *slab, PairState *state,
+                   const NscGicpParams *p, double *transforms, double *fitness_rmse, int64_t *corr_iterations,
+                   double *information, double *system0, hipStream_t s)
+{
+    for (int r = 0; r <= p->max_iteration; ++r) {
+        hipLaunchKernelGGL(linearize_kernel<Pairs>, dim3(GEO_BLOCKS, n_pairs), dim3(GEO_THREADS), 0, s, pairs,
+                           transforms, state, slab, p->voxel_size, p->max_correspondence_distance);
+        hipLaunchKernelGGL(finalize_kernel, dim3(n_pairs), dim3(64), 0, s, count, slab, state, transforms,
+                           fitness_rmse, reinterpret_cast<long long *>(corr_iterations), information, system0, n_pairs,
+                           p->max_iteration, p->relative_fitness, p->relative_rmse);
+    }
 }
 
 inline int launch_status() { return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH; }
@@ -861,7 +900,8 @@ void nsc_gicp_default_params(NscGicpParams *p)
 size_t nsc_gicp_workspace_bytes(int32_t n_pairs, int64_t total_source_points, int64_t total_target_points)
 {
     if (n_pairs < 0 || total_source_points < 0 || total_target_points < 0) return 0;
-    return layout(n_pairs, total_source_points, total_target_points).total;
+    const size_t clouds = cloud_regions(nullptr, 2 * (size_t)n_pairs, total_source_points + total_target_points).total;
+    return pair_regions(nullptr, n_pairs, false, clouds).total;
 }
 
 int nsc_gicp_register(const float *source_points, const int64_t *source_offsets, const float *target_points,
@@ -871,104 +911,70 @@ int nsc_gicp_register(const float *source_points, const int64_t *source_offsets,
                       int64_t *corr_iterations, double *information, const NscGicpStages *stages, void *ws,
                       size_t ws_bytes, void *stream)
 {
-    if (n_pairs < 0 || total_source_points < 0 || total_target_points < 0 || !p) return NSC_EINVAL;
-    if (stride_floats != 3 && stride_floats != 4) return NSC_EINVAL;
+    if (n_pairs < 0 || total_source_points < 0 || total_target_points < 0 || !stride_ok(stride_floats))
+        return NSC_EINVAL;
     if (const int st = check_params(p)) return st;
-    if (n_pairs > MAX_PAIRS) return NSC_EUNSUPPORTED;
+    if (n_pairs > NSC_GICP_MAX_PAIRS) return NSC_EUNSUPPORTED;
     if (n_pairs == 0) return NSC_OK;
-    if (!source_offsets || !target_offsets || !init_transforms || !transforms || !fitness_rmse || !corr_iterations ||
-        !information)
+    if (!source_offsets || !target_offsets ||
+        !outputs_ok(init_transforms, transforms, fitness_rmse, corr_iterations, information))
         return NSC_EINVAL;
     if ((total_source_points > 0 && !source_points) || (total_target_points > 0 && !target_points)) return NSC_EINVAL;
-    const Layout L = layout(n_pairs, total_source_points, total_target_points);
-    if (!ws || ws_bytes < L.total) return NSC_EWORKSPACE;
-    char *w = static_cast<char *>(ws);
-    double *partial = reinterpret_cast<double *>(w + L.partial), *bound = reinterpret_cast<double *>(w + L.bound);
-    long long *count = reinterpret_cast<long long *>(w + L.count);
-    Slot *slots = reinterpret_cast<Slot *>(w + L.slots);
-    double *points = reinterpret_cast<double *>(w + L.points), *cov = reinterpret_cast<double *>(w + L.cov);
-    double *slab = reinterpret_cast<double *>(w + L.slab);
-    PairState *state = reinterpret_cast<PairState *>(w + L.state);
+    CloudRegions r = cloud_regions(ws, 2 * (size_t)n_pairs, total_source_points + total_target_points);
+    const PairRegions q = pair_regions(ws, n_pairs, false, r.total);
+    if (!ws || ws_bytes < q.total) return NSC_EWORKSPACE;
     double *system0 = nullptr;
     if (stages) {                        // stage outputs replace the workspace regions they name
-        if (stages->points) points = stages->points;
-        if (stages->covariances) cov = stages->covariances;
-        if (stages->counts) count = reinterpret_cast<long long *>(stages->counts);
+        if (stages->points) r.points = stages->points;
+        if (stages->covariances) r.cov = stages->covariances;
+        if (stages->counts) r.count = reinterpret_cast<long long *>(stages->counts);
         system0 = stages->system0;
     }
-    Clouds cl{source_points, target_points, reinterpret_cast<const long long *>(source_offsets),
-              reinterpret_cast<const long long *>(target_offsets), (long long)total_source_points, stride_floats,
-              n_pairs};
+    const Clouds cl{source_points, target_points, reinterpret_cast<const long long *>(source_offsets),
+                    reinterpret_cast<const long long *>(target_offsets), (long long)total_source_points,
+                    stride_floats, n_pairs};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 per_cloud(GEO_BLOCKS, 2 * n_pairs), per_pair(GEO_BLOCKS, n_pairs);
-    hipLaunchKernelGGL(ds_prepare_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, partial, init_transforms,
-                       transforms, state);
-    hipLaunchKernelGGL(ds_insert_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, partial, bound, p->voxel_size);
-    hipLaunchKernelGGL(ds_compact_kernel, dim3(2 * n_pairs), dim3(COMPACT_THREADS), 0, s, cl, slots, bound,
-                       p->voxel_size, points, count);
-    hipLaunchKernelGGL(covariance_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, bound, count, points, cov,
-                       p->voxel_size, p->covariance_knn, p->epsilon);
-    const BatchPairs pairs{cl, slots, bound, points, cov, count};
-    for (int r = 0; r <= p->max_iteration; ++r) {
-        hipLaunchKernelGGL(linearize_kernel<BatchPairs>, per_pair, dim3(GEO_THREADS), 0, s, pairs, transforms, state,
-                           slab, p->voxel_size, p->max_correspondence_distance);
-        hipLaunchKernelGGL(finalize_kernel, dim3(n_pairs), dim3(64), 0, s, count, slab, state, transforms,
-                           fitness_rmse, reinterpret_cast<long long *>(corr_iterations), information, system0, n_pairs,
-                           p->max_iteration, p->relative_fitness, p->relative_rmse);
-    }
+    launch_prepare(cl, 2 * n_pairs, r, p, init_transforms, transforms, q.state, s);
+    launch_rounds(BatchPairs{cl, r.slots, r.bound, r.points, r.cov, r.count}, n_pairs, r.count, q.slab, q.state, p,
+                  transforms, fitness_rmse, corr_iterations, information, system0, s);
     return launch_status();
 }
 
 size_t nsc_gicp_prepare_workspace_bytes(int32_t n_clouds, int64_t total_points)
 {
     if (n_clouds < 0 || total_points < 0) return 0;
-    return prep_layout(n_clouds, total_points).total;
+    return cloud_regions(nullptr, n_clouds, total_points).total;
 }
 
 int nsc_gicp_prepare(const float *points, const int64_t *offsets, int32_t n_clouds, int64_t total_points,
                      int32_t stride_floats, const NscGicpParams *p, const NscGicpCloudSet *set, void *ws,
                      size_t ws_bytes, void *stream)
 {
-    if (n_clouds < 0 || total_points < 0 || !p || !set) return NSC_EINVAL;
-    if (stride_floats != 3 && stride_floats != 4) return NSC_EINVAL;
+    if (n_clouds < 0 || total_points < 0 || !set || !stride_ok(stride_floats)) return NSC_EINVAL;
     if (const int st = check_params(p)) return st;
     if (!set_ok(set, p)) return NSC_EINVAL;
-    if (n_clouds > MAX_CLOUDS) return NSC_EUNSUPPORTED;
+    if (n_clouds > NSC_GICP_MAX_CLOUDS) return NSC_EUNSUPPORTED;
     if (n_clouds == 0) return NSC_OK;
     if (!offsets || (total_points > 0 && !points)) return NSC_EINVAL;
     // room for the batch's upper bound: every input row a voxel of its own
     if ((int64_t)set->n_clouds + n_clouds > set->cap_clouds || set->n_rows > set->cap_rows - total_points ||
         set->n_slots > set->cap_slots - 2 * total_points)
         return NSC_EWORKSPACE;
-    const PrepLayout L = prep_layout(n_clouds, total_points);
-    if (!ws || ws_bytes < L.total) return NSC_EWORKSPACE;
-    char *w = static_cast<char *>(ws);
-    double *partial = reinterpret_cast<double *>(w + L.partial), *bound = reinterpret_cast<double *>(w + L.bound);
-    long long *count = reinterpret_cast<long long *>(w + L.count);
-    Slot *slots = reinterpret_cast<Slot *>(w + L.slots);
-    double *pts = reinterpret_cast<double *>(w + L.points), *cov = reinterpret_cast<double *>(w + L.cov);
-    // every cloud of the batch is a "target" of a batch without pairs: Clouds::rows addresses it at offsets[c], and
-    // ds_prepare has no pair state to reset
-    const long long *off = reinterpret_cast<const long long *>(offsets);
-    const Clouds cl{points, points, off, off, 0, stride_floats, 0};
+    const CloudRegions r = cloud_regions(ws, n_clouds, total_points);
+    if (!ws || ws_bytes < r.total) return NSC_EWORKSPACE;
+    const Clouds cl = unpaired_clouds(points, offsets, stride_floats);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 per_cloud(GEO_BLOCKS, n_clouds);
-    hipLaunchKernelGGL(ds_prepare_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, partial, nullptr, nullptr,
-                       nullptr);
-    hipLaunchKernelGGL(ds_insert_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, partial, bound, p->voxel_size);
-    hipLaunchKernelGGL(ds_compact_kernel, dim3(n_clouds), dim3(COMPACT_THREADS), 0, s, cl, slots, bound,
-                       p->voxel_size, pts, count);
-    hipLaunchKernelGGL(covariance_kernel, per_cloud, dim3(GEO_THREADS), 0, s, cl, slots, bound, count, pts, cov,
-                       p->voxel_size, p->covariance_knn, p->epsilon);
-    hipLaunchKernelGGL(store_kernel, dim3(n_clouds), dim3(COMPACT_THREADS), 0, s, cl, slots, bound, count, pts, cov,
-                       store_view(set), (long long)set->n_clouds, (long long)set->n_rows, (long long)set->n_slots);
+    launch_prepare(cl, n_clouds, r, p, nullptr, nullptr, nullptr, s);
+    hipLaunchKernelGGL(store_kernel, dim3(n_clouds), dim3(COMPACT_THREADS), 0, s, cl, r.slots, r.bound, r.count,
+                       r.points, r.cov, store_view(set), (long long)set->n_clouds, (long long)set->n_rows,
+                       (long long)set->n_slots);
     return launch_status();
 }
 
 size_t nsc_gicp_register_prepared_workspace_bytes(int32_t n_pairs)
 {
     if (n_pairs < 0) return 0;
-    return prepared_layout(n_pairs).total;
+    return pair_regions(nullptr, n_pairs, true, 0).total;
 }
 
 int nsc_gicp_register_prepared(const NscGicpCloudSet *sources, const NscGicpCloudSet *targets,
@@ -977,35 +983,25 @@ int nsc_gicp_register_prepared(const NscGicpCloudSet *sources, const NscGicpClou
                                double *fitness_rmse, int64_t *corr_iterations, double *information, double *system0,
                                void *ws, size_t ws_bytes, void *stream)
 {
-    if (n_pairs < 0 || !p || !sources || !targets) return NSC_EINVAL;
+    if (n_pairs < 0 || !sources || !targets) return NSC_EINVAL;
     if (const int st = check_params(p)) return st;
     if (!set_ok(sources, p) || !set_ok(targets, p)) return NSC_EINVAL;
-    if (n_pairs > MAX_PREPARED_PAIRS) return NSC_EUNSUPPORTED;
+    if (n_pairs > NSC_GICP_MAX_PREPARED_PAIRS) return NSC_EUNSUPPORTED;
     if (n_pairs == 0) return NSC_OK;
-    if (!source_ids || !target_ids || !init_transforms || !transforms || !fitness_rmse || !corr_iterations ||
-        !information)
+    if (!source_ids || !target_ids ||
+        !outputs_ok(init_transforms, transforms, fitness_rmse, corr_iterations, information))
         return NSC_EINVAL;
-    const PreparedLayout L = prepared_layout(n_pairs);
-    if (!ws || ws_bytes < L.total) return NSC_EWORKSPACE;
-    char *w = static_cast<char *>(ws);
-    long long *count = reinterpret_cast<long long *>(w + L.count);
-    PairRows *rows = reinterpret_cast<PairRows *>(w + L.rows);
-    double *slab = reinterpret_cast<double *>(w + L.slab);
-    PairState *state = reinterpret_cast<PairState *>(w + L.state);
-    long long *ci = reinterpret_cast<long long *>(corr_iterations);
-    const StoredPairs pairs{store_view(sources), store_view(targets), rows, count, n_pairs};
+    const PairRegions q = pair_regions(ws, n_pairs, true, 0);
+    if (!ws || ws_bytes < q.total) return NSC_EWORKSPACE;
+    const StoredPairs pairs{store_view(sources), store_view(targets), q.rows, q.count, n_pairs};
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(prepared_setup_kernel, dim3((n_pairs + GEO_THREADS - 1) / GEO_THREADS), dim3(GEO_THREADS), 0, s,
                        pairs.src, pairs.tgt, reinterpret_cast<const long long *>(source_ids),
-                       reinterpret_cast<const long long *>(target_ids), n_pairs, init_transforms, transforms, state,
-                       count, rows, fitness_rmse, ci, information, system0);
-    for (int r = 0; r <= p->max_iteration; ++r) {
-        hipLaunchKernelGGL(linearize_kernel<StoredPairs>, dim3(GEO_BLOCKS, n_pairs), dim3(GEO_THREADS), 0, s, pairs,
-                           transforms, state, slab, p->voxel_size, p->max_correspondence_distance);
-        hipLaunchKernelGGL(finalize_kernel, dim3(n_pairs), dim3(64), 0, s, count, slab, state, transforms,
-                           fitness_rmse, ci, information, system0, n_pairs, p->max_iteration, p->relative_fitness,
-                           p->relative_rmse);
-    }
+                       reinterpret_cast<const long long *>(target_ids), n_pairs, init_transforms, transforms, q.state,
+                       q.count, q.rows, fitness_rmse, reinterpret_cast<long long *>(corr_iterations), information,
+                       system0);
+    launch_rounds(pairs, n_pairs, q.count, q.slab, q.state, p, transforms, fitness_rmse, corr_iterations, information,
+                  system0, s);
     return launch_status();
 }
 

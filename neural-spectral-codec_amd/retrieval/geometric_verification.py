@@ -76,6 +76,29 @@ def _params(voxel_size=0.5, max_correspondence_distance=1.0, max_iteration=30, r
                            covariance_knn=int(covariance_knn))
 
 
+def _outputs(P, device, system0=False):
+    """the tensors one library call over P pairs writes; system0 (P,29) when asked for"""
+    f64 = dict(dtype=torch.float64, device=device)
+    out = dict(transform=torch.empty((P, 4, 4), **f64), fit_rmse=torch.empty((P, 2), **f64),
+               corr_iters=torch.empty((P, 2), dtype=torch.int64, device=device),
+               information=torch.empty((P, 6, 6), **f64))
+    if system0:
+        out["system0"] = torch.empty((P, 29), **f64)
+    return out
+
+
+def _unpacked(out):
+    """_outputs after the call: fit_rmse and corr_iters become fitness, rmse, n_correspondences and iterations"""
+    fr, ci = out.pop("fit_rmse"), out.pop("corr_iters")
+    out.update(fitness=fr[:, 0], rmse=fr[:, 1], n_correspondences=ci[:, 0], iterations=ci[:, 1])
+    return out
+
+
+def _workspace(nbytes, device):
+    """the size a *_workspace_bytes query gave -> that many uint8 on ``device`` (one at least)"""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
 def register_packed(source_points, source_offsets, target_points, target_offsets, init_transforms, stages=False,
                     **params):
     """Register packed clouds on the device: no host copy, allocation outside torch's allocator or sync, so a call
@@ -107,17 +130,14 @@ def register_packed(source_points, source_offsets, target_points, target_offsets
     Ns, Nt = int(src.shape[0]), int(tgt.shape[0])
     p = _params(**params)
     L = _lib.lib()
-    f64 = dict(dtype=torch.float64, device=dev)
-    out = dict(transform=torch.empty((P, 4, 4), **f64), fit_rmse=torch.empty((P, 2), **f64),
-               corr_iters=torch.empty((P, 2), dtype=torch.int64, device=dev),
-               information=torch.empty((P, 6, 6), **f64))
+    out = _outputs(P, dev, system0=stages)
     st = None
     if stages:
+        f64 = dict(dtype=torch.float64, device=dev)
         out.update(points=torch.empty((Ns + Nt, 3), **f64), counts=torch.empty(2 * P, dtype=torch.int64, device=dev),
-                   covariances=torch.empty((Ns + Nt, 6), **f64), system0=torch.empty((P, 29), **f64))
+                   covariances=torch.empty((Ns + Nt, 6), **f64))
         st = _lib.GicpStages(*(out[k].data_ptr() for k in ("points", "counts", "covariances", "system0")))
-    nbytes = L.nsc_gicp_workspace_bytes(P, Ns, Nt)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.nsc_gicp_workspace_bytes(P, Ns, Nt), dev)
     with torch.cuda.device(dev):
         status = L.nsc_gicp_register(_lib.ptr(src), _lib.ptr(so), _lib.ptr(tgt), _lib.ptr(to), P, Ns, Nt, stride,
                                      C.byref(p), _lib.ptr(init), _lib.ptr(out["transform"]), _lib.ptr(out["fit_rmse"]),
@@ -125,9 +145,7 @@ def register_packed(source_points, source_offsets, target_points, target_offsets
                                      C.byref(st) if st is not None else None, _lib.ptr(ws), int(ws.numel()),
                                      _lib.stream_ptr(dev))
     _lib.check(status, "nsc_gicp_register")
-    fr, ci = out.pop("fit_rmse"), out.pop("corr_iters")
-    out.update(fitness=fr[:, 0], rmse=fr[:, 1], n_correspondences=ci[:, 0], iterations=ci[:, 1])
-    return out
+    return _unpacked(out)
 
 
 def _register_packed_chunked(source_points, source_offsets, target_points, target_offsets, init_transforms, stages,
@@ -175,8 +193,10 @@ def _pack(clouds, device):
 
 
 def _init_tensor(init_transforms, k, device):
-    """(k,4,4) initial transforms, a host array or a tensor (a device tensor is used in place: no host visit) ->
-    (k,4,4) float64 tensor on ``device``"""
+    """(k,4,4) initial transforms -- None (the identity), a host array or a tensor (a device tensor is used in
+    place: no host visit) -> (k,4,4) float64 tensor on ``device``"""
+    if init_transforms is None:
+        return torch.eye(4, dtype=torch.float64, device=device).repeat(k, 1, 1)
     t = init_transforms if isinstance(init_transforms, torch.Tensor) else \
         torch.from_numpy(np.ascontiguousarray(np.asarray(init_transforms, np.float64).reshape(k, 4, 4)))
     return t.to(device=device, dtype=torch.float64).reshape(k, 4, 4).contiguous()
@@ -273,8 +293,7 @@ class PreparedClouds:
         st = self._set()
         p = _params(**self.params)
         L = _lib.lib()
-        nbytes = L.nsc_gicp_prepare_workspace_bytes(B, N)
-        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
+        ws = _workspace(L.nsc_gicp_prepare_workspace_bytes(B, N), self.device)
         with torch.cuda.device(self.device):
             status = L.nsc_gicp_prepare(_lib.ptr(pts), _lib.ptr(off), B, N, int(pts.shape[1]), C.byref(p),
                                         C.byref(st), _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(self.device))
@@ -320,26 +339,15 @@ def register_prepared(sources: PreparedClouds, source_ids, targets: PreparedClou
     P = int(sid.numel())
     if int(tid.numel()) != P:
         raise _lib.NscError("register_prepared needs as many target ids as source ids")
-    if init_transforms is None:
-        init = torch.eye(4, dtype=torch.float64, device=dev).repeat(P, 1, 1)
-    else:
-        init = init_transforms if isinstance(init_transforms, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(np.asarray(init_transforms, np.float64)))
-        init = init.to(device=dev, dtype=torch.float64).reshape(P, 4, 4).contiguous()
+    init = _init_tensor(init_transforms, P, dev)
     if P > MAX_PREPARED_PAIRS_PER_CALL:
         step = MAX_PREPARED_PAIRS_PER_CALL
         return _cat_outputs([register_prepared(sources, sid[a:a + step], targets, tid[a:a + step], init[a:a + step],
                                                stages=stages, **params) for a in range(0, P, step)])
     L = _lib.lib()
-    f64 = dict(dtype=torch.float64, device=dev)
-    out = dict(transform=torch.empty((P, 4, 4), **f64), fit_rmse=torch.empty((P, 2), **f64),
-               corr_iters=torch.empty((P, 2), dtype=torch.int64, device=dev),
-               information=torch.empty((P, 6, 6), **f64))
-    if stages:
-        out["system0"] = torch.empty((P, 29), **f64)
+    out = _outputs(P, dev, system0=stages)
     ss, ts = sources._set(), targets._set()
-    nbytes = L.nsc_gicp_register_prepared_workspace_bytes(P)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.nsc_gicp_register_prepared_workspace_bytes(P), dev)
     with torch.cuda.device(dev):
         status = L.nsc_gicp_register_prepared(C.byref(ss), C.byref(ts), _lib.ptr(sid), _lib.ptr(tid), P, C.byref(p),
                                               _lib.ptr(init), _lib.ptr(out["transform"]), _lib.ptr(out["fit_rmse"]),
@@ -347,9 +355,7 @@ def register_prepared(sources: PreparedClouds, source_ids, targets: PreparedClou
                                               _lib.ptr(out["system0"]) if stages else None, _lib.ptr(ws),
                                               int(ws.numel()), _lib.stream_ptr(dev))
     _lib.check(status, "nsc_gicp_register_prepared")
-    fr, ci = out.pop("fit_rmse"), out.pop("corr_iters")
-    out.update(fitness=fr[:, 0], rmse=fr[:, 1], n_correspondences=ci[:, 0], iterations=ci[:, 1])
-    return out
+    return _unpacked(out)
 
 
 def register_batch(sources: Sequence, targets: Sequence, init_transforms=None, device="cuda", **params):
@@ -358,19 +364,10 @@ def register_batch(sources: Sequence, targets: Sequence, init_transforms=None, d
     Returns register_packed's dict of device tensors."""
     if len(sources) != len(targets):
         raise _lib.NscError("register_batch needs as many targets as sources")
-    dev = torch.device(device)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    P = len(sources)
+    dev = _device(device)
     sp, so = _pack(sources, dev)
     tp, to = _pack(targets, dev)
-    if init_transforms is None:
-        init = torch.eye(4, dtype=torch.float64, device=dev).repeat(P, 1, 1)
-    else:
-        init = torch.as_tensor(np.asarray(init_transforms, np.float64).reshape(P, 4, 4)
-                               if not isinstance(init_transforms, torch.Tensor) else init_transforms,
-                               dtype=torch.float64).to(dev).reshape(P, 4, 4)
-    return register_packed(sp, so, tp, to, init, **params)
+    return register_packed(sp, so, tp, to, _init_tensor(init_transforms, len(sources), dev), **params)
 
 
 class GeometricVerifier:
@@ -414,18 +411,13 @@ class GeometricVerifier:
         k = len(candidate_points_list)
         if k == 0:
             return []
-        dev = torch.device(self.device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = _device(self.device)
         q = _xyz(query_points, dev)
         n = int(q.shape[0])
         sp = q.repeat(k, 1)
         so = torch.arange(k + 1, dtype=torch.int64).mul_(n).to(dev)
         tp, to = _pack(candidate_points_list, dev)
-        if init_transforms is None:
-            init = torch.eye(4, dtype=torch.float64, device=dev).repeat(k, 1, 1)
-        else:
-            init = _init_tensor(init_transforms, k, dev)
+        init = _init_tensor(init_transforms, k, dev)
         return self._decide(register_packed(sp, so, tp, to, init, **self.params), k)
 
     def prepare(self, clouds: Sequence = ()) -> PreparedClouds:
@@ -450,8 +442,8 @@ class GeometricVerifier:
         k = len(candidate_ids)
         if k == 0:
             return []
-        init = None if init_transforms is None else _init_tensor(init_transforms, k, query_store.device)
-        return self._decide(register_prepared(query_store, query_ids, store, candidate_ids, init, **self.params), k)
+        return self._decide(register_prepared(query_store, query_ids, store, candidate_ids, init_transforms,
+                                              **self.params), k)
 
     def _decide(self, out, k):
         """register_* outputs of k pairs -> [(verified, transform, info)]"""

@@ -216,28 +216,21 @@ class TwoStageRetrieval:
             raise _lib.NscError("stage 2 (GICP) is outside the MI355X descriptor path: construct TwoStageRetrieval "
                                 "with verifier=<object with the reference's GeometricVerifier.verify> or call "
                                 "query(..., verify=False)")
+        ids = [c.database_idx for c in candidates]
+        yaw, init = None, {}             # no yaw estimate, no init_transforms: an injected verifier need not take it
         if self.yaw_images is not None:
-            ids = [c.database_idx for c in candidates]
             yaw = _yaw.estimate_yaw(query_image, [0] * len(ids), self.yaw_images, ids)      # one launch, no sync
-            if self.geometry is not None:
-                self._query_geometry.clear()
-                self._query_geometry.add([query_points])
-                results = self.verifier.verify_prepared(self._query_geometry, 0, self.geometry, ids,
-                                                        init_transforms=yaw["init_transforms"])
-            else:
-                results = self.verifier.verify_batch(query_points, [self.keyframes[i].points for i in ids],
-                                                     init_transforms=yaw["init_transforms"])
-            results = _with_yaw_info(results, yaw)
-        elif self.geometry is not None:
+            init = dict(init_transforms=yaw["init_transforms"])
+        if self.geometry is not None:
             self._query_geometry.clear()
             self._query_geometry.add([query_points])
-            results = self.verifier.verify_prepared(self._query_geometry, 0, self.geometry,
-                                                    [c.database_idx for c in candidates])
+            results = self.verifier.verify_prepared(self._query_geometry, 0, self.geometry, ids, **init)
         elif hasattr(self.verifier, "verify_batch"):
-            results = self.verifier.verify_batch(query_points,
-                                                 [self.keyframes[c.database_idx].points for c in candidates])
+            results = self.verifier.verify_batch(query_points, [self.keyframes[i].points for i in ids], **init)
         else:
-            results = (self.verifier.verify(query_points, self.keyframes[c.database_idx].points) for c in candidates)
+            results = (self.verifier.verify(query_points, self.keyframes[i].points) for i in ids)
+        if yaw is not None:
+            results = _with_yaw_info(results, yaw)
         return _apply(candidates, results)
 
     def query(self, query_keyframe, query_points: Optional[np.ndarray] = None, verify: bool = True

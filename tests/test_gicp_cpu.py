@@ -144,3 +144,24 @@ def test_gicp_batch_limits_on_host(lib):
                                               fake, fake, fake, None, fake, need - 1, None)
     assert register_prepared(_lib.GICP_MAX_PREPARED_PAIRS + 1) == EUNSUP and register_prepared(2 ** 31 - 1) == EUNSUP
     assert register_prepared(_lib.GICP_MAX_PREPARED_PAIRS) == EWS
+
+
+def test_gicp_workspace_sizes(lib):
+    """The three size queries, pinned where nsc_geometry.hip carved each workspace by hand (the values are that
+    library's), and the structure they share: nsc_gicp_register's workspace is nsc_gicp_prepare's for its 2P clouds
+    and Ns + Nt rows, followed by nsc_gicp_register_prepared's without the latter's first two regions (count: 2P
+    int64; rows: P records of 64 bytes; every region is rounded up to 256 bytes)."""
+    register, prepare = lib.nsc_gicp_workspace_bytes, lib.nsc_gicp_prepare_workspace_bytes
+    prepared = lib.nsc_gicp_register_prepared_workspace_bytes
+    assert [register(*a) for a in ((0, 0, 0), (1, 0, 0), (1, 1, 1), (3, 1000, 2000), (10, 255, 256),
+                                   (32767, 1 << 20, 1 << 20))] == \
+        [0, 29440, 30208, 687104, 390656, 1362595840]
+    assert [prepare(*a) for a in ((0, 0), (1, 1), (6, 3000), (65535, 1 << 20))] == [0, 2816, 610048, 312998400]
+    assert [prepared(P) for P in (0, 1, 3, 17, 65535)] == [0, 26368, 77568, 437760, 1685036032]
+
+    def a256(x):
+        return (x + 255) & ~255
+    for P in (0, 1, 3, 17, 300, 32767):
+        for Ns, Nt in ((0, 0), (1, 0), (255, 256), (1000, 2000), (1 << 20, 1 << 20)):
+            assert register(P, Ns, Nt) == prepare(2 * P, Ns + Nt) + prepared(P) - a256(16 * P) - a256(64 * P), \
+                (P, Ns, Nt)

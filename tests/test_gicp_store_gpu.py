@@ -205,6 +205,52 @@ def test_capture_replays_bit_identical(pairs):
     assert types.get("kernel", 0) == 1 + 2 * 31
 
 
+def _pair_rows(res):
+    """a register_* dict of device tensors or a verify_* list -> per pair (transform bytes, fitness, rmse,
+    n_correspondences, iterations, information bytes)"""
+    if isinstance(res, dict):
+        torch.cuda.synchronize()
+        h = {k: res[k].cpu().numpy() for k in KEYS}
+        return [(h["transform"][i].tobytes(), float(h["fitness"][i]), float(h["rmse"][i]),
+                 int(h["n_correspondences"][i]), int(h["iterations"][i]), h["information"][i].tobytes())
+                for i in range(len(h["fitness"]))]
+    return [(T.tobytes(), info["fitness"], info["rmse"], info["n_correspondences"], info["iterations"],
+             info["information_matrix"].tobytes()) for _, T, info in res]
+
+
+def test_init_transform_forms():
+    """Every entry point takes ``init_transforms`` as a host float64 array or a device float64 tensor and, for the
+    identity, as None or an explicit array; whatever the form and the entry point, raw or stored, the results are
+    the same bits.  Two pairs of 400-row patches of one surface, the targets moved by about 4 degrees of yaw and
+    0.2 m; the guess is that yaw and shift."""
+    import gicp_clouds as GC
+    gv = _gv()
+    guess = synth.pose_xyz_yaw(0.2, 0.0, 0.0, 4.0)
+    T_true = guess @ G.delta_transform(0.2 * GC.MOTION)
+    A = GC.surface(0, 400, ext=6.0, relief=0.5)
+    B = [GC.moved(GC.surface(1000 + j, 400, ext=6.0, relief=0.5), T_true) for j in range(2)]
+    v = gv.GeometricVerifier()
+    query, store = v.prepare([A]), v.prepare(B)
+    calls = {"register_batch": lambda X: gv.register_batch([A, A], B, X),
+             "register_prepared": lambda X: gv.register_prepared(query, [0, 0], store, [0, 1], X),
+             "verify_batch": lambda X: v.verify_batch(A, B, X),
+             "verify_prepared": lambda X: v.verify_prepared(query, 0, store, [0, 1], X),
+             "verify_pairs": lambda X: v.verify_pairs(query, [0, 0], store, [0, 1], X)}
+    guesses, eyes = np.stack([guess, guess]).astype(np.float64), np.tile(np.eye(4), (2, 1, 1))
+    found = []
+    for forms in ((guesses, torch.from_numpy(guesses).cuda()), (None, eyes, torch.from_numpy(eyes).cuda())):
+        ref = None
+        for name, call in calls.items():
+            for X in forms:
+                rows = _pair_rows(call(X))
+                if ref is None:
+                    ref = rows
+                    assert len(ref) == 2 and all(r[3] > 0 for r in ref), ref
+                assert rows == ref, (name, type(X))
+        found.append(ref)
+    assert found[0][0][0] != found[1][0][0]              # the guess is used: another start, other last bits
+
+
 def _edge_fn(source_pose, target_pose, relative_transform, information_matrix):
     return {"transform": relative_transform, "information": information_matrix}
 
