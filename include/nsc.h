@@ -539,6 +539,74 @@ int nsc_yaw_align(const float *images_q, int32_t n_q, const float *images_c, int
                   const int64_t *ids_c, int32_t n_pairs, int32_t rows, int32_t *shift, double *scores,
                   double *init_transforms, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Planar initial guess (yaw, x, y) for stage 2: a joint vote over yaw hypotheses and planar translation bins, cast
+ * by the structure rows of two prepared clouds.  It covers what the yaw guess cannot: a revisit that is also
+ * translated by more than GICP's basin (about 1 m), e.g. in the other lane.
+ *
+ * Inputs: cloud source_ids[i] of sources and cloud target_ids[i] of targets (rows of an NscGicpCloudSet: points
+ * (m,3), covariances (m,6), both float64; the two sets may be one), and a table yaw_cs (n_yaw, 2) float64 of
+ * hypotheses (cos theta_h, sin theta_h).
+ * Structure row: (1 - C_zz) < normal_z2_max * (1 - epsilon), epsilon being the row's set's.  The stored covariance
+ * is I - (1 - epsilon) n n^T, so this is n_z^2 < normal_z2_max: a surface steeper than 30 degrees from horizontal at
+ * the default.  A row with fewer than 3 neighbours has the x axis as its normal and is a structure row.
+ * Rows taken: the source's structure rows whose row index within the cloud is divisible by source_stride, and all
+ * structure rows of the target.
+ * Vote, for hypothesis h = (c, s), source row a and target row b, in float64, every operation rounded on its own
+ * (no fused multiply-add), inv_cell = 1 / cell computed once:
+ *   xr = c a.x - s a.y;  yr = s a.x + c a.y
+ *   bx = floor((b.x - xr) inv_cell + 0.5);  by = floor((b.y - yr) inv_cell + 0.5)
+ *   one vote for (h, bx, by) iff |bx| <= half_bins and |by| <= half_bins and |b.z - a.z| <= z_window (inclusive;
+ *   compared as float64, before any conversion to an integer).
+ * Per hypothesis: peak_h = its largest count, bin_h = that bin, ties to the smaller flat index
+ *   (bx + half_bins) (2 half_bins + 1) + (by + half_bins).
+ * Per pair: best = the h of the largest peak_h, ties to the smaller h; peak = peak_best; runner_up = the largest
+ * peak_h among hypotheses more than guard indices from best, circularly over n_yaw (0 if there are none).  The
+ * guess [Rz from (c, s) of best | (bx cell, by cell, 0)] maps query (source) into candidate (target) coordinates.
+ * With peak = 0 (no structure rows, nothing inside the window) best = (-1, 0, 0) and the guess is the identity.  A
+ * pair with an id outside its set gets best = (-1, 0, 0), peak = runner_up = -1, counts 0 and the identity; nothing
+ * of the sets is read for it.
+ *
+ * Out: best (n_pairs,3) int32 = [h, bx, by]; scores (n_pairs,2) int32 = [peak, runner_up]; counts (n_pairs,2) int32
+ * = [source rows taken, target structure rows]; init_transforms (n_pairs,4,4) float64 row-major.  Optional stage
+ * outputs (either pointer may be NULL): yaw_peaks (n_pairs, n_yaw, 2) int32 = [peak_h, flat bin_h] and votes
+ * (n_pairs, n_yaw, 2 half_bins + 1, 2 half_bins + 1) int32, all zero for a pair with an invalid id.
+ *
+ * Counts: a target row is the centroid of one voxel of the target set's voxel_size, so one source row casts at most
+ * K = (floor(cell / voxel_size) + 2)^2 (floor(2 z_window / voxel_size) + 2) votes into one bin (36 at the defaults),
+ * and never more than the target has rows.  A cloud has at most its set's n_rows rows: the call returns
+ * NSC_EUNSUPPORTED, before anything is launched, unless sources->n_rows * min(K, targets->n_rows) <= 2^31 - 1 (59
+ * million source rows in the set at the defaults).  Pairs are indexed by a grid dimension: more than
+ * NSC_PLANAR_MAX_PAIRS pairs return NSC_EUNSUPPORTED and the caller splits the batch; a pair's outputs depend on its
+ * two clouds, the table and the parameters alone.
+ * Three kernel launches (resolve ids and count rows; vote, one workgroup per hypothesis and pair; reduce over the
+ * hypotheses) and nothing else.
+ * ------------------------------------------------------------------------------------------ */
+#define NSC_PLANAR_MAX_HALF_BINS 32
+#define NSC_PLANAR_MAX_PAIRS     65535
+
+typedef struct NscPlanarParams {
+    double  cell;            /* 0.5   bin edge (m), > 0                                            */
+    double  z_window;        /* 0.5   a pair votes iff |dz| <= this (m), >= 0                      */
+    double  normal_z2_max;   /* 0.25  structure rows have n_z^2 below this                         */
+    int32_t half_bins;       /* 24    bins -half_bins .. half_bins per axis; 1 .. 32               */
+    int32_t source_stride;   /* 2     source rows taken: row index % source_stride == 0; >= 1      */
+    int32_t guard;           /* 5     hypotheses either side of best the runner-up skips; >= 0     */
+} NscPlanarParams;
+
+typedef struct NscPlanarStages {   /* optional stage outputs (any pointer may be NULL) */
+    int32_t *yaw_peaks;
+    int32_t *votes;
+} NscPlanarStages;
+
+void   nsc_planar_default_params(NscPlanarParams *p);
+size_t nsc_planar_align_workspace_bytes(int32_t n_pairs, int32_t n_yaw);
+int    nsc_planar_align(const NscGicpCloudSet *sources, const NscGicpCloudSet *targets, const int64_t *source_ids,
+                        const int64_t *target_ids, int32_t n_pairs, const double *yaw_cs, int32_t n_yaw,
+                        const NscPlanarParams *params, int32_t *best, int32_t *scores, int32_t *counts,
+                        double *init_transforms, const NscPlanarStages *stages, void *ws, size_t ws_bytes,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

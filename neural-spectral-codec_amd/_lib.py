@@ -93,11 +93,24 @@ class GicpCloudSet(C.Structure):
         (n, C.c_void_p) for n in ("row_offsets", "slot_offsets", "bounds", "points", "covariances", "slots")]
 
 
+class PlanarParams(C.Structure):
+    """struct NscPlanarParams"""
+    _fields_ = [("cell", C.c_double), ("z_window", C.c_double), ("normal_z2_max", C.c_double),
+                ("half_bins", C.c_int32), ("source_stride", C.c_int32), ("guard", C.c_int32)]
+
+
+class PlanarStages(C.Structure):
+    """struct NscPlanarStages"""
+    _fields_ = [(n, C.c_void_p) for n in ("yaw_peaks", "votes")]
+
+
 GICP_MAX_KNN = 32
 # include/nsc.h NSC_GICP_MAX_PAIRS, NSC_GICP_MAX_CLOUDS, NSC_GICP_MAX_PREPARED_PAIRS: the largest batch of one call
 GICP_MAX_PAIRS, GICP_MAX_CLOUDS, GICP_MAX_PREPARED_PAIRS = 32767, 65535, 65535
 # include/nsc.h NSC_YAW_GUARD_BINS, NSC_YAW_MAX_PAIRS
 YAW_GUARD_BINS, YAW_MAX_PAIRS = 10, 4194304
+# include/nsc.h NSC_PLANAR_MAX_HALF_BINS, NSC_PLANAR_MAX_PAIRS
+PLANAR_MAX_HALF_BINS, PLANAR_MAX_PAIRS = 32, 65535
 
 
 class GatGradLayer(C.Structure):
@@ -182,6 +195,11 @@ SYMBOLS = {
     "nsc_gicp_register_prepared": (C.c_int, [C.POINTER(GicpCloudSet), C.POINTER(GicpCloudSet), _vp, _vp, _i32,
                                              C.POINTER(GicpParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nsc_yaw_align": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "nsc_planar_default_params": (None, [C.POINTER(PlanarParams)]),
+    "nsc_planar_align_workspace_bytes": (_sz, [_i32, _i32]),
+    "nsc_planar_align": (C.c_int, [C.POINTER(GicpCloudSet), C.POINTER(GicpCloudSet), _vp, _vp, _i32, _vp, _i32,
+                                   C.POINTER(PlanarParams), _vp, _vp, _vp, _vp, C.POINTER(PlanarStages), _vp, _sz,
+                                   _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

@@ -43,8 +43,10 @@ GICP is a local method: from the identity it converges for offsets of about the 
 about 10 degrees of yaw alone, and from further away it can end on the ground plane alone with a fitness that passes
 the default thresholds and a transform that is wrong by the whole yaw.  ``TwoStageRetrieval(yaw_init=True)`` covers
 any yaw about the vertical axis: it starts every pair from the rotation ``estimate_yaw`` (yaw_alignment.py) reads
-off the two range images, good to a few degrees.  It does not cover a translation beyond about 1 m, or roll and
-pitch: pass ``init_transforms`` (odometry; host arrays or device tensors) for those.
+off the two range images, good to a few degrees.  It does not cover a translation beyond about 1 m:
+``TwoStageRetrieval(planar_init=True)`` does, by searching yaw and planar translation jointly over the structure rows
+of the prepared clouds (planar_alignment.py).  For roll and pitch pass ``init_transforms`` (odometry; host arrays or
+device tensors).
 """
 import ctypes as C
 from typing import List, Optional, Sequence

@@ -25,6 +25,12 @@ What runs where
     interpolated range image (``keyframe.range_image``, else ``yaw_encoder`` on its points) goes into a device store
     (YawImages, 23 KB per keyframe at 16 rows) when it is inserted, a query's candidates are estimated in one launch
     and the guesses reach the registration as a device tensor.  Off (the default) nothing of this runs.
+    With ``planar_init=True`` (needs ``prepare_geometry=True``; not together with ``yaw_init``) every pair starts from
+    the yaw and planar translation that the structure rows of the two prepared clouds vote for (planar_alignment.py,
+    nsc_planar_align), so a revisit that is rotated and metres away -- the other lane -- verifies: a query's
+    candidates are estimated in one call on the stores stage 2 already holds.  ``planar_min_support``, when given,
+    marks a candidate whose ``planar_support`` is below it as not verified, whatever GICP returned.  Off (the
+    default) nothing of this runs.
   * With ``compressed=True`` stage 1 runs over 16-bit rows: ``retriever`` is a ``CompressedRetriever`` (compressed.py),
     descriptors and queries are quantised as the wire format quantises them and ranked by the integer W1 of their
     CDFs -- a quarter of the HBM per keyframe, distances that are those of the dequantised descriptors.  Off (the
@@ -46,6 +52,7 @@ import torch.distributed as dist
 
 from .. import _lib
 from . import geometric_verification as _gv
+from . import planar_alignment as _planar
 from . import yaw_alignment as _yaw
 from .compressed import CompressedRetriever
 from .wasserstein import WassersteinRetriever, _topk
@@ -64,7 +71,8 @@ class LoopClosureCandidate:
     fitness: Optional[float] = None
     rmse: Optional[float] = None
     information_matrix: Optional[np.ndarray] = None
-    info: Optional[dict] = None          # the verifier's info dict (with yaw_init: + init_yaw_deg, yaw_peak_ratio)
+    info: Optional[dict] = None          # the verifier's info dict (with yaw_init: + init_yaw_deg, yaw_peak_ratio;
+                                         # with planar_init: + planar_info's keys)
 
 
 def _position(pose) -> np.ndarray:
@@ -79,7 +87,8 @@ class TwoStageRetrieval:
     def __init__(self, top_k: int = 10, spatial_filter_distance: float = 50.0, context_window: int = 10,
                  fitness_threshold: float = 0.3, rmse_threshold: float = 0.5, verification_method: str = "gicp",
                  use_torch: bool = True, device: str = 'cuda', verifier=None, edge_fn=None,
-                 prepare_geometry: bool = False, yaw_init: bool = False, yaw_encoder=None, compressed: bool = False):
+                 prepare_geometry: bool = False, yaw_init: bool = False, yaw_encoder=None, compressed: bool = False,
+                 planar_init: bool = False, planar_min_support: Optional[float] = None):
         self.top_k = top_k
         self.spatial_filter_distance = spatial_filter_distance
         self.context_window = context_window
@@ -99,6 +108,12 @@ class TwoStageRetrieval:
                 raise _lib.NscError("prepare_geometry=True needs verifier=GeometricVerifier(...)")
             self.geometry = verifier.prepare()
             self._query_geometry = verifier.prepare()
+        if planar_init and yaw_init:
+            raise ValueError("planar_init=True already searches the yaw: do not combine it with yaw_init=True")
+        if planar_init and self.geometry is None:
+            raise _lib.NscError("planar_init=True reads the prepared stores: it needs prepare_geometry=True")
+        self.planar_init = bool(planar_init)
+        self.planar_min_support = None if planar_min_support is None else float(planar_min_support)
         self.yaw_images = None           # yaw_init: YawImages of the keyframes, id = database index
         self.yaw_encoder = None
         if yaw_init:
@@ -224,7 +239,13 @@ class TwoStageRetrieval:
         if self.geometry is not None:
             self._query_geometry.clear()
             self._query_geometry.add([query_points])
+            planar = None
+            if self.planar_init:                                 # three launches, no sync
+                planar = _planar.estimate_planar(self._query_geometry, [0] * len(ids), self.geometry, ids)
+                init = dict(init_transforms=planar["init_transforms"])
             results = self.verifier.verify_prepared(self._query_geometry, 0, self.geometry, ids, **init)
+            if planar is not None:
+                results = _with_planar_info(results, planar, self.planar_min_support)
         elif hasattr(self.verifier, "verify_batch"):
             results = self.verifier.verify_batch(query_points, [self.keyframes[i].points for i in ids], **init)
         else:
@@ -302,6 +323,20 @@ def _with_yaw_info(results, yaw):
     return results
 
 
+def _with_planar_info(results, planar, min_support=None):
+    """Add planar_info's keys of estimate_planar's outputs to the info dicts of the pairs' results (read after the
+    verifier's sync); with ``min_support`` a pair whose planar_support is below it is not verified."""
+    host = torch.cat([planar["init_transforms"].reshape(-1, 16), planar["scores"].double(),
+                      planar["counts"].double()], 1).cpu().numpy()
+    out = []
+    for (verified, transform, info), row in zip(results, host):
+        info.update(_planar.planar_info(row[:16], row[16], row[17], row[18]))
+        if min_support is not None and info["planar_support"] < min_support:
+            verified = False
+        out.append((verified, transform, info))
+    return out
+
+
 def prepare_chunked(store, clouds, max_rows: int = _PREPARE_ROWS):
     """store.add(clouds) in calls of at most ``max_rows`` raw rows (one cloud at least) -> ids"""
     ids, chunk, rows = [], [], 0
@@ -326,17 +361,20 @@ def create_two_stage_retrieval(top_k: int = 10, spatial_filter_distance: float =
 
 def batch_loop_closing(query_keyframes, database_keyframes, top_k: int = 10, spatial_filter_distance: float = 50.0,
                        verify: bool = True, verifier=None, edge_fn=None, prepare_geometry: bool = False,
-                       yaw_init: bool = False) -> Dict[int, list]:
+                       yaw_init: bool = False, planar_init: bool = False,
+                       planar_min_support: Optional[float] = None) -> Dict[int, list]:
     """:322-359.  With ``verify=False`` the values are the stage-1 candidate lists (one database pass for all
     queries); with ``verify=True`` the injected stage 2 runs per query as in the reference.  With
     ``prepare_geometry=True`` (a GeometricVerifier) every database and query cloud is prepared once, stage 1 runs
     for all queries in one pass and stage 2 registers all queries' candidate pairs in one register_prepared call;
     the result equals the per-query one.  ``yaw_init=True`` starts every pair from its yaw guess (TwoStageRetrieval);
     with ``prepare_geometry=True`` all queries' pairs are estimated in one estimate_yaw call before the one
-    registration."""
+    registration.  ``planar_init=True`` (with ``prepare_geometry=True``) starts every pair from its planar guess
+    (TwoStageRetrieval), all queries' pairs estimated in one estimate_planar call."""
     retrieval = create_two_stage_retrieval(top_k=top_k, spatial_filter_distance=spatial_filter_distance,
                                            verifier=verifier, edge_fn=edge_fn, prepare_geometry=prepare_geometry,
-                                           yaw_init=yaw_init)
+                                           yaw_init=yaw_init, planar_init=planar_init,
+                                           planar_min_support=planar_min_support)
     retrieval.add_keyframes(database_keyframes)
     if not verify:
         return dict(enumerate(retrieval.global_retrieval_batch(query_keyframes)))
@@ -358,6 +396,11 @@ def batch_loop_closing(query_keyframes, database_keyframes, top_k: int = 10, spa
         yaw = _yaw.estimate_yaw(retrieval._range_images(query_keyframes), qids, retrieval.yaw_images, cids)
         results = _with_yaw_info(verifier.verify_pairs(queries, qids, retrieval.geometry, cids,
                                                        init_transforms=yaw["init_transforms"]), yaw)
+    elif planar_init and qids:
+        planar = _planar.estimate_planar(queries, qids, retrieval.geometry, cids)
+        results = _with_planar_info(verifier.verify_pairs(queries, qids, retrieval.geometry, cids,
+                                                          init_transforms=planar["init_transforms"]), planar,
+                                    planar_min_support)
     else:
         results = verifier.verify_pairs(queries, qids, retrieval.geometry, cids)
     out, at = {}, 0
