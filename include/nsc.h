@@ -607,6 +607,87 @@ int    nsc_planar_align(const NscGicpCloudSet *sources, const NscGicpCloudSet *t
                         double *init_transforms, const NscPlanarStages *stages, void *ws, size_t ws_bytes,
                         void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Pose-graph optimisation: the consumer of stage 2's `transform` and `information`.  Odometry edges and verified loop
+ * closures in, corrected poses out (restated in tests/posegraph_restatement.py).  Float64.
+ *
+ * Problem.  poses (n_poses,4,4) row-major, sensor to world, rigid: rows 0..2 are read and written, row 3 is copied.
+ * edge_ij (n_edges,2) int64.  measurements (n_edges,4,4) with Z ~ X_i^-1 X_j: stage 2's `transform` for i = candidate,
+ * j = query.  information (n_edges,6,6), rotation first (the order of nsc_gicp_register's `information`), symmetric
+ * positive definite; only the upper triangle is read.  fixed (n_poses) uint8: a pose with fixed != 0 is never changed.
+ * An edge with i == j or an index outside [0, n_poses) is skipped: it contributes nothing and is counted.  A pose no
+ * counted edge touches, or whose damped diagonal block is not positive definite, is not moved either.
+ *
+ * Residual of an edge.  D = Z^-1 X_i^-1 X_j;  r = [Log_SO3(R_D); t_D];  cost F = sum r^T Omega r.
+ *   Log_SO3(R): v = vee(R - R^T) / 2, theta = atan2(|v|, (tr R - 1) / 2), phi = v theta / |v|, and phi = v for
+ *   |v| < 1e-12.  Residual rotations beyond 179 degrees are out of scope: the axis is lost where |v| -> 0 at pi.
+ * Update.  X_k <- [R_k Exp(phi_k) | t_k + R_k rho_k] for delta_k = (phi_k, rho_k); Exp is Rodrigues' formula, with
+ *   its series below |phi|^2 = 1e-8.
+ * Jacobians, exact for this residual and this update.  With A = X_i^-1 X_j and B = blockdiag(Jr^-1(r_phi), R_D):
+ *   J_j = B,  J_i = -B Ad(A^-1),  Ad(R, t) = [[R, 0], [[t]x R, R]],
+ *   Jr^-1(phi) = I + [phi]x / 2 + c [phi]x^2,  c = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta), and
+ *   c = 1/12 + theta^2 / 720 for theta < 1e-4.
+ * System.  g = sum J^T Omega r (half the gradient of F), H = sum J^T Omega J.
+ *
+ * Solver.  Levenberg-Marquardt with Marquardt scaling.  Per outer iteration, at damping lambda:
+ *   (H + lambda diag H) delta = -g over the poses that move, delta = 0 elsewhere, by preconditioned conjugate
+ *   gradients from delta = 0.  Preconditioner: the Cholesky factor of each node's 6 x 6 diagonal block of the damped
+ *   matrix.  An inner iteration is counted once its step is applied; the loop ends at |r| <= pcg_tolerance |g|, at
+ *   max_pcg_iterations, or when p.Ap or r.z is not positive (that iteration applies no step).  No inner iteration
+ *   runs for g = 0.
+ *   Candidate poses = the update by delta; F_c = their cost; step = |delta| over all poses.
+ *   F_c < F: accepted, the candidate replaces the poses, lambda <- max(lambda / lambda_factor, lambda_min), and the
+ *     optimiser stops (converged) when F - F_c < relative_cost F.
+ *   Otherwise: rejected, lambda <- lambda lambda_factor.
+ *   Either way it stops (converged) when step < min_step, and (capped) after max_iteration outer iterations.
+ *
+ * Determinism.  Node quantities are gathered over a node's incident edges in ascending edge index; scalars (the cost
+ * too: a node sums the edges it is the first end of) are summed as fixed-shape partials over the nodes; no floating-
+ * point atomics.  Two calls on the same inputs agree bit for bit, and where the skipped edges stand among the others
+ * changes no bit of any other output.
+ * Launches.  A sequence that depends on n_poses > 0, n_edges > 0, poses_out == poses, max_iteration and
+ * max_pcg_iterations alone: 5 (lists) + 1 (copy, unless aliased) + 3 + max_iteration (8 + 4 max_pcg_iterations) + 1,
+ * at most NSC_POSEGRAPH_MAX_LAUNCHES in the loop (else NSC_EUNSUPPORTED).  Kernels of a finished phase return at once.
+ * No host synchronisation, no memset or memcpy nodes: the call can be captured.
+ * ------------------------------------------------------------------------------------------ */
+#define NSC_POSEGRAPH_MAX_EDGES    1073741823   /* list entries are 2 edge + side in int32 */
+#define NSC_POSEGRAPH_MAX_LAUNCHES 1000000
+#define NSC_POSEGRAPH_STATS        10
+
+typedef struct NscPoseGraphParams {
+    int32_t max_iteration;        /* 20     outer iterations at most, >= 0                                  */
+    int32_t max_pcg_iterations;   /* 100    inner iterations per outer iteration at most, >= 0              */
+    double  pcg_tolerance;        /* 1e-6   inner loop ends at |r| <= this |g|, >= 0                        */
+    double  lambda0;              /* 1e-4   initial damping, > 0                                            */
+    double  lambda_min;           /* 1e-9   floor of the damping, > 0                                       */
+    double  lambda_factor;        /* 10     lambda is divided (accept) or multiplied (reject) by this, > 1  */
+    double  relative_cost;        /* 1e-9   stop when an accepted step gains less than this times F, >= 0   */
+    double  min_step;             /* 1e-9   stop when |delta| is below this, >= 0                           */
+} NscPoseGraphParams;
+
+void   nsc_posegraph_default_params(NscPoseGraphParams *p);
+/* Bytes of workspace for a graph of this size; params may be NULL (the layout does not depend on the caps). */
+size_t nsc_posegraph_workspace_bytes(int32_t n_poses, int32_t n_edges, const NscPoseGraphParams *params);
+
+/* The system at `poses`: residuals (n_edges,6), zero rows for skipped edges; cost (1) = F; gradient (n_poses,6) = g;
+ * blocks (n_poses,21) = upper triangle, row-major, of each pose's diagonal block of H; skipped (1) int64.  Fixed poses
+ * play no part here: every pose gets its row.  The outputs of the counted edges do not depend on the skipped ones. */
+int    nsc_posegraph_linearize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
+                               const double *information, int32_t n_edges, double *residuals, double *cost,
+                               double *gradient, double *blocks, int64_t *skipped, void *ws, size_t ws_bytes,
+                               void *stream);
+
+/* poses_out (n_poses,4,4) may alias poses.  stats (NSC_POSEGRAPH_STATS) float64 = [outer iterations done, accepted,
+ * rejected, inner iterations in total, initial cost, final cost, final lambda, skipped edges, 1 = stopped by a
+ * criterion / 0 = capped at max_iteration, |delta| of the last outer iteration].  cost_history (max_iteration + 1):
+ * entry 0 the initial cost, entry k the cost after outer iteration k (unchanged by a rejected step), entries past the
+ * last iteration the final cost.  step0 (n_poses,6), nullable: the first delta (not written when max_iteration = 0).
+ * With max_iteration = 0 poses_out = poses bit for bit and the costs are those of the input. */
+int    nsc_posegraph_optimize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
+                              const double *information, int32_t n_edges, const uint8_t *fixed,
+                              const NscPoseGraphParams *params, double *poses_out, double *stats, double *cost_history,
+                              double *step0, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,16 @@ class PlanarStages(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("yaw_peaks", "votes")]
 
 
+class PoseGraphParams(C.Structure):
+    """struct NscPoseGraphParams"""
+    _fields_ = [("max_iteration", C.c_int32), ("max_pcg_iterations", C.c_int32), ("pcg_tolerance", C.c_double),
+                ("lambda0", C.c_double), ("lambda_min", C.c_double), ("lambda_factor", C.c_double),
+                ("relative_cost", C.c_double), ("min_step", C.c_double)]
+
+
+# include/nsc.h NSC_POSEGRAPH_MAX_EDGES, NSC_POSEGRAPH_MAX_LAUNCHES, NSC_POSEGRAPH_STATS
+POSEGRAPH_MAX_EDGES, POSEGRAPH_MAX_LAUNCHES, POSEGRAPH_STATS = 1073741823, 1000000, 10
+
 GICP_MAX_KNN = 32
 # include/nsc.h NSC_GICP_MAX_PAIRS, NSC_GICP_MAX_CLOUDS, NSC_GICP_MAX_PREPARED_PAIRS: the largest batch of one call
 GICP_MAX_PAIRS, GICP_MAX_CLOUDS, GICP_MAX_PREPARED_PAIRS = 32767, 65535, 65535
@@ -200,6 +210,11 @@ SYMBOLS = {
     "nsc_planar_align": (C.c_int, [C.POINTER(GicpCloudSet), C.POINTER(GicpCloudSet), _vp, _vp, _i32, _vp, _i32,
                                    C.POINTER(PlanarParams), _vp, _vp, _vp, _vp, C.POINTER(PlanarStages), _vp, _sz,
                                    _vp]),
+    "nsc_posegraph_default_params": (None, [C.POINTER(PoseGraphParams)]),
+    "nsc_posegraph_workspace_bytes": (_sz, [_i32, _i32, C.POINTER(PoseGraphParams)]),
+    "nsc_posegraph_linearize": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nsc_posegraph_optimize": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PoseGraphParams), _vp, _vp,
+                                         _vp, _vp, _vp, _sz, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

@@ -1,0 +1,969 @@
+// nsc_posegraph.hip -- pose-graph optimisation: odometry edges and verified loop closures in, corrected poses out.
+// Float64 throughout.  The contract is stated in include/nsc.h (nsc_posegraph_optimize); tests/posegraph_restatement.py
+// restates it in numpy; DESIGN.md section 4.11 has the launch sequence and the measurements.
+//
+//   D = Z^-1 X_i^-1 X_j,  r = [Log_SO3(R_D); t_D],  F = sum r^T Omega r,  update X_k <- [R_k Exp(phi_k) | t_k + R_k rho_k]
+//   J_j = B = blockdiag(Jr^-1(r_phi), R_D),  J_i = -B Ad(A^-1) with A = X_i^-1 X_j
+//   Levenberg-Marquardt with Marquardt scaling, (H + lambda diag H) delta = -g, solved by conjugate gradients
+//   preconditioned with the Cholesky factor of each node's damped 6 x 6 diagonal block.
+//
+// Shape.  Every workgroup is one wave of 64 lanes: a graph of a few thousand poses is a few dozen waves, and one wave per
+// workgroup spreads them over as many CUs; every reduction is then a butterfly of the wave, with no LDS and no barrier.
+// One lane per edge linearises (pg_linearize_kernel: the four blocks of J^T Omega J and the two halves of J^T Omega r, kept
+// structure-of-arrays so that the 78 block values of 64 neighbouring edges are read in 78 coalesced requests) and forms the
+// edge half of H p (pg_edge_matvec_kernel); one lane per node gathers over the node's incident edges, in ascending
+// edge index (the lists are built once per call).  A node of degree 300 is one lane walking 300 entries: correct, not
+// fast; the graphs this is for have degree 2 to 4 almost everywhere.
+//
+// Determinism.  No floating-point atomics.  Node quantities are gathered in list order.  A scalar (cost, p.Ap, r.r,
+// r.z, |delta|^2) is written as one partial per workgroup of nodes (the cost too: each node sums the edges it is the
+// first end of); every consumer sums the partials itself, lane l taking partials l, l + 64, ... in ascending order and
+// the wave finishing with the same butterfly, so every workgroup of every consumer holds the same bits.  The integer
+// atomics that build the lists only count; the order they hand places out in is removed by ranking each node's
+// entries.
+//
+// Control.  The launch sequence depends on the parameters alone.  All solver state lives in PgState on the device.
+// `done` is written by single-wave kernels only and read at the top of every later kernel.  The inner loop ends through
+// `stop_k`: iteration k runs iff k < stop_k, and the kernel that ends the loop at iteration k writes k + 1, so its own
+// workgroups, which read stop_k while it is being written, see "run" either way.  The two r.z values alternate between
+// two slots for the same reason.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/nsc.h"
+#include "nsc_fill.h"
+
+namespace {
+
+constexpr int TB = 64;                       // lanes per workgroup: one wave
+
+struct PgState {
+    double lambda, cost, cost0, bb, rz[2], step;
+    int done, converged, stop_k, accept_it, iterations, accepted, rejected, pcg_total, skipped, pad;
+};
+
+struct PgParams {                            // NscPoseGraphParams as the kernels read them
+    double tol2, lambda0, lambda_min, factor, relative_cost, min_step;
+    int max_iteration, max_pcg;
+};
+
+struct Buffers {                             // the workspace
+    PgState *st;
+    int *row_ptr, *cursor, *tmp, *list, *ei, *ej, *free_node;
+    double *hii, *hjj, *hij;                 // (21,E), (21,E), (36,E)
+    double *fe;                              // (E): r^T Omega r
+    double *ge, *ye;                         // (E,12): J^T Omega r and the edge half of H p, node i's six then node j's
+    double *g, *blocks, *chol;               // (N,6), (N,21), (N,21)
+    double *x, *r, *z, *p, *ap;              // (N,6)
+    double *cand;                            // (N,4,4), rows 0..2 used
+    double *part_e, *part_a, *part_b, *part_s;   // partials, one per workgroup of nodes: cost, p.Ap, (r.r, r.z), |delta|^2
+};
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// the sum of nb partials, the same bits in every lane of every wave that calls it
+__device__ __forceinline__ double finish(const double *part, int nb)
+{
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nb; i += TB) s += part[i];
+    return wave_sum(s);
+}
+
+__device__ __forceinline__ void write_partial(double *part, double v)
+{
+    v = wave_sum(v);
+    if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+
+// ---- rotations -------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ void load_pose(const double *P, long long n, double R[9], double t[3])
+{
+    const double *q = P + 16 * n;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        R[3 * r] = q[4 * r];
+        R[3 * r + 1] = q[4 * r + 1];
+        R[3 * r + 2] = q[4 * r + 2];
+        t[r] = q[4 * r + 3];
+    }
+}
+
+// C = A^T B
+__device__ __forceinline__ void mul_tn(const double A[9], const double B[9], double C[9])
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) C[3 * r + c] = A[r] * B[c] + A[3 + r] * B[3 + c] + A[6 + r] * B[6 + c];
+}
+
+// y = A^T x
+__device__ __forceinline__ void mulv_t(const double A[9], const double x[3], double y[3])
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r) y[r] = A[r] * x[0] + A[3 + r] * x[1] + A[6 + r] * x[2];
+}
+
+__device__ __forceinline__ void hat(const double v[3], double K[9])
+{
+    K[0] = 0.0;   K[1] = -v[2]; K[2] = v[1];
+    K[3] = v[2];  K[4] = 0.0;   K[5] = -v[0];
+    K[6] = -v[1]; K[7] = v[0];  K[8] = 0.0;
+}
+
+// M = I + a [v]x + b [v]x^2, with [v]x^2 = v v^T - |v|^2 I
+__device__ __forceinline__ void rodrigues_form(const double v[3], double a, double b, double M[9])
+{
+    const double n2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+    double K[9];
+    hat(v, K);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            M[3 * r + c] = (r == c ? 1.0 : 0.0) + a * K[3 * r + c] + b * (v[r] * v[c] - (r == c ? n2 : 0.0));
+}
+
+__device__ __forceinline__ void exp_so3(const double phi[3], double R[9])
+{
+    const double t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
+    double a, b;
+    if (t2 < 1e-8) {
+        a = 1.0 - t2 / 6.0 + t2 * t2 / 120.0;
+        b = 0.5 - t2 / 24.0 + t2 * t2 / 720.0;
+    } else {
+        const double t = sqrt(t2);
+        a = sin(t) / t;
+        b = (1.0 - cos(t)) / t2;
+    }
+    rodrigues_form(phi, a, b, R);
+}
+
+__device__ __forceinline__ void log_so3(const double R[9], double phi[3])
+{
+    const double v[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
+    const double s = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    const double k = s < 1e-12 ? 1.0 : atan2(s, 0.5 * (R[0] + R[4] + R[8] - 1.0)) / s;
+    phi[0] = v[0] * k;
+    phi[1] = v[1] * k;
+    phi[2] = v[2] * k;
+}
+
+__device__ __forceinline__ void jr_inv(const double phi[3], double J[9])
+{
+    const double t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
+    const double t = sqrt(t2);
+    const double c = t < 1e-4 ? 1.0 / 12.0 + t2 / 720.0 : 1.0 / t2 - (1.0 + cos(t)) / (2.0 * t * sin(t));
+    rodrigues_form(phi, 0.5, c, J);
+}
+
+// A = X_i^-1 X_j and D = Z^-1 A of one edge, and the residual
+struct EdgeGeom {
+    double RA[9], tA[3], RD[9], RZ[9], r[6];
+};
+
+__device__ __forceinline__ void edge_geometry(const double *poses, long long i, long long j, const double *Z, long long e,
+                                              EdgeGeom &q)
+{
+    double Ri[9], ti[3], Rj[9], tj[3], tz[3];
+    load_pose(poses, i, Ri, ti);
+    load_pose(poses, j, Rj, tj);
+    load_pose(Z, e, q.RZ, tz);
+    mul_tn(Ri, Rj, q.RA);
+    const double d[3] = {tj[0] - ti[0], tj[1] - ti[1], tj[2] - ti[2]};
+    mulv_t(Ri, d, q.tA);
+    mul_tn(q.RZ, q.RA, q.RD);
+    const double f[3] = {q.tA[0] - tz[0], q.tA[1] - tz[1], q.tA[2] - tz[2]};
+    mulv_t(q.RZ, f, q.r + 3);
+    log_so3(q.RD, q.r);
+}
+
+// Omega of edge e as a full symmetric matrix; only the upper triangle of the input is read
+__device__ __forceinline__ void load_information(const double *information, long long e, double W[36])
+{
+    const double *q = information + 36 * e;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 6; ++c) W[6 * r + c] = W[6 * c + r] = q[6 * r + c];
+}
+
+__device__ __forceinline__ double quad_form(const double W[36], const double r[6])
+{
+    double f = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        double w = 0.0;
+#pragma unroll
+        for (int b = 0; b < 6; ++b) w += W[6 * a + b] * r[b];
+        f += r[a] * w;
+    }
+    return f;
+}
+
+// index of (r, c), r <= c, in a row-major upper triangle of a 6 x 6 matrix
+__device__ __host__ constexpr int tri(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }
+
+// ---- incident-edge lists -----------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(TB) void pg_count_kernel(const long long *__restrict__ edge_ij, int n_edges, int n_poses,
+                                                      Buffers b)
+{
+    const int e = blockIdx.x * TB + threadIdx.x;
+    if (e >= n_edges) return;
+    const long long i = edge_ij[2 * (long long)e], j = edge_ij[2 * (long long)e + 1];
+    const bool ok = i != j && i >= 0 && i < n_poses && j >= 0 && j < n_poses;
+    b.ei[e] = ok ? (int)i : -1;
+    b.ej[e] = ok ? (int)j : -1;
+    if (ok) {
+        atomicAdd(&b.row_ptr[i + 1], 1);
+        atomicAdd(&b.row_ptr[j + 1], 1);
+    } else {
+        atomicAdd(&b.st->skipped, 1);
+    }
+}
+
+// exclusive scan of the degrees in row_ptr[1 .. N] (row_ptr[0] = 0), in place, by one wave; cursor = row_ptr
+__global__ __launch_bounds__(TB) void pg_scan_kernel(int n_poses, Buffers b)
+{
+    const int lane = threadIdx.x;
+    const int per = (n_poses + TB - 1) / TB;
+    const int lo = min(lane * per, n_poses), hi = min(lo + per, n_poses);
+    int sum = 0;
+    for (int n = lo; n < hi; ++n) sum += b.row_ptr[n + 1];
+    int incl = sum;
+    for (int off = 1; off < TB; off <<= 1) {
+        const int o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    int run = incl - sum;                    // entries of the nodes before this lane's
+    for (int n = lo; n < hi; ++n) {
+        const int d = b.row_ptr[n + 1];
+        b.cursor[n] = run;
+        run += d;
+        b.row_ptr[n + 1] = run;
+    }
+}
+
+__global__ __launch_bounds__(TB) void pg_fill_kernel(int n_edges, Buffers b)
+{
+    const int e = blockIdx.x * TB + threadIdx.x;
+    if (e >= n_edges) return;
+    const int i = b.ei[e], j = b.ej[e];
+    if (i < 0) return;
+    b.tmp[atomicAdd(&b.cursor[i], 1)] = 2 * e;
+    b.tmp[atomicAdd(&b.cursor[j], 1)] = 2 * e + 1;
+}
+
+// one wave per node: its entries (2 e + side, all different) into ascending order by rank
+__global__ __launch_bounds__(TB) void pg_sort_kernel(Buffers b)
+{
+    const int n = blockIdx.x;
+    const int lo = b.row_ptr[n], hi = b.row_ptr[n + 1];
+    for (int a = lo + threadIdx.x; a < hi; a += TB) {
+        const int v = b.tmp[a];
+        int rank = 0;
+        for (int c = lo; c < hi; ++c) rank += b.tmp[c] < v;
+        b.list[lo + rank] = v;
+    }
+}
+
+__global__ __launch_bounds__(TB) void pg_copy_kernel(const double *__restrict__ src, double *__restrict__ dst, long long n)
+{
+    const long long i = (long long)blockIdx.x * TB + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}
+
+// ---- edges -------------------------------------------------------------------------------------------------------
+
+// r^T Omega r of every counted edge at `poses`
+__global__ __launch_bounds__(TB) void pg_cost_kernel(const double *poses, const double *__restrict__ Z,
+                                                     const double *__restrict__ information, int n_edges, Buffers b,
+                                                     int check_done)
+{
+    if (check_done && b.st->done) return;
+    const int e = blockIdx.x * TB + threadIdx.x;
+    if (e >= n_edges || b.ei[e] < 0) return;
+    EdgeGeom q;
+    double W[36];
+    edge_geometry(poses, b.ei[e], b.ej[e], Z, e, q);
+    load_information(information, e, W);
+    b.fe[e] = quad_form(W, q.r);
+}
+
+// F: every node sums the edges it is the first end of, in list order; one partial per workgroup.  The sum walks the
+// lists, which hold counted edges only, so where the skipped edges stand among the others does not change a bit of it.
+__global__ __launch_bounds__(TB) void pg_cost_gather_kernel(int n_poses, Buffers b, int check_done)
+{
+    if (check_done && b.st->done) return;
+    const int n = blockIdx.x * TB + threadIdx.x;
+    double f = 0.0;
+    if (n < n_poses) {
+        const int lo = b.row_ptr[n], hi = b.row_ptr[n + 1];
+        for (int a = lo; a < hi; ++a) {
+            const int code = b.list[a];
+            if (!(code & 1)) f += b.fe[code >> 1];
+        }
+    }
+    write_partial(b.part_e, f);
+}
+
+// residual, the blocks of J^T Omega J and the halves of J^T Omega r of every edge
+__global__ __launch_bounds__(TB) void pg_linearize_kernel(const double *poses, const double *__restrict__ Z,
+                                                          const double *__restrict__ information, int n_edges,
+                                                          Buffers b, double *__restrict__ residuals, int check_done)
+{
+    if (check_done && b.st->done) return;
+    const int e = blockIdx.x * TB + threadIdx.x;
+    if (e >= n_edges) return;
+    if (b.ei[e] < 0) {
+        if (residuals)
+            for (int k = 0; k < 6; ++k) residuals[6 * (long long)e + k] = 0.0;
+        return;
+    }
+    EdgeGeom q;
+    edge_geometry(poses, b.ei[e], b.ej[e], Z, e, q);
+    if (residuals)
+        for (int k = 0; k < 6; ++k) residuals[6 * (long long)e + k] = q.r[k];
+
+    // J_j = blockdiag(Jr^-1, R_D);  J_i = -[[Jr^-1 R_A^T, 0], [-R_Z^T [t_A]x, R_Z^T]]  (R_D R_A^T = R_Z^T)
+    double Ji[36], Jj[36], Jr[9], K[9];
+    jr_inv(q.r, Jr);
+    hat(q.tA, K);
+#pragma unroll
+    for (int k = 0; k < 36; ++k) Ji[k] = Jj[k] = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            Jj[6 * r + c] = Jr[3 * r + c];
+            Jj[6 * (r + 3) + c + 3] = q.RD[3 * r + c];
+            // (Jr R_A^T)[r][c] = sum_k Jr[r][k] R_A[c][k];  (R_Z^T K)[r][c] = sum_k R_Z[k][r] K[k][c]
+            Ji[6 * r + c] = -(Jr[3 * r] * q.RA[3 * c] + Jr[3 * r + 1] * q.RA[3 * c + 1] + Jr[3 * r + 2] * q.RA[3 * c + 2]);
+            Ji[6 * (r + 3) + c] = q.RZ[r] * K[c] + q.RZ[3 + r] * K[3 + c] + q.RZ[6 + r] * K[6 + c];
+            Ji[6 * (r + 3) + c + 3] = -q.RZ[3 * c + r];
+        }
+
+    double W[36], Wi[36], Wj[36], wr[6];
+    load_information(information, e, W);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            double si = 0.0, sj = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                si += W[6 * a + k] * Ji[6 * k + c];
+                sj += W[6 * a + k] * Jj[6 * k + c];
+            }
+            Wi[6 * a + c] = si;
+            Wj[6 * a + c] = sj;
+            s += W[6 * a + c] * q.r[c];
+        }
+        wr[a] = s;
+    }
+    const long long E = n_edges;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        double gi = 0.0, gj = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            gi += Ji[6 * k + r] * wr[k];
+            gj += Jj[6 * k + r] * wr[k];
+        }
+        b.ge[12 * (long long)e + r] = gi;
+        b.ge[12 * (long long)e + 6 + r] = gj;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            double hii = 0.0, hjj = 0.0, hij = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                hii += Ji[6 * k + r] * Wi[6 * k + c];
+                hjj += Jj[6 * k + r] * Wj[6 * k + c];
+                hij += Ji[6 * k + r] * Wj[6 * k + c];
+            }
+            b.hij[(6 * r + c) * E + e] = hij;
+            if (c >= r) {
+                b.hii[tri(r, c) * E + e] = hii;
+                b.hjj[tri(r, c) * E + e] = hjj;
+            }
+        }
+    }
+}
+
+// the edge half of H p: y_i = H_ii p_i + H_ij p_j, y_j = H_ij^T p_i + H_jj p_j
+__global__ __launch_bounds__(TB) void pg_edge_matvec_kernel(int n_edges, Buffers b, int k)
+{
+    if (b.st->done || k >= b.st->stop_k) return;
+    const int e = blockIdx.x * TB + threadIdx.x;
+    if (e >= n_edges) return;
+    const int i = b.ei[e], j = b.ej[e];
+    if (i < 0) return;
+    const long long E = n_edges;
+    double pi[6], pj[6], yi[6], yj[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        pi[a] = b.p[6 * (long long)i + a];
+        pj[a] = b.p[6 * (long long)j + a];
+        yi[a] = yj[a] = 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const double hij = b.hij[(6 * r + c) * E + e];
+            yi[r] += hij * pj[c];
+            yj[c] += hij * pi[r];
+            if (c >= r) {
+                const double hii = b.hii[tri(r, c) * E + e], hjj = b.hjj[tri(r, c) * E + e];
+                yi[r] += hii * pi[c];
+                yj[r] += hjj * pj[c];
+                if (c > r) {
+                    yi[c] += hii * pi[r];
+                    yj[c] += hjj * pj[r];
+                }
+            }
+        }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        b.ye[12 * (long long)e + a] = yi[a];
+        b.ye[12 * (long long)e + 6 + a] = yj[a];
+    }
+}
+
+// ---- nodes -------------------------------------------------------------------------------------------------------
+
+// U^T U = M (upper triangle in place); false when a pivot is not positive
+__device__ __forceinline__ bool cholesky6(double U[21])
+{
+    bool ok = true;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        double d = U[tri(r, r)];
+#pragma unroll
+        for (int k = 0; k < r; ++k) d -= U[tri(k, r)] * U[tri(k, r)];
+        ok = ok && d > 0.0;
+        d = sqrt(d);
+        U[tri(r, r)] = d;
+#pragma unroll
+        for (int c = r + 1; c < 6; ++c) {
+            double s = U[tri(r, c)];
+#pragma unroll
+            for (int k = 0; k < r; ++k) s -= U[tri(k, r)] * U[tri(k, c)];
+            U[tri(r, c)] = s / d;
+        }
+    }
+    return ok;
+}
+
+// z = (U^T U)^-1 r
+__device__ __forceinline__ void cholesky_solve6(const double U[21], const double r[6], double z[6])
+{
+    double y[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        double s = r[a];
+#pragma unroll
+        for (int k = 0; k < a; ++k) s -= U[tri(k, a)] * y[k];
+        y[a] = s / U[tri(a, a)];
+    }
+#pragma unroll
+    for (int a = 5; a >= 0; --a) {
+        double s = y[a];
+#pragma unroll
+        for (int k = a + 1; k < 6; ++k) s -= U[tri(a, k)] * z[k];
+        z[a] = s / U[tri(a, a)];
+    }
+}
+
+// gather of g and the diagonal blocks; with solve != 0 also the damped factor and the start of PCG:
+// x = 0, r = -g, z = M^-1 r, p = z, partials of r.r and r.z
+__global__ __launch_bounds__(TB) void pg_assemble_kernel(int n_poses, int n_edges, const uint8_t *__restrict__ fixed,
+                                                         Buffers b, double *__restrict__ g_out,
+                                                         double *__restrict__ blocks_out, int solve)
+{
+    if (solve && b.st->done) return;
+    const int n = blockIdx.x * TB + threadIdx.x;
+    const int nb = gridDim.x;
+    double rr = 0.0, rz = 0.0;
+    if (n < n_poses) {
+        const long long E = n_edges;
+        double g[6] = {0, 0, 0, 0, 0, 0}, D[21];
+#pragma unroll
+        for (int k = 0; k < 21; ++k) D[k] = 0.0;
+        const int lo = b.row_ptr[n], hi = b.row_ptr[n + 1];
+        for (int a = lo; a < hi; ++a) {
+            const int code = b.list[a], e = code >> 1, side = code & 1;
+            const double *h = side ? b.hjj : b.hii;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) g[k] += b.ge[12 * (long long)e + 6 * side + k];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) D[k] += h[k * E + e];
+        }
+        for (int k = 0; k < 6; ++k) g_out[6 * (long long)n + k] = g[k];
+        for (int k = 0; k < 21; ++k) blocks_out[21 * (long long)n + k] = D[k];
+        if (solve) {
+            const double lambda = b.st->lambda;
+            double U[21], r[6], z[6];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) U[k] = D[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) U[tri(k, k)] += lambda * D[tri(k, k)];
+            bool free_n = !fixed[n] && hi > lo;
+            free_n = cholesky6(U) && free_n;
+            b.free_node[n] = free_n;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) r[k] = free_n ? -g[k] : 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) z[k] = 0.0;
+            if (free_n) cholesky_solve6(U, r, z);
+            for (int k = 0; k < 21; ++k) b.chol[21 * (long long)n + k] = U[k];
+            for (int k = 0; k < 6; ++k) {
+                const long long at = 6 * (long long)n + k;
+                b.x[at] = 0.0;
+                b.r[at] = r[k];
+                b.z[at] = z[k];
+                b.p[at] = z[k];
+                b.ap[at] = 0.0;
+                rr += r[k] * r[k];
+                rz += r[k] * z[k];
+            }
+        }
+    }
+    if (solve) {
+        write_partial(b.part_b, rr);
+        write_partial(b.part_b + nb, rz);
+    }
+}
+
+// one wave: |g|^2 and r.z of the start; no inner iteration when the gradient is zero
+__global__ __launch_bounds__(TB) void pg_pcg_begin_kernel(int nb, Buffers b)
+{
+    if (b.st->done) return;
+    const double bb = finish(b.part_b, nb), rz = finish(b.part_b + nb, nb);
+    if (threadIdx.x == 0) {
+        b.st->bb = bb;
+        b.st->rz[0] = rz;
+        b.st->stop_k = bb > 0.0 && rz > 0.0 ? INT_MAX : 0;
+    }
+}
+
+// A p = gather + lambda diag(H) p on the free nodes; partial of p.Ap
+__global__ __launch_bounds__(TB) void pg_node_matvec_kernel(int n_poses, Buffers b, int k)
+{
+    if (b.st->done || k >= b.st->stop_k) return;
+    const int n = blockIdx.x * TB + threadIdx.x;
+    double pap = 0.0;
+    if (n < n_poses && b.free_node[n]) {
+        const double lambda = b.st->lambda;
+        double y[6] = {0, 0, 0, 0, 0, 0};
+        const int lo = b.row_ptr[n], hi = b.row_ptr[n + 1];
+        for (int a = lo; a < hi; ++a) {
+            const int code = b.list[a], e = code >> 1, side = code & 1;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) y[c] += b.ye[12 * (long long)e + 6 * side + c];
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const long long at = 6 * (long long)n + c;
+            const double p = b.p[at];
+            y[c] += lambda * b.blocks[21 * (long long)n + tri(c, c)] * p;
+            b.ap[at] = y[c];
+            pap += p * y[c];
+        }
+    }
+    write_partial(b.part_a, pap);
+}
+
+// alpha = r.z / p.Ap;  x += alpha p;  r -= alpha A p;  z = M^-1 r;  partials of r.r and r.z
+__global__ __launch_bounds__(TB) void pg_pcg_step_kernel(int n_poses, Buffers b, int k)
+{
+    if (b.st->done || k >= b.st->stop_k) return;
+    const int nb = gridDim.x;
+    const double pap = finish(b.part_a, nb);
+    const double alpha = pap > 0.0 ? b.st->rz[k & 1] / pap : 0.0;
+    const int n = blockIdx.x * TB + threadIdx.x;
+    double rr = 0.0, rz = 0.0;
+    if (n < n_poses && b.free_node[n]) {
+        double U[21], r[6], z[6];
+        for (int c = 0; c < 21; ++c) U[c] = b.chol[21 * (long long)n + c];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const long long at = 6 * (long long)n + c;
+            b.x[at] += alpha * b.p[at];
+            r[c] = b.r[at] - alpha * b.ap[at];
+            b.r[at] = r[c];
+        }
+        cholesky_solve6(U, r, z);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            b.z[6 * (long long)n + c] = z[c];
+            rr += r[c] * r[c];
+            rz += r[c] * z[c];
+        }
+    }
+    write_partial(b.part_b, rr);
+    write_partial(b.part_b + nb, rz);
+}
+
+// beta = r.z (new) / r.z (old);  p = z + beta p;  the first lane of the grid counts the iteration and ends the loop at
+// |r| <= tolerance |g|, at p.Ap <= 0 or at r.z <= 0
+__global__ __launch_bounds__(TB) void pg_pcg_direction_kernel(int n_poses, Buffers b, int k, double tol2)
+{
+    if (b.st->done || k >= b.st->stop_k) return;
+    const int nb = gridDim.x;
+    const double pap = finish(b.part_a, nb), rr = finish(b.part_b, nb), rz = finish(b.part_b + nb, nb);
+    const double beta = rz / b.st->rz[k & 1];
+    const int n = blockIdx.x * TB + threadIdx.x;
+    if (n < n_poses && b.free_node[n]) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const long long at = 6 * (long long)n + c;
+            b.p[at] = b.z[at] + beta * b.p[at];
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        b.st->rz[(k + 1) & 1] = rz;
+        b.st->pcg_total += 1;
+        if (!(pap > 0.0) || rr <= tol2 * b.st->bb || !(rz > 0.0)) b.st->stop_k = k + 1;
+    }
+}
+
+// candidate poses X_k [Exp(phi_k) | rho_k]; partial of |delta|^2; the first delta of the call on request
+__global__ __launch_bounds__(TB) void pg_update_kernel(const double *poses, int n_poses, Buffers b, int it,
+                                                       double *__restrict__ step0)
+{
+    if (b.st->done) return;
+    const int n = blockIdx.x * TB + threadIdx.x;
+    double s2 = 0.0;
+    if (n < n_poses) {
+        double d[6];
+        for (int c = 0; c < 6; ++c) {
+            d[c] = b.x[6 * (long long)n + c];
+            s2 += d[c] * d[c];
+            if (it == 0 && step0) step0[6 * (long long)n + c] = d[c];
+        }
+        double R[9], t[3], Q[9];
+        load_pose(poses, n, R, t);
+        double *out = b.cand + 16 * (long long)n;
+        if (b.free_node[n]) {
+            exp_so3(d, Q);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) out[4 * r + c] = R[3 * r] * Q[c] + R[3 * r + 1] * Q[3 + c] + R[3 * r + 2] * Q[6 + c];
+                out[4 * r + 3] = t[r] + (R[3 * r] * d[3] + R[3 * r + 1] * d[4] + R[3 * r + 2] * d[5]);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) out[4 * r + c] = R[3 * r + c];
+                out[4 * r + 3] = t[r];
+            }
+        }
+    }
+    write_partial(b.part_s, s2);
+}
+
+// one wave: the cost at the start
+__global__ __launch_bounds__(TB) void pg_init_kernel(int nb_n, Buffers b, double lambda0, double *__restrict__ history)
+{
+    const double f = finish(b.part_e, nb_n);
+    if (threadIdx.x == 0) {
+        b.st->cost = b.st->cost0 = f;
+        b.st->lambda = lambda0;
+        b.st->accept_it = -1;
+        b.st->stop_k = 0;
+        history[0] = f;
+    }
+}
+
+// one wave: accept or reject the candidate, move lambda, test the stopping rules
+__global__ __launch_bounds__(TB) void pg_accept_kernel(int nb_n, Buffers b, PgParams prm, int it,
+                                                       double *__restrict__ history)
+{
+    if (b.st->done) return;
+    const double fc = finish(b.part_e, nb_n), step = sqrt(finish(b.part_s, nb_n));
+    if (threadIdx.x != 0) return;
+    PgState *st = b.st;
+    const double f = st->cost;
+    bool stop = false;
+    st->iterations += 1;
+    st->step = step;
+    if (fc < f) {
+        st->accepted += 1;
+        st->accept_it = it;
+        stop = (f - fc) < prm.relative_cost * f;
+        st->cost = fc;
+        st->lambda = fmax(st->lambda / prm.factor, prm.lambda_min);
+    } else {
+        st->rejected += 1;
+        st->lambda = st->lambda * prm.factor;
+    }
+    history[it + 1] = st->cost;
+    if (stop || step < prm.min_step) {
+        st->done = 1;
+        st->converged = 1;
+    }
+}
+
+// the accepted candidate becomes the pose of every free node
+__global__ __launch_bounds__(TB) void pg_commit_kernel(double *poses, int n_poses, Buffers b, int it)
+{
+    if (b.st->accept_it != it) return;
+    const int n = blockIdx.x * TB + threadIdx.x;
+    if (n >= n_poses || !b.free_node[n]) return;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) poses[16 * (long long)n + k] = b.cand[16 * (long long)n + k];
+}
+
+__global__ __launch_bounds__(TB) void pg_finalize_kernel(Buffers b, int max_iteration, double *__restrict__ stats,
+                                                         double *__restrict__ history)
+{
+    const PgState *st = b.st;
+    for (int k = st->iterations + 1 + threadIdx.x; k <= max_iteration; k += TB) history[k] = st->cost;
+    if (threadIdx.x != 0) return;
+    stats[0] = st->iterations;
+    stats[1] = st->accepted;
+    stats[2] = st->rejected;
+    stats[3] = st->pcg_total;
+    stats[4] = st->cost0;
+    stats[5] = st->cost;
+    stats[6] = st->lambda;
+    stats[7] = st->skipped;
+    stats[8] = st->converged;
+    stats[9] = st->step;
+}
+
+// one wave: the outputs of nsc_posegraph_linearize that are scalars
+__global__ __launch_bounds__(TB) void pg_linearize_out_kernel(int nb_n, Buffers b, double *__restrict__ cost,
+                                                              long long *__restrict__ skipped)
+{
+    const double f = finish(b.part_e, nb_n);
+    if (threadIdx.x == 0) {
+        *cost = f;
+        *skipped = b.st->skipped;
+    }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------
+
+inline size_t carve(size_t &o, size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; }
+
+inline int blocks_of(long long n) { return (int)((n + TB - 1) / TB); }
+
+struct Layout {
+    size_t st, row_ptr, cursor, tmp, list, ei, ej, free_node, hii, hjj, hij, fe, ge, ye, g, blocks, chol, x, r, z, p, ap, cand,
+        part_e, part_a, part_b, part_s, total;
+};
+
+Layout layout(size_t N, size_t E)
+{
+    Layout l;
+    size_t o = 0;
+    const size_t d = sizeof(double), i = sizeof(int), nbn = (N + TB - 1) / TB;
+    l.st = carve(o, sizeof(PgState));
+    l.row_ptr = carve(o, (N + 1) * i);
+    l.cursor = carve(o, N * i);
+    l.tmp = carve(o, 2 * E * i);
+    l.list = carve(o, 2 * E * i);
+    l.ei = carve(o, E * i);
+    l.ej = carve(o, E * i);
+    l.free_node = carve(o, N * i);
+    l.hii = carve(o, 21 * E * d);
+    l.hjj = carve(o, 21 * E * d);
+    l.hij = carve(o, 36 * E * d);
+    l.fe = carve(o, E * d);
+    l.ge = carve(o, 12 * E * d);
+    l.ye = carve(o, 12 * E * d);
+    l.g = carve(o, 6 * N * d);
+    l.blocks = carve(o, 21 * N * d);
+    l.chol = carve(o, 21 * N * d);
+    l.x = carve(o, 6 * N * d);
+    l.r = carve(o, 6 * N * d);
+    l.z = carve(o, 6 * N * d);
+    l.p = carve(o, 6 * N * d);
+    l.ap = carve(o, 6 * N * d);
+    l.cand = carve(o, 16 * N * d);
+    l.part_e = carve(o, nbn * d);
+    l.part_a = carve(o, nbn * d);
+    l.part_b = carve(o, 2 * nbn * d);
+    l.part_s = carve(o, nbn * d);
+    l.total = o;
+    return l;
+}
+
+Buffers buffers(void *ws, const Layout &l)
+{
+    char *w = static_cast<char *>(ws);
+    Buffers b;
+    b.st = reinterpret_cast<PgState *>(w + l.st);
+    b.row_ptr = reinterpret_cast<int *>(w + l.row_ptr);
+    b.cursor = reinterpret_cast<int *>(w + l.cursor);
+    b.tmp = reinterpret_cast<int *>(w + l.tmp);
+    b.list = reinterpret_cast<int *>(w + l.list);
+    b.ei = reinterpret_cast<int *>(w + l.ei);
+    b.ej = reinterpret_cast<int *>(w + l.ej);
+    b.free_node = reinterpret_cast<int *>(w + l.free_node);
+    b.hii = reinterpret_cast<double *>(w + l.hii);
+    b.hjj = reinterpret_cast<double *>(w + l.hjj);
+    b.hij = reinterpret_cast<double *>(w + l.hij);
+    b.fe = reinterpret_cast<double *>(w + l.fe);
+    b.ge = reinterpret_cast<double *>(w + l.ge);
+    b.ye = reinterpret_cast<double *>(w + l.ye);
+    b.g = reinterpret_cast<double *>(w + l.g);
+    b.blocks = reinterpret_cast<double *>(w + l.blocks);
+    b.chol = reinterpret_cast<double *>(w + l.chol);
+    b.x = reinterpret_cast<double *>(w + l.x);
+    b.r = reinterpret_cast<double *>(w + l.r);
+    b.z = reinterpret_cast<double *>(w + l.z);
+    b.p = reinterpret_cast<double *>(w + l.p);
+    b.ap = reinterpret_cast<double *>(w + l.ap);
+    b.cand = reinterpret_cast<double *>(w + l.cand);
+    b.part_e = reinterpret_cast<double *>(w + l.part_e);
+    b.part_a = reinterpret_cast<double *>(w + l.part_a);
+    b.part_b = reinterpret_cast<double *>(w + l.part_b);
+    b.part_s = reinterpret_cast<double *>(w + l.part_s);
+    return b;
+}
+
+bool params_ok(const NscPoseGraphParams *p)
+{
+    return p->max_iteration >= 0 && p->max_pcg_iterations >= 0 && p->pcg_tolerance >= 0.0 && isfinite(p->pcg_tolerance) &&
+           p->lambda0 > 0.0 && isfinite(p->lambda0) && p->lambda_min > 0.0 && isfinite(p->lambda_min) &&
+           p->lambda_factor > 1.0 && isfinite(p->lambda_factor) && p->relative_cost >= 0.0 && isfinite(p->relative_cost) &&
+           p->min_step >= 0.0 && isfinite(p->min_step);
+}
+
+// state and degrees zeroed, then the lists: 5 launches (2 when there are no edges)
+void build_lists(hipStream_t s, const int64_t *edge_ij, int N, int E, const Layout &l, const Buffers &b)
+{
+    // the state and the degree array are neighbours in the workspace: one fill
+    nsc_fill_u32(s, b.st, 0u, (long long)((l.cursor - l.st) / 4));
+    if (E > 0) {
+        hipLaunchKernelGGL(pg_count_kernel, dim3(blocks_of(E)), dim3(TB), 0, s,
+                           reinterpret_cast<const long long *>(edge_ij), E, N, b);
+    }
+    hipLaunchKernelGGL(pg_scan_kernel, dim3(1), dim3(TB), 0, s, N, b);
+    if (E > 0) {
+        hipLaunchKernelGGL(pg_fill_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, E, b);
+        if (N > 0) hipLaunchKernelGGL(pg_sort_kernel, dim3(N), dim3(TB), 0, s, b);
+    }
+}
+
+inline int launch_status() { return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH; }
+
+}  // namespace
+
+extern "C" {
+
+void nsc_posegraph_default_params(NscPoseGraphParams *p)
+{
+    if (!p) return;
+    p->max_iteration = 20;
+    p->max_pcg_iterations = 100;
+    p->pcg_tolerance = 1e-6;
+    p->lambda0 = 1e-4;
+    p->lambda_min = 1e-9;
+    p->lambda_factor = 10.0;
+    p->relative_cost = 1e-9;
+    p->min_step = 1e-9;
+}
+
+size_t nsc_posegraph_workspace_bytes(int32_t n_poses, int32_t n_edges, const NscPoseGraphParams *params)
+{
+    (void)params;                            // the layout holds one outer and one inner iteration whatever the caps
+    if (n_poses < 0 || n_edges < 0) return 0;
+    return layout(n_poses, n_edges).total;
+}
+
+int nsc_posegraph_linearize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
+                            const double *information, int32_t n_edges, double *residuals, double *cost,
+                            double *gradient, double *blocks, int64_t *skipped, void *ws, size_t ws_bytes, void *stream)
+{
+    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES) return NSC_EINVAL;
+    if (!cost || !skipped) return NSC_EINVAL;
+    if (n_poses > 0 && (!poses || !gradient || !blocks)) return NSC_EINVAL;
+    if (n_edges > 0 && (!edge_ij || !measurements || !information || !residuals)) return NSC_EINVAL;
+    const Layout l = layout(n_poses, n_edges);
+    if (!ws || ws_bytes < l.total) return NSC_EWORKSPACE;
+    const Buffers b = buffers(ws, l);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int N = n_poses, E = n_edges;
+    build_lists(s, edge_ij, N, E, l, b);
+    if (E > 0) {
+        hipLaunchKernelGGL(pg_cost_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b, 0);
+        hipLaunchKernelGGL(pg_linearize_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b,
+                           residuals, 0);
+    }
+    if (N > 0) {
+        hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(blocks_of(N)), dim3(TB), 0, s, N, b, 0);
+        hipLaunchKernelGGL(pg_assemble_kernel, dim3(blocks_of(N)), dim3(TB), 0, s, N, E, nullptr, b, gradient, blocks, 0);
+    }
+    hipLaunchKernelGGL(pg_linearize_out_kernel, dim3(1), dim3(TB), 0, s, blocks_of(N), b, cost,
+                       reinterpret_cast<long long *>(skipped));
+    return launch_status();
+}
+
+int nsc_posegraph_optimize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
+                           const double *information, int32_t n_edges, const uint8_t *fixed,
+                           const NscPoseGraphParams *params, double *poses_out, double *stats, double *cost_history,
+                           double *step0, void *ws, size_t ws_bytes, void *stream)
+{
+    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES || !params || !params_ok(params))
+        return NSC_EINVAL;
+    if (!stats || !cost_history) return NSC_EINVAL;
+    if (n_poses > 0 && (!poses || !poses_out || !fixed)) return NSC_EINVAL;
+    if (n_edges > 0 && (!edge_ij || !measurements || !information)) return NSC_EINVAL;
+    if ((long long)params->max_iteration * (4LL * params->max_pcg_iterations + 8) > NSC_POSEGRAPH_MAX_LAUNCHES)
+        return NSC_EUNSUPPORTED;
+    const Layout l = layout(n_poses, n_edges);
+    if (!ws || ws_bytes < l.total) return NSC_EWORKSPACE;
+    const Buffers b = buffers(ws, l);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int N = n_poses, E = n_edges, gn = blocks_of(N), ge = blocks_of(E);
+    const PgParams prm{params->pcg_tolerance * params->pcg_tolerance, params->lambda0, params->lambda_min,
+                       params->lambda_factor, params->relative_cost, params->min_step, params->max_iteration,
+                       params->max_pcg_iterations};
+
+    build_lists(s, edge_ij, N, E, l, b);
+    if (N > 0 && poses_out != poses)
+        hipLaunchKernelGGL(pg_copy_kernel, dim3(blocks_of(16LL * N)), dim3(TB), 0, s, poses, poses_out, 16LL * N);
+    if (E > 0)
+        hipLaunchKernelGGL(pg_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0);
+    if (N > 0) hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 0);
+    hipLaunchKernelGGL(pg_init_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm.lambda0, cost_history);
+
+    for (int it = 0; it < prm.max_iteration && N > 0; ++it) {
+        if (E > 0)
+            hipLaunchKernelGGL(pg_linearize_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b,
+                               nullptr, 1);
+        hipLaunchKernelGGL(pg_assemble_kernel, dim3(gn), dim3(TB), 0, s, N, E, fixed, b, b.g, b.blocks, 1);
+        hipLaunchKernelGGL(pg_pcg_begin_kernel, dim3(1), dim3(TB), 0, s, gn, b);
+        for (int k = 0; k < prm.max_pcg && E > 0; ++k) {
+            hipLaunchKernelGGL(pg_edge_matvec_kernel, dim3(ge), dim3(TB), 0, s, E, b, k);
+            hipLaunchKernelGGL(pg_node_matvec_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
+            hipLaunchKernelGGL(pg_pcg_step_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
+            hipLaunchKernelGGL(pg_pcg_direction_kernel, dim3(gn), dim3(TB), 0, s, N, b, k, prm.tol2);
+        }
+        hipLaunchKernelGGL(pg_update_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it, step0);
+        if (E > 0)
+            hipLaunchKernelGGL(pg_cost_kernel, dim3(ge), dim3(TB), 0, s, b.cand, measurements, information, E, b, 1);
+        hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 1);
+        hipLaunchKernelGGL(pg_accept_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm, it, cost_history);
+        hipLaunchKernelGGL(pg_commit_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it);
+    }
+    hipLaunchKernelGGL(pg_finalize_kernel, dim3(1), dim3(TB), 0, s, b, prm.max_iteration, stats, cost_history);
+    return launch_status();
+}
+
+}  // extern "C"

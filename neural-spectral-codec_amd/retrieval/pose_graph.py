@@ -1,0 +1,204 @@
+"""Pose-graph optimisation on the device (csrc/nsc_posegraph.hip): the consumer of stage 2's ``transform`` and
+``information_matrix``.  Odometry edges and verified loop closures in, corrected poses out.
+
+Definition (the contract nsc_posegraph_optimize and tests/posegraph_restatement.py share; include/nsc.h), float64:
+
+    poses        (N,4,4) sensor to world;  edge (i, j) measures Z ~ X_i^-1 X_j with information Omega (6,6), rotation
+                 first, upper triangle read
+    residual     D = Z^-1 X_i^-1 X_j,  r = [Log_SO3(R_D); t_D],  cost F = sum r^T Omega r
+    update       X_k <- [R_k Exp(phi_k) | t_k + R_k rho_k]
+    Jacobians    J_j = B = blockdiag(Jr^-1(r_phi), R_D),  J_i = -B Ad(A^-1),  A = X_i^-1 X_j
+    solver       Levenberg-Marquardt, (H + lambda diag H) delta = -g by block-Jacobi preconditioned conjugate gradients;
+                 a step is accepted when the cost decreases
+
+Edges with i == j or an index outside [0, N) are skipped and counted.  Residual rotations beyond 179 degrees are out of
+scope.  Robust kernels, marginal covariances, 2-D graphs and g2o files are not part of this module.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+# this module's order is rotation first (phi, rho), as nsc_gicp_register's information; g2o's EDGE_SE3 is translation first
+_G2O = np.array([3, 4, 5, 0, 1, 2])
+
+
+def information_to_g2o(information):
+    """(…,6,6) rotation-first -> translation-first (the block order of g2o's EDGE_SE3:QUAT).  The rotation block stays
+    that of a rotation vector: g2o's quaternion-vector parametrisation differs from it by a factor 2 per axis, which
+    the caller applies when writing a file."""
+    m = np.asarray(information, np.float64)
+    return m[..., _G2O, :][..., :, _G2O]
+
+
+def information_from_g2o(information):
+    """The inverse of information_to_g2o (the permutation is its own inverse)."""
+    return information_to_g2o(information)
+
+
+def _hat(t):
+    return np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+
+
+def adjoint(T):
+    """Ad(R, t) = [[R, 0], [[t]x R, R]] for twists ordered rotation first."""
+    T = np.asarray(T, np.float64)
+    R, t = T[:3, :3], T[:3, 3]
+    A = np.zeros((6, 6))
+    A[:3, :3] = R
+    A[3:, 3:] = R
+    A[3:, :3] = _hat(t) @ R
+    return A
+
+
+def _inverse(T):
+    R, t = T[..., :3, :3], T[..., :3, 3]
+    out = np.zeros_like(T)
+    out[..., :3, :3] = np.swapaxes(R, -1, -2)
+    out[..., :3, 3] = -np.einsum("...ji,...j->...i", R, t)
+    out[..., 3, 3] = 1.0
+    return out
+
+
+def odometry_edges(poses, information=None):
+    """Chain edges of a trajectory: -> (edge_ij (N-1,2) int64, Z (N-1,4,4) with Z_k = X_k^-1 X_{k+1}, Omega (N-1,6,6)).
+    ``information``: one (6,6) matrix for every edge, a (N-1,6,6) stack, or None for the identity."""
+    X = poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else np.asarray(poses)
+    X = np.asarray(X, np.float64).reshape(-1, 4, 4)
+    n = max(len(X) - 1, 0)
+    e = np.stack([np.arange(n), np.arange(1, n + 1)], 1).astype(np.int64).reshape(n, 2)
+    Z = _inverse(X[:-1]) @ X[1:] if n else np.zeros((0, 4, 4))
+    om = np.eye(6) if information is None else np.asarray(information, np.float64)
+    om = np.broadcast_to(om, (n, 6, 6)).copy()
+    return e, Z, om
+
+
+def closure_edges(query_index, candidates):
+    """The verified ``LoopClosureCandidate``s of ``TwoStageRetrieval.query`` as edges: i = ``database_idx``, j =
+    ``query_index``, Z = ``transform`` (query into candidate coordinates = X_i^-1 X_j).  GICP's information matrix is
+    that of a left perturbation xi in the candidate's frame, T = Exp(xi) Z; the residual of this module is a right one,
+    r = Ad(Z^-1) xi to first order, so Omega_r = Ad(Z)^T Omega Ad(Z).  The [t]x term of Ad carries the lever arm of an
+    other-lane closure.  -> (edge_ij (M,2) int64, Z (M,4,4), Omega (M,6,6))"""
+    e, Z, om = [], [], []
+    for c in candidates:
+        if not c.verified or c.transform is None or c.information_matrix is None:
+            continue
+        T = np.asarray(c.transform, np.float64).reshape(4, 4)
+        A = adjoint(T)
+        W = np.asarray(c.information_matrix, np.float64).reshape(6, 6)
+        e.append((int(c.database_idx), int(query_index)))
+        Z.append(T)
+        om.append(A.T @ (0.5 * (W + W.T)) @ A)
+    m = len(e)
+    return (np.asarray(e, np.int64).reshape(m, 2), np.asarray(Z, np.float64).reshape(m, 4, 4),
+            np.asarray(om, np.float64).reshape(m, 6, 6))
+
+
+def _f64(a, dev, shape):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64)))
+    return t.to(device=dev, dtype=torch.float64).reshape(shape).contiguous()
+
+
+class PoseGraphOptimizer:
+    """Levenberg-Marquardt over SE(3) poses on the device.  Parameters (include/nsc.h NscPoseGraphParams):
+    max_iteration, max_pcg_iterations, pcg_tolerance, lambda0, lambda_min, lambda_factor, relative_cost, min_step."""
+
+    def __init__(self, device="cuda", **params):
+        self.device = torch.device(device)
+        p = _lib.PoseGraphParams()
+        _lib.lib().nsc_posegraph_default_params(C.byref(p))
+        names = {n for n, _ in _lib.PoseGraphParams._fields_}
+        for k, v in params.items():
+            if k not in names:
+                raise _lib.NscError(f"PoseGraphOptimizer: unknown parameter {k!r}")
+            setattr(p, k, int(v) if k in ("max_iteration", "max_pcg_iterations") else float(v))
+        self.params = p
+
+    def _inputs(self, poses, edge_ij, measurements, information):
+        dev = poses.device if isinstance(poses, torch.Tensor) else self.device
+        if dev.type != "cuda":
+            raise _lib.NscError(f"PoseGraphOptimizer runs on a HIP device (got {dev}); there is no CPU fallback")
+        X = _f64(poses, dev, (-1, 4, 4))
+        e = edge_ij if isinstance(edge_ij, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(edge_ij, np.int64).reshape(-1, 2)))
+        e = e.to(device=dev, dtype=torch.int64).reshape(-1, 2).contiguous()
+        E = int(e.shape[0])
+        Z = _f64(measurements, dev, (-1, 4, 4))
+        om = _f64(information, dev, (-1, 6, 6))
+        if int(Z.shape[0]) != E or int(om.shape[0]) != E:
+            raise _lib.NscError("pose graph: edge_ij, measurements and information must have one row per edge")
+        return dev, X, e, Z, om
+
+    def linearize(self, poses, edge_ij, measurements, information, fixed=None):
+        """The system at ``poses`` (``fixed`` plays no part: every pose gets its row).  -> dict of device tensors:
+        residuals (E,6), cost (1,), gradient (N,6) = sum J^T Omega r, blocks (N,21) = upper triangles of the diagonal
+        blocks of H, skipped (1,) int64.  No sync: it can be captured."""
+        dev, X, e, Z, om = self._inputs(poses, edge_ij, measurements, information)
+        N, E = int(X.shape[0]), int(e.shape[0])
+        f64 = dict(dtype=torch.float64, device=dev)
+        out = dict(residuals=torch.empty((E, 6), **f64), cost=torch.empty(1, **f64),
+                   gradient=torch.empty((N, 6), **f64), blocks=torch.empty((N, 21), **f64),
+                   skipped=torch.empty(1, dtype=torch.int64, device=dev))
+        L = _lib.lib()
+        ws = torch.empty(max(int(L.nsc_posegraph_workspace_bytes(N, E, C.byref(self.params))), 1), dtype=torch.uint8,
+                         device=dev)
+        with torch.cuda.device(dev):
+            status = L.nsc_posegraph_linearize(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E,
+                                               _lib.ptr(out["residuals"]), _lib.ptr(out["cost"]),
+                                               _lib.ptr(out["gradient"]), _lib.ptr(out["blocks"]),
+                                               _lib.ptr(out["skipped"]), _lib.ptr(ws), int(ws.numel()),
+                                               _lib.stream_ptr(dev))
+        _lib.check(status, "nsc_posegraph_linearize")
+        return out
+
+    def optimize_device(self, poses, edge_ij, measurements, information, fixed=None, poses_out=None, step0=False):
+        """``optimize`` without the read-back: device tensors in (or numpy), a dict of device tensors out -- poses
+        (N,4,4), stats (10,) as include/nsc.h orders them, cost_history (max_iteration + 1,), step0 (N,6) on request (the
+        first delta; not written when max_iteration = 0).
+        Nothing is synchronised, so a call on device tensors can be captured.  ``poses_out`` may be ``poses``."""
+        dev, X, e, Z, om = self._inputs(poses, edge_ij, measurements, information)
+        N, E = int(X.shape[0]), int(e.shape[0])
+        if fixed is None:
+            fx = torch.zeros(N, dtype=torch.uint8, device=dev)
+            fx[:1] = 1
+        else:
+            fx = fixed if isinstance(fixed, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray((np.asarray(fixed) != 0).astype(np.uint8)))
+            if fx.dtype != torch.uint8:                      # a uint8 device tensor is used as it is: no launch
+                fx = fx != 0
+            fx = fx.to(device=dev, dtype=torch.uint8).reshape(-1).contiguous()
+            if int(fx.numel()) != N:
+                raise _lib.NscError("pose graph: fixed must have one entry per pose")
+        f64 = dict(dtype=torch.float64, device=dev)
+        out = dict(poses=torch.empty((N, 4, 4), **f64) if poses_out is None else poses_out,
+                   stats=torch.empty(_lib.POSEGRAPH_STATS, **f64),
+                   cost_history=torch.empty(self.params.max_iteration + 1, **f64))
+        if out["poses"].dtype != torch.float64 or not out["poses"].is_contiguous() or \
+                tuple(out["poses"].shape) != (N, 4, 4) or not out["poses"].is_cuda:
+            raise _lib.NscError("pose graph: poses_out must be a contiguous (N,4,4) float64 tensor on the device")
+        if step0:
+            out["step0"] = torch.empty((N, 6), **f64)         # not written when max_iteration = 0
+        L = _lib.lib()
+        ws = torch.empty(max(int(L.nsc_posegraph_workspace_bytes(N, E, C.byref(self.params))), 1), dtype=torch.uint8,
+                         device=dev)
+        with torch.cuda.device(dev):
+            status = L.nsc_posegraph_optimize(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E, _lib.ptr(fx),
+                                              C.byref(self.params), _lib.ptr(out["poses"]), _lib.ptr(out["stats"]),
+                                              _lib.ptr(out["cost_history"]), _lib.ptr(out.get("step0")), _lib.ptr(ws),
+                                              int(ws.numel()), _lib.stream_ptr(dev))
+        _lib.check(status, "nsc_posegraph_optimize")
+        return out
+
+    def optimize(self, poses, edge_ij, measurements, information, fixed=None):
+        """-> dict: poses (N,4,4) (a device tensor for device poses, numpy for numpy), cost0, cost, iterations, accepted,
+        rejected, pcg_iterations, converged, cost_history (iterations + 1,), and lambda, skipped, step.  ``fixed``: (N,)
+        mask of the poses that stay; None fixes pose 0.  Reads the statistics back, so it synchronises."""
+        out = self.optimize_device(poses, edge_ij, measurements, information, fixed)
+        s = out["stats"].cpu().numpy()
+        its = int(s[0])
+        X = out["poses"] if isinstance(poses, torch.Tensor) else out["poses"].cpu().numpy()
+        return dict(poses=X, cost0=float(s[4]), cost=float(s[5]), iterations=its, accepted=int(s[1]), rejected=int(s[2]),
+                    pcg_iterations=int(s[3]), converged=bool(s[8]), cost_history=out["cost_history"].cpu().numpy()[:its + 1],
+                    skipped=int(s[7]), step=float(s[9]), **{"lambda": float(s[6])})

@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Pose-graph optimisation (retrieval/pose_graph.py, nsc_posegraph_optimize) on a KITTI-00-shaped graph: 4 541 poses of
+synth.make_pose_chain, 4 540 odometry edges with noise (the start is their integration: accumulated drift) and 200
+closures between random poses at least 50 frames apart.  Times ``optimize``
+  * eagerly: device events around one call, warm, median and spread of ``reps`` calls, and
+  * as a replayed hipGraph of the same call,
+and, as a host baseline on the same residuals and Jacobians, Gauss-Newton with scipy.sparse.linalg.spsolve on the
+normal equations (tests/posegraph_restatement.py builds them, edge by edge, in numpy: the linearisation time is
+reported apart from the solve time).  Prints the launch count and the inner iterations per outer step.
+usage: posegraph_probe.py [reps=10] [max_pcg_iterations=100] [max_iteration=20] [graph=1]
+``graph=0`` leaves the capture out (for caps whose launch count makes a graph of several hundred thousand nodes)."""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spl
+import torch
+import posegraph_restatement as P
+from neural_spectral_codec_amd import synth
+from neural_spectral_codec_amd.retrieval import PoseGraphOptimizer
+
+reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+max_pcg = int(sys.argv[2]) if len(sys.argv) > 2 else 100
+max_it = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+with_graph = (int(sys.argv[4]) if len(sys.argv) > 4 else 1) != 0
+N, CLOSURES = 4541, 200
+
+rng = np.random.default_rng(0)
+truth = synth.make_pose_chain(N, seed=0)
+oe = P.chain_edges(N)
+oZ = P.noisy(P.relative(truth, oe), rng, rot=0.001, trans=0.01)
+init = P.integrate(oZ, truth[0])
+a = rng.integers(0, N, (4 * CLOSURES, 2))
+ce = a[np.abs(a[:, 0] - a[:, 1]) >= 50][:CLOSURES].astype(np.int64)
+cZ = P.noisy(P.relative(truth, ce), rng, rot=0.002, trans=0.02)
+e, Z = np.concatenate([oe, ce]), np.concatenate([oZ, cZ])
+Om = np.concatenate([np.tile(np.diag([1e6, 1e6, 1e6, 1e4, 1e4, 1e4]), (len(oe), 1, 1)),
+                     np.tile(np.diag([2.5e5, 2.5e5, 2.5e5, 2.5e3, 2.5e3, 2.5e3]), (len(ce), 1, 1))])
+print(f"graph: {N} poses, {len(oe)} odometry edges, {len(ce)} closures; trajectory error of the start "
+      f"{P.trajectory_error(init, truth):.3f} m")
+
+dev = torch.device("cuda")
+opt = PoseGraphOptimizer(max_pcg_iterations=max_pcg, max_iteration=max_it)
+args = [torch.from_numpy(x).to(dev) for x in (init, e, Z, Om)]
+fixed = torch.zeros(N, dtype=torch.uint8, device=dev)
+fixed[0] = 1
+
+
+def call():
+    return opt.optimize_device(*args, fixed=fixed)
+
+
+def device_times(fn, n):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(n):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        torch.cuda.synchronize()
+        out.append(t0.elapsed_time(t1))
+    return np.array(out)
+
+
+out = call()
+torch.cuda.synchronize()
+s = out["stats"].cpu().numpy()
+its = int(s[0])
+launches = 5 + 1 + 3 + max_it * (8 + 4 * max_pcg) + 1
+print(f"optimize: {its} outer iterations ({int(s[1])} accepted, {int(s[2])} rejected), {int(s[3])} inner iterations "
+      f"({s[3] / max(its, 1):.1f} per outer step), cost {s[4]:.6g} -> {s[5]:.6g}, converged {bool(s[8])}, "
+      f"trajectory error {P.trajectory_error(out['poses'].cpu().numpy(), truth):.3f} m; {launches} launches per call")
+t = device_times(call, reps)
+print(f"eager: median {np.median(t):.2f} ms (min {t.min():.2f}, max {t.max():.2f}; {reps} calls)")
+
+if with_graph:
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        call()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        cap = call()
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(cap["poses"], out["poses"]) and torch.equal(cap["stats"], out["stats"])
+    t = device_times(g.replay, reps)
+    print(f"replayed hipGraph: median {np.median(t):.2f} ms (min {t.min():.2f}, max {t.max():.2f}); bitwise the eager "
+          "result")
+
+# host baseline: Gauss-Newton, normal equations of the same residuals and Jacobians, scipy.sparse.linalg.spsolve
+X = init.copy()
+F = P.cost(X, e, Z, Om)
+t_lin = t_solve = 0.0
+for it in range(20):
+    t0 = time.perf_counter()
+    rows, cols, vals, rhs = [], [], [], np.zeros(6 * N)
+    blk = np.arange(6)
+    for k, (i, j) in enumerate(e):
+        r, Ji, Jj = P.edge_terms(X[i], X[j], Z[k])
+        W = Om[k]
+        for (a_, Ja), (b_, Jb) in (((i, Ji), (i, Ji)), ((i, Ji), (j, Jj)), ((j, Jj), (i, Ji)), ((j, Jj), (j, Jj))):
+            rows.append(np.repeat(6 * a_ + blk, 6))
+            cols.append(np.tile(6 * b_ + blk, 6))
+            vals.append((Ja.T @ W @ Jb).reshape(-1))
+        rhs[6 * i:6 * i + 6] -= Ji.T @ W @ r
+        rhs[6 * j:6 * j + 6] -= Jj.T @ W @ r
+    H = sp.csc_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(6 * N, 6 * N))
+    t1 = time.perf_counter()
+    d = np.zeros(6 * N)
+    d[6:] = spl.spsolve(H[6:, 6:].tocsc(), rhs[6:])
+    t2 = time.perf_counter()
+    X = np.stack([P.retract(X[k], d[6 * k:6 * k + 6]) for k in range(N)])
+    Fn = P.cost(X, e, Z, Om)
+    t_lin += t1 - t0
+    t_solve += t2 - t1
+    done = F - Fn < 1e-9 * F
+    F = Fn
+    if done:
+        break
+print(f"host Gauss-Newton (scipy spsolve): {it + 1} iterations, cost {F:.6g}, trajectory error "
+      f"{P.trajectory_error(X, truth):.3f} m; spsolve {1e3 * t_solve:.0f} ms in total, numpy linearisation "
+      f"{1e3 * t_lin:.0f} ms in total")
