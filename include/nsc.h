@@ -641,18 +641,42 @@ int    nsc_planar_align(const NscGicpCloudSet *sources, const NscGicpCloudSet *t
  *   Otherwise: rejected, lambda <- lambda lambda_factor.
  *   Either way it stops (converged) when step < min_step, and (capped) after max_iteration outer iterations.
  *
+ * Robust kernels (nsc_posegraph_linearize_robust, nsc_posegraph_optimize_robust).  One kernel id per call and a width
+ * per edge, edge_scale (n_edges) float64, in units of sqrt(chi^2).  With s = r^T Omega r and c the edge's width:
+ *   kernel                               rho(s)                                w(s) = rho'(s)
+ *   NSC_POSEGRAPH_KERNEL_NONE            s                                     1
+ *   NSC_POSEGRAPH_KERNEL_HUBER           s for s <= c^2, else 2 c sqrt(s) - c^2  1 for s <= c^2, else c / sqrt(s)
+ *   NSC_POSEGRAPH_KERNEL_CAUCHY          c^2 log1p(s / c^2)                    1 / (1 + s / c^2)
+ *   NSC_POSEGRAPH_KERNEL_GEMAN_MCCLURE   c^2 s / (c^2 + s)                     (c^2 / (c^2 + s))^2
+ *   Geman-McClure is the closed form of a switchable constraint, min over sigma of sigma^2 s + c^2 (1 - sigma)^2, with
+ *   w = sigma^2: what dynamic covariance scaling computes.
+ *   F = sum rho(s_e),  g = sum w J^T Omega r,  H = sum w J^T Omega J: iteratively reweighted least squares, first order
+ *   (no second-order correction of H, as in g2o).  s is formed with Omega as given; then Omega is scaled by w.
+ *   Accept, reject, lambda and the stopping rules are those above, applied to the robust F; cost0, cost and
+ *   cost_history are robust costs.
+ *   An edge is quadratic, rho = s and w = 1 exactly, when edge_scale is NULL, when its width is not finite and positive
+ *   (<= 0, NaN, +-inf; likewise a width whose square underflows to 0 or overflows), or when s <= 0.  So odometry edges
+ *   with width 0 stay quadratic.  With kernel NONE, or with quadratic edges only, every output has the bits of the
+ *   plain entry points.  A kernel id outside 0..3 is NSC_EINVAL.  A skipped edge reports chi2 = 0 and weight = 0.
+ *
  * Determinism.  Node quantities are gathered over a node's incident edges in ascending edge index; scalars (the cost
  * too: a node sums the edges it is the first end of) are summed as fixed-shape partials over the nodes; no floating-
  * point atomics.  Two calls on the same inputs agree bit for bit, and where the skipped edges stand among the others
  * changes no bit of any other output.
  * Launches.  A sequence that depends on n_poses > 0, n_edges > 0, poses_out == poses, max_iteration and
  * max_pcg_iterations alone: 5 (lists) + 1 (copy, unless aliased) + 3 + max_iteration (8 + 4 max_pcg_iterations) + 1,
- * at most NSC_POSEGRAPH_MAX_LAUNCHES in the loop (else NSC_EUNSUPPORTED).  Kernels of a finished phase return at once.
+ * at most NSC_POSEGRAPH_MAX_LAUNCHES in the loop (else NSC_EUNSUPPORTED), + 1 at the end when nsc_posegraph_optimize_robust
+ * is given edge_chi2 or edge_weight and n_edges > 0.  Kernels of a finished phase return at once.
  * No host synchronisation, no memset or memcpy nodes: the call can be captured.
  * ------------------------------------------------------------------------------------------ */
 #define NSC_POSEGRAPH_MAX_EDGES    1073741823   /* list entries are 2 edge + side in int32 */
 #define NSC_POSEGRAPH_MAX_LAUNCHES 1000000
 #define NSC_POSEGRAPH_STATS        10
+
+#define NSC_POSEGRAPH_KERNEL_NONE           0
+#define NSC_POSEGRAPH_KERNEL_HUBER          1
+#define NSC_POSEGRAPH_KERNEL_CAUCHY         2
+#define NSC_POSEGRAPH_KERNEL_GEMAN_MCCLURE  3
 
 typedef struct NscPoseGraphParams {
     int32_t max_iteration;        /* 20     outer iterations at most, >= 0                                  */
@@ -676,6 +700,14 @@ int    nsc_posegraph_linearize(const double *poses, int32_t n_poses, const int64
                                const double *information, int32_t n_edges, double *residuals, double *cost,
                                double *gradient, double *blocks, int64_t *skipped, void *ws, size_t ws_bytes,
                                void *stream);
+/* The same with a robust kernel: nsc_posegraph_linearize is this call with kernel NONE and NULLs.  edge_scale
+ * (n_edges), nullable.  residuals stay unweighted; cost = sum rho(s), gradient and blocks carry w.  weights (n_edges),
+ * nullable: w of every edge, 0 for a skipped one. */
+int    nsc_posegraph_linearize_robust(const double *poses, int32_t n_poses, const int64_t *edge_ij,
+                                      const double *measurements, const double *information, int32_t n_edges,
+                                      double *residuals, double *cost, double *gradient, double *blocks,
+                                      int64_t *skipped, void *ws, size_t ws_bytes, void *stream, int32_t kernel,
+                                      const double *edge_scale, double *weights);
 
 /* poses_out (n_poses,4,4) may alias poses.  stats (NSC_POSEGRAPH_STATS) float64 = [outer iterations done, accepted,
  * rejected, inner iterations in total, initial cost, final cost, final lambda, skipped edges, 1 = stopped by a
@@ -687,6 +719,15 @@ int    nsc_posegraph_optimize(const double *poses, int32_t n_poses, const int64_
                               const double *information, int32_t n_edges, const uint8_t *fixed,
                               const NscPoseGraphParams *params, double *poses_out, double *stats, double *cost_history,
                               double *step0, void *ws, size_t ws_bytes, void *stream);
+/* The same with a robust kernel: nsc_posegraph_optimize is this call with kernel NONE and NULLs.  edge_scale (n_edges),
+ * nullable.  edge_chi2 (n_edges) = r^T Omega r and edge_weight (n_edges) = w of every edge at poses_out, zeros for a
+ * skipped edge; both nullable, one more launch when either is given: what a caller decides by which closures to drop. */
+int    nsc_posegraph_optimize_robust(const double *poses, int32_t n_poses, const int64_t *edge_ij,
+                                     const double *measurements, const double *information, int32_t n_edges,
+                                     const uint8_t *fixed, const NscPoseGraphParams *params, double *poses_out,
+                                     double *stats, double *cost_history, double *step0, void *ws, size_t ws_bytes,
+                                     void *stream, int32_t kernel, const double *edge_scale, double *edge_chi2,
+                                     double *edge_weight);
 
 #ifdef __cplusplus
 }

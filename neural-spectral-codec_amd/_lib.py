@@ -113,6 +113,8 @@ class PoseGraphParams(C.Structure):
 
 # include/nsc.h NSC_POSEGRAPH_MAX_EDGES, NSC_POSEGRAPH_MAX_LAUNCHES, NSC_POSEGRAPH_STATS
 POSEGRAPH_MAX_EDGES, POSEGRAPH_MAX_LAUNCHES, POSEGRAPH_STATS = 1073741823, 1000000, 10
+# include/nsc.h NSC_POSEGRAPH_KERNEL_*
+POSEGRAPH_KERNELS = {None: 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
 
 GICP_MAX_KNN = 32
 # include/nsc.h NSC_GICP_MAX_PAIRS, NSC_GICP_MAX_CLOUDS, NSC_GICP_MAX_PREPARED_PAIRS: the largest batch of one call
@@ -215,6 +217,10 @@ SYMBOLS = {
     "nsc_posegraph_linearize": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nsc_posegraph_optimize": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PoseGraphParams), _vp, _vp,
                                          _vp, _vp, _vp, _sz, _vp]),
+    "nsc_posegraph_linearize_robust": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                                 _vp, _i32, _vp, _vp]),
+    "nsc_posegraph_optimize_robust": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PoseGraphParams), _vp,
+                                                _vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp, _vp, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

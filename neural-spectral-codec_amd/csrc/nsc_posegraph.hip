@@ -6,6 +6,8 @@
 //   J_j = B = blockdiag(Jr^-1(r_phi), R_D),  J_i = -B Ad(A^-1) with A = X_i^-1 X_j
 //   Levenberg-Marquardt with Marquardt scaling, (H + lambda diag H) delta = -g, solved by conjugate gradients
 //   preconditioned with the Cholesky factor of each node's damped 6 x 6 diagonal block.
+//   Robust kernels (nsc_posegraph_*_robust): with s = r^T Omega r and an edge's width c, F = sum rho(s),
+//   g = sum w J^T Omega r, H = sum w J^T Omega J, w = rho'(s): iteratively reweighted, no second-order term.
 //
 // Shape.  Every workgroup is one wave of 64 lanes: a graph of a few thousand poses is a few dozen waves, and one wave per
 // workgroup spreads them over as many CUs; every reduction is then a butterfly of the wave, with no LDS and no barrier.
@@ -208,6 +210,36 @@ __device__ __forceinline__ double quad_form(const double W[36], const double r[6
     return f;
 }
 
+// rho(s) and w = rho'(s) of one edge (include/nsc.h has the table).  The edge is quadratic, rho = s and w = 1 exactly, for
+// kernel 0, without widths, for a width c that is not finite and positive or whose square is not, and for s <= 0 or NaN.
+struct Robust {
+    double rho, w;
+};
+
+__device__ __forceinline__ Robust robust_kernel(int kernel, const double *__restrict__ edge_scale, long long e, double s)
+{
+    Robust out{s, 1.0};
+    if (kernel == NSC_POSEGRAPH_KERNEL_NONE || !edge_scale) return out;
+    const double c = edge_scale[e], c2 = c * c;
+    if (!(c > 0.0) || !(c2 > 0.0) || !isfinite(c2) || !(s > 0.0)) return out;
+    if (kernel == NSC_POSEGRAPH_KERNEL_HUBER) {
+        if (s > c2) {
+            const double q = sqrt(s);
+            out.rho = 2.0 * c * q - c2;
+            out.w = c / q;
+        }
+    } else if (kernel == NSC_POSEGRAPH_KERNEL_CAUCHY) {
+        const double u = s / c2;
+        out.rho = c2 * log1p(u);
+        out.w = 1.0 / (1.0 + u);
+    } else {                                 // Geman-McClure
+        const double t = c2 / (c2 + s);
+        out.rho = t * s;
+        out.w = t * t;
+    }
+    return out;
+}
+
 // index of (r, c), r <= c, in a row-major upper triangle of a 6 x 6 matrix
 __device__ __host__ constexpr int tri(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }
 
@@ -283,10 +315,10 @@ __global__ __launch_bounds__(TB) void pg_copy_kernel(const double *__restrict__ 
 
 // ---- edges -------------------------------------------------------------------------------------------------------
 
-// r^T Omega r of every counted edge at `poses`
+// rho(r^T Omega r) of every counted edge at `poses`
 __global__ __launch_bounds__(TB) void pg_cost_kernel(const double *poses, const double *__restrict__ Z,
                                                      const double *__restrict__ information, int n_edges, Buffers b,
-                                                     int check_done)
+                                                     int check_done, int kernel, const double *__restrict__ edge_scale)
 {
     if (check_done && b.st->done) return;
     const int e = blockIdx.x * TB + threadIdx.x;
@@ -295,7 +327,28 @@ __global__ __launch_bounds__(TB) void pg_cost_kernel(const double *poses, const 
     double W[36];
     edge_geometry(poses, b.ei[e], b.ej[e], Z, e, q);
     load_information(information, e, W);
-    b.fe[e] = quad_form(W, q.r);
+    b.fe[e] = robust_kernel(kernel, edge_scale, e, quad_form(W, q.r)).rho;
+}
+
+// r^T Omega r and the weight of every edge at `poses`, zeros for a skipped one: what a caller drops closures by
+__global__ __launch_bounds__(TB) void pg_edge_report_kernel(const double *__restrict__ poses, const double *__restrict__ Z,
+                                                            const double *__restrict__ information, int n_edges,
+                                                            Buffers b, int kernel, const double *__restrict__ edge_scale,
+                                                            double *__restrict__ chi2, double *__restrict__ weight)
+{
+    const int e = blockIdx.x * TB + threadIdx.x;
+    if (e >= n_edges) return;
+    double s = 0.0, w = 0.0;
+    if (b.ei[e] >= 0) {
+        EdgeGeom q;
+        double W[36];
+        edge_geometry(poses, b.ei[e], b.ej[e], Z, e, q);
+        load_information(information, e, W);
+        s = quad_form(W, q.r);
+        w = robust_kernel(kernel, edge_scale, e, s).w;
+    }
+    if (chi2) chi2[e] = s;
+    if (weight) weight[e] = w;
 }
 
 // F: every node sums the edges it is the first end of, in list order; one partial per workgroup.  The sum walks the
@@ -315,10 +368,12 @@ __global__ __launch_bounds__(TB) void pg_cost_gather_kernel(int n_poses, Buffers
     write_partial(b.part_e, f);
 }
 
-// residual, the blocks of J^T Omega J and the halves of J^T Omega r of every edge
+// residual, weight, the blocks of w J^T Omega J and the halves of w J^T Omega r of every edge
 __global__ __launch_bounds__(TB) void pg_linearize_kernel(const double *poses, const double *__restrict__ Z,
                                                           const double *__restrict__ information, int n_edges,
-                                                          Buffers b, double *__restrict__ residuals, int check_done)
+                                                          Buffers b, double *__restrict__ residuals, int check_done,
+                                                          int kernel, const double *__restrict__ edge_scale,
+                                                          double *__restrict__ weights)
 {
     if (check_done && b.st->done) return;
     const int e = blockIdx.x * TB + threadIdx.x;
@@ -326,6 +381,7 @@ __global__ __launch_bounds__(TB) void pg_linearize_kernel(const double *poses, c
     if (b.ei[e] < 0) {
         if (residuals)
             for (int k = 0; k < 6; ++k) residuals[6 * (long long)e + k] = 0.0;
+        if (weights) weights[e] = 0.0;
         return;
     }
     EdgeGeom q;
@@ -351,8 +407,20 @@ __global__ __launch_bounds__(TB) void pg_linearize_kernel(const double *poses, c
             Ji[6 * (r + 3) + c + 3] = -q.RZ[3 * c + r];
         }
 
-    double W[36], Wi[36], Wj[36], wr[6];
+    // s = r^T Omega r with Omega as given (the sum of pg_cost_kernel, term for term); then Omega <- w Omega
+    double W[36], Wi[36], Wj[36], wr[6], chi2 = 0.0;
     load_information(information, e, W);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) s += W[6 * a + c] * q.r[c];
+        chi2 += q.r[a] * s;
+    }
+    const double w = robust_kernel(kernel, edge_scale, e, chi2).w;
+    if (weights) weights[e] = w;
+#pragma unroll
+    for (int k = 0; k < 36; ++k) W[k] *= w;
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
         double s = 0.0;
@@ -844,6 +912,8 @@ bool params_ok(const NscPoseGraphParams *p)
            p->min_step >= 0.0 && isfinite(p->min_step);
 }
 
+bool kernel_ok(int32_t k) { return k >= NSC_POSEGRAPH_KERNEL_NONE && k <= NSC_POSEGRAPH_KERNEL_GEMAN_MCCLURE; }
+
 // state and degrees zeroed, then the lists: 5 launches (2 when there are no edges)
 void build_lists(hipStream_t s, const int64_t *edge_ij, int N, int E, const Layout &l, const Buffers &b)
 {
@@ -890,7 +960,18 @@ int nsc_posegraph_linearize(const double *poses, int32_t n_poses, const int64_t 
                             const double *information, int32_t n_edges, double *residuals, double *cost,
                             double *gradient, double *blocks, int64_t *skipped, void *ws, size_t ws_bytes, void *stream)
 {
-    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES) return NSC_EINVAL;
+    return nsc_posegraph_linearize_robust(poses, n_poses, edge_ij, measurements, information, n_edges, residuals, cost,
+                                          gradient, blocks, skipped, ws, ws_bytes, stream, NSC_POSEGRAPH_KERNEL_NONE,
+                                          nullptr, nullptr);
+}
+
+int nsc_posegraph_linearize_robust(const double *poses, int32_t n_poses, const int64_t *edge_ij,
+                                   const double *measurements, const double *information, int32_t n_edges,
+                                   double *residuals, double *cost, double *gradient, double *blocks, int64_t *skipped,
+                                   void *ws, size_t ws_bytes, void *stream, int32_t kernel, const double *edge_scale,
+                                   double *weights)
+{
+    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES || !kernel_ok(kernel)) return NSC_EINVAL;
     if (!cost || !skipped) return NSC_EINVAL;
     if (n_poses > 0 && (!poses || !gradient || !blocks)) return NSC_EINVAL;
     if (n_edges > 0 && (!edge_ij || !measurements || !information || !residuals)) return NSC_EINVAL;
@@ -901,9 +982,10 @@ int nsc_posegraph_linearize(const double *poses, int32_t n_poses, const int64_t 
     const int N = n_poses, E = n_edges;
     build_lists(s, edge_ij, N, E, l, b);
     if (E > 0) {
-        hipLaunchKernelGGL(pg_cost_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b, 0);
+        hipLaunchKernelGGL(pg_cost_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b, 0,
+                           kernel, edge_scale);
         hipLaunchKernelGGL(pg_linearize_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b,
-                           residuals, 0);
+                           residuals, 0, kernel, edge_scale, weights);
     }
     if (N > 0) {
         hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(blocks_of(N)), dim3(TB), 0, s, N, b, 0);
@@ -919,7 +1001,20 @@ int nsc_posegraph_optimize(const double *poses, int32_t n_poses, const int64_t *
                            const NscPoseGraphParams *params, double *poses_out, double *stats, double *cost_history,
                            double *step0, void *ws, size_t ws_bytes, void *stream)
 {
-    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES || !params || !params_ok(params))
+    return nsc_posegraph_optimize_robust(poses, n_poses, edge_ij, measurements, information, n_edges, fixed, params,
+                                         poses_out, stats, cost_history, step0, ws, ws_bytes, stream,
+                                         NSC_POSEGRAPH_KERNEL_NONE, nullptr, nullptr, nullptr);
+}
+
+int nsc_posegraph_optimize_robust(const double *poses, int32_t n_poses, const int64_t *edge_ij,
+                                  const double *measurements, const double *information, int32_t n_edges,
+                                  const uint8_t *fixed, const NscPoseGraphParams *params, double *poses_out,
+                                  double *stats, double *cost_history, double *step0, void *ws, size_t ws_bytes,
+                                  void *stream, int32_t kernel, const double *edge_scale, double *edge_chi2,
+                                  double *edge_weight)
+{
+    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES || !params || !params_ok(params) ||
+        !kernel_ok(kernel))
         return NSC_EINVAL;
     if (!stats || !cost_history) return NSC_EINVAL;
     if (n_poses > 0 && (!poses || !poses_out || !fixed)) return NSC_EINVAL;
@@ -939,14 +1034,15 @@ int nsc_posegraph_optimize(const double *poses, int32_t n_poses, const int64_t *
     if (N > 0 && poses_out != poses)
         hipLaunchKernelGGL(pg_copy_kernel, dim3(blocks_of(16LL * N)), dim3(TB), 0, s, poses, poses_out, 16LL * N);
     if (E > 0)
-        hipLaunchKernelGGL(pg_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0);
+        hipLaunchKernelGGL(pg_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0, kernel,
+                           edge_scale);
     if (N > 0) hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 0);
     hipLaunchKernelGGL(pg_init_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm.lambda0, cost_history);
 
     for (int it = 0; it < prm.max_iteration && N > 0; ++it) {
         if (E > 0)
             hipLaunchKernelGGL(pg_linearize_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b,
-                               nullptr, 1);
+                               nullptr, 1, kernel, edge_scale, nullptr);
         hipLaunchKernelGGL(pg_assemble_kernel, dim3(gn), dim3(TB), 0, s, N, E, fixed, b, b.g, b.blocks, 1);
         hipLaunchKernelGGL(pg_pcg_begin_kernel, dim3(1), dim3(TB), 0, s, gn, b);
         for (int k = 0; k < prm.max_pcg && E > 0; ++k) {
@@ -957,12 +1053,16 @@ int nsc_posegraph_optimize(const double *poses, int32_t n_poses, const int64_t *
         }
         hipLaunchKernelGGL(pg_update_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it, step0);
         if (E > 0)
-            hipLaunchKernelGGL(pg_cost_kernel, dim3(ge), dim3(TB), 0, s, b.cand, measurements, information, E, b, 1);
+            hipLaunchKernelGGL(pg_cost_kernel, dim3(ge), dim3(TB), 0, s, b.cand, measurements, information, E, b, 1,
+                               kernel, edge_scale);
         hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 1);
         hipLaunchKernelGGL(pg_accept_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm, it, cost_history);
         hipLaunchKernelGGL(pg_commit_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it);
     }
     hipLaunchKernelGGL(pg_finalize_kernel, dim3(1), dim3(TB), 0, s, b, prm.max_iteration, stats, cost_history);
+    if (E > 0 && (edge_chi2 || edge_weight))
+        hipLaunchKernelGGL(pg_edge_report_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b,
+                           kernel, edge_scale, edge_chi2, edge_weight);
     return launch_status();
 }
 

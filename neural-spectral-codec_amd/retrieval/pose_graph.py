@@ -11,8 +11,19 @@ Definition (the contract nsc_posegraph_optimize and tests/posegraph_restatement.
     solver       Levenberg-Marquardt, (H + lambda diag H) delta = -g by block-Jacobi preconditioned conjugate gradients;
                  a step is accepted when the cost decreases
 
+    robust       with s = r^T Omega r and a width c per edge (``robust_scale``, in units of sqrt(chi^2)):
+                 F = sum rho(s), g = sum w J^T Omega r, H = sum w J^T Omega J, w = rho'(s) (first order: IRLS)
+                   huber          rho = s for s <= c^2, else 2 c sqrt(s) - c^2    w = 1, else c / sqrt(s)
+                   cauchy         rho = c^2 log1p(s / c^2)                        w = 1 / (1 + s / c^2)
+                   geman_mcclure  rho = c^2 s / (c^2 + s)                         w = (c^2 / (c^2 + s))^2
+                 an edge whose width is not finite and positive is quadratic (rho = s, w = 1): give odometry edges 0
+
 Edges with i == j or an index outside [0, N) are skipped and counted.  Residual rotations beyond 179 degrees are out of
-scope.  Robust kernels, marginal covariances, 2-D graphs and g2o files are not part of this module.
+scope.  Marginal covariances, 2-D graphs and g2o files are not part of this module.
+
+A false closure that passed geometric verification keeps weight 1 under the quadratic cost and bends the whole
+trajectory; with ``kernel="cauchy"`` and a width of about 3 on the closure edges it ends with a weight below 1e-3, and
+``optimize`` returns ``chi2`` and ``weights`` per edge so that the caller can drop it.
 """
 import ctypes as C
 
@@ -103,10 +114,15 @@ def _f64(a, dev, shape):
 
 class PoseGraphOptimizer:
     """Levenberg-Marquardt over SE(3) poses on the device.  Parameters (include/nsc.h NscPoseGraphParams):
-    max_iteration, max_pcg_iterations, pcg_tolerance, lambda0, lambda_min, lambda_factor, relative_cost, min_step."""
+    max_iteration, max_pcg_iterations, pcg_tolerance, lambda0, lambda_min, lambda_factor, relative_cost, min_step.
+    ``kernel``: None (quadratic), "huber", "cauchy" or "geman_mcclure"; it acts on the edges that the ``robust_scale``
+    of a call gives a width."""
 
-    def __init__(self, device="cuda", **params):
+    def __init__(self, device="cuda", kernel=None, **params):
         self.device = torch.device(device)
+        if kernel not in _lib.POSEGRAPH_KERNELS:
+            raise _lib.NscError(f"PoseGraphOptimizer: unknown kernel {kernel!r}")
+        self.kernel = _lib.POSEGRAPH_KERNELS[kernel]
         p = _lib.PoseGraphParams()
         _lib.lib().nsc_posegraph_default_params(C.byref(p))
         names = {n for n, _ in _lib.PoseGraphParams._fields_}
@@ -131,35 +147,56 @@ class PoseGraphOptimizer:
             raise _lib.NscError("pose graph: edge_ij, measurements and information must have one row per edge")
         return dev, X, e, Z, om
 
-    def linearize(self, poses, edge_ij, measurements, information, fixed=None):
+    @staticmethod
+    def _scale(robust_scale, dev, E):
+        """the (E,) widths on the device, or None"""
+        if robust_scale is None:
+            return None
+        if (robust_scale.dim() if isinstance(robust_scale, torch.Tensor) else np.ndim(robust_scale)) != 1:
+            raise _lib.NscError("pose graph: robust_scale is one width per edge, shape (E,); give the edges that stay "
+                                "quadratic (odometry) the width 0")
+        c = _f64(robust_scale, dev, (-1,))
+        if int(c.numel()) != E:
+            raise _lib.NscError("pose graph: robust_scale must have one entry per edge")
+        return c
+
+    def linearize(self, poses, edge_ij, measurements, information, fixed=None, robust_scale=None):
         """The system at ``poses`` (``fixed`` plays no part: every pose gets its row).  -> dict of device tensors:
-        residuals (E,6), cost (1,), gradient (N,6) = sum J^T Omega r, blocks (N,21) = upper triangles of the diagonal
-        blocks of H, skipped (1,) int64.  No sync: it can be captured."""
+        residuals (E,6) (never weighted), cost (1,), gradient (N,6) = sum w J^T Omega r, blocks (N,21) = upper triangles
+        of the diagonal blocks of H, skipped (1,) int64, and with ``robust_scale`` (E,) weights (E,).  No sync: it can be
+        captured."""
         dev, X, e, Z, om = self._inputs(poses, edge_ij, measurements, information)
         N, E = int(X.shape[0]), int(e.shape[0])
+        c = self._scale(robust_scale, dev, E)
         f64 = dict(dtype=torch.float64, device=dev)
         out = dict(residuals=torch.empty((E, 6), **f64), cost=torch.empty(1, **f64),
                    gradient=torch.empty((N, 6), **f64), blocks=torch.empty((N, 21), **f64),
                    skipped=torch.empty(1, dtype=torch.int64, device=dev))
+        if c is not None:
+            out["weights"] = torch.empty(E, **f64)
         L = _lib.lib()
         ws = torch.empty(max(int(L.nsc_posegraph_workspace_bytes(N, E, C.byref(self.params))), 1), dtype=torch.uint8,
                          device=dev)
         with torch.cuda.device(dev):
-            status = L.nsc_posegraph_linearize(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E,
-                                               _lib.ptr(out["residuals"]), _lib.ptr(out["cost"]),
-                                               _lib.ptr(out["gradient"]), _lib.ptr(out["blocks"]),
-                                               _lib.ptr(out["skipped"]), _lib.ptr(ws), int(ws.numel()),
-                                               _lib.stream_ptr(dev))
-        _lib.check(status, "nsc_posegraph_linearize")
+            status = L.nsc_posegraph_linearize_robust(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E,
+                                                      _lib.ptr(out["residuals"]), _lib.ptr(out["cost"]),
+                                                      _lib.ptr(out["gradient"]), _lib.ptr(out["blocks"]),
+                                                      _lib.ptr(out["skipped"]), _lib.ptr(ws), int(ws.numel()),
+                                                      _lib.stream_ptr(dev), self.kernel, _lib.ptr(c),
+                                                      _lib.ptr(out.get("weights")))
+        _lib.check(status, "nsc_posegraph_linearize_robust")
         return out
 
-    def optimize_device(self, poses, edge_ij, measurements, information, fixed=None, poses_out=None, step0=False):
+    def optimize_device(self, poses, edge_ij, measurements, information, fixed=None, poses_out=None, step0=False,
+                        robust_scale=None):
         """``optimize`` without the read-back: device tensors in (or numpy), a dict of device tensors out -- poses
         (N,4,4), stats (10,) as include/nsc.h orders them, cost_history (max_iteration + 1,), step0 (N,6) on request (the
-        first delta; not written when max_iteration = 0).
+        first delta; not written when max_iteration = 0), and with ``robust_scale`` (E,) chi2 (E,) = r^T Omega r and
+        weights (E,) of every edge at the final poses (one more launch; zeros for skipped edges).
         Nothing is synchronised, so a call on device tensors can be captured.  ``poses_out`` may be ``poses``."""
         dev, X, e, Z, om = self._inputs(poses, edge_ij, measurements, information)
         N, E = int(X.shape[0]), int(e.shape[0])
+        c = self._scale(robust_scale, dev, E)
         if fixed is None:
             fx = torch.zeros(N, dtype=torch.uint8, device=dev)
             fx[:1] = 1
@@ -180,25 +217,35 @@ class PoseGraphOptimizer:
             raise _lib.NscError("pose graph: poses_out must be a contiguous (N,4,4) float64 tensor on the device")
         if step0:
             out["step0"] = torch.empty((N, 6), **f64)         # not written when max_iteration = 0
+        if c is not None:
+            out["chi2"], out["weights"] = torch.empty(E, **f64), torch.empty(E, **f64)
         L = _lib.lib()
         ws = torch.empty(max(int(L.nsc_posegraph_workspace_bytes(N, E, C.byref(self.params))), 1), dtype=torch.uint8,
                          device=dev)
         with torch.cuda.device(dev):
-            status = L.nsc_posegraph_optimize(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E, _lib.ptr(fx),
-                                              C.byref(self.params), _lib.ptr(out["poses"]), _lib.ptr(out["stats"]),
-                                              _lib.ptr(out["cost_history"]), _lib.ptr(out.get("step0")), _lib.ptr(ws),
-                                              int(ws.numel()), _lib.stream_ptr(dev))
-        _lib.check(status, "nsc_posegraph_optimize")
+            status = L.nsc_posegraph_optimize_robust(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E,
+                                                     _lib.ptr(fx), C.byref(self.params), _lib.ptr(out["poses"]),
+                                                     _lib.ptr(out["stats"]), _lib.ptr(out["cost_history"]),
+                                                     _lib.ptr(out.get("step0")), _lib.ptr(ws), int(ws.numel()),
+                                                     _lib.stream_ptr(dev), self.kernel, _lib.ptr(c),
+                                                     _lib.ptr(out.get("chi2")), _lib.ptr(out.get("weights")))
+        _lib.check(status, "nsc_posegraph_optimize_robust")
         return out
 
-    def optimize(self, poses, edge_ij, measurements, information, fixed=None):
+    def optimize(self, poses, edge_ij, measurements, information, fixed=None, robust_scale=None):
         """-> dict: poses (N,4,4) (a device tensor for device poses, numpy for numpy), cost0, cost, iterations, accepted,
-        rejected, pcg_iterations, converged, cost_history (iterations + 1,), and lambda, skipped, step.  ``fixed``: (N,)
-        mask of the poses that stay; None fixes pose 0.  Reads the statistics back, so it synchronises."""
-        out = self.optimize_device(poses, edge_ij, measurements, information, fixed)
+        rejected, pcg_iterations, converged, cost_history (iterations + 1,), and lambda, skipped, step; the costs are
+        robust costs.  ``fixed``: (N,) mask of the poses that stay; None fixes pose 0.  ``robust_scale``: (E,) widths of
+        this optimiser's kernel, 0 for the edges that stay quadratic; with it the result has chi2 (E,) and weights (E,)
+        as numpy arrays: a closure whose weight ends near 0 was rejected.  Reads the statistics back, so it
+        synchronises."""
+        out = self.optimize_device(poses, edge_ij, measurements, information, fixed, robust_scale=robust_scale)
         s = out["stats"].cpu().numpy()
         its = int(s[0])
         X = out["poses"] if isinstance(poses, torch.Tensor) else out["poses"].cpu().numpy()
-        return dict(poses=X, cost0=float(s[4]), cost=float(s[5]), iterations=its, accepted=int(s[1]), rejected=int(s[2]),
-                    pcg_iterations=int(s[3]), converged=bool(s[8]), cost_history=out["cost_history"].cpu().numpy()[:its + 1],
-                    skipped=int(s[7]), step=float(s[9]), **{"lambda": float(s[6])})
+        res = dict(poses=X, cost0=float(s[4]), cost=float(s[5]), iterations=its, accepted=int(s[1]), rejected=int(s[2]),
+                   pcg_iterations=int(s[3]), converged=bool(s[8]), cost_history=out["cost_history"].cpu().numpy()[:its + 1],
+                   skipped=int(s[7]), step=float(s[9]), **{"lambda": float(s[6])})
+        if robust_scale is not None:
+            res.update(chi2=out["chi2"].cpu().numpy(), weights=out["weights"].cpu().numpy())
+        return res

@@ -7,8 +7,10 @@ closures between random poses at least 50 frames apart.  Times ``optimize``
 and, as a host baseline on the same residuals and Jacobians, Gauss-Newton with scipy.sparse.linalg.spsolve on the
 normal equations (tests/posegraph_restatement.py builds them, edge by edge, in numpy: the linearisation time is
 reported apart from the solve time).  Prints the launch count and the inner iterations per outer step.
-usage: posegraph_probe.py [reps=10] [max_pcg_iterations=100] [max_iteration=20] [graph=1]
-``graph=0`` leaves the capture out (for caps whose launch count makes a graph of several hundred thousand nodes)."""
+usage: posegraph_probe.py [reps=10] [max_pcg_iterations=100] [max_iteration=20] [graph=1] [kernel=none] [width=3]
+``graph=0`` leaves the capture out (for caps whose launch count makes a graph of several hundred thousand nodes).
+``kernel`` = huber, cauchy or geman_mcclure puts that robust kernel, with ``width``, on the closure edges (the odometry
+edges stay quadratic) and asks for the per-edge chi2 and weights: one more launch.  The host baseline stays quadratic."""
 import os
 import sys
 import time
@@ -28,6 +30,8 @@ reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 max_pcg = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 max_it = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 with_graph = (int(sys.argv[4]) if len(sys.argv) > 4 else 1) != 0
+kernel = sys.argv[5] if len(sys.argv) > 5 and sys.argv[5] != "none" else None
+width = float(sys.argv[6]) if len(sys.argv) > 6 else 3.0
 N, CLOSURES = 4541, 200
 
 rng = np.random.default_rng(0)
@@ -45,14 +49,19 @@ print(f"graph: {N} poses, {len(oe)} odometry edges, {len(ce)} closures; trajecto
       f"{P.trajectory_error(init, truth):.3f} m")
 
 dev = torch.device("cuda")
-opt = PoseGraphOptimizer(max_pcg_iterations=max_pcg, max_iteration=max_it)
+opt = PoseGraphOptimizer(kernel=kernel, max_pcg_iterations=max_pcg, max_iteration=max_it)
 args = [torch.from_numpy(x).to(dev) for x in (init, e, Z, Om)]
 fixed = torch.zeros(N, dtype=torch.uint8, device=dev)
 fixed[0] = 1
+scale = None
+if kernel is not None:
+    scale = torch.zeros(len(e), dtype=torch.float64, device=dev)
+    scale[len(oe):] = width
+    print(f"robust kernel {kernel}, width {width:g} on the {len(ce)} closure edges")
 
 
 def call():
-    return opt.optimize_device(*args, fixed=fixed)
+    return opt.optimize_device(*args, fixed=fixed, robust_scale=scale)
 
 
 def device_times(fn, n):
@@ -74,10 +83,13 @@ out = call()
 torch.cuda.synchronize()
 s = out["stats"].cpu().numpy()
 its = int(s[0])
-launches = 5 + 1 + 3 + max_it * (8 + 4 * max_pcg) + 1
+launches = 5 + 1 + 3 + max_it * (8 + 4 * max_pcg) + 1 + (kernel is not None)
 print(f"optimize: {its} outer iterations ({int(s[1])} accepted, {int(s[2])} rejected), {int(s[3])} inner iterations "
       f"({s[3] / max(its, 1):.1f} per outer step), cost {s[4]:.6g} -> {s[5]:.6g}, converged {bool(s[8])}, "
       f"trajectory error {P.trajectory_error(out['poses'].cpu().numpy(), truth):.3f} m; {launches} launches per call")
+if kernel is not None:
+    w = out["weights"].cpu().numpy()[len(oe):]
+    print(f"closure weights: min {w.min():.3g}, median {np.median(w):.3g}, max {w.max():.3g}")
 t = device_times(call, reps)
 print(f"eager: median {np.median(t):.2f} ms (min {t.min():.2f}, max {t.max():.2f}; {reps} calls)")
 
@@ -92,7 +104,7 @@ if with_graph:
         cap = call()
     g.replay()
     torch.cuda.synchronize()
-    assert torch.equal(cap["poses"], out["poses"]) and torch.equal(cap["stats"], out["stats"])
+    assert all(torch.equal(cap[k], out[k]) for k in out)
     t = device_times(g.replay, reps)
     print(f"replayed hipGraph: median {np.median(t):.2f} ms (min {t.min():.2f}, max {t.max():.2f}); bitwise the eager "
           "result")
