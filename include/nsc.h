@@ -709,6 +709,18 @@ int    nsc_posegraph_linearize_robust(const double *poses, int32_t n_poses, cons
                                       int64_t *skipped, void *ws, size_t ws_bytes, void *stream, int32_t kernel,
                                       const double *edge_scale, double *weights);
 
+/* stats[...] of nsc_posegraph_optimize, in the order of the list below */
+#define NSC_POSEGRAPH_STAT_ITERATIONS      0
+#define NSC_POSEGRAPH_STAT_ACCEPTED        1
+#define NSC_POSEGRAPH_STAT_REJECTED        2
+#define NSC_POSEGRAPH_STAT_PCG_ITERATIONS  3
+#define NSC_POSEGRAPH_STAT_INITIAL_COST    4
+#define NSC_POSEGRAPH_STAT_FINAL_COST      5
+#define NSC_POSEGRAPH_STAT_LAMBDA          6
+#define NSC_POSEGRAPH_STAT_SKIPPED         7
+#define NSC_POSEGRAPH_STAT_CONVERGED       8
+#define NSC_POSEGRAPH_STAT_STEP            9
+
 /* poses_out (n_poses,4,4) may alias poses.  stats (NSC_POSEGRAPH_STATS) float64 = [outer iterations done, accepted,
  * rejected, inner iterations in total, initial cost, final cost, final lambda, skipped edges, 1 = stopped by a
  * criterion / 0 = capped at max_iteration, |delta| of the last outer iteration].  cost_history (max_iteration + 1):

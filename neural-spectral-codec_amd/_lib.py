@@ -113,6 +113,10 @@ class PoseGraphParams(C.Structure):
 
 # include/nsc.h NSC_POSEGRAPH_MAX_EDGES, NSC_POSEGRAPH_MAX_LAUNCHES, NSC_POSEGRAPH_STATS
 POSEGRAPH_MAX_EDGES, POSEGRAPH_MAX_LAUNCHES, POSEGRAPH_STATS = 1073741823, 1000000, 10
+# include/nsc.h NSC_POSEGRAPH_STAT_*: where each statistic stands in `stats`
+(POSEGRAPH_STAT_ITERATIONS, POSEGRAPH_STAT_ACCEPTED, POSEGRAPH_STAT_REJECTED, POSEGRAPH_STAT_PCG_ITERATIONS,
+ POSEGRAPH_STAT_INITIAL_COST, POSEGRAPH_STAT_FINAL_COST, POSEGRAPH_STAT_LAMBDA, POSEGRAPH_STAT_SKIPPED,
+ POSEGRAPH_STAT_CONVERGED, POSEGRAPH_STAT_STEP) = range(POSEGRAPH_STATS)
 # include/nsc.h NSC_POSEGRAPH_KERNEL_*
 POSEGRAPH_KERNELS = {None: 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
 

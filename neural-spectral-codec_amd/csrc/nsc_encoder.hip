@@ -24,11 +24,11 @@
 
 #include "../../include/nsc.h"
 #include "../../include/nsc_debug.h"
+#include "nsc_fill.h"
 #include "nsc_math.h"
+#include "nsc_util.h"
 
 namespace {
-
-#include "nsc_fill.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -446,13 +446,6 @@ __device__ __forceinline__ void fft_row(const float *x, double2 *buf, const doub
     fft_row_regs(in, buf, tw, mags, lane);
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Twiddles and histogram segments -> LDS, by `nthr` cooperating threads (index t).  In the fused
 // kernel one wave does this while the others already stream points, so none of its global-load
@@ -585,7 +578,7 @@ __device__ __forceinline__ void finish_image(unsigned char *lds, const EncDev &d
             hist[b] = h;
             part += (double)h;
         }
-        part = wave_sum(part);
+        part = nsc_wave_sum(part);
         if (lane == 0) rowsum[r] = part;
     }
     __syncthreads();
@@ -950,7 +943,7 @@ __device__ __forceinline__ void finish_fast(unsigned char *lds, const EncDev &d,
         }
         wave_sync();                                              // the magnitudes are overwritten by the next pair
     }
-    part = wave_sum(part);
+    part = nsc_wave_sum(part);
     if (lane == 0) rowsum[wave] = part;
     __syncthreads();
 
@@ -1348,7 +1341,7 @@ int nsc_encode_clouds(const float *pts, const int64_t *cloud_offsets, int32_t n_
         st = launch_finish<FUSED_NW>(stream, d, n_clouds, sqr, nullptr, 0, lut, out_desc, out_raw, out_interp);
         if (st != NSC_OK) return st;
     }
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_project_intensity(const float *pts, const int64_t *cloud_offsets, int32_t n_clouds, int64_t total_points,
@@ -1374,7 +1367,7 @@ int nsc_project_intensity(const float *pts, const int64_t *cloud_offsets, int32_
     hipLaunchKernelGGL(intensity_kernel, dim3((unsigned)(n_clouds * parts)), dim3(256), 0, stream, pts,
                        reinterpret_cast<const long long *>(cloud_offsets), parts, d.bp, npix, range_raw,
                        reinterpret_cast<int *>(out_intensity));
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_scatter_clouds(const float *pts, const int64_t *cloud_offsets, int32_t n_clouds, int64_t total_points,
@@ -1400,7 +1393,7 @@ int nsc_scatter_clouds(const float *pts, const int64_t *cloud_offsets, int32_t n
         st = launch_scatter<4, 8>(stream, d, img_bytes, n_clouds, 1, pts, off, stride, out_sqr);
     }
     if (st != NSC_OK) return st;
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_finish_images(const uint32_t *sqr, int32_t n_images, const NscEncParams *p, const int32_t *lut,
@@ -1415,7 +1408,7 @@ int nsc_finish_images(const uint32_t *sqr, int32_t n_images, const NscEncParams 
     const EncDev d = make_dev(p, p->n_elevation);
     st = launch_finish<FUSED_NW>(stream, d, n_images, sqr, nullptr, 0, lut, out_desc, out_raw, out_interp);
     if (st != NSC_OK) return st;
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_encode_range_images(const float *imgs, int32_t n_images, int32_t rows, const NscEncParams *p,
@@ -1431,7 +1424,7 @@ int nsc_encode_range_images(const float *imgs, int32_t n_images, int32_t rows, c
     const EncDev d = make_dev(p, rows);
     st = launch_finish<FUSED_NW>(stream, d, n_images, nullptr, imgs, 1, lut, out_desc, nullptr, nullptr);
     if (st != NSC_OK) return st;
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_interpolate_range_images(const float *imgs, int32_t n_images, int32_t rows, const int32_t *lut,
@@ -1457,7 +1450,7 @@ int nsc_interpolate_range_images_ex(const float *imgs, int32_t n_images, int32_t
     const EncDev d = make_dev(&p, rows);
     const int st = launch_finish<FUSED_NW>(stream, d, n_images, nullptr, imgs, 2, lut, nullptr, nullptr, out);
     if (st != NSC_OK) return st;
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_debug_point_bins(const float *pts, int64_t n_points, int32_t stride, const NscEncParams *p,
@@ -1474,7 +1467,7 @@ int nsc_debug_point_bins(const float *pts, int64_t n_points, int32_t stride, con
     hipLaunchKernelGGL(point_bins_kernel, dim3((unsigned)blocks), dim3(256), 0,
                        static_cast<hipStream_t>(stream_), pts, (long long)n_points, stride, d.bp,
                        (int)(stride == 4 && d.E == 16 && nsc_lean_ok(d.bp)), out_idx, out_flags);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

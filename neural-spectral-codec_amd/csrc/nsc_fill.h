@@ -3,6 +3,9 @@
 // kernel node that follows it in the captured stream -- the buffer was accumulated into before it was zeroed.  Kernel nodes keep
 // their stream order, so nothing in this library uses hipMemsetAsync / hipMemcpyAsync on a path that can be captured.
 #pragma once
+#include <hip/hip_runtime.h>
+
+namespace {
 
 __global__ __launch_bounds__(256) void nsc_fill_u32_kernel(unsigned *__restrict__ p, unsigned v, long long n)
 {
@@ -20,3 +23,5 @@ inline bool nsc_fill_u32(hipStream_t st, void *p, unsigned v, long long n)
     hipLaunchKernelGGL(nsc_fill_u32_kernel, dim3((unsigned)b), dim3(256), 0, st, static_cast<unsigned *>(p), v, n);
     return true;
 }
+
+}  // namespace

@@ -25,12 +25,13 @@
 
 #include "../../include/nsc.h"
 #include "../../include/nsc_debug.h"
+#include "nsc_fill.h"
+#include "nsc_util.h"
 
 namespace {
 
 #include "nsc_gemm_glds.h"
 #include "nsc_gat_banded.h"
-#include "nsc_fill.h"
 
 // ---------------------------------------------------------------------------------------------
 // CSR build
@@ -43,29 +44,6 @@ __global__ __launch_bounds__(256) void csr_count_kernel(const long long *__restr
         if (s == t || s < 0 || s >= N || t < 0 || t >= N) continue;     // remove_self_loops
         atomicAdd(&deg[t], 1);
     }
-}
-
-// exclusive scan of (deg[i] + 1) -> row_ptr, single workgroup of 1024 threads
-__global__ __launch_bounds__(1024) void csr_scan_kernel(const int *__restrict__ deg, int N,
-                                                        int *__restrict__ row_ptr)
-{
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    const int chunk = (N + 1023) / 1024;
-    const int b = tid * chunk, e = min(b + chunk, N);
-    int s = 0;
-    for (int i = b; i < e; ++i) s += deg[i] + 1;
-    part[tid] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = (tid >= off) ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - s;
-    for (int i = b; i < e; ++i) { row_ptr[i] = run; run += deg[i] + 1; }
-    if (tid == 1023) row_ptr[N] = part[1023];
 }
 
 __global__ __launch_bounds__(256) void csr_fill_kernel(const long long *__restrict__ ei, long long E, int N,
@@ -91,12 +69,7 @@ __global__ __launch_bounds__(256) void csr_finalize_kernel(const long long *__re
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     const int b = row_ptr[i], e = row_ptr[i + 1] - 1;     // [b,e) real edges, slot e = self loop
-    for (int a = b + 1; a < e; ++a) {                     // insertion sort (in-degrees are small)
-        const int v = eid[a];
-        int c = a - 1;
-        while (c >= b && eid[c] > v) { eid[c + 1] = eid[c]; --c; }
-        eid[c + 1] = v;
-    }
+    nsc_sort_row(eid, b, e);
     float acc[NSC_GAT_MAX_EDGE_DIM];
 #pragma unroll
     for (int d = 0; d < NSC_GAT_MAX_EDGE_DIM; ++d) acc[d] = 0.0f;
@@ -868,23 +841,23 @@ __global__ __launch_bounds__(256) void burn_kernel(int mode, int per_wave, float
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct GatWs {
-    size_t h0, h1, g, a_src, a_dst, total;
+    float *h0, *h1, *g, *a_src, *a_dst;
+    size_t total;                                                   // bytes
 };
 
-GatWs gat_ws(const NscGatModel *m, int N)
+// base = nullptr: sizes only
+GatWs gat_ws(const NscGatModel *m, int N, void *base)
 {
+    Carver c = {reinterpret_cast<uintptr_t>(base), 0};
     GatWs w;
-    size_t o = 0;
-    const size_t nh = align256((size_t)N * m->hidden * sizeof(float));
-    w.h0 = o; o += nh;
-    w.h1 = o; o += nh;
-    w.g = o;  o += nh;
-    w.a_src = o; o += align256((size_t)N * sizeof(float));
-    w.a_dst = o; o += align256((size_t)N * sizeof(float));
-    w.total = o;
+    const size_t nh = (size_t)N * m->hidden;
+    w.h0 = c.take<float>(nh);
+    w.h1 = c.take<float>(nh);
+    w.g = c.take<float>(nh);
+    w.a_src = c.take<float>(N);
+    w.a_dst = c.take<float>(N);
+    w.total = c.o;
     return w;
 }
 
@@ -1005,13 +978,13 @@ int nsc_graph_build_csr(const int64_t *edge_index, int64_t E, int32_t N, const f
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(csr_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ei, (long long)E, N, deg);
-    hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), 0, st, deg, N, row_ptr);
+    hipLaunchKernelGGL(nsc_csr_scan_kernel<1>, dim3(1), dim3(1024), 0, st, deg, N, row_ptr);
     hipLaunchKernelGGL(csr_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ei, (long long)E, N, row_ptr,
                        cursor, eid);
     hipLaunchKernelGGL(csr_finalize_kernel, dim3((N + 255) / 256), dim3(256), 0, st, ei, N,
                        (edge_dim > 0) ? edge_attr : nullptr, edge_dim, row_ptr, src, eid,
                        (edge_attr && edge_dim > 0) ? loop_attr : nullptr);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_graph_band_entries(const NscGraph *g, const float *edge_attr, int32_t edge_dim, float *entries, int32_t *info,
@@ -1027,7 +1000,7 @@ int nsc_graph_band_entries(const NscGraph *g, const float *edge_attr, int32_t ed
     hipLaunchKernelGGL(band_entries_kernel, dim3((g->n_nodes + 255) / 256), dim3(256), 0, st, g->row_ptr, g->src, g->eid,
                        (edge_dim > 0) ? edge_attr : nullptr, edge_dim, g->loop_attr, g->n_nodes,
                        reinterpret_cast<f32x4 *>(entries), info);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 size_t nsc_gat_folded_floats(const NscGatModel *m)
@@ -1053,13 +1026,13 @@ int nsc_gat_fold_weights(const NscGatModel *m, float *folded, void *stream_)
     }
     hipLaunchKernelGGL(gat_fold_kernel, dim3(m->n_layers, 3), dim3(256), 0, static_cast<hipStream_t>(stream_),
                        pa, folded);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 size_t nsc_gat_workspace_bytes(const NscGatModel *m, int32_t n_nodes)
 {
     if (check_model(m) != NSC_OK || n_nodes <= 0) return 0;
-    return gat_ws(m, n_nodes).total;
+    return gat_ws(m, n_nodes, nullptr).total;
 }
 
 int nsc_gat_forward(const NscGatModel *m, const NscGraph *g, const float *x, const float *edge_attr,
@@ -1074,7 +1047,7 @@ int nsc_debug_burn(int32_t mode, int32_t workgroups, int32_t per_wave, float *sc
     if (mode < 0 || mode > 5 || workgroups < 0 || per_wave < 0 || !scratch || scratch_bytes < (1u << 20)) return NSC_EINVAL;
     if (workgroups == 0) return NSC_OK;
     hipLaunchKernelGGL(burn_kernel, dim3((unsigned)workgroups), dim3(256), 0, static_cast<hipStream_t>(stream_), mode, per_wave, scratch);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 #endif
 
@@ -1104,13 +1077,10 @@ int nsc_gat_forward_ex(const NscGatModel *m, const NscGraph *g, const float *x, 
     const int N = g->n_nodes;
     if (N == 0) return NSC_OK;
     if (!x || !out || !g->row_ptr || !g->src || !g->eid || !m->folded) return NSC_EINVAL;
-    const GatWs w = gat_ws(m, N);
+    const GatWs w = gat_ws(m, N, ws);
     if (!ws || ws_bytes < w.total) return NSC_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    char *base = static_cast<char *>(ws);
-    float *h0 = reinterpret_cast<float *>(base + w.h0), *h1 = reinterpret_cast<float *>(base + w.h1);
-    float *G = reinterpret_cast<float *>(base + w.g);
-    float *a_src = reinterpret_cast<float *>(base + w.a_src), *a_dst = reinterpret_cast<float *>(base + w.a_dst);
+    float *h0 = w.h0, *h1 = w.h1, *G = w.g, *a_src = w.a_src, *a_dst = w.a_dst;
     const float *aux = m->folded;
     const int H = m->hidden, L = m->n_layers;
     const bool use_edge = m->edge_dim > 0 && edge_attr && g->loop_attr;      // model.py:126
@@ -1196,7 +1166,7 @@ int nsc_gat_forward_ex(const NscGatModel *m, const NscGraph *g, const float *x, 
         launch_gemm<2>(st, cores, x, m->in_dim, m->res_w, m->in_dim, nullptr, N, m->out_dim, m->out_dim, m->in_dim, out,
                        m->out_dim, e4);
     }
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -19,13 +19,12 @@
 #include <type_traits>
 
 #include "../../include/nsc.h"
+#include "nsc_fill.h"
+#include "nsc_util.h"
 
 namespace {
 
 #include "nsc_gemm_glds.h"
-#include "nsc_fill.h"
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------------------------------------
 // counter-based dropout mask: keep iff u01(hash(seed, stream, idx)) >= p
@@ -1250,25 +1249,6 @@ __global__ __launch_bounds__(256) void tcsr_count_kernel(const int *__restrict__
     if (i >= N) return;
     for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) { atomicAdd(&cnt[src[e]], 1); tgt[e] = i; }
 }
-__global__ __launch_bounds__(1024) void tcsr_scan_kernel(const int *__restrict__ cnt, int N, int *__restrict__ t_ptr)
-{
-    __shared__ int part[1024];
-    const int tid = threadIdx.x, chunk = (N + 1023) / 1024;
-    const int b = tid * chunk, e = min(b + chunk, N);
-    int s = 0;
-    for (int i = b; i < e; ++i) s += cnt[i];
-    part[tid] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = (tid >= off) ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - s;
-    for (int i = b; i < e; ++i) { t_ptr[i] = run; run += cnt[i]; }
-    if (tid == 1023) t_ptr[N] = part[1023];
-}
 __global__ __launch_bounds__(256) void tcsr_fill_kernel(const int *__restrict__ row_ptr, const int *__restrict__ src,
                                                         int N, const int *__restrict__ t_ptr, int *__restrict__ cursor,
                                                         int *__restrict__ t_entry)
@@ -1284,13 +1264,7 @@ __global__ __launch_bounds__(256) void tcsr_sort_kernel(const int *__restrict__ 
 {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= N) return;
-    const int b = t_ptr[j], e = t_ptr[j + 1];
-    for (int a = b + 1; a < e; ++a) {
-        const int v = t_entry[a];
-        int c = a - 1;
-        while (c >= b && t_entry[c] > v) { t_entry[c + 1] = t_entry[c]; --c; }
-        t_entry[c + 1] = v;
-    }
+    nsc_sort_row(t_entry, t_ptr[j], t_ptr[j + 1]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1349,23 +1323,8 @@ __global__ __launch_bounds__(256) void triplet_reduce_kernel(const float *__rest
 // ---------------------------------------------------------------------------------------------
 constexpr int COLRED_MAXR = 64;
 
-template <class T> struct Slots {                                   // `count` equal regions, `stride` elements apart
-    T *p;
-    size_t stride;
-    T *operator()(int i) const { return p + stride * i; }
-};
-
-struct Carver {                                                      // consecutive regions from base (0: offsets only)
-    uintptr_t base;
-    size_t o;
-    template <class T> T *take(size_t n) { T *p = reinterpret_cast<T *>(base + o); o += align256(n * sizeof(T)); return p; }
-    template <class T> Slots<T> slots(size_t n, int count)
-    {
-        const size_t s = align256(n * sizeof(T)) / sizeof(T);
-        return {take<T>(s * count), s};
-    }
-    Region region(size_t n) { return {take<float>(n), n}; }
-};
+// a Region of n floats off the carver
+inline Region take_region(Carver &c, size_t n) { return {c.take<float>(n), n}; }
 
 // The training workspace.  train_ws() is the one place that knows its layout: nsc_gat_train_workspace_bytes takes the size from it,
 // the forward and the backward their pointers, so both see the same saved-state regions.  Every region starts on 256 bytes.
@@ -1414,11 +1373,11 @@ TrainWs train_ws(const NscGatModel *m, int N, int nnz, void *base)
     w.da_src = c.slots<float>(N, L);
     w.da_dst = c.slots<float>(N, L);
     // the dX = dY W products: dOut W_out (Dout x H), dOut W_res (Dout x Din), dG W_lin (H x H), dZ0 W_in (H x Din)
-    w.tw = c.region(std::max({Dout * H, res_proj ? Dout * Din : 0, H * H, H * Din}));
-    w.slabs.out_w = c.region(Dout * H * SPLITK_SLABS);
-    if (res_proj) w.slabs.res_w = c.region(Dout * Din * SPLITK_SLABS);
-    for (int l = 0; l < L; ++l) w.slabs.lin_w[l] = c.region(H * H * SPLITK_SLABS);
-    w.slabs.in_w = c.region(H * Din * SPLITK_SLABS);
+    w.tw = take_region(c, std::max({Dout * H, res_proj ? Dout * Din : 0, H * H, H * Din}));
+    w.slabs.out_w = take_region(c, Dout * H * SPLITK_SLABS);
+    if (res_proj) w.slabs.res_w = take_region(c, Dout * Din * SPLITK_SLABS);
+    for (int l = 0; l < L; ++l) w.slabs.lin_w[l] = take_region(c, H * H * SPLITK_SLABS);
+    w.slabs.in_w = take_region(c, H * Din * SPLITK_SLABS);
     w.colpart = c.take<double>((size_t)COLRED_MAXR * std::max(std::max(H, Dout), Din) * 2);
     w.colpart2 = c.slots<double>((size_t)COLRED_MAXR * H, L + 1);   // partials of a bias gradient (bn_apply_colsum_kernel)
     w.attpart = c.slots<double>((size_t)COLRED_MAXR * H * 2, L);    // partials of a layer's two attention-vector gradients
@@ -1598,10 +1557,10 @@ int nsc_graph_transpose(const NscGraph *g, int32_t *t_ptr, int32_t *t_entry, int
     int *cursor = reinterpret_cast<int *>(static_cast<char *>(ws) + need / 2);
     nsc_fill_u32(st, ws, 0u, (long long)(need / 4));
     hipLaunchKernelGGL(tcsr_count_kernel, dim3(blocks(N)), dim3(256), 0, st, g->row_ptr, g->src, N, cnt, tgt);
-    hipLaunchKernelGGL(tcsr_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, N, t_ptr);
+    hipLaunchKernelGGL(nsc_csr_scan_kernel<0>, dim3(1), dim3(1024), 0, st, cnt, N, t_ptr);
     hipLaunchKernelGGL(tcsr_fill_kernel, dim3(blocks(N)), dim3(256), 0, st, g->row_ptr, g->src, N, t_ptr, cursor, t_entry);
     hipLaunchKernelGGL(tcsr_sort_kernel, dim3(blocks(N)), dim3(256), 0, st, t_ptr, N, t_entry);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 size_t nsc_gat_train_workspace_bytes(const NscGatModel *m, const NscGraph *g)
@@ -1658,7 +1617,7 @@ int nsc_gat_forward_train(const NscGatModel *m, const NscGraph *g, const float *
     gemm<false>(st, w.h(L), H, m->out_w, H, N, m->out_dim, H, out, m->out_dim, m->out_b, 0, {}, res_id ? x : nullptr);
     if (m->residual && !res_id)                                                // out += residual_proj(x)  model.py:147-149
         gemm<false>(st, x, m->in_dim, m->res_w, m->in_dim, N, m->out_dim, m->in_dim, out, m->out_dim, m->res_b, 1);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, const float *edge_attr,
@@ -1785,7 +1744,7 @@ int nsc_gat_backward(const NscGatModel *m, const NscGraph *g, const float *x, co
         fa.slabs = slabs;                                           // (the weight gradients' slab sums: after the last product above)
         hipLaunchKernelGGL(backward_end_finals_kernel, dim3(fa.n_fin + fa.n_edge + slabs.blocks), dim3(256), 0, st, fa);
     }
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 size_t nsc_triplet_workspace_bytes(int32_t n_triplets) { return n_triplets > 0 ? align256((size_t)n_triplets * 4) : 0; }
@@ -1800,7 +1759,7 @@ int nsc_triplet_loss(const float *emb, const int64_t *anchors, const int64_t *po
     if (grad_emb) fill_zero(st, grad_emb, (long long)N * D);
     if (T == 0) {
         fill_zero(st, loss, 1);
-        return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+        return launch_status();
     }
     if (!emb || !anchors || !positives || !negatives) return NSC_EINVAL;
     if (!ws || ws_bytes < nsc_triplet_workspace_bytes(T)) return NSC_EWORKSPACE;
@@ -1809,7 +1768,7 @@ int nsc_triplet_loss(const float *emb, const int64_t *anchors, const int64_t *po
                        reinterpret_cast<const long long *>(positives), reinterpret_cast<const long long *>(negatives), T, N, D,
                        margin, scale, per, grad_emb);
     hipLaunchKernelGGL(triplet_reduce_kernel, dim3(1), dim3(256), 0, st, per, T, scale, loss);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include "../../include/nsc.h"
+#include "nsc_util.h"
 
 namespace {
 
@@ -757,12 +758,8 @@ __global__ __launch_bounds__(GEO_THREADS) void prepared_setup_kernel(StoreView s
     state[p] = PairState{0.0, 0.0, 0, 0, 0, 0};
 }
 
-// The workspaces are regions carved in order, each rounded up to 256 bytes: the offset of the next one, `bytes` long.
-inline size_t carve(size_t &o, size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; }
-
-// Byte `offset` of a workspace as a T*.  Integer arithmetic: a size query lays out a null workspace.
-template <class T>
-inline T *at(void *ws, size_t offset) { return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(ws) + offset); }
+// The workspaces are regions carved in order (Carver, nsc_util.h), each rounded up to 256 bytes; a size query lays out a
+// null workspace.
 
 // Per-cloud regions for n_clouds clouds of total_rows input rows in all, and the bytes they take: nsc_gicp_prepare's
 // workspace, and the head of nsc_gicp_register's (2 clouds per pair; source rows, then target rows).
@@ -775,14 +772,15 @@ struct CloudRegions {
 
 CloudRegions cloud_regions(void *ws, size_t n_clouds, size_t total_rows)
 {
+    Carver c = {reinterpret_cast<uintptr_t>(ws), 0};
     CloudRegions r;
-    r.total = 0;
-    r.partial = at<double>(ws, carve(r.total, n_clouds * GEO_BLOCKS * 3 * sizeof(double)));
-    r.bound = at<double>(ws, carve(r.total, n_clouds * 4 * sizeof(double)));
-    r.count = at<long long>(ws, carve(r.total, n_clouds * sizeof(long long)));
-    r.slots = at<Slot>(ws, carve(r.total, 2 * total_rows * sizeof(Slot)));
-    r.points = at<double>(ws, carve(r.total, total_rows * 3 * sizeof(double)));
-    r.cov = at<double>(ws, carve(r.total, total_rows * 6 * sizeof(double)));
+    r.partial = c.take<double>(n_clouds * GEO_BLOCKS * 3);
+    r.bound = c.take<double>(n_clouds * 4);
+    r.count = c.take<long long>(n_clouds);
+    r.slots = c.take<Slot>(2 * total_rows);
+    r.points = c.take<double>(total_rows * 3);
+    r.cov = c.take<double>(total_rows * 6);
+    r.total = c.o;
     return r;
 }
 
@@ -796,12 +794,13 @@ struct PairRegions {
 
 PairRegions pair_regions(void *ws, size_t n_pairs, bool stored, size_t base)
 {
+    Carver c = {reinterpret_cast<uintptr_t>(ws), base};
     PairRegions r;
-    r.total = base;
-    r.count = at<long long>(ws, carve(r.total, stored ? 2 * n_pairs * sizeof(long long) : 0));
-    r.rows = at<PairRows>(ws, carve(r.total, stored ? n_pairs * sizeof(PairRows) : 0));
-    r.slab = at<double>(ws, carve(r.total, n_pairs * GEO_BLOCKS * SLAB * sizeof(double)));
-    r.state = at<PairState>(ws, carve(r.total, n_pairs * sizeof(PairState)));
+    r.count = c.take<long long>(stored ? 2 * n_pairs : 0);
+    r.rows = c.take<PairRows>(stored ? n_pairs : 0);
+    r.slab = c.take<double>(n_pairs * GEO_BLOCKS * SLAB);
+    r.state = c.take<PairState>(n_pairs);
+    r.total = c.o;
     return r;
 }
 
@@ -878,8 +877,6 @@ void launch_rounds(const Pairs &pairs, int n_pairs, const long long *count, doub
                            p->max_iteration, p->relative_fitness, p->relative_rmse);
     }
 }
-
-inline int launch_status() { return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH; }
 
 }  // namespace
 

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/nsc.h"
+#include "nsc_util.h"
 
 namespace {
 
@@ -394,8 +395,6 @@ __global__ __launch_bounds__(512) void voxel_overlap_kernel(const float *__restr
         iou[p] = uni > 0 ? (double)inter / (double)uni : 0.0;            // :386-389
     }
 }
-
-inline int launch_status() { return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH; }
 
 int quantize_common(bool deq, const void *in, int32_t n, int32_t dim, float eps, void *out, void *stream)
 {

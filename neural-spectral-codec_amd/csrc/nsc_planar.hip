@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "../../include/nsc.h"
+#include "nsc_util.h"
 
 // The definition rounds every operation on its own.  hipcc's default contracts a * b + c into an fma, also through the
 // _rn intrinsics (plain operators in a header, out of this pragma's reach), so the arithmetic below is written with
@@ -67,12 +68,6 @@ struct Vote {                        // the parameters of the vote
 // a row is a structure row iff (1 - C_zz) < normal_z2_max (1 - epsilon); zz is the last of the six stored terms
 __device__ __forceinline__ bool is_structure(const double *cov6, double thr) { return 1.0 - cov6[5] < thr; }
 
-__device__ __forceinline__ int wave_sum_int(int v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(SETUP_THREADS) void planar_setup_kernel(Sets st, const long long *source_ids,
                                                                      const long long *target_ids, int stride,
                                                                      PairRows *rows)
@@ -89,8 +84,8 @@ __global__ __launch_bounds__(SETUP_THREADS) void planar_setup_kernel(Sets st, co
     for (long long i = tid; i < ms; i += SETUP_THREADS)
         taken += (i % stride == 0) && is_structure(st.s_cov + 6 * (s0 + i), st.s_thr);
     for (long long i = tid; i < mt; i += SETUP_THREADS) structure += is_structure(st.t_cov + 6 * (t0 + i), st.t_thr);
-    taken = wave_sum_int(taken);
-    structure = wave_sum_int(structure);
+    taken = nsc_wave_sum(taken);
+    structure = nsc_wave_sum(structure);
     if ((tid & 63) == 0) {
         part[0][tid >> 6] = taken;
         part[1][tid >> 6] = structure;
@@ -299,18 +294,20 @@ __global__ __launch_bounds__(64) void planar_reduce_kernel(const PairRows *__res
     }
 }
 
-inline size_t carve(size_t &o, size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; }
-
-struct Regions {
-    size_t rows, peaks, total;
+struct Regions {                     // the workspace
+    PairRows *rows;
+    int *peaks;
+    size_t total;
 };
 
-Regions regions(size_t n_pairs, size_t n_yaw)
+// ws = nullptr: the size only
+Regions regions(void *ws, size_t n_pairs, size_t n_yaw)
 {
+    Carver c = {reinterpret_cast<uintptr_t>(ws), 0};
     Regions r;
-    r.total = 0;
-    r.rows = carve(r.total, n_pairs * sizeof(PairRows));
-    r.peaks = carve(r.total, n_pairs * n_yaw * 2 * sizeof(int));
+    r.rows = c.take<PairRows>(n_pairs);
+    r.peaks = c.take<int>(n_pairs * n_yaw * 2);
+    r.total = c.o;
     return r;
 }
 
@@ -331,8 +328,6 @@ bool counts_fit(const NscGicpCloudSet *sources, const NscGicpCloudSet *targets, 
     return (double)sources->n_rows * per_row <= 2147483647.0;
 }
 
-inline int launch_status() { return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH; }
-
 }  // namespace
 
 extern "C" {
@@ -351,7 +346,7 @@ void nsc_planar_default_params(NscPlanarParams *p)
 size_t nsc_planar_align_workspace_bytes(int32_t n_pairs, int32_t n_yaw)
 {
     if (n_pairs < 0 || n_yaw < 1) return 0;
-    return regions(n_pairs, n_yaw).total;
+    return regions(nullptr, n_pairs, n_yaw).total;
 }
 
 int nsc_planar_align(const NscGicpCloudSet *sources, const NscGicpCloudSet *targets, const int64_t *source_ids,
@@ -369,10 +364,10 @@ int nsc_planar_align(const NscGicpCloudSet *sources, const NscGicpCloudSet *targ
     if (n_pairs > NSC_PLANAR_MAX_PAIRS || !counts_fit(sources, targets, params)) return NSC_EUNSUPPORTED;
     if (n_pairs == 0) return NSC_OK;
     if (!source_ids || !target_ids || !yaw_cs || !best || !scores || !counts || !init_transforms) return NSC_EINVAL;
-    const Regions r = regions(n_pairs, n_yaw);
+    const Regions r = regions(ws, n_pairs, n_yaw);
     if (!ws || ws_bytes < r.total) return NSC_EWORKSPACE;
-    PairRows *rows = reinterpret_cast<PairRows *>(static_cast<char *>(ws) + r.rows);
-    int *peaks = reinterpret_cast<int *>(static_cast<char *>(ws) + r.peaks);
+    PairRows *rows = r.rows;
+    int *peaks = r.peaks;
     int *votes = nullptr;
     if (stages) {                        // a stage output replaces the workspace region it names
         if (stages->yaw_peaks) peaks = stages->yaw_peaks;

@@ -8,6 +8,8 @@
 //   preconditioned with the Cholesky factor of each node's damped 6 x 6 diagonal block.
 //   Robust kernels (nsc_posegraph_*_robust): with s = r^T Omega r and an edge's width c, F = sum rho(s),
 //   g = sum w J^T Omega r, H = sum w J^T Omega J, w = rho'(s): iteratively reweighted, no second-order term.
+//   edge_eval() is the one place s, rho and w are formed: pg_edge_cost_kernel (the cost, and the per-edge chi2 and w a
+//   caller asks for) and pg_linearize_kernel both call it.
 //
 // Shape.  Every workgroup is one wave of 64 lanes: a graph of a few thousand poses is a few dozen waves, and one wave per
 // workgroup spreads them over as many CUs; every reduction is then a butterfly of the wave, with no LDS and no barrier.
@@ -36,6 +38,7 @@
 
 #include "../../include/nsc.h"
 #include "nsc_fill.h"
+#include "nsc_util.h"
 
 namespace {
 
@@ -46,40 +49,30 @@ struct PgState {
     int done, converged, stop_k, accept_it, iterations, accepted, rejected, pcg_total, skipped, pad;
 };
 
-struct PgParams {                            // NscPoseGraphParams as the kernels read them
-    double tol2, lambda0, lambda_min, factor, relative_cost, min_step;
-    int max_iteration, max_pcg;
-};
-
-struct Buffers {                             // the workspace
+struct Buffers {                             // the workspace: typed pointers into it, and its size
     PgState *st;
     int *row_ptr, *cursor, *tmp, *list, *ei, *ej, *free_node;
     double *hii, *hjj, *hij;                 // (21,E), (21,E), (36,E)
-    double *fe;                              // (E): r^T Omega r
+    double *fe;                              // (E): rho(r^T Omega r)
     double *ge, *ye;                         // (E,12): J^T Omega r and the edge half of H p, node i's six then node j's
     double *g, *blocks, *chol;               // (N,6), (N,21), (N,21)
     double *x, *r, *z, *p, *ap;              // (N,6)
     double *cand;                            // (N,4,4), rows 0..2 used
     double *part_e, *part_a, *part_b, *part_s;   // partials, one per workgroup of nodes: cost, p.Ap, (r.r, r.z), |delta|^2
+    size_t total;                            // bytes
 };
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // the sum of nb partials, the same bits in every lane of every wave that calls it
 __device__ __forceinline__ double finish(const double *part, int nb)
 {
     double s = 0.0;
     for (int i = threadIdx.x; i < nb; i += TB) s += part[i];
-    return wave_sum(s);
+    return nsc_wave_sum(s);
 }
 
 __device__ __forceinline__ void write_partial(double *part, double v)
 {
-    v = wave_sum(v);
+    v = nsc_wave_sum(v);
     if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 
@@ -240,6 +233,18 @@ __device__ __forceinline__ Robust robust_kernel(int kernel, const double *__rest
     return out;
 }
 
+// One edge at `poses`: its geometry, Omega as given, s = r^T Omega r, and rho(s) and w.  Every kernel that needs any of
+// them takes them from here, so the cost the accept test compares and the model it is compared with are one sum.
+__device__ __forceinline__ Robust edge_eval(const double *poses, long long i, long long j, const double *Z,
+                                            const double *information, long long e, int kernel, const double *edge_scale,
+                                            EdgeGeom &q, double W[36], double &s)
+{
+    edge_geometry(poses, i, j, Z, e, q);
+    load_information(information, e, W);
+    s = quad_form(W, q.r);
+    return robust_kernel(kernel, edge_scale, e, s);
+}
+
 // index of (r, c), r <= c, in a row-major upper triangle of a 6 x 6 matrix
 __device__ __host__ constexpr int tri(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }
 
@@ -315,40 +320,28 @@ __global__ __launch_bounds__(TB) void pg_copy_kernel(const double *__restrict__ 
 
 // ---- edges -------------------------------------------------------------------------------------------------------
 
-// rho(r^T Omega r) of every counted edge at `poses`
-__global__ __launch_bounds__(TB) void pg_cost_kernel(const double *poses, const double *__restrict__ Z,
-                                                     const double *__restrict__ information, int n_edges, Buffers b,
-                                                     int check_done, int kernel, const double *__restrict__ edge_scale)
+// One lane per edge at `poses`, each output where its pointer is given: rho(s) into fe (what the cost sums), s = r^T Omega r
+// into chi2 and w into weight (what a caller drops closures by).  A skipped edge writes nothing to fe, zeros to the others.
+__global__ __launch_bounds__(TB) void pg_edge_cost_kernel(const double *poses, const double *__restrict__ Z,
+                                                          const double *__restrict__ information, int n_edges, Buffers b,
+                                                          int check_done, int kernel, const double *__restrict__ edge_scale,
+                                                          double *fe, double *__restrict__ chi2,
+                                                          double *__restrict__ weight)
 {
     if (check_done && b.st->done) return;
     const int e = blockIdx.x * TB + threadIdx.x;
-    if (e >= n_edges || b.ei[e] < 0) return;
-    EdgeGeom q;
-    double W[36];
-    edge_geometry(poses, b.ei[e], b.ej[e], Z, e, q);
-    load_information(information, e, W);
-    b.fe[e] = robust_kernel(kernel, edge_scale, e, quad_form(W, q.r)).rho;
-}
-
-// r^T Omega r and the weight of every edge at `poses`, zeros for a skipped one: what a caller drops closures by
-__global__ __launch_bounds__(TB) void pg_edge_report_kernel(const double *__restrict__ poses, const double *__restrict__ Z,
-                                                            const double *__restrict__ information, int n_edges,
-                                                            Buffers b, int kernel, const double *__restrict__ edge_scale,
-                                                            double *__restrict__ chi2, double *__restrict__ weight)
-{
-    const int e = blockIdx.x * TB + threadIdx.x;
     if (e >= n_edges) return;
-    double s = 0.0, w = 0.0;
-    if (b.ei[e] >= 0) {
+    const bool counted = b.ei[e] >= 0;
+    double s = 0.0;
+    Robust rb{0.0, 0.0};
+    if (counted) {
         EdgeGeom q;
         double W[36];
-        edge_geometry(poses, b.ei[e], b.ej[e], Z, e, q);
-        load_information(information, e, W);
-        s = quad_form(W, q.r);
-        w = robust_kernel(kernel, edge_scale, e, s).w;
+        rb = edge_eval(poses, b.ei[e], b.ej[e], Z, information, e, kernel, edge_scale, q, W, s);
     }
+    if (fe && counted) fe[e] = rb.rho;
     if (chi2) chi2[e] = s;
-    if (weight) weight[e] = w;
+    if (weight) weight[e] = rb.w;
 }
 
 // F: every node sums the edges it is the first end of, in list order; one partial per workgroup.  The sum walks the
@@ -385,9 +378,11 @@ __global__ __launch_bounds__(TB) void pg_linearize_kernel(const double *poses, c
         return;
     }
     EdgeGeom q;
-    edge_geometry(poses, b.ei[e], b.ej[e], Z, e, q);
+    double W[36], chi2;
+    const double w = edge_eval(poses, b.ei[e], b.ej[e], Z, information, e, kernel, edge_scale, q, W, chi2).w;
     if (residuals)
         for (int k = 0; k < 6; ++k) residuals[6 * (long long)e + k] = q.r[k];
+    if (weights) weights[e] = w;
 
     // J_j = blockdiag(Jr^-1, R_D);  J_i = -[[Jr^-1 R_A^T, 0], [-R_Z^T [t_A]x, R_Z^T]]  (R_D R_A^T = R_Z^T)
     double Ji[36], Jj[36], Jr[9], K[9];
@@ -407,18 +402,8 @@ __global__ __launch_bounds__(TB) void pg_linearize_kernel(const double *poses, c
             Ji[6 * (r + 3) + c + 3] = -q.RZ[3 * c + r];
         }
 
-    // s = r^T Omega r with Omega as given (the sum of pg_cost_kernel, term for term); then Omega <- w Omega
-    double W[36], Wi[36], Wj[36], wr[6], chi2 = 0.0;
-    load_information(information, e, W);
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-        double s = 0.0;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) s += W[6 * a + c] * q.r[c];
-        chi2 += q.r[a] * s;
-    }
-    const double w = robust_kernel(kernel, edge_scale, e, chi2).w;
-    if (weights) weights[e] = w;
+    // Omega <- w Omega
+    double Wi[36], Wj[36], wr[6];
 #pragma unroll
     for (int k = 0; k < 36; ++k) W[k] *= w;
 #pragma unroll
@@ -756,7 +741,7 @@ __global__ __launch_bounds__(TB) void pg_init_kernel(int nb_n, Buffers b, double
 }
 
 // one wave: accept or reject the candidate, move lambda, test the stopping rules
-__global__ __launch_bounds__(TB) void pg_accept_kernel(int nb_n, Buffers b, PgParams prm, int it,
+__global__ __launch_bounds__(TB) void pg_accept_kernel(int nb_n, Buffers b, NscPoseGraphParams prm, int it,
                                                        double *__restrict__ history)
 {
     if (b.st->done) return;
@@ -772,10 +757,10 @@ __global__ __launch_bounds__(TB) void pg_accept_kernel(int nb_n, Buffers b, PgPa
         st->accept_it = it;
         stop = (f - fc) < prm.relative_cost * f;
         st->cost = fc;
-        st->lambda = fmax(st->lambda / prm.factor, prm.lambda_min);
+        st->lambda = fmax(st->lambda / prm.lambda_factor, prm.lambda_min);
     } else {
         st->rejected += 1;
-        st->lambda = st->lambda * prm.factor;
+        st->lambda = st->lambda * prm.lambda_factor;
     }
     history[it + 1] = st->cost;
     if (stop || step < prm.min_step) {
@@ -800,16 +785,16 @@ __global__ __launch_bounds__(TB) void pg_finalize_kernel(Buffers b, int max_iter
     const PgState *st = b.st;
     for (int k = st->iterations + 1 + threadIdx.x; k <= max_iteration; k += TB) history[k] = st->cost;
     if (threadIdx.x != 0) return;
-    stats[0] = st->iterations;
-    stats[1] = st->accepted;
-    stats[2] = st->rejected;
-    stats[3] = st->pcg_total;
-    stats[4] = st->cost0;
-    stats[5] = st->cost;
-    stats[6] = st->lambda;
-    stats[7] = st->skipped;
-    stats[8] = st->converged;
-    stats[9] = st->step;
+    stats[NSC_POSEGRAPH_STAT_ITERATIONS] = st->iterations;
+    stats[NSC_POSEGRAPH_STAT_ACCEPTED] = st->accepted;
+    stats[NSC_POSEGRAPH_STAT_REJECTED] = st->rejected;
+    stats[NSC_POSEGRAPH_STAT_PCG_ITERATIONS] = st->pcg_total;
+    stats[NSC_POSEGRAPH_STAT_INITIAL_COST] = st->cost0;
+    stats[NSC_POSEGRAPH_STAT_FINAL_COST] = st->cost;
+    stats[NSC_POSEGRAPH_STAT_LAMBDA] = st->lambda;
+    stats[NSC_POSEGRAPH_STAT_SKIPPED] = st->skipped;
+    stats[NSC_POSEGRAPH_STAT_CONVERGED] = st->converged;
+    stats[NSC_POSEGRAPH_STAT_STEP] = st->step;
 }
 
 // one wave: the outputs of nsc_posegraph_linearize that are scalars
@@ -825,82 +810,42 @@ __global__ __launch_bounds__(TB) void pg_linearize_out_kernel(int nb_n, Buffers 
 
 // ---- host ----------------------------------------------------------------------------------------------------------
 
-inline size_t carve(size_t &o, size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; }
-
 inline int blocks_of(long long n) { return (int)((n + TB - 1) / TB); }
 
-struct Layout {
-    size_t st, row_ptr, cursor, tmp, list, ei, ej, free_node, hii, hjj, hij, fe, ge, ye, g, blocks, chol, x, r, z, p, ap, cand,
-        part_e, part_a, part_b, part_s, total;
-};
-
-Layout layout(size_t N, size_t E)
+// the one place that knows the workspace's layout; ws = nullptr: the size only
+Buffers buffers(void *ws, size_t N, size_t E)
 {
-    Layout l;
-    size_t o = 0;
-    const size_t d = sizeof(double), i = sizeof(int), nbn = (N + TB - 1) / TB;
-    l.st = carve(o, sizeof(PgState));
-    l.row_ptr = carve(o, (N + 1) * i);
-    l.cursor = carve(o, N * i);
-    l.tmp = carve(o, 2 * E * i);
-    l.list = carve(o, 2 * E * i);
-    l.ei = carve(o, E * i);
-    l.ej = carve(o, E * i);
-    l.free_node = carve(o, N * i);
-    l.hii = carve(o, 21 * E * d);
-    l.hjj = carve(o, 21 * E * d);
-    l.hij = carve(o, 36 * E * d);
-    l.fe = carve(o, E * d);
-    l.ge = carve(o, 12 * E * d);
-    l.ye = carve(o, 12 * E * d);
-    l.g = carve(o, 6 * N * d);
-    l.blocks = carve(o, 21 * N * d);
-    l.chol = carve(o, 21 * N * d);
-    l.x = carve(o, 6 * N * d);
-    l.r = carve(o, 6 * N * d);
-    l.z = carve(o, 6 * N * d);
-    l.p = carve(o, 6 * N * d);
-    l.ap = carve(o, 6 * N * d);
-    l.cand = carve(o, 16 * N * d);
-    l.part_e = carve(o, nbn * d);
-    l.part_a = carve(o, nbn * d);
-    l.part_b = carve(o, 2 * nbn * d);
-    l.part_s = carve(o, nbn * d);
-    l.total = o;
-    return l;
-}
-
-Buffers buffers(void *ws, const Layout &l)
-{
-    char *w = static_cast<char *>(ws);
+    Carver c = {reinterpret_cast<uintptr_t>(ws), 0};
     Buffers b;
-    b.st = reinterpret_cast<PgState *>(w + l.st);
-    b.row_ptr = reinterpret_cast<int *>(w + l.row_ptr);
-    b.cursor = reinterpret_cast<int *>(w + l.cursor);
-    b.tmp = reinterpret_cast<int *>(w + l.tmp);
-    b.list = reinterpret_cast<int *>(w + l.list);
-    b.ei = reinterpret_cast<int *>(w + l.ei);
-    b.ej = reinterpret_cast<int *>(w + l.ej);
-    b.free_node = reinterpret_cast<int *>(w + l.free_node);
-    b.hii = reinterpret_cast<double *>(w + l.hii);
-    b.hjj = reinterpret_cast<double *>(w + l.hjj);
-    b.hij = reinterpret_cast<double *>(w + l.hij);
-    b.fe = reinterpret_cast<double *>(w + l.fe);
-    b.ge = reinterpret_cast<double *>(w + l.ge);
-    b.ye = reinterpret_cast<double *>(w + l.ye);
-    b.g = reinterpret_cast<double *>(w + l.g);
-    b.blocks = reinterpret_cast<double *>(w + l.blocks);
-    b.chol = reinterpret_cast<double *>(w + l.chol);
-    b.x = reinterpret_cast<double *>(w + l.x);
-    b.r = reinterpret_cast<double *>(w + l.r);
-    b.z = reinterpret_cast<double *>(w + l.z);
-    b.p = reinterpret_cast<double *>(w + l.p);
-    b.ap = reinterpret_cast<double *>(w + l.ap);
-    b.cand = reinterpret_cast<double *>(w + l.cand);
-    b.part_e = reinterpret_cast<double *>(w + l.part_e);
-    b.part_a = reinterpret_cast<double *>(w + l.part_a);
-    b.part_b = reinterpret_cast<double *>(w + l.part_b);
-    b.part_s = reinterpret_cast<double *>(w + l.part_s);
+    const size_t nbn = (N + TB - 1) / TB;
+    b.st = c.take<PgState>(1);
+    b.row_ptr = c.take<int>(N + 1);
+    b.cursor = c.take<int>(N);
+    b.tmp = c.take<int>(2 * E);
+    b.list = c.take<int>(2 * E);
+    b.ei = c.take<int>(E);
+    b.ej = c.take<int>(E);
+    b.free_node = c.take<int>(N);
+    b.hii = c.take<double>(21 * E);
+    b.hjj = c.take<double>(21 * E);
+    b.hij = c.take<double>(36 * E);
+    b.fe = c.take<double>(E);
+    b.ge = c.take<double>(12 * E);
+    b.ye = c.take<double>(12 * E);
+    b.g = c.take<double>(6 * N);
+    b.blocks = c.take<double>(21 * N);
+    b.chol = c.take<double>(21 * N);
+    b.x = c.take<double>(6 * N);
+    b.r = c.take<double>(6 * N);
+    b.z = c.take<double>(6 * N);
+    b.p = c.take<double>(6 * N);
+    b.ap = c.take<double>(6 * N);
+    b.cand = c.take<double>(16 * N);
+    b.part_e = c.take<double>(nbn);
+    b.part_a = c.take<double>(nbn);
+    b.part_b = c.take<double>(2 * nbn);
+    b.part_s = c.take<double>(nbn);
+    b.total = c.o;
     return b;
 }
 
@@ -915,10 +860,10 @@ bool params_ok(const NscPoseGraphParams *p)
 bool kernel_ok(int32_t k) { return k >= NSC_POSEGRAPH_KERNEL_NONE && k <= NSC_POSEGRAPH_KERNEL_GEMAN_MCCLURE; }
 
 // state and degrees zeroed, then the lists: 5 launches (2 when there are no edges)
-void build_lists(hipStream_t s, const int64_t *edge_ij, int N, int E, const Layout &l, const Buffers &b)
+void build_lists(hipStream_t s, const int64_t *edge_ij, int N, int E, const Buffers &b)
 {
-    // the state and the degree array are neighbours in the workspace: one fill
-    nsc_fill_u32(s, b.st, 0u, (long long)((l.cursor - l.st) / 4));
+    // one fill over what lies from the state up to the cursors: the state and the degree array
+    nsc_fill_u32(s, b.st, 0u, (long long)((reinterpret_cast<char *>(b.cursor) - reinterpret_cast<char *>(b.st)) / 4));
     if (E > 0) {
         hipLaunchKernelGGL(pg_count_kernel, dim3(blocks_of(E)), dim3(TB), 0, s,
                            reinterpret_cast<const long long *>(edge_ij), E, N, b);
@@ -929,8 +874,6 @@ void build_lists(hipStream_t s, const int64_t *edge_ij, int N, int E, const Layo
         if (N > 0) hipLaunchKernelGGL(pg_sort_kernel, dim3(N), dim3(TB), 0, s, b);
     }
 }
-
-inline int launch_status() { return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH; }
 
 }  // namespace
 
@@ -953,7 +896,7 @@ size_t nsc_posegraph_workspace_bytes(int32_t n_poses, int32_t n_edges, const Nsc
 {
     (void)params;                            // the layout holds one outer and one inner iteration whatever the caps
     if (n_poses < 0 || n_edges < 0) return 0;
-    return layout(n_poses, n_edges).total;
+    return buffers(nullptr, n_poses, n_edges).total;
 }
 
 int nsc_posegraph_linearize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
@@ -975,15 +918,14 @@ int nsc_posegraph_linearize_robust(const double *poses, int32_t n_poses, const i
     if (!cost || !skipped) return NSC_EINVAL;
     if (n_poses > 0 && (!poses || !gradient || !blocks)) return NSC_EINVAL;
     if (n_edges > 0 && (!edge_ij || !measurements || !information || !residuals)) return NSC_EINVAL;
-    const Layout l = layout(n_poses, n_edges);
-    if (!ws || ws_bytes < l.total) return NSC_EWORKSPACE;
-    const Buffers b = buffers(ws, l);
+    const Buffers b = buffers(ws, n_poses, n_edges);
+    if (!ws || ws_bytes < b.total) return NSC_EWORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int N = n_poses, E = n_edges;
-    build_lists(s, edge_ij, N, E, l, b);
+    build_lists(s, edge_ij, N, E, b);
     if (E > 0) {
-        hipLaunchKernelGGL(pg_cost_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b, 0,
-                           kernel, edge_scale);
+        hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b,
+                           0, kernel, edge_scale, b.fe, nullptr, nullptr);
         hipLaunchKernelGGL(pg_linearize_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b,
                            residuals, 0, kernel, edge_scale, weights);
     }
@@ -1021,21 +963,19 @@ int nsc_posegraph_optimize_robust(const double *poses, int32_t n_poses, const in
     if (n_edges > 0 && (!edge_ij || !measurements || !information)) return NSC_EINVAL;
     if ((long long)params->max_iteration * (4LL * params->max_pcg_iterations + 8) > NSC_POSEGRAPH_MAX_LAUNCHES)
         return NSC_EUNSUPPORTED;
-    const Layout l = layout(n_poses, n_edges);
-    if (!ws || ws_bytes < l.total) return NSC_EWORKSPACE;
-    const Buffers b = buffers(ws, l);
+    const Buffers b = buffers(ws, n_poses, n_edges);
+    if (!ws || ws_bytes < b.total) return NSC_EWORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int N = n_poses, E = n_edges, gn = blocks_of(N), ge = blocks_of(E);
-    const PgParams prm{params->pcg_tolerance * params->pcg_tolerance, params->lambda0, params->lambda_min,
-                       params->lambda_factor, params->relative_cost, params->min_step, params->max_iteration,
-                       params->max_pcg_iterations};
+    const NscPoseGraphParams prm = *params;
+    const double tol2 = prm.pcg_tolerance * prm.pcg_tolerance;
 
-    build_lists(s, edge_ij, N, E, l, b);
+    build_lists(s, edge_ij, N, E, b);
     if (N > 0 && poses_out != poses)
         hipLaunchKernelGGL(pg_copy_kernel, dim3(blocks_of(16LL * N)), dim3(TB), 0, s, poses, poses_out, 16LL * N);
     if (E > 0)
-        hipLaunchKernelGGL(pg_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0, kernel,
-                           edge_scale);
+        hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0,
+                           kernel, edge_scale, b.fe, nullptr, nullptr);
     if (N > 0) hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 0);
     hipLaunchKernelGGL(pg_init_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm.lambda0, cost_history);
 
@@ -1045,24 +985,24 @@ int nsc_posegraph_optimize_robust(const double *poses, int32_t n_poses, const in
                                nullptr, 1, kernel, edge_scale, nullptr);
         hipLaunchKernelGGL(pg_assemble_kernel, dim3(gn), dim3(TB), 0, s, N, E, fixed, b, b.g, b.blocks, 1);
         hipLaunchKernelGGL(pg_pcg_begin_kernel, dim3(1), dim3(TB), 0, s, gn, b);
-        for (int k = 0; k < prm.max_pcg && E > 0; ++k) {
+        for (int k = 0; k < prm.max_pcg_iterations && E > 0; ++k) {
             hipLaunchKernelGGL(pg_edge_matvec_kernel, dim3(ge), dim3(TB), 0, s, E, b, k);
             hipLaunchKernelGGL(pg_node_matvec_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
             hipLaunchKernelGGL(pg_pcg_step_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
-            hipLaunchKernelGGL(pg_pcg_direction_kernel, dim3(gn), dim3(TB), 0, s, N, b, k, prm.tol2);
+            hipLaunchKernelGGL(pg_pcg_direction_kernel, dim3(gn), dim3(TB), 0, s, N, b, k, tol2);
         }
         hipLaunchKernelGGL(pg_update_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it, step0);
         if (E > 0)
-            hipLaunchKernelGGL(pg_cost_kernel, dim3(ge), dim3(TB), 0, s, b.cand, measurements, information, E, b, 1,
-                               kernel, edge_scale);
+            hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, b.cand, measurements, information, E, b, 1,
+                               kernel, edge_scale, b.fe, nullptr, nullptr);
         hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 1);
         hipLaunchKernelGGL(pg_accept_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm, it, cost_history);
         hipLaunchKernelGGL(pg_commit_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it);
     }
     hipLaunchKernelGGL(pg_finalize_kernel, dim3(1), dim3(TB), 0, s, b, prm.max_iteration, stats, cost_history);
     if (E > 0 && (edge_chi2 || edge_weight))
-        hipLaunchKernelGGL(pg_edge_report_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b,
-                           kernel, edge_scale, edge_chi2, edge_weight);
+        hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0,
+                           kernel, edge_scale, nullptr, edge_chi2, edge_weight);
     return launch_status();
 }
 

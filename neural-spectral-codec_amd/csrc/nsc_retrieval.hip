@@ -18,6 +18,7 @@
 
 #include "../../include/nsc.h"
 #include "nsc_w1_rows.h"
+#include "nsc_util.h"
 
 namespace {
 
@@ -504,7 +505,7 @@ int nsc_w1_cdf(const float *hists, int32_t n, int32_t D, float eps, int32_t divi
     case 12: hipLaunchKernelGGL(w1_cdf_kernel<12>, grid, block, 0, st, hists, n, D, eps, divide_plain, cdf); break;
     default: hipLaunchKernelGGL(w1_cdf_kernel<16>, grid, block, 0, st, hists, n, D, eps, divide_plain, cdf); break;
     }
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_w1_distances(const float *db, int32_t N, int32_t D, float eps, const float *q_cdf, int32_t Q,
@@ -521,7 +522,7 @@ int nsc_w1_distances(const float *db, int32_t N, int32_t D, float eps, const flo
     case 12: hipLaunchKernelGGL(w1_dist_kernel<12>, grid, block, 0, st, db, N, D, eps, q_cdf, Q, db_pos, q_pos, min_dist, dist); break;
     default: hipLaunchKernelGGL(w1_dist_kernel<16>, grid, block, 0, st, db, N, D, eps, q_cdf, Q, db_pos, q_pos, min_dist, dist); break;
     }
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_w1_distances_cdf(const float *db_cdf, int32_t N, int32_t D, const float *q_cdf, int32_t Q,
@@ -537,7 +538,7 @@ int nsc_w1_distances_cdf(const float *db_cdf, int32_t N, int32_t D, const float 
         if (Q == 1) hipLaunchKernelGGL(w1_stream_kernel<1>, grid, block, 0, st, db_cdf, N, D, q_cdf, Q, db_pos, q_pos, min_dist, dist);
         else if (Q == 2) hipLaunchKernelGGL(w1_stream_kernel<2>, grid, block, 0, st, db_cdf, N, D, q_cdf, Q, db_pos, q_pos, min_dist, dist);
         else hipLaunchKernelGGL(w1_stream_kernel<4>, grid, block, 0, st, db_cdf, N, D, q_cdf, Q, db_pos, q_pos, min_dist, dist);
-        return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+        return launch_status();
     }
     return launch_w1_tile(st, F32Rows{db_cdf, q_cdf}, N, D, Q, db_pos, q_pos, min_dist, dist);
 }
@@ -550,7 +551,7 @@ int nsc_revisit_queries(const double *positions, int32_t n, int32_t skip_frames,
     if (!positions || !first_revisit) return NSC_EINVAL;
     hipLaunchKernelGGL(revisit_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream_), positions, n,
                        skip_frames, distance_threshold, first_revisit);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_pairwise_l2(const float *emb, const int32_t *query_idx, int32_t Q, int32_t n, int32_t D, int32_t skip_frames,
@@ -562,7 +563,7 @@ int nsc_pairwise_l2(const float *emb, const int32_t *query_idx, int32_t Q, int32
     if (Q > 65535) return NSC_EUNSUPPORTED;              // grid.y; callers chunk the queries
     hipLaunchKernelGGL(pair_l2_kernel, dim3((n + 63) / 64, Q), dim3(256), 0, static_cast<hipStream_t>(stream_), emb, query_idx,
                        n, D, skip_frames, dist);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_recall_rank(const double *positions, const int32_t *query_idx, const int64_t *topk_idx, int32_t Q, int32_t k,
@@ -573,7 +574,7 @@ int nsc_recall_rank(const double *positions, const int32_t *query_idx, const int
     if (!positions || !query_idx || !topk_idx || !rank) return NSC_EINVAL;
     hipLaunchKernelGGL(recall_rank_kernel, dim3((Q + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream_), positions,
                        query_idx, reinterpret_cast<const long long *>(topk_idx), Q, k, distance_threshold, rank);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 size_t nsc_mine_workspace_bytes(int32_t n, int32_t strategy)
@@ -603,7 +604,7 @@ int nsc_mine_triplets_ws(const double *positions, const float *cdf, int32_t n, i
     p.strategy = mp->strategy; p.per_anchor = mp->triplets_per_anchor; p.seed = mp->seed;
     hipLaunchKernelGGL(mine_kernel, dim3((n + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream_), positions, cdf, n, D,
                        p, out_pos, out_neg, counts, static_cast<float *>(ws));
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 size_t nsc_topk_workspace_bytes(int32_t Q, int32_t N, int32_t k)
@@ -628,7 +629,7 @@ int nsc_topk_smallest(const float *dist, int32_t Q, int32_t N, int32_t k, int64_
     hipLaunchKernelGGL(topk_stage1_kernel, dim3(chunks, Q), dim3(256), 0, st, dist, N, k, cv, ci);
     hipLaunchKernelGGL(topk_stage2_kernel, dim3(Q), dim3(256), 0, st, cv, ci, chunks * k, k,
                        reinterpret_cast<long long *>(idx), val);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

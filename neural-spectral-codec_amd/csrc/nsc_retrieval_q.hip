@@ -20,6 +20,7 @@
 
 #include "../../include/nsc.h"
 #include "nsc_w1_rows.h"
+#include "nsc_util.h"
 
 namespace {
 
@@ -195,7 +196,7 @@ int nsc_w1q_cdf(const uint16_t *quantized, int32_t n, int32_t D, uint16_t *cdf, 
     if (!quantized || !cdf || !canonical) return NSC_EINVAL;
     hipLaunchKernelGGL(w1q_cdf_kernel, dim3((n + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream_), quantized, n, D,
                        cdf, canonical);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 int nsc_w1q_distances(const uint16_t *db_cdf, const uint8_t *db_canonical, int32_t N, int32_t D,
@@ -220,7 +221,7 @@ int nsc_w1q_distances(const uint16_t *db_cdf, const uint8_t *db_canonical, int32
         return launch_w1_tile(st, U16Rows{db_cdf, db_canonical, q_cdf, q_canonical}, N, D, Q, db_pos, q_pos, min_dist, dist);
     }
 #undef W1Q_ARGS
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/nsc.h"
+#include "nsc_util.h"
 
 namespace {
 
@@ -186,7 +187,7 @@ int launch_w1_tile(hipStream_t st, Rows rows, int N, int D, int Q, const float *
     if (nq == 1) hipLaunchKernelGGL((w1_tile_kernel<Rows, 1>), grid, block, 0, st, rows, N, D, Q, db_pos, q_pos, min_dist, dist);
     else if (nq == 2) hipLaunchKernelGGL((w1_tile_kernel<Rows, 2>), grid, block, 0, st, rows, N, D, Q, db_pos, q_pos, min_dist, dist);
     else hipLaunchKernelGGL((w1_tile_kernel<Rows, 4>), grid, block, 0, st, rows, N, D, Q, db_pos, q_pos, min_dist, dist);
-    return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH;
+    return launch_status();
 }
 
 }  // namespace

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/nsc.h"
+#include "nsc_util.h"
 
 namespace {
 
@@ -44,12 +45,6 @@ constexpr int GUARD = NSC_YAW_GUARD_BINS;
 // hipLaunchKernel takes at most 2^32 - 1 threads per grid
 static_assert((long long)NSC_YAW_MAX_PAIRS * YAW_THREADS < (1LL << 32), "NSC_YAW_MAX_PAIRS must fit one launch");
 static_assert(SHIFT_WAVES * 128 >= COLS && COLS % 2 == 0 && CHUNK % ROW_SPLIT == 0, "layout");
-
-__device__ inline double wave_sum(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(YAW_THREADS) void yaw_align_kernel(const float *__restrict__ images_q, long long n_q,
                                                                const float *__restrict__ images_c, long long n_c,
@@ -94,8 +89,8 @@ __global__ __launch_bounds__(YAW_THREADS) void yaw_align_kernel(const float *__r
                 sq += (double)qr[r * COLS + k];
                 sc += (double)cr[r * COLS + k];
             }
-            sq = wave_sum(sq);
-            sc = wave_sum(sc);
+            sq = nsc_wave_sum(sq);
+            sc = nsc_wave_sum(sc);
             if (lane == 0) {
                 mean_q[r] = sq / (double)COLS;
                 mean_c[r] = sc / (double)COLS;
@@ -183,8 +178,6 @@ __global__ __launch_bounds__(YAW_THREADS) void yaw_align_kernel(const float *__r
         scores_out[2 * pair + 1] = runner;
     }
 }
-
-inline int launch_status() { return hipGetLastError() == hipSuccess ? NSC_OK : NSC_ELAUNCH; }
 
 }  // namespace
 

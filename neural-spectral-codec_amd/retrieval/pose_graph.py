@@ -241,11 +241,14 @@ class PoseGraphOptimizer:
         synchronises."""
         out = self.optimize_device(poses, edge_ij, measurements, information, fixed, robust_scale=robust_scale)
         s = out["stats"].cpu().numpy()
-        its = int(s[0])
+        L = _lib
+        its = int(s[L.POSEGRAPH_STAT_ITERATIONS])
         X = out["poses"] if isinstance(poses, torch.Tensor) else out["poses"].cpu().numpy()
-        res = dict(poses=X, cost0=float(s[4]), cost=float(s[5]), iterations=its, accepted=int(s[1]), rejected=int(s[2]),
-                   pcg_iterations=int(s[3]), converged=bool(s[8]), cost_history=out["cost_history"].cpu().numpy()[:its + 1],
-                   skipped=int(s[7]), step=float(s[9]), **{"lambda": float(s[6])})
+        res = dict(poses=X, cost0=float(s[L.POSEGRAPH_STAT_INITIAL_COST]), cost=float(s[L.POSEGRAPH_STAT_FINAL_COST]),
+                   iterations=its, accepted=int(s[L.POSEGRAPH_STAT_ACCEPTED]), rejected=int(s[L.POSEGRAPH_STAT_REJECTED]),
+                   pcg_iterations=int(s[L.POSEGRAPH_STAT_PCG_ITERATIONS]), converged=bool(s[L.POSEGRAPH_STAT_CONVERGED]),
+                   cost_history=out["cost_history"].cpu().numpy()[:its + 1], skipped=int(s[L.POSEGRAPH_STAT_SKIPPED]),
+                   step=float(s[L.POSEGRAPH_STAT_STEP]), **{"lambda": float(s[L.POSEGRAPH_STAT_LAMBDA])})
         if robust_scale is not None:
             res.update(chi2=out["chi2"].cpu().numpy(), weights=out["weights"].cpu().numpy())
         return res

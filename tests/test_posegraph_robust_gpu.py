@@ -357,3 +357,39 @@ def test_sizes(name):
     else:
         assert out["accepted"] >= 1
         close(out["weights"], R.edge_weights(out["poses"], e, Z, Om, R.CAUCHY, scale)[1], (name, "final weights"))
+
+
+# ---- 8. one evaluation of an edge --------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_one_edge_evaluation(kernel):
+    """Every kernel takes an edge's s = r^T Omega r, rho and w from one device function, so what linearize and optimize
+    say about the same edges at the same poses is the same bits: the weights, and the cost in the three places it comes
+    out.  65 poses and 106 edges: two workgroups of edges and of nodes, two skipped edges among the counted ones, a width
+    on every second edge."""
+    X, e, Z, Om = graph(65, 40, 8)
+    n = len(X)
+    at = np.array([20, 70])
+    e = np.insert(e, at, np.array([[7, 7], [3, n]], np.int64), axis=0)
+    Z = np.insert(Z, at, np.tile(np.eye(4) * np.nan, (2, 1, 1)), axis=0)
+    Om = np.insert(Om, at, np.tile(np.eye(6) * np.nan, (2, 1, 1)), axis=0)
+    keep = P.valid_edges(n, e)
+    assert keep.sum() == len(e) - 2 and len(e) > 64 and n > 64
+    widths = np.arange(len(e)) % 2 == 0
+    chi2 = R.edge_chi2(X, e, Z, Om)
+    scale = np.where(widths, np.sqrt(np.median(chi2[keep & widths])), 0.0)     # half the edges with a width in Huber's tail
+    ref = R.edge_weights(X, e, Z, Om, R.KERNELS[kernel], scale)[1]
+    assert (ref[keep] < 1.0).sum() >= 10 and (ref[keep] == 1.0).sum() >= 10
+
+    lin = host(optimizer(kernel=kernel).linearize(X, e, Z, Om, robust_scale=scale))
+    out = host(optimizer(kernel=kernel, max_iteration=0).optimize_device(X, e, Z, Om, first_fixed(n), robust_scale=scale))
+    assert lin["skipped"][0] == out["stats"][7] == 2
+    print(kernel, "cost", lin["cost"][0], out["stats"][4], out["cost_history"][0], "weights < 1:",
+          (lin["weights"] < 1.0).sum(), "differing weights:", (lin["weights"] != out["weights"]).sum())
+    assert lin["weights"].tobytes() == out["weights"].tobytes()
+    assert lin["cost"][:1].tobytes() == out["stats"][4:5].tobytes() == out["cost_history"][:1].tobytes()
+    r = lin["residuals"]
+    want = np.array([r[k] @ P.sym_upper(Om[k]) @ r[k] if keep[k] else 0.0 for k in range(len(e))])
+    close(out["chi2"], want, "chi2")
+    assert not out["chi2"][~keep].any() and not out["weights"][~keep].any()
+    close(out["weights"], ref, "weights")

@@ -23,7 +23,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spl
 import torch
 import posegraph_restatement as P
-from neural_spectral_codec_amd import synth
+from neural_spectral_codec_amd import _lib as L, synth
 from neural_spectral_codec_amd.retrieval import PoseGraphOptimizer
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
@@ -82,10 +82,12 @@ def device_times(fn, n):
 out = call()
 torch.cuda.synchronize()
 s = out["stats"].cpu().numpy()
-its = int(s[0])
+its, inner = int(s[L.POSEGRAPH_STAT_ITERATIONS]), int(s[L.POSEGRAPH_STAT_PCG_ITERATIONS])
 launches = 5 + 1 + 3 + max_it * (8 + 4 * max_pcg) + 1 + (kernel is not None)
-print(f"optimize: {its} outer iterations ({int(s[1])} accepted, {int(s[2])} rejected), {int(s[3])} inner iterations "
-      f"({s[3] / max(its, 1):.1f} per outer step), cost {s[4]:.6g} -> {s[5]:.6g}, converged {bool(s[8])}, "
+print(f"optimize: {its} outer iterations ({int(s[L.POSEGRAPH_STAT_ACCEPTED])} accepted, "
+      f"{int(s[L.POSEGRAPH_STAT_REJECTED])} rejected), {inner} inner iterations ({inner / max(its, 1):.1f} per outer "
+      f"step), cost {s[L.POSEGRAPH_STAT_INITIAL_COST]:.6g} -> {s[L.POSEGRAPH_STAT_FINAL_COST]:.6g}, "
+      f"converged {bool(s[L.POSEGRAPH_STAT_CONVERGED])}, "
       f"trajectory error {P.trajectory_error(out['poses'].cpu().numpy(), truth):.3f} m; {launches} launches per call")
 if kernel is not None:
     w = out["weights"].cpu().numpy()[len(oe):]
