@@ -668,9 +668,31 @@ int    nsc_planar_align(const NscGicpCloudSet *sources, const NscGicpCloudSet *t
  * at most NSC_POSEGRAPH_MAX_LAUNCHES in the loop (else NSC_EUNSUPPORTED), + 1 at the end when nsc_posegraph_optimize_robust
  * is given edge_chi2 or edge_weight and n_edges > 0.  Kernels of a finished phase return at once.
  * No host synchronisation, no memset or memcpy nodes: the call can be captured.
+ *
+ * Two-level preconditioner (nsc_posegraph_optimize_coarse; restated, sparse, in tests/posegraph_coarse_restatement.py).
+ * Block-Jacobi PCG needs of the order of n_poses inner iterations for the long wavelengths of a trajectory, which are
+ * what a closure corrects.  With coarse_block = L >= 2, pose k belongs to aggregate a(k) = k / L; there are
+ * n_a = ceil(n_poses / L) aggregates, the last one possibly ragged.
+ *   Prolongation P (6 n_poses, 6 n_a): the block of a free pose k in column a(k) is Ad(X_k^-1 X_ref), X_ref the first
+ *     pose of the aggregate at the linearisation point, fixed or not: a coarse 6-vector is a rigid motion of the whole
+ *     aggregate in the frame of X_ref.  Rows of poses that are not free (fixed, without a counted edge, or with a
+ *     damped diagonal block that is not positive definite) are zero.
+ *   A = H + lambda diag H on the free poses, with the robust weights as assembled;  A_c = P^T A P, and the identity
+ *     block for an aggregate without a free pose.
+ *   Preconditioner  M^-1 r = B^-1 r + P A_c^-1 P^T r,  B^-1 the per-node Cholesky solve above: additive, symmetric
+ *     positive definite, so PCG, its stopping rule and the count of inner iterations are those above.
+ *   A_c is factored by Cholesky and inverted explicitly once per outer step.  A pivot that is not positive and finite
+ *     leaves that outer step with B^-1 alone; coarse_stats counts such steps.
+ *   Aggregation by index assumes that consecutive indices are neighbours in the graph, which holds for a trajectory.
+ *     On any other graph M^-1 is still symmetric positive definite, only less useful.
+ *   At most NSC_POSEGRAPH_MAX_AGGREGATES aggregates (A_c is at most 768 x 768), else NSC_EUNSUPPORTED.
+ *   Launches: 5 (lists) + 1 (copy, unless aliased) + 3 + max_iteration (14 + 5 max_pcg_iterations) + 1, the loop's share
+ *     at most NSC_POSEGRAPH_MAX_LAUNCHES, + 1 for edge_chi2 or edge_weight: a sequence that depends on the parameters,
+ *     n_poses > 0, n_edges > 0, the aliasing and coarse_block alone.  The determinism and capture rules above hold.
  * ------------------------------------------------------------------------------------------ */
 #define NSC_POSEGRAPH_MAX_EDGES    1073741823   /* list entries are 2 edge + side in int32 */
 #define NSC_POSEGRAPH_MAX_LAUNCHES 1000000
+#define NSC_POSEGRAPH_MAX_AGGREGATES 128        /* A_c is (6 x this)^2 float64: 768 x 768 */
 #define NSC_POSEGRAPH_STATS        10
 
 #define NSC_POSEGRAPH_KERNEL_NONE           0
@@ -740,6 +762,20 @@ int    nsc_posegraph_optimize_robust(const double *poses, int32_t n_poses, const
                                      double *stats, double *cost_history, double *step0, void *ws, size_t ws_bytes,
                                      void *stream, int32_t kernel, const double *edge_scale, double *edge_chi2,
                                      double *edge_weight);
+
+/* Bytes of workspace for nsc_posegraph_optimize_coarse.  coarse_block = 0: nsc_posegraph_workspace_bytes.  0 for a
+ * negative size, for coarse_block < 0 or == 1, and for more than NSC_POSEGRAPH_MAX_AGGREGATES aggregates. */
+size_t nsc_posegraph_coarse_workspace_bytes(int32_t n_poses, int32_t n_edges, int32_t coarse_block);
+/* nsc_posegraph_optimize_robust with the two-level preconditioner above.  coarse_block = 0 is the robust call, launch for
+ * launch and bit for bit (then the workspace of nsc_posegraph_workspace_bytes suffices); 1 or a negative value is
+ * NSC_EINVAL; more than NSC_POSEGRAPH_MAX_AGGREGATES aggregates is NSC_EUNSUPPORTED.  coarse_stats (2) float64, nullable:
+ * [aggregates, outer steps whose coarse factor failed and that ran with the block-Jacobi preconditioner alone]. */
+int    nsc_posegraph_optimize_coarse(const double *poses, int32_t n_poses, const int64_t *edge_ij,
+                                     const double *measurements, const double *information, int32_t n_edges,
+                                     const uint8_t *fixed, const NscPoseGraphParams *params, double *poses_out,
+                                     double *stats, double *cost_history, double *step0, void *ws, size_t ws_bytes,
+                                     void *stream, int32_t kernel, const double *edge_scale, double *edge_chi2,
+                                     double *edge_weight, int32_t coarse_block, double *coarse_stats);
 
 #ifdef __cplusplus
 }

@@ -113,6 +113,7 @@ class PoseGraphParams(C.Structure):
 
 # include/nsc.h NSC_POSEGRAPH_MAX_EDGES, NSC_POSEGRAPH_MAX_LAUNCHES, NSC_POSEGRAPH_STATS
 POSEGRAPH_MAX_EDGES, POSEGRAPH_MAX_LAUNCHES, POSEGRAPH_STATS = 1073741823, 1000000, 10
+POSEGRAPH_MAX_AGGREGATES = 128                   # include/nsc.h NSC_POSEGRAPH_MAX_AGGREGATES
 # include/nsc.h NSC_POSEGRAPH_STAT_*: where each statistic stands in `stats`
 (POSEGRAPH_STAT_ITERATIONS, POSEGRAPH_STAT_ACCEPTED, POSEGRAPH_STAT_REJECTED, POSEGRAPH_STAT_PCG_ITERATIONS,
  POSEGRAPH_STAT_INITIAL_COST, POSEGRAPH_STAT_FINAL_COST, POSEGRAPH_STAT_LAMBDA, POSEGRAPH_STAT_SKIPPED,
@@ -225,6 +226,9 @@ SYMBOLS = {
                                                  _vp, _i32, _vp, _vp]),
     "nsc_posegraph_optimize_robust": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PoseGraphParams), _vp,
                                                 _vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp, _vp, _vp]),
+    "nsc_posegraph_coarse_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "nsc_posegraph_optimize_coarse": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PoseGraphParams), _vp,
+                                                _vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

@@ -31,6 +31,23 @@
 // `stop_k`: iteration k runs iff k < stop_k, and the kernel that ends the loop at iteration k writes k + 1, so its own
 // workgroups, which read stop_k while it is being written, see "run" either way.  The two r.z values alternate between
 // two slots for the same reason.
+//
+// Two-level preconditioner (nsc_posegraph_optimize_coarse, coarse_block = L >= 2; include/nsc.h has the mathematics).
+// Aggregate a holds the poses a L .. a L + L - 1; the coarse space is one rigid motion per aggregate, P's block of a free
+// pose k being Ad(X_k^-1 X_ref); M^-1 r = B^-1 r + P A_c^-1 P^T r with A_c = P^T (H + lambda diag H) P.  Per outer step,
+// after linearise and assemble: pg_coarse_basis_kernel (one lane per node: P), pg_coarse_galerkin_kernel (one wave per
+// block (a, b), a <= b, of A_c: it walks the incident lists of a's nodes in ascending order and writes the block and its
+// transpose), pg_coarse_factor_kernel (one workgroup of 512: right-looking Cholesky in global memory, U and U^T),
+// pg_coarse_invert_kernel (one wave per column of A_c^-1: two substitutions in axpy form, the running column in
+// registers), then the restrict and prolong kernels once on the start of PCG.  Per inner iteration the step kernel is
+// replaced by pg_coarse_restrict_kernel (one wave per aggregate: the step, B^-1 r and its six entries of P^T r) and
+// pg_coarse_prolong_kernel (one wave per aggregate: its six rows of A_c^-1 r_c, z += P y, the partials of r.r and r.z,
+// one per aggregate, which pg_coarse_begin_kernel and pg_coarse_direction_kernel sum): five launches per inner iteration.  The same house rules hold: no floating-point atomics, every
+// sum in a fixed order (a lane sums its nodes in ascending order, the wave finishes with the butterfly), no host
+// synchronisation, no memset or memcpy nodes, no cooperative launch or grid barrier, `done` and `stop_k` honoured by
+// every kernel, and a launch sequence that depends only on the parameters, N > 0, E > 0 and coarse_block:
+//   5 (lists) + 1 (copy, unless aliased) + 3 + max_iteration (14 + 5 max_pcg_iterations) + 1 (+ 1 for chi2 / weights).
+// A pivot of A_c that is not positive and finite leaves that outer step with B^-1 alone and is counted.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -60,6 +77,20 @@ struct Buffers {                             // the workspace: typed pointers in
     double *cand;                            // (N,4,4), rows 0..2 used
     double *part_e, *part_a, *part_b, *part_s;   // partials, one per workgroup of nodes: cost, p.Ap, (r.r, r.z), |delta|^2
     size_t total;                            // bytes
+};
+
+struct PgCoarse {
+    int ok, failed;                          // this outer step's factor of A_c stands; outer steps whose factor failed
+};
+
+struct Coarse {                              // the coarse space's part of the workspace, behind Buffers'
+    PgCoarse *cs;
+    double *t;                               // (N,36): P's block of every node, row-major, zero for a node that is not free
+    double *ac, *lt, *ainv;                  // (nc,nc): A_c, then U (upper triangle);  U^T;  A_c^-1
+    double *rc;                              // (nc): P^T r
+    double *part;                            // (2 n_agg): partials of r.r and r.z, one per aggregate
+    int L, n_agg, nc;                        // nc = 6 n_agg
+    size_t total;                            // bytes, Buffers' included
 };
 
 // the sum of nb partials, the same bits in every lane of every wave that calls it
@@ -598,15 +629,20 @@ __global__ __launch_bounds__(TB) void pg_assemble_kernel(int n_poses, int n_edge
 }
 
 // one wave: |g|^2 and r.z of the start; no inner iteration when the gradient is zero
-__global__ __launch_bounds__(TB) void pg_pcg_begin_kernel(int nb, Buffers b)
+__device__ __forceinline__ void pcg_begin(const Buffers &b, const double *part_b, int nb)
 {
-    if (b.st->done) return;
-    const double bb = finish(b.part_b, nb), rz = finish(b.part_b + nb, nb);
+    const double bb = finish(part_b, nb), rz = finish(part_b + nb, nb);
     if (threadIdx.x == 0) {
         b.st->bb = bb;
         b.st->rz[0] = rz;
         b.st->stop_k = bb > 0.0 && rz > 0.0 ? INT_MAX : 0;
     }
+}
+
+__global__ __launch_bounds__(TB) void pg_pcg_begin_kernel(int nb, Buffers b)
+{
+    if (b.st->done) return;
+    pcg_begin(b, b.part_b, nb);
 }
 
 // A p = gather + lambda diag(H) p on the free nodes; partial of p.Ap
@@ -668,12 +704,12 @@ __global__ __launch_bounds__(TB) void pg_pcg_step_kernel(int n_poses, Buffers b,
 }
 
 // beta = r.z (new) / r.z (old);  p = z + beta p;  the first lane of the grid counts the iteration and ends the loop at
-// |r| <= tolerance |g|, at p.Ap <= 0 or at r.z <= 0
-__global__ __launch_bounds__(TB) void pg_pcg_direction_kernel(int n_poses, Buffers b, int k, double tol2)
+// |r| <= tolerance |g|, at p.Ap <= 0 or at r.z <= 0.  part_b: the nb_b partials of r.r, then those of r.z
+__device__ __forceinline__ void pcg_direction(int n_poses, const Buffers &b, int k, double tol2, const double *part_b,
+                                              int nb_b)
 {
-    if (b.st->done || k >= b.st->stop_k) return;
     const int nb = gridDim.x;
-    const double pap = finish(b.part_a, nb), rr = finish(b.part_b, nb), rz = finish(b.part_b + nb, nb);
+    const double pap = finish(b.part_a, nb), rr = finish(part_b, nb_b), rz = finish(part_b + nb_b, nb_b);
     const double beta = rz / b.st->rz[k & 1];
     const int n = blockIdx.x * TB + threadIdx.x;
     if (n < n_poses && b.free_node[n]) {
@@ -688,6 +724,340 @@ __global__ __launch_bounds__(TB) void pg_pcg_direction_kernel(int n_poses, Buffe
         b.st->pcg_total += 1;
         if (!(pap > 0.0) || rr <= tol2 * b.st->bb || !(rz > 0.0)) b.st->stop_k = k + 1;
     }
+}
+
+__global__ __launch_bounds__(TB) void pg_pcg_direction_kernel(int n_poses, Buffers b, int k, double tol2)
+{
+    if (b.st->done || k >= b.st->stop_k) return;
+    pcg_direction(n_poses, b, k, tol2, b.part_b, gridDim.x);
+}
+
+// ---- the coarse space ----------------------------------------------------------------------------------------------
+
+constexpr int CB = 512;                      // lanes of the one workgroup that factors A_c: two waves per SIMD, 256 VGPRs
+constexpr int CW = CB / TB;                  // its waves
+constexpr int CR = 4;                        // rows a wave loads before it stores any
+constexpr int CM = 6 * NSC_POSEGRAPH_MAX_AGGREGATES / TB;   // entries of a coarse vector per lane: 12
+
+__device__ __forceinline__ void load36(const double *__restrict__ src, double M[36])
+{
+#pragma unroll
+    for (int q = 0; q < 36; ++q) M[q] = src[q];
+}
+
+// acc += Tk^T H Tm, row of H by row
+__device__ __forceinline__ void add_tht(const double Tk[36], const double H[36], const double Tm[36], double acc[36])
+{
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        double row[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            double s = 0.0;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) s += H[6 * r + q] * Tm[6 * q + c];
+            row[c] = s;
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int c = 0; c < 6; ++c) acc[6 * i + c] += Tk[6 * r + i] * row[c];
+    }
+}
+
+// P: the block of node k is Ad(X_k^-1 X_ref) = [[R, 0], [[t]x R, R]] with R = R_k^T R_ref, t = R_k^T (t_ref - t_k), X_ref
+// the first pose of k's aggregate at the linearisation point; zeros for a node that is not free
+__global__ __launch_bounds__(TB) void pg_coarse_basis_kernel(const double *poses, int n_poses, Buffers b, Coarse c)
+{
+    if (b.st->done) return;
+    const int n = blockIdx.x * TB + threadIdx.x;
+    if (n >= n_poses) return;
+    double T[36];
+#pragma unroll
+    for (int q = 0; q < 36; ++q) T[q] = 0.0;
+    if (b.free_node[n]) {
+        double Rk[9], tk[3], Rf[9], tf[3], R[9], t[3], K[9];
+        load_pose(poses, n, Rk, tk);
+        load_pose(poses, (long long)(n / c.L) * c.L, Rf, tf);
+        mul_tn(Rk, Rf, R);
+        const double d[3] = {tf[0] - tk[0], tf[1] - tk[1], tf[2] - tk[2]};
+        mulv_t(Rk, d, t);
+        hat(t, K);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                T[6 * r + q] = T[6 * (r + 3) + q + 3] = R[3 * r + q];
+                T[6 * (r + 3) + q] = K[3 * r] * R[q] + K[3 * r + 1] * R[3 + q] + K[3 * r + 2] * R[6 + q];
+            }
+    }
+    for (int q = 0; q < 36; ++q) c.t[36 * (long long)n + q] = T[q];
+}
+
+// A_c = P^T (H + lambda diag H) P over the free nodes: one wave per block (a, b), a <= b.  Lane l takes the nodes
+// a L + l, a L + l + 64, ... of aggregate a, each with its diagonal block (a == b) and its incident edges whose other end
+// is a free node of aggregate b, in list order; the wave finishes with the butterfly and writes the block and, for
+// a < b, its transpose, so every entry of A_c is written.  An aggregate without a free node gets the identity.
+__global__ __launch_bounds__(TB) void pg_coarse_galerkin_kernel(int n_poses, int n_edges, Buffers b, Coarse c)
+{
+    if (b.st->done) return;
+    const int ca = blockIdx.x / c.n_agg, cb = blockIdx.x % c.n_agg;
+    if (ca > cb) return;
+    const long long E = n_edges;
+    const double lambda = b.st->lambda;
+    double acc[36];
+#pragma unroll
+    for (int q = 0; q < 36; ++q) acc[q] = 0.0;
+    int n_free = 0;
+    const int lo = ca * c.L, hi = min(lo + c.L, n_poses);
+    for (int n = lo + threadIdx.x; n < hi; n += TB) {
+        if (!b.free_node[n]) continue;
+        ++n_free;
+        double Tk[36], Tm[36], H[36];
+        load36(c.t + 36 * (long long)n, Tk);
+        if (ca == cb) {
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int q = r; q < 6; ++q) {
+                    const double v = b.blocks[21 * (long long)n + tri(r, q)];
+                    H[6 * r + q] = H[6 * q + r] = r == q ? v + lambda * v : v;
+                }
+            add_tht(Tk, H, Tk, acc);
+        }
+        for (int a = b.row_ptr[n]; a < b.row_ptr[n + 1]; ++a) {
+            const int code = b.list[a], e = code >> 1, side = code & 1;
+            const int m = side ? b.ei[e] : b.ej[e];
+            if (!b.free_node[m] || m / c.L != cb) continue;
+            load36(c.t + 36 * (long long)m, Tm);
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int q = 0; q < 6; ++q) H[6 * r + q] = b.hij[(side ? 6 * q + r : 6 * r + q) * E + e];
+            add_tht(Tk, H, Tm, acc);
+        }
+    }
+    n_free = nsc_wave_sum(n_free);
+#pragma unroll
+    for (int q = 0; q < 36; ++q) acc[q] = nsc_wave_sum(acc[q]);
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const double v = ca == cb && n_free == 0 ? (r == q ? 1.0 : 0.0) : acc[6 * r + q];
+            c.ac[(6LL * ca + r) * c.nc + 6 * cb + q] = v;
+            if (ca != cb) c.ac[(6LL * cb + q) * c.nc + 6 * ca + r] = v;
+        }
+}
+
+// U^T U = A_c by one workgroup, in global memory (768^2 doubles do not fit the LDS), reading the upper triangle only.
+// Right-looking, one barrier per column: at column j the rows below it lose (A_jr / A_jj) A_j., row j stays unscaled
+// until the end, where U_j. = A_j. / sqrt(A_jj) is written over A_c and, transposed, into lt.  Lane l of every wave
+// holds columns j + 1 + l, + 64, ... of the pivot row in registers; a wave takes four rows at a time and loads all
+// before it stores any.  A pivot that is not positive and finite ends the factor: ok = 0, and the event is counted.
+__global__ __launch_bounds__(CB) void pg_coarse_factor_kernel(Buffers b, Coarse c)
+{
+    if (b.st->done) return;
+    const int n = c.nc, wave = threadIdx.x / TB, lane = threadIdx.x % TB;
+    double *A = c.ac;
+    bool ok = true;
+    for (int j = 0; j < n; ++j) {
+        const double *Aj = A + (long long)j * n;
+        const double piv = Aj[j];                            // final since the barrier of column j - 1: the same in every lane
+        if (!(piv > 0.0) || !isfinite(piv)) {
+            ok = false;
+            break;
+        }
+        const double inv = 1.0 / piv;
+        double rowj[CM];
+#pragma unroll
+        for (int m = 0; m < CM; ++m) {
+            const int col = j + 1 + lane + TB * m;
+            rowj[m] = col < n ? Aj[col] : 0.0;
+        }
+        for (int r0 = j + 1 + CR * wave; r0 < n; r0 += CR * CW) {
+            double f[CR], v[CR][CM];
+#pragma unroll
+            for (int q = 0; q < CR; ++q) {
+                const int r = r0 + q;
+                f[q] = r < n ? Aj[r] * inv : 0.0;
+#pragma unroll
+                for (int m = 0; m < CM; ++m) {
+                    const int col = j + 1 + lane + TB * m;
+                    v[q][m] = r < n && col >= r && col < n ? A[r * n + col] : 0.0;        // nc^2 < 2^31
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < CR; ++q) {
+                const int r = r0 + q;
+#pragma unroll
+                for (int m = 0; m < CM; ++m) {
+                    const int col = j + 1 + lane + TB * m;
+                    if (r < n && col >= r && col < n) A[r * n + col] = v[q][m] - f[q] * rowj[m];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (ok) {
+        for (int j = wave; j < n; j += CW) {
+            const double d = 1.0 / sqrt(A[(long long)j * n + j]);
+            for (int col = j + lane; col < n; col += TB) {
+                const double u = A[(long long)j * n + col] * d;
+                A[(long long)j * n + col] = u;
+                c.lt[(long long)col * n + j] = u;
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        c.cs->ok = ok;
+        if (!ok) c.cs->failed += 1;
+    }
+}
+
+// A_c^-1, one column per wave: U^T y = e_col, then U x = y, both in axpy form so that every read is a contiguous row (of
+// U, then of U^T).  Lane l holds entries l, l + 64, ... of the running column.
+__global__ __launch_bounds__(TB) void pg_coarse_invert_kernel(Buffers b, Coarse c)
+{
+    if (b.st->done || !c.cs->ok) return;
+    const int n = c.nc, col = blockIdx.x, lane = threadIdx.x;
+    double v[CM];
+#pragma unroll
+    for (int m = 0; m < CM; ++m) v[m] = lane + TB * m == col ? 1.0 : 0.0;
+#pragma unroll
+    for (int mk = 0; mk < CM; ++mk)
+        for (int kk = 0; kk < TB; ++kk) {
+            const int k = TB * mk + kk;
+            if (k < col || k >= n) continue;                 // y is zero above the column's own row
+            const double *Uk = c.ac + (long long)k * n;
+            const double yk = __shfl(v[mk], kk, 64) / Uk[k];
+            if (lane == kk) v[mk] = yk;
+#pragma unroll
+            for (int m = mk; m < CM; ++m) {
+                const int i = lane + TB * m;
+                if (i > k && i < n) v[m] -= Uk[i] * yk;
+            }
+        }
+#pragma unroll
+    for (int mk = CM - 1; mk >= 0; --mk)
+        for (int kk = TB - 1; kk >= 0; --kk) {
+            const int k = TB * mk + kk;
+            if (k >= n) continue;
+            const double *Lk = c.lt + (long long)k * n;      // row k of U^T: column k of U
+            const double xk = __shfl(v[mk], kk, 64) / Lk[k];
+            if (lane == kk) v[mk] = xk;
+#pragma unroll
+            for (int m = 0; m <= mk; ++m) {
+                const int i = lane + TB * m;
+                if (i < k) v[m] -= Lk[i] * xk;
+            }
+        }
+#pragma unroll
+    for (int m = 0; m < CM; ++m) {
+        const int i = lane + TB * m;
+        if (i < n) c.ainv[(long long)i * n + col] = v[m];    // A_c^-1 is symmetric: row i of column col
+    }
+}
+
+// One wave per aggregate.  k >= 0: the step of inner iteration k on the aggregate's free nodes, alpha = r.z / p.Ap;
+// x += alpha p;  r -= alpha A p;  z = B^-1 r.  k < 0: the start, r and z as pg_assemble_kernel left them.  Either way
+// the aggregate's six entries of r_c = P^T r, each lane summing its nodes in ascending order.
+__global__ __launch_bounds__(TB) void pg_coarse_restrict_kernel(int n_poses, int nb_a, Buffers b, Coarse c, int k)
+{
+    if (b.st->done || k >= b.st->stop_k) return;
+    double alpha = 0.0;
+    if (k >= 0) {
+        const double pap = finish(b.part_a, nb_a);
+        alpha = pap > 0.0 ? b.st->rz[k & 1] / pap : 0.0;
+    }
+    double rc[6] = {0, 0, 0, 0, 0, 0};
+    const int lo = blockIdx.x * c.L, hi = min(lo + c.L, n_poses);
+    for (int n = lo + threadIdx.x; n < hi; n += TB) {
+        if (!b.free_node[n]) continue;
+        double r[6];
+        if (k >= 0) {
+            double U[21], z[6];
+            for (int q = 0; q < 21; ++q) U[q] = b.chol[21 * (long long)n + q];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const long long at = 6 * (long long)n + q;
+                b.x[at] += alpha * b.p[at];
+                r[q] = b.r[at] - alpha * b.ap[at];
+                b.r[at] = r[q];
+            }
+            cholesky_solve6(U, r, z);
+#pragma unroll
+            for (int q = 0; q < 6; ++q) b.z[6 * (long long)n + q] = z[q];
+        } else {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) r[q] = b.r[6 * (long long)n + q];
+        }
+        const double *T = c.t + 36 * (long long)n;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int q = 0; q < 6; ++q) rc[q] += T[6 * i + q] * r[i];
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) rc[q] = nsc_wave_sum(rc[q]);
+    if (threadIdx.x == 0)
+        for (int q = 0; q < 6; ++q) c.rc[6 * blockIdx.x + q] = rc[q];
+}
+
+// One wave per aggregate: its six rows of y = A_c^-1 r_c (none when the factor failed: B^-1 alone), z += P y on its free
+// nodes, p = z at the start (k < 0), and the aggregate's partials of r.r and r.z
+__global__ __launch_bounds__(TB) void pg_coarse_prolong_kernel(int n_poses, Buffers b, Coarse c, int k)
+{
+    if (b.st->done || k >= b.st->stop_k) return;
+    const bool coarse = c.cs->ok;
+    double y[6] = {0, 0, 0, 0, 0, 0};
+    if (coarse) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const double *row = c.ainv + (6LL * blockIdx.x + q) * c.nc;
+            double s = 0.0;
+            for (int i = threadIdx.x; i < c.nc; i += TB) s += row[i] * c.rc[i];
+            y[q] = nsc_wave_sum(s);
+        }
+    }
+    double rr = 0.0, rz = 0.0;
+    const int lo = blockIdx.x * c.L, hi = min(lo + c.L, n_poses);
+    for (int n = lo + threadIdx.x; n < hi; n += TB) {
+        if (!b.free_node[n]) continue;
+        const double *T = c.t + 36 * (long long)n;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const long long at = 6 * (long long)n + i;
+            double z = b.z[at];
+            if (coarse) {
+                double s = 0.0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) s += T[6 * i + q] * y[q];
+                z += s;
+                b.z[at] = z;
+            }
+            if (k < 0) b.p[at] = z;
+            const double r = b.r[at];
+            rr += r * r;
+            rz += r * z;
+        }
+    }
+    write_partial(c.part, rr);
+    write_partial(c.part + c.n_agg, rz);
+}
+
+// pg_pcg_begin_kernel and pg_pcg_direction_kernel on the partials of the prolong kernel, one per aggregate
+__global__ __launch_bounds__(TB) void pg_coarse_begin_kernel(Buffers b, Coarse c)
+{
+    if (b.st->done) return;
+    pcg_begin(b, c.part, c.n_agg);
+}
+
+__global__ __launch_bounds__(TB) void pg_coarse_direction_kernel(int n_poses, Buffers b, Coarse c, int k, double tol2)
+{
+    if (b.st->done || k >= b.st->stop_k) return;
+    pcg_direction(n_poses, b, k, tol2, c.part, c.n_agg);
 }
 
 // candidate poses X_k [Exp(phi_k) | rho_k]; partial of |delta|^2; the first delta of the call on request
@@ -728,10 +1098,12 @@ __global__ __launch_bounds__(TB) void pg_update_kernel(const double *poses, int 
 }
 
 // one wave: the cost at the start
-__global__ __launch_bounds__(TB) void pg_init_kernel(int nb_n, Buffers b, double lambda0, double *__restrict__ history)
+__global__ __launch_bounds__(TB) void pg_init_kernel(int nb_n, Buffers b, double lambda0, double *__restrict__ history,
+                                                     PgCoarse *__restrict__ cs)
 {
     const double f = finish(b.part_e, nb_n);
     if (threadIdx.x == 0) {
+        if (cs) cs->ok = cs->failed = 0;
         b.st->cost = b.st->cost0 = f;
         b.st->lambda = lambda0;
         b.st->accept_it = -1;
@@ -780,11 +1152,16 @@ __global__ __launch_bounds__(TB) void pg_commit_kernel(double *poses, int n_pose
 }
 
 __global__ __launch_bounds__(TB) void pg_finalize_kernel(Buffers b, int max_iteration, double *__restrict__ stats,
-                                                         double *__restrict__ history)
+                                                         double *__restrict__ history, const PgCoarse *__restrict__ cs,
+                                                         int n_agg, double *__restrict__ coarse_stats)
 {
     const PgState *st = b.st;
     for (int k = st->iterations + 1 + threadIdx.x; k <= max_iteration; k += TB) history[k] = st->cost;
     if (threadIdx.x != 0) return;
+    if (coarse_stats) {
+        coarse_stats[0] = n_agg;
+        coarse_stats[1] = cs ? cs->failed : 0;
+    }
     stats[NSC_POSEGRAPH_STAT_ITERATIONS] = st->iterations;
     stats[NSC_POSEGRAPH_STAT_ACCEPTED] = st->accepted;
     stats[NSC_POSEGRAPH_STAT_REJECTED] = st->rejected;
@@ -849,6 +1226,29 @@ Buffers buffers(void *ws, size_t N, size_t E)
     return b;
 }
 
+// the coarse space's regions, carved behind the `base` bytes of Buffers; ws = nullptr: the size only
+Coarse coarse_buffers(void *ws, size_t base, size_t N, int L, int n_agg)
+{
+    Carver c = {reinterpret_cast<uintptr_t>(ws), base};
+    Coarse q;
+    const size_t nc = 6 * (size_t)n_agg;
+    q.cs = c.take<PgCoarse>(1);
+    q.t = c.take<double>(36 * N);
+    q.ac = c.take<double>(nc * nc);
+    q.lt = c.take<double>(nc * nc);
+    q.ainv = c.take<double>(nc * nc);
+    q.rc = c.take<double>(nc);
+    q.part = c.take<double>(2 * (size_t)n_agg);
+    q.L = L;
+    q.n_agg = n_agg;
+    q.nc = (int)nc;
+    q.total = c.o;
+    return q;
+}
+
+// aggregates of L >= 2 consecutive poses
+long long aggregates_of(long long N, long long L) { return (N + L - 1) / L; }
+
 bool params_ok(const NscPoseGraphParams *p)
 {
     return p->max_iteration >= 0 && p->max_pcg_iterations >= 0 && p->pcg_tolerance >= 0.0 && isfinite(p->pcg_tolerance) &&
@@ -873,6 +1273,88 @@ void build_lists(hipStream_t s, const int64_t *edge_ij, int N, int E, const Buff
         hipLaunchKernelGGL(pg_fill_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, E, b);
         if (N > 0) hipLaunchKernelGGL(pg_sort_kernel, dim3(N), dim3(TB), 0, s, b);
     }
+}
+
+// nsc_posegraph_optimize_robust (coarse_block = 0) and nsc_posegraph_optimize_coarse
+int optimize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
+             const double *information, int32_t n_edges, const uint8_t *fixed, const NscPoseGraphParams *params,
+             double *poses_out, double *stats, double *cost_history, double *step0, void *ws, size_t ws_bytes,
+             void *stream, int32_t kernel, const double *edge_scale, double *edge_chi2, double *edge_weight,
+             int32_t coarse_block, double *coarse_stats)
+{
+    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES || !params || !params_ok(params) ||
+        !kernel_ok(kernel) || coarse_block < 0 || coarse_block == 1)
+        return NSC_EINVAL;
+    if (!stats || !cost_history) return NSC_EINVAL;
+    if (n_poses > 0 && (!poses || !poses_out || !fixed)) return NSC_EINVAL;
+    if (n_edges > 0 && (!edge_ij || !measurements || !information)) return NSC_EINVAL;
+    const int L = coarse_block;
+    const long long n_agg = L ? aggregates_of(n_poses, L) : 0;
+    if (n_agg > NSC_POSEGRAPH_MAX_AGGREGATES) return NSC_EUNSUPPORTED;
+    // per outer step 8 launches and 4 per inner iteration; with the coarse space 14 and 5
+    if ((long long)params->max_iteration * ((L ? 5LL : 4LL) * params->max_pcg_iterations + (L ? 14 : 8)) >
+        NSC_POSEGRAPH_MAX_LAUNCHES)
+        return NSC_EUNSUPPORTED;
+    const Buffers b = buffers(ws, n_poses, n_edges);
+    const Coarse c = coarse_buffers(ws, b.total, n_poses, L, (int)n_agg);
+    if (!ws || ws_bytes < (L ? c.total : b.total)) return NSC_EWORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int N = n_poses, E = n_edges, gn = blocks_of(N), ge = blocks_of(E), ga = (int)n_agg;
+    const NscPoseGraphParams prm = *params;
+    const double tol2 = prm.pcg_tolerance * prm.pcg_tolerance;
+
+    build_lists(s, edge_ij, N, E, b);
+    if (N > 0 && poses_out != poses)
+        hipLaunchKernelGGL(pg_copy_kernel, dim3(blocks_of(16LL * N)), dim3(TB), 0, s, poses, poses_out, 16LL * N);
+    if (E > 0)
+        hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0,
+                           kernel, edge_scale, b.fe, nullptr, nullptr);
+    if (N > 0) hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 0);
+    hipLaunchKernelGGL(pg_init_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm.lambda0, cost_history, L ? c.cs : nullptr);
+
+    for (int it = 0; it < prm.max_iteration && N > 0; ++it) {
+        if (E > 0)
+            hipLaunchKernelGGL(pg_linearize_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b,
+                               nullptr, 1, kernel, edge_scale, nullptr);
+        hipLaunchKernelGGL(pg_assemble_kernel, dim3(gn), dim3(TB), 0, s, N, E, fixed, b, b.g, b.blocks, 1);
+        if (L) {
+            hipLaunchKernelGGL(pg_coarse_basis_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, c);
+            hipLaunchKernelGGL(pg_coarse_galerkin_kernel, dim3(ga * ga), dim3(TB), 0, s, N, E, b, c);
+            hipLaunchKernelGGL(pg_coarse_factor_kernel, dim3(1), dim3(CB), 0, s, b, c);
+            hipLaunchKernelGGL(pg_coarse_invert_kernel, dim3(c.nc), dim3(TB), 0, s, b, c);
+            hipLaunchKernelGGL(pg_coarse_restrict_kernel, dim3(ga), dim3(TB), 0, s, N, gn, b, c, -1);
+            hipLaunchKernelGGL(pg_coarse_prolong_kernel, dim3(ga), dim3(TB), 0, s, N, b, c, -1);
+        }
+        if (L)
+            hipLaunchKernelGGL(pg_coarse_begin_kernel, dim3(1), dim3(TB), 0, s, b, c);
+        else
+            hipLaunchKernelGGL(pg_pcg_begin_kernel, dim3(1), dim3(TB), 0, s, gn, b);
+        for (int k = 0; k < prm.max_pcg_iterations && E > 0; ++k) {
+            hipLaunchKernelGGL(pg_edge_matvec_kernel, dim3(ge), dim3(TB), 0, s, E, b, k);
+            hipLaunchKernelGGL(pg_node_matvec_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
+            if (L) {
+                hipLaunchKernelGGL(pg_coarse_restrict_kernel, dim3(ga), dim3(TB), 0, s, N, gn, b, c, k);
+                hipLaunchKernelGGL(pg_coarse_prolong_kernel, dim3(ga), dim3(TB), 0, s, N, b, c, k);
+                hipLaunchKernelGGL(pg_coarse_direction_kernel, dim3(gn), dim3(TB), 0, s, N, b, c, k, tol2);
+            } else {
+                hipLaunchKernelGGL(pg_pcg_step_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
+                hipLaunchKernelGGL(pg_pcg_direction_kernel, dim3(gn), dim3(TB), 0, s, N, b, k, tol2);
+            }
+        }
+        hipLaunchKernelGGL(pg_update_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it, step0);
+        if (E > 0)
+            hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, b.cand, measurements, information, E, b, 1,
+                               kernel, edge_scale, b.fe, nullptr, nullptr);
+        hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 1);
+        hipLaunchKernelGGL(pg_accept_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm, it, cost_history);
+        hipLaunchKernelGGL(pg_commit_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it);
+    }
+    hipLaunchKernelGGL(pg_finalize_kernel, dim3(1), dim3(TB), 0, s, b, prm.max_iteration, stats, cost_history,
+                       L ? c.cs : nullptr, ga, coarse_stats);
+    if (E > 0 && (edge_chi2 || edge_weight))
+        hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0,
+                           kernel, edge_scale, nullptr, edge_chi2, edge_weight);
+    return launch_status();
 }
 
 }  // namespace
@@ -955,55 +1437,30 @@ int nsc_posegraph_optimize_robust(const double *poses, int32_t n_poses, const in
                                   void *stream, int32_t kernel, const double *edge_scale, double *edge_chi2,
                                   double *edge_weight)
 {
-    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES || !params || !params_ok(params) ||
-        !kernel_ok(kernel))
-        return NSC_EINVAL;
-    if (!stats || !cost_history) return NSC_EINVAL;
-    if (n_poses > 0 && (!poses || !poses_out || !fixed)) return NSC_EINVAL;
-    if (n_edges > 0 && (!edge_ij || !measurements || !information)) return NSC_EINVAL;
-    if ((long long)params->max_iteration * (4LL * params->max_pcg_iterations + 8) > NSC_POSEGRAPH_MAX_LAUNCHES)
-        return NSC_EUNSUPPORTED;
-    const Buffers b = buffers(ws, n_poses, n_edges);
-    if (!ws || ws_bytes < b.total) return NSC_EWORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int N = n_poses, E = n_edges, gn = blocks_of(N), ge = blocks_of(E);
-    const NscPoseGraphParams prm = *params;
-    const double tol2 = prm.pcg_tolerance * prm.pcg_tolerance;
+    return optimize(poses, n_poses, edge_ij, measurements, information, n_edges, fixed, params, poses_out, stats,
+                    cost_history, step0, ws, ws_bytes, stream, kernel, edge_scale, edge_chi2, edge_weight, 0, nullptr);
+}
 
-    build_lists(s, edge_ij, N, E, b);
-    if (N > 0 && poses_out != poses)
-        hipLaunchKernelGGL(pg_copy_kernel, dim3(blocks_of(16LL * N)), dim3(TB), 0, s, poses, poses_out, 16LL * N);
-    if (E > 0)
-        hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0,
-                           kernel, edge_scale, b.fe, nullptr, nullptr);
-    if (N > 0) hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 0);
-    hipLaunchKernelGGL(pg_init_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm.lambda0, cost_history);
+size_t nsc_posegraph_coarse_workspace_bytes(int32_t n_poses, int32_t n_edges, int32_t coarse_block)
+{
+    if (n_poses < 0 || n_edges < 0 || coarse_block < 0 || coarse_block == 1) return 0;
+    const size_t base = buffers(nullptr, n_poses, n_edges).total;
+    if (coarse_block == 0) return base;
+    const long long n_agg = aggregates_of(n_poses, coarse_block);
+    if (n_agg > NSC_POSEGRAPH_MAX_AGGREGATES) return 0;
+    return coarse_buffers(nullptr, base, n_poses, coarse_block, (int)n_agg).total;
+}
 
-    for (int it = 0; it < prm.max_iteration && N > 0; ++it) {
-        if (E > 0)
-            hipLaunchKernelGGL(pg_linearize_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b,
-                               nullptr, 1, kernel, edge_scale, nullptr);
-        hipLaunchKernelGGL(pg_assemble_kernel, dim3(gn), dim3(TB), 0, s, N, E, fixed, b, b.g, b.blocks, 1);
-        hipLaunchKernelGGL(pg_pcg_begin_kernel, dim3(1), dim3(TB), 0, s, gn, b);
-        for (int k = 0; k < prm.max_pcg_iterations && E > 0; ++k) {
-            hipLaunchKernelGGL(pg_edge_matvec_kernel, dim3(ge), dim3(TB), 0, s, E, b, k);
-            hipLaunchKernelGGL(pg_node_matvec_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
-            hipLaunchKernelGGL(pg_pcg_step_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
-            hipLaunchKernelGGL(pg_pcg_direction_kernel, dim3(gn), dim3(TB), 0, s, N, b, k, tol2);
-        }
-        hipLaunchKernelGGL(pg_update_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it, step0);
-        if (E > 0)
-            hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, b.cand, measurements, information, E, b, 1,
-                               kernel, edge_scale, b.fe, nullptr, nullptr);
-        hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 1);
-        hipLaunchKernelGGL(pg_accept_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm, it, cost_history);
-        hipLaunchKernelGGL(pg_commit_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it);
-    }
-    hipLaunchKernelGGL(pg_finalize_kernel, dim3(1), dim3(TB), 0, s, b, prm.max_iteration, stats, cost_history);
-    if (E > 0 && (edge_chi2 || edge_weight))
-        hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0,
-                           kernel, edge_scale, nullptr, edge_chi2, edge_weight);
-    return launch_status();
+int nsc_posegraph_optimize_coarse(const double *poses, int32_t n_poses, const int64_t *edge_ij,
+                                  const double *measurements, const double *information, int32_t n_edges,
+                                  const uint8_t *fixed, const NscPoseGraphParams *params, double *poses_out,
+                                  double *stats, double *cost_history, double *step0, void *ws, size_t ws_bytes,
+                                  void *stream, int32_t kernel, const double *edge_scale, double *edge_chi2,
+                                  double *edge_weight, int32_t coarse_block, double *coarse_stats)
+{
+    return optimize(poses, n_poses, edge_ij, measurements, information, n_edges, fixed, params, poses_out, stats,
+                    cost_history, step0, ws, ws_bytes, stream, kernel, edge_scale, edge_chi2, edge_weight, coarse_block,
+                    coarse_stats);
 }
 
 }  // extern "C"

@@ -11,6 +11,10 @@ Definition (the contract nsc_posegraph_optimize and tests/posegraph_restatement.
     solver       Levenberg-Marquardt, (H + lambda diag H) delta = -g by block-Jacobi preconditioned conjugate gradients;
                  a step is accepted when the cost decreases
 
+    coarse       ``coarse_block`` = L adds a coarse space to the preconditioner: one rigid motion per aggregate of L
+                 consecutive poses, M^-1 r = B^-1 r + P (P^T A P)^-1 P^T r (include/nsc.h).  It carries the long
+                 wavelengths of a trajectory that block-Jacobi needs of the order of N inner iterations for
+
     robust       with s = r^T Omega r and a width c per edge (``robust_scale``, in units of sqrt(chi^2)):
                  F = sum rho(s), g = sum w J^T Omega r, H = sum w J^T Omega J, w = rho'(s) (first order: IRLS)
                    huber          rho = s for s <= c^2, else 2 c sqrt(s) - c^2    w = 1, else c / sqrt(s)
@@ -116,13 +120,19 @@ class PoseGraphOptimizer:
     """Levenberg-Marquardt over SE(3) poses on the device.  Parameters (include/nsc.h NscPoseGraphParams):
     max_iteration, max_pcg_iterations, pcg_tolerance, lambda0, lambda_min, lambda_factor, relative_cost, min_step.
     ``kernel``: None (quadratic), "huber", "cauchy" or "geman_mcclure"; it acts on the edges that the ``robust_scale``
-    of a call gives a width."""
+    of a call gives a width.  ``coarse_block``: None (block-Jacobi alone: nothing changes), an int >= 2 (poses per
+    aggregate of the two-level preconditioner) or "auto" = max(8, ceil(N / 64)) per call.  Aggregation is by index: it
+    assumes consecutive poses are neighbours, as on a trajectory.  At most 128 aggregates."""
 
-    def __init__(self, device="cuda", kernel=None, **params):
+    def __init__(self, device="cuda", kernel=None, coarse_block=None, **params):
         self.device = torch.device(device)
         if kernel not in _lib.POSEGRAPH_KERNELS:
             raise _lib.NscError(f"PoseGraphOptimizer: unknown kernel {kernel!r}")
         self.kernel = _lib.POSEGRAPH_KERNELS[kernel]
+        if not (coarse_block is None or coarse_block == "auto" or
+                (isinstance(coarse_block, (int, np.integer)) and not isinstance(coarse_block, bool) and coarse_block >= 2)):
+            raise _lib.NscError(f"PoseGraphOptimizer: coarse_block is None, an int >= 2 or 'auto' (got {coarse_block!r})")
+        self.coarse_block = coarse_block
         p = _lib.PoseGraphParams()
         _lib.lib().nsc_posegraph_default_params(C.byref(p))
         names = {n for n, _ in _lib.PoseGraphParams._fields_}
@@ -131,6 +141,12 @@ class PoseGraphOptimizer:
                 raise _lib.NscError(f"PoseGraphOptimizer: unknown parameter {k!r}")
             setattr(p, k, int(v) if k in ("max_iteration", "max_pcg_iterations") else float(v))
         self.params = p
+
+    def _coarse(self, N):
+        """poses per aggregate for a graph of N poses; 0 without the coarse space"""
+        if self.coarse_block is None:
+            return 0
+        return max(8, -(-N // 64)) if self.coarse_block == "auto" else int(self.coarse_block)
 
     def _inputs(self, poses, edge_ij, measurements, information):
         dev = poses.device if isinstance(poses, torch.Tensor) else self.device
@@ -192,7 +208,8 @@ class PoseGraphOptimizer:
         """``optimize`` without the read-back: device tensors in (or numpy), a dict of device tensors out -- poses
         (N,4,4), stats (10,) as include/nsc.h orders them, cost_history (max_iteration + 1,), step0 (N,6) on request (the
         first delta; not written when max_iteration = 0), and with ``robust_scale`` (E,) chi2 (E,) = r^T Omega r and
-        weights (E,) of every edge at the final poses (one more launch; zeros for skipped edges).
+        weights (E,) of every edge at the final poses (one more launch; zeros for skipped edges), and with
+        ``coarse_block`` coarse_stats (2,) = [aggregates, outer steps whose coarse factor failed].
         Nothing is synchronised, so a call on device tensors can be captured.  ``poses_out`` may be ``poses``."""
         dev, X, e, Z, om = self._inputs(poses, edge_ij, measurements, information)
         N, E = int(X.shape[0]), int(e.shape[0])
@@ -220,16 +237,26 @@ class PoseGraphOptimizer:
         if c is not None:
             out["chi2"], out["weights"] = torch.empty(E, **f64), torch.empty(E, **f64)
         L = _lib.lib()
-        ws = torch.empty(max(int(L.nsc_posegraph_workspace_bytes(N, E, C.byref(self.params))), 1), dtype=torch.uint8,
-                         device=dev)
+        block = self._coarse(N)
+        if block:
+            if -(-N // block) > _lib.POSEGRAPH_MAX_AGGREGATES:
+                raise _lib.NscError(f"pose graph: coarse_block {block} gives {-(-N // block)} aggregates of {N} poses; "
+                                    f"at most {_lib.POSEGRAPH_MAX_AGGREGATES}")
+            out["coarse_stats"] = torch.empty(2, **f64)
+            need = L.nsc_posegraph_coarse_workspace_bytes(N, E, block)
+        else:
+            need = L.nsc_posegraph_workspace_bytes(N, E, C.byref(self.params))
+        ws = torch.empty(max(int(need), 1), dtype=torch.uint8, device=dev)
+        args = (_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E, _lib.ptr(fx), C.byref(self.params),
+                _lib.ptr(out["poses"]), _lib.ptr(out["stats"]), _lib.ptr(out["cost_history"]), _lib.ptr(out.get("step0")),
+                _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev), self.kernel, _lib.ptr(c), _lib.ptr(out.get("chi2")),
+                _lib.ptr(out.get("weights")))
         with torch.cuda.device(dev):
-            status = L.nsc_posegraph_optimize_robust(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E,
-                                                     _lib.ptr(fx), C.byref(self.params), _lib.ptr(out["poses"]),
-                                                     _lib.ptr(out["stats"]), _lib.ptr(out["cost_history"]),
-                                                     _lib.ptr(out.get("step0")), _lib.ptr(ws), int(ws.numel()),
-                                                     _lib.stream_ptr(dev), self.kernel, _lib.ptr(c),
-                                                     _lib.ptr(out.get("chi2")), _lib.ptr(out.get("weights")))
-        _lib.check(status, "nsc_posegraph_optimize_robust")
+            if block:
+                _lib.check(L.nsc_posegraph_optimize_coarse(*args, block, _lib.ptr(out["coarse_stats"])),
+                           "nsc_posegraph_optimize_coarse")
+            else:
+                _lib.check(L.nsc_posegraph_optimize_robust(*args), "nsc_posegraph_optimize_robust")
         return out
 
     def optimize(self, poses, edge_ij, measurements, information, fixed=None, robust_scale=None):
@@ -237,8 +264,9 @@ class PoseGraphOptimizer:
         rejected, pcg_iterations, converged, cost_history (iterations + 1,), and lambda, skipped, step; the costs are
         robust costs.  ``fixed``: (N,) mask of the poses that stay; None fixes pose 0.  ``robust_scale``: (E,) widths of
         this optimiser's kernel, 0 for the edges that stay quadratic; with it the result has chi2 (E,) and weights (E,)
-        as numpy arrays: a closure whose weight ends near 0 was rejected.  Reads the statistics back, so it
-        synchronises."""
+        as numpy arrays: a closure whose weight ends near 0 was rejected.  With ``coarse_block`` also coarse_aggregates
+        and coarse_failed (outer steps whose coarse factor failed and that ran with block-Jacobi alone).  Reads the
+        statistics back, so it synchronises."""
         out = self.optimize_device(poses, edge_ij, measurements, information, fixed, robust_scale=robust_scale)
         s = out["stats"].cpu().numpy()
         L = _lib
@@ -251,4 +279,7 @@ class PoseGraphOptimizer:
                    step=float(s[L.POSEGRAPH_STAT_STEP]), **{"lambda": float(s[L.POSEGRAPH_STAT_LAMBDA])})
         if robust_scale is not None:
             res.update(chi2=out["chi2"].cpu().numpy(), weights=out["weights"].cpu().numpy())
+        if "coarse_stats" in out:
+            cs = out["coarse_stats"].cpu().numpy()
+            res.update(coarse_aggregates=int(cs[0]), coarse_failed=int(cs[1]))
         return res

@@ -8,9 +8,12 @@ and, as a host baseline on the same residuals and Jacobians, Gauss-Newton with s
 normal equations (tests/posegraph_restatement.py builds them, edge by edge, in numpy: the linearisation time is
 reported apart from the solve time).  Prints the launch count and the inner iterations per outer step.
 usage: posegraph_probe.py [reps=10] [max_pcg_iterations=100] [max_iteration=20] [graph=1] [kernel=none] [width=3]
+                          [coarse_block=N|auto] [lambda0=X] [lambda_min=X] [host=0]
 ``graph=0`` leaves the capture out (for caps whose launch count makes a graph of several hundred thousand nodes).
 ``kernel`` = huber, cauchy or geman_mcclure puts that robust kernel, with ``width``, on the closure edges (the odometry
-edges stay quadratic) and asks for the per-edge chi2 and weights: one more launch.  The host baseline stays quadratic."""
+edges stay quadratic) and asks for the per-edge chi2 and weights: one more launch.  The host baseline stays quadratic.
+The arguments written name=value may stand anywhere: ``coarse_block`` switches the two-level preconditioner on (poses per
+aggregate, or auto), ``lambda0`` and ``lambda_min`` set the damping, ``host=0`` leaves the host baseline out."""
 import os
 import sys
 import time
@@ -26,12 +29,20 @@ import posegraph_restatement as P
 from neural_spectral_codec_amd import _lib as L, synth
 from neural_spectral_codec_amd.retrieval import PoseGraphOptimizer
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-max_pcg = int(sys.argv[2]) if len(sys.argv) > 2 else 100
-max_it = int(sys.argv[3]) if len(sys.argv) > 3 else 20
-with_graph = (int(sys.argv[4]) if len(sys.argv) > 4 else 1) != 0
-kernel = sys.argv[5] if len(sys.argv) > 5 and sys.argv[5] != "none" else None
-width = float(sys.argv[6]) if len(sys.argv) > 6 else 3.0
+named = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
+argv = sys.argv[:1] + [a for a in sys.argv[1:] if "=" not in a]
+reps = int(argv[1]) if len(argv) > 1 else 10
+max_pcg = int(argv[2]) if len(argv) > 2 else 100
+max_it = int(argv[3]) if len(argv) > 3 else 20
+with_graph = (int(argv[4]) if len(argv) > 4 else 1) != 0
+kernel = argv[5] if len(argv) > 5 and argv[5] != "none" else None
+width = float(argv[6]) if len(argv) > 6 else 3.0
+coarse_block = named.pop("coarse_block", None)
+if coarse_block not in (None, "auto"):
+    coarse_block = int(coarse_block)
+with_host = int(named.pop("host", 1)) != 0
+damping = {k: float(named.pop(k)) for k in ("lambda0", "lambda_min") if k in named}
+assert not named, f"unknown arguments {sorted(named)}"
 N, CLOSURES = 4541, 200
 
 rng = np.random.default_rng(0)
@@ -49,7 +60,11 @@ print(f"graph: {N} poses, {len(oe)} odometry edges, {len(ce)} closures; trajecto
       f"{P.trajectory_error(init, truth):.3f} m")
 
 dev = torch.device("cuda")
-opt = PoseGraphOptimizer(kernel=kernel, max_pcg_iterations=max_pcg, max_iteration=max_it)
+opt = PoseGraphOptimizer(kernel=kernel, coarse_block=coarse_block, max_pcg_iterations=max_pcg, max_iteration=max_it,
+                         **damping)
+block = opt._coarse(N)
+if block:
+    print(f"two-level preconditioner: {block} poses per aggregate, {-(-N // block)} aggregates; {damping}")
 args = [torch.from_numpy(x).to(dev) for x in (init, e, Z, Om)]
 fixed = torch.zeros(N, dtype=torch.uint8, device=dev)
 fixed[0] = 1
@@ -83,12 +98,14 @@ out = call()
 torch.cuda.synchronize()
 s = out["stats"].cpu().numpy()
 its, inner = int(s[L.POSEGRAPH_STAT_ITERATIONS]), int(s[L.POSEGRAPH_STAT_PCG_ITERATIONS])
-launches = 5 + 1 + 3 + max_it * (8 + 4 * max_pcg) + 1 + (kernel is not None)
+launches = 5 + 1 + 3 + max_it * ((14 + 5 * max_pcg) if block else (8 + 4 * max_pcg)) + 1 + (kernel is not None)
 print(f"optimize: {its} outer iterations ({int(s[L.POSEGRAPH_STAT_ACCEPTED])} accepted, "
       f"{int(s[L.POSEGRAPH_STAT_REJECTED])} rejected), {inner} inner iterations ({inner / max(its, 1):.1f} per outer "
       f"step), cost {s[L.POSEGRAPH_STAT_INITIAL_COST]:.6g} -> {s[L.POSEGRAPH_STAT_FINAL_COST]:.6g}, "
       f"converged {bool(s[L.POSEGRAPH_STAT_CONVERGED])}, "
       f"trajectory error {P.trajectory_error(out['poses'].cpu().numpy(), truth):.3f} m; {launches} launches per call")
+if block:
+    print(f"coarse factor failed in {int(out['coarse_stats'][1].item())} outer steps")
 if kernel is not None:
     w = out["weights"].cpu().numpy()[len(oe):]
     print(f"closure weights: min {w.min():.3g}, median {np.median(w):.3g}, max {w.max():.3g}")
@@ -111,6 +128,8 @@ if with_graph:
     print(f"replayed hipGraph: median {np.median(t):.2f} ms (min {t.min():.2f}, max {t.max():.2f}); bitwise the eager "
           "result")
 
+if not with_host:
+    sys.exit(0)
 # host baseline: Gauss-Newton, normal equations of the same residuals and Jacobians, scipy.sparse.linalg.spsolve
 X = init.copy()
 F = P.cost(X, e, Z, Om)
