@@ -777,6 +777,57 @@ int    nsc_posegraph_optimize_coarse(const double *poses, int32_t n_poses, const
                                      void *stream, int32_t kernel, const double *edge_scale, double *edge_chi2,
                                      double *edge_weight, int32_t coarse_block, double *coarse_stats);
 
+/* ------------------------------------------------------------------------------------------
+ * Marginal covariances of selected poses (nsc_posegraph_covariance; restated in tests/posegraph_cov_restatement.py):
+ * how uncertain pose j is relative to pose i, which is what a Mahalanobis gate on a loop closure needs.
+ *
+ * System.  The one nsc_posegraph_linearize_robust forms at `poses`: H = sum w J^T Omega J with `kernel` and `edge_scale`
+ *   as they are there, so a closure whose weight is ~ 0 adds no information.  The damping is lambda = 0.  The free poses
+ *   are those of the optimiser: not fixed, at least one counted edge, and a positive definite (here undamped) diagonal
+ *   block.  Sigma is the inverse of H restricted to the free poses, and zero elsewhere: the covariance of the right
+ *   perturbations delta_k in X_k Exp(delta_k), rotation first, in the gauge the fixed poses set.
+ * Output.  For the selected poses nodes[0 .. n_nodes): joint (n_nodes,n_nodes,6,6), joint[a,b] the block (nodes[a],
+ *   nodes[b]) of Sigma, taken from the six columns solved for nodes[b]: H x = e_{6 nodes[b] + c}, joint[a,b][:,c] =
+ *   x[nodes[a]].  It is not symmetrised.  residual (n_nodes,6) = |r| of each column at exit (|b| = 1: the relative
+ *   residual); iterations (n_nodes,6) int32; stats (NSC_POSEGRAPH_COV_STATS) int64 = [skipped edges, selected indices
+ *   outside [0, n_poses), selected poses that are not free, columns whose residual is above pcg_tolerance].
+ *   An index outside [0, n_poses) gives zero rows and columns and is counted; a pose that is not free has b = 0: its
+ *   columns run no iteration and are zero.  Duplicates are allowed.  At most NSC_POSEGRAPH_MAX_COV_NODES poses.
+ * Solver.  Each of the R = 6 n_nodes columns is a preconditioned conjugate gradient iteration of its own, from x = 0,
+ *   with the rules of the optimiser's inner loop: it ends at r.r <= pcg_tolerance^2 b.b, when p.Ap or r.z is not
+ *   positive, or at max_pcg_iterations; its alpha, beta, stop and count are its own, and a column that has stopped
+ *   changes nothing.  Of params only max_pcg_iterations and pcg_tolerance are used; all of it must be valid.
+ *   Preconditioner: block-Jacobi, and with coarse_block = L >= 2 the two-level one above (lambda = 0), its coarse matrix
+ *   factored once.  coarse_stats (2), nullable: [aggregates, 1 when that factor failed and B^-1 ran alone].
+ *   A column's bits do not depend on the other selected poses nor on its place among them, and two calls agree bitwise.
+ * Launches.  5 (lists; 2 without edges) + 1 (the final gather), and for n_poses > 0 and n_nodes > 0 in between
+ *   2 (linearise and pack, n_edges > 0) + 1 (assemble) + 2 (start) + max_pcg_iterations x 3 (n_edges > 0), or with
+ *   coarse_block 2 + 1 + 5 (coarse matrix) + 4 (start) + max_pcg_iterations x 4: a sequence that depends on the parameters,
+ *   n_poses > 0, n_edges > 0, n_nodes and coarse_block alone; 18 + 4 max_pcg_iterations (3 without the coarse space) above
+ *   NSC_POSEGRAPH_MAX_LAUNCHES is NSC_EUNSUPPORTED.  No host synchronisation, no memset or memcpy nodes: the call can be
+ *   captured.
+ * ------------------------------------------------------------------------------------------ */
+#define NSC_POSEGRAPH_MAX_COV_NODES 64
+#define NSC_POSEGRAPH_COV_TILE      16          /* consecutive poses one wave of the covariance kernels walks */
+#define NSC_POSEGRAPH_COV_STATS     4
+#define NSC_POSEGRAPH_COV_STAT_SKIPPED        0
+#define NSC_POSEGRAPH_COV_STAT_OUTSIDE        1
+#define NSC_POSEGRAPH_COV_STAT_NOT_FREE       2
+#define NSC_POSEGRAPH_COV_STAT_NOT_CONVERGED  3
+
+/* Bytes of workspace for nsc_posegraph_covariance; 0 for arguments the call would refuse: a negative size, n_nodes above
+ * NSC_POSEGRAPH_MAX_COV_NODES, coarse_block < 0 or == 1, more than NSC_POSEGRAPH_MAX_AGGREGATES aggregates. */
+size_t nsc_posegraph_covariance_workspace_bytes(int32_t n_poses, int32_t n_edges, int32_t n_nodes, int32_t coarse_block);
+/* nodes (n_nodes) int64 on the device.  NSC_EINVAL for a null or negative argument, a kernel id outside 0..3, invalid
+ * params, coarse_block < 0 or == 1; NSC_EUNSUPPORTED for n_nodes above NSC_POSEGRAPH_MAX_COV_NODES, too many aggregates or
+ * launches; NSC_EWORKSPACE for a workspace that is missing or too small: all before anything is launched. */
+int    nsc_posegraph_covariance(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
+                                const double *information, int32_t n_edges, const uint8_t *fixed,
+                                const NscPoseGraphParams *params, const int64_t *nodes, int32_t n_nodes, double *joint,
+                                double *residual, int32_t *iterations, int64_t *stats, void *ws, size_t ws_bytes,
+                                void *stream, int32_t kernel, const double *edge_scale, int32_t coarse_block,
+                                double *coarse_stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,9 @@ POSEGRAPH_MAX_AGGREGATES = 128                   # include/nsc.h NSC_POSEGRAPH_M
  POSEGRAPH_STAT_CONVERGED, POSEGRAPH_STAT_STEP) = range(POSEGRAPH_STATS)
 # include/nsc.h NSC_POSEGRAPH_KERNEL_*
 POSEGRAPH_KERNELS = {None: 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
+# include/nsc.h NSC_POSEGRAPH_MAX_COV_NODES, NSC_POSEGRAPH_COV_TILE, NSC_POSEGRAPH_COV_STATS and NSC_POSEGRAPH_COV_STAT_*
+POSEGRAPH_MAX_COV_NODES, POSEGRAPH_COV_TILE, POSEGRAPH_COV_STATS = 64, 16, 4
+POSEGRAPH_COV_STAT_NAMES = ("skipped", "outside", "not_free", "not_converged")
 
 GICP_MAX_KNN = 32
 # include/nsc.h NSC_GICP_MAX_PAIRS, NSC_GICP_MAX_CLOUDS, NSC_GICP_MAX_PREPARED_PAIRS: the largest batch of one call
@@ -229,6 +232,9 @@ SYMBOLS = {
     "nsc_posegraph_coarse_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "nsc_posegraph_optimize_coarse": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PoseGraphParams), _vp,
                                                 _vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "nsc_posegraph_covariance_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "nsc_posegraph_covariance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PoseGraphParams), _vp, _i32,
+                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp, _i32, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

@@ -1,6 +1,7 @@
 // nsc_posegraph.hip -- pose-graph optimisation: odometry edges and verified loop closures in, corrected poses out.
 // Float64 throughout.  The contract is stated in include/nsc.h (nsc_posegraph_optimize); tests/posegraph_restatement.py
-// restates it in numpy; DESIGN.md section 4.11 has the launch sequence and the measurements.
+// restates it in numpy; DESIGN.md section 4.11 has the launch sequence and the measurements.  nsc_posegraph_covariance
+// (marginal covariances of selected poses: PCG on many right-hand sides at once) has a section of its own below.
 //
 //   D = Z^-1 X_i^-1 X_j,  r = [Log_SO3(R_D); t_D],  F = sum r^T Omega r,  update X_k <- [R_k Exp(phi_k) | t_k + R_k rho_k]
 //   J_j = B = blockdiag(Jr^-1(r_phi), R_D),  J_i = -B Ad(A^-1) with A = X_i^-1 X_j
@@ -1185,6 +1186,445 @@ __global__ __launch_bounds__(TB) void pg_linearize_out_kernel(int nb_n, Buffers 
     }
 }
 
+// ---- marginal covariances: PCG on many right-hand sides ----------------------------------------------------------------
+//
+// nsc_posegraph_covariance solves H x = e for the R = 6 Q unit vectors of the selected poses, each an independent PCG.
+// One lane per right-hand side: the vectors x, r, z, p, A p are (N, 6, R_pad) with the right-hand side fastest, R_pad = R
+// rounded up to 64, and a workgroup owns a tile of CT consecutive nodes (an aggregate in the two coarse kernels) times one
+// chunk of 64 right-hand sides.  Its VW waves all work on the same 64 columns and share the tile's nodes, wave w taking
+// nodes w, w + VW, ...: with one wave a tile (measured on the 4 541-pose graph) every kernel was a chain of dependent trips
+// to memory, 100 to 140 us each, whatever the number of columns.  The node, its incident list and therefore every address
+// of hii / hjj / hij, chol, P and A_c^-1 are the same in all 64 lanes (scalar or broadcast loads); every vector load is 64
+// consecutive doubles.  Every dot product stays in its lane: a wave sums its nodes in ascending order, the first wave the VW
+// sums through the LDS in ascending order, and a scalar is one partial per (tile, right-hand side), or per (aggregate,
+// right-hand side) behind the prolong kernel; a consumer sums the partials of its column in the fixed order of
+// column_sum().  No cross-lane reduction, no floating-point atomics.  So a column's bits do not depend on which lane or
+// chunk it sits in, nor on what the other columns are.  Column state (r.z in two slots, b.b, r.r, stop_k, iterations) lives in
+// arrays of R_pad; the wave of tile 0 writes it in the direction kernel, with the stop_k and two-slot rules of the
+// optimiser's loop.  A lane whose column has stopped stores nothing; a wave all of whose columns have stopped returns.
+
+constexpr int CT = NSC_POSEGRAPH_COV_TILE;   // nodes per wave
+constexpr int VW = 8;                       // waves of a workgroup of the two coarse kernels: they share an aggregate's nodes
+constexpr int VB = VW * TB;
+
+struct Cov {                                 // the covariance call's part of the workspace, behind Buffers' and Coarse's
+    double *x, *r, *z, *p, *ap;              // (N,6,R_pad)
+    double *part_a, *part_rr, *part_rz;      // (max(tiles, aggregates), R_pad): p.Ap per tile; r.r and r.z per tile or aggregate
+    double *rc;                              // (nc, R_pad): P^T r
+    double *hp;                              // (E,78): the blocks of every edge, edge by edge
+    double *rz, *bb, *rr;                    // (2,R_pad), (R_pad), (R_pad)
+    int *stop_k, *iters;                     // (R_pad)
+    int R, R_pad, n_tiles;
+    size_t total;                            // bytes, everything in front included
+};
+
+__device__ __forceinline__ size_t cov_at(int n, int c, int Rp, int col) { return ((size_t)n * 6 + c) * Rp + col; }
+
+// The nb partials of one column, for all VW waves of a workgroup at once (they share their 64 columns), the same bits in
+// every wave of every workgroup of every kernel: wave w sums partials w, w + VW, ... in ascending order (four loads in
+// flight), then every wave sums the VW results in ascending order.  red: VW rows of the workgroup's LDS.
+__device__ __forceinline__ double column_sum(const double *part, int nb, int Rp, int col, double (*red)[TB])
+{
+    const int wave = threadIdx.x / TB, lane = threadIdx.x % TB;
+    double s = 0.0;
+    int t = wave;
+    for (; t + 3 * VW < nb; t += 4 * VW) {
+        const double a0 = part[(size_t)t * Rp + col], a1 = part[(size_t)(t + VW) * Rp + col],
+                     a2 = part[(size_t)(t + 2 * VW) * Rp + col], a3 = part[(size_t)(t + 3 * VW) * Rp + col];
+        s += a0;
+        s += a1;
+        s += a2;
+        s += a3;
+    }
+    for (; t < nb; t += VW) s += part[(size_t)t * Rp + col];
+    __syncthreads();                                         // whoever still reads red has finished
+    red[wave][lane] = s;
+    __syncthreads();
+    s = 0.0;
+#pragma unroll
+    for (int w = 0; w < VW; ++w) s += red[w][lane];
+    return s;
+}
+
+// the sums of two lane-local values over the VW waves, in ascending wave order; the result stands in wave 0.  red: 2 VW rows
+__device__ __forceinline__ void wave_sums(double &a, double &b, double (*red)[TB])
+{
+    const int wave = threadIdx.x / TB, lane = threadIdx.x % TB;
+    __syncthreads();
+    red[wave][lane] = a;
+    red[VW + wave][lane] = b;
+    __syncthreads();
+    if (wave != 0) return;
+    a = b = 0.0;
+#pragma unroll
+    for (int w = 0; w < VW; ++w) {
+        a += red[w][lane];
+        b += red[VW + w][lane];
+    }
+}
+
+// x = 0, r = e (column 6 q + c is the unit vector of entry c of pose nodes[q]; zero when that index is out of range or
+// the pose is not free, and in the padding), z = B^-1 r, p = z, A p = 0; partials of r.r and r.z per tile
+__global__ __launch_bounds__(VB) void pg_cov_init_kernel(int n_poses, const long long *__restrict__ nodes, Buffers b, Cov v)
+{
+    __shared__ double red[2 * VW][TB];
+    const int wave = threadIdx.x / TB, col = blockIdx.y * TB + threadIdx.x % TB, Rp = v.R_pad;
+    long long node = -1;
+    if (col < v.R) {
+        node = nodes[col / 6];
+        if (node < 0 || node >= n_poses || !b.free_node[node]) node = -1;
+    }
+    const int comp = col % 6;
+    double rr = 0.0, rz = 0.0;
+    const int lo = blockIdx.x * CT, hi = min(lo + CT, n_poses);
+    for (int n = lo + wave; n < hi; n += VW) {
+        double r[6], z[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < 6; ++c) r[c] = node == n && comp == c ? 1.0 : 0.0;
+        if (b.free_node[n]) {
+            double U[21];
+            for (int q = 0; q < 21; ++q) U[q] = b.chol[21 * (long long)n + q];
+            cholesky_solve6(U, r, z);
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const size_t at = cov_at(n, c, Rp, col);
+            v.x[at] = 0.0;
+            v.r[at] = r[c];
+            v.z[at] = z[c];
+            v.p[at] = z[c];
+            v.ap[at] = 0.0;
+            rr += r[c] * r[c];
+            rz += r[c] * z[c];
+        }
+    }
+    wave_sums(rr, rz, red);
+    if (wave != 0) return;
+    v.part_rr[(size_t)blockIdx.x * Rp + col] = rr;
+    v.part_rz[(size_t)blockIdx.x * Rp + col] = rz;
+}
+
+// one workgroup per chunk: b.b and r.z of the start from nb partials; a column with b = 0 runs no iteration
+__global__ __launch_bounds__(VB) void pg_cov_begin_kernel(int nb, Cov v)
+{
+    __shared__ double red[VW][TB];
+    const int col = blockIdx.x * TB + threadIdx.x % TB, Rp = v.R_pad;
+    const double bb = column_sum(v.part_rr, nb, Rp, col, red), rz = column_sum(v.part_rz, nb, Rp, col, red);
+    if (threadIdx.x >= TB) return;
+    v.bb[col] = bb;
+    v.rr[col] = bb;
+    v.rz[col] = rz;
+    v.rz[Rp + col] = 0.0;
+    v.iters[col] = 0;
+    v.stop_k[col] = bb > 0.0 && rz > 0.0 ? INT_MAX : 0;
+}
+
+// The blocks of every counted edge once more, edge by edge: hp (E,78) = [H_ii (21), H_jj (21), H_ij (36)].  The
+// linearisation keeps them structure-of-arrays for one lane per edge; read by a whole wave for ONE edge that layout is 57
+// cache lines a side (measured: 87 us a matvec on the 4 541-pose graph).  One lane per edge, once per call.
+__global__ __launch_bounds__(TB) void pg_cov_pack_kernel(int n_edges, Buffers b, double *__restrict__ hp)
+{
+    const int e = blockIdx.x * TB + threadIdx.x;
+    if (e >= n_edges || b.ei[e] < 0) return;
+    const long long E = n_edges;
+    double *out = hp + 78LL * e;
+    for (int q = 0; q < 21; ++q) {
+        out[q] = b.hii[q * E + e];
+        out[21 + q] = b.hjj[q * E + e];
+    }
+    for (int q = 0; q < 36; ++q) out[42 + q] = b.hij[q * E + e];
+}
+
+// A p on the free nodes of the tile, gathered on the node side: for every incident (edge, side) H_ss p_n + H_st p_other,
+// straight from the packed edge blocks; partial of p.Ap
+__global__ __launch_bounds__(VB) void pg_cov_matvec_kernel(int n_poses, const int *__restrict__ row_ptr,
+                                                           const int *__restrict__ list, const int *__restrict__ ei,
+                                                           const int *__restrict__ ej, const int *__restrict__ free_node,
+                                                           const double *__restrict__ hp, Cov v, int k)
+{
+    __shared__ double red[2 * VW][TB];
+    const int wave = threadIdx.x / TB, col = blockIdx.y * TB + threadIdx.x % TB, Rp = v.R_pad;
+    const bool active = k < v.stop_k[col];
+    if (!__any(active)) return;                              // the same columns in every wave: the workgroup leaves as one
+    const double *__restrict__ P = v.p;
+    double pap = 0.0, unused = 0.0;
+    const int lo = blockIdx.x * CT, hi = min(lo + CT, n_poses);
+    for (int n = lo + wave; n < hi; n += VW) {
+        if (!free_node[n]) continue;
+        double pn[6], y[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < 6; ++c) pn[c] = P[cov_at(n, c, Rp, col)];
+        for (int a = row_ptr[n]; a < row_ptr[n + 1]; ++a) {
+            const int code = list[a], e = code >> 1, side = code & 1;
+            const int m = side ? ei[e] : ej[e];
+            const double *__restrict__ hs = hp + 78LL * e + (side ? 21 : 0), *__restrict__ hx = hp + 78LL * e + 42;
+            double pm[6];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) pm[c] = P[cov_at(m, c, Rp, col)];
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    // side 0: this node is i, y_i += H_ij p_j;  side 1: this node is j, y_j += H_ij^T p_i
+                    y[r] += hx[side ? 6 * c + r : 6 * r + c] * pm[c];
+                    if (c >= r) {
+                        const double h = hs[tri(r, c)];
+                        y[r] += h * pn[c];
+                        if (c > r) y[c] += h * pn[r];
+                    }
+                }
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            if (active) v.ap[cov_at(n, c, Rp, col)] = y[c];
+            pap += pn[c] * y[c];
+        }
+    }
+    wave_sums(pap, unused, red);
+    if (wave == 0 && active) v.part_a[(size_t)blockIdx.x * Rp + col] = pap;
+}
+
+// alpha = r.z / p.Ap;  x += alpha p;  r -= alpha A p;  z = B^-1 r on node n, one column per lane; adds to r.r and r.z
+__device__ __forceinline__ void cov_step_node(const Buffers &b, const Cov &v, int n, int col, double alpha, bool active,
+                                              double r[6], double z[6])
+{
+    const int Rp = v.R_pad;
+    double U[21];
+    for (int q = 0; q < 21; ++q) U[q] = b.chol[21 * (long long)n + q];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        const size_t at = cov_at(n, c, Rp, col);
+        const double x = v.x[at] + alpha * v.p[at];
+        r[c] = v.r[at] - alpha * v.ap[at];
+        if (active) {
+            v.x[at] = x;
+            v.r[at] = r[c];
+        }
+    }
+    cholesky_solve6(U, r, z);
+    if (active) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) v.z[cov_at(n, c, Rp, col)] = z[c];
+    }
+}
+
+__device__ __forceinline__ double cov_alpha(const Cov &v, int k, int col, double (*red)[TB])
+{
+    const double pap = column_sum(v.part_a, v.n_tiles, v.R_pad, col, red);
+    return pap > 0.0 ? v.rz[(k & 1) * v.R_pad + col] / pap : 0.0;
+}
+
+// the step on the free nodes of the tile; partials of r.r and r.z
+__global__ __launch_bounds__(VB) void pg_cov_step_kernel(int n_poses, Buffers b, Cov v, int k)
+{
+    __shared__ double red[2 * VW][TB];
+    const int wave = threadIdx.x / TB, col = blockIdx.y * TB + threadIdx.x % TB, Rp = v.R_pad;
+    const bool active = k < v.stop_k[col];
+    if (!__any(active)) return;                              // the same columns in every wave: the workgroup leaves as one
+    const double alpha = cov_alpha(v, k, col, red);
+    double rr = 0.0, rz = 0.0;
+    const int lo = blockIdx.x * CT, hi = min(lo + CT, n_poses);
+    for (int n = lo + wave; n < hi; n += VW) {
+        if (!b.free_node[n]) continue;
+        double r[6], z[6];
+        cov_step_node(b, v, n, col, alpha, active, r, z);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            rr += r[c] * r[c];
+            rz += r[c] * z[c];
+        }
+    }
+    wave_sums(rr, rz, red);
+    if (wave == 0 && active) {
+        v.part_rr[(size_t)blockIdx.x * Rp + col] = rr;
+        v.part_rz[(size_t)blockIdx.x * Rp + col] = rz;
+    }
+}
+
+// beta = r.z (new) / r.z (old);  p = z + beta p on the tile; the first wave of tile 0 counts the iteration of its columns, keeps
+// r.r and ends a column at r.r <= tol^2 b.b, at p.Ap <= 0 or at r.z <= 0.  nb_b partials of r.r and of r.z
+__global__ __launch_bounds__(VB) void pg_cov_direction_kernel(int n_poses, Buffers b, Cov v, int k, double tol2, int nb_b)
+{
+    __shared__ double red[VW][TB];
+    const int wave = threadIdx.x / TB, col = blockIdx.y * TB + threadIdx.x % TB, Rp = v.R_pad;
+    const bool active = k < v.stop_k[col];
+    if (!__any(active)) return;                              // the same columns in every wave: the workgroup leaves as one
+    const double pap = column_sum(v.part_a, v.n_tiles, Rp, col, red), rr = column_sum(v.part_rr, nb_b, Rp, col, red),
+                 rz = column_sum(v.part_rz, nb_b, Rp, col, red);
+    const double beta = rz / v.rz[(k & 1) * Rp + col];
+    const int lo = blockIdx.x * CT, hi = min(lo + CT, n_poses);
+    for (int n = lo + wave; n < hi; n += VW) {
+        if (!b.free_node[n]) continue;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const size_t at = cov_at(n, c, Rp, col);
+            const double p = v.z[at] + beta * v.p[at];
+            if (active) v.p[at] = p;
+        }
+    }
+    if (blockIdx.x == 0 && wave == 0 && active) {
+        v.rz[((k + 1) & 1) * Rp + col] = rz;
+        v.rr[col] = rr;
+        v.iters[col] += 1;
+        if (!(pap > 0.0) || rr <= tol2 * v.bb[col] || !(rz > 0.0)) v.stop_k[col] = k + 1;
+    }
+}
+
+// One workgroup of VW waves per (aggregate, chunk), every wave on the same 64 columns: wave w takes the aggregate's nodes
+// w, w + VW, ...  k >= 0: the step of inner iteration k on the aggregate's free nodes; k < 0: the start, r as the init
+// kernel left it.  Either way the aggregate's six rows of r_c = P^T r: a wave sums its nodes in ascending order, the first
+// wave the VW sums in the LDS in ascending order.
+__global__ __launch_bounds__(VB) void pg_cov_restrict_kernel(int n_poses, Buffers b, Coarse c, Cov v, int k)
+{
+    __shared__ double red[VW][6][TB];
+    const int wave = threadIdx.x / TB, lane = threadIdx.x % TB;
+    const int col = blockIdx.y * TB + lane, Rp = v.R_pad;
+    const bool active = k < 0 || k < v.stop_k[col];
+    if (!__any(active)) return;                              // the same columns in every wave: the workgroup leaves as one
+    const double alpha = k >= 0 ? cov_alpha(v, k, col, reinterpret_cast<double(*)[TB]>(red)) : 0.0;
+    double rc[6] = {0, 0, 0, 0, 0, 0};
+    const int lo = blockIdx.x * c.L, hi = min(lo + c.L, n_poses);
+    for (int n = lo + wave; n < hi; n += VW) {
+        if (!b.free_node[n]) continue;
+        double r[6], z[6];
+        if (k >= 0) {
+            cov_step_node(b, v, n, col, alpha, active, r, z);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) r[q] = v.r[cov_at(n, q, Rp, col)];
+        }
+        const double *T = c.t + 36 * (long long)n;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int q = 0; q < 6; ++q) rc[q] += T[6 * i + q] * r[i];
+    }
+    __syncthreads();                                         // the sum for alpha has been read by every wave
+#pragma unroll
+    for (int q = 0; q < 6; ++q) red[wave][q][lane] = rc[q];
+    __syncthreads();
+    if (wave == 0 && active) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            double s = 0.0;
+#pragma unroll
+            for (int w = 0; w < VW; ++w) s += red[w][q][lane];
+            v.rc[(6 * (size_t)blockIdx.x + q) * Rp + col] = s;
+        }
+    }
+}
+
+// One workgroup of VW waves per (aggregate, chunk): its six rows of y = A_c^-1 r_c (none when the factor failed: B^-1
+// alone; wave w sums entries w, w + VW, ... of each row, every wave the VW sums), z += P y on its free nodes, p = z at
+// the start (k < 0), and the aggregate's partials of r.r and r.z, summed as the restrict kernel sums
+__global__ __launch_bounds__(VB) void pg_cov_prolong_kernel(int n_poses, Buffers b, Coarse c, Cov v, int k)
+{
+    __shared__ double red[VW][6][TB];
+    const int wave = threadIdx.x / TB, lane = threadIdx.x % TB;
+    const int col = blockIdx.y * TB + lane, Rp = v.R_pad;
+    const bool active = k < 0 || k < v.stop_k[col];
+    if (!__any(active)) return;                              // the same columns in every wave: the workgroup leaves as one
+    const bool coarse = c.cs->ok;
+    double y[6] = {0, 0, 0, 0, 0, 0};
+    if (coarse) {
+        const double *row = c.ainv + 6LL * blockIdx.x * c.nc;
+        for (int i = wave; i < c.nc; i += VW) {
+            const double rc = v.rc[(size_t)i * Rp + col];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) y[q] += row[(long long)q * c.nc + i] * rc;
+        }
+#pragma unroll
+        for (int q = 0; q < 6; ++q) red[wave][q][lane] = y[q];
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            y[q] = 0.0;
+#pragma unroll
+            for (int w = 0; w < VW; ++w) y[q] += red[w][q][lane];
+        }
+        __syncthreads();                                     // red is used again below
+    }
+    double rr = 0.0, rz = 0.0;
+    const int lo = blockIdx.x * c.L, hi = min(lo + c.L, n_poses);
+    for (int n = lo + wave; n < hi; n += VW) {
+        if (!b.free_node[n]) continue;
+        const double *T = c.t + 36 * (long long)n;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const size_t at = cov_at(n, i, Rp, col);
+            double z = v.z[at];
+            if (coarse) {
+                double s = 0.0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) s += T[6 * i + q] * y[q];
+                z += s;
+                if (active) v.z[at] = z;
+            }
+            if (k < 0) v.p[at] = z;
+            const double r = v.r[at];
+            rr += r * r;
+            rz += r * z;
+        }
+    }
+    red[wave][0][lane] = rr;
+    red[wave][1][lane] = rz;
+    __syncthreads();
+    if (wave == 0 && active) {
+        rr = rz = 0.0;
+#pragma unroll
+        for (int w = 0; w < VW; ++w) {
+            rr += red[w][0][lane];
+            rz += red[w][1][lane];
+        }
+        v.part_rr[(size_t)blockIdx.x * Rp + col] = rr;
+        v.part_rz[(size_t)blockIdx.x * Rp + col] = rz;
+    }
+}
+
+// One wave per selected pose b: joint[a, b] = rows of nodes[a] of the six columns solved for nodes[b], zero where
+// nodes[a] is out of range; residual and iterations of those columns.  The first wave also counts: skipped edges, selected
+// indices outside [0, N), selected poses that are not free, columns that did not reach the tolerance.  solved = 0 (no
+// pose at all): nothing was solved and every output is zero.
+__global__ __launch_bounds__(TB) void pg_cov_final_kernel(int n_poses, int n_nodes, const long long *__restrict__ nodes,
+                                                          Buffers b, Cov v, int solved, double tol2,
+                                                          double *__restrict__ joint, double *__restrict__ residual,
+                                                          int *__restrict__ iterations, long long *__restrict__ stats,
+                                                          const PgCoarse *__restrict__ cs, int n_agg,
+                                                          double *__restrict__ coarse_stats)
+{
+    const int qb = blockIdx.x, lane = threadIdx.x, Rp = v.R_pad;
+    if (qb < n_nodes && lane < 36) {
+        const int r = lane / 6, c = lane % 6;
+        for (int qa = 0; qa < n_nodes; ++qa) {
+            const long long na = nodes[qa];
+            const bool in = solved && na >= 0 && na < n_poses;
+            joint[((long long)qa * n_nodes + qb) * 36 + lane] = in ? v.x[cov_at((int)na, r, Rp, 6 * qb + c)] : 0.0;
+        }
+    }
+    if (qb < n_nodes && lane < 6) {
+        residual[6 * qb + lane] = solved ? sqrt(v.rr[6 * qb + lane]) : 0.0;
+        iterations[6 * qb + lane] = solved ? v.iters[6 * qb + lane] : 0;
+    }
+    if (qb != 0 || lane != 0) return;
+    long long outside = 0, not_free = 0, open = 0;
+    for (int q = 0; q < n_nodes; ++q) {
+        const long long n = nodes[q];
+        if (n < 0 || n >= n_poses)
+            ++outside;
+        else if (!solved || !b.free_node[n])
+            ++not_free;
+    }
+    for (int j = 0; solved && j < 6 * n_nodes; ++j) open += !(v.rr[j] <= tol2 * v.bb[j]);
+    stats[NSC_POSEGRAPH_COV_STAT_SKIPPED] = b.st->skipped;
+    stats[NSC_POSEGRAPH_COV_STAT_OUTSIDE] = outside;
+    stats[NSC_POSEGRAPH_COV_STAT_NOT_FREE] = not_free;
+    stats[NSC_POSEGRAPH_COV_STAT_NOT_CONVERGED] = open;
+    if (coarse_stats) {
+        coarse_stats[0] = n_agg;
+        coarse_stats[1] = cs && solved ? cs->failed : 0;
+    }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------
 
 inline int blocks_of(long long n) { return (int)((n + TB - 1) / TB); }
@@ -1357,9 +1797,132 @@ int optimize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const
     return launch_status();
 }
 
+// the covariance call's regions, carved behind the `base` bytes of Buffers and Coarse; ws = nullptr: the size only
+Cov cov_buffers(void *ws, size_t base, size_t N, size_t E, int Q, int n_agg)
+{
+    Carver c = {reinterpret_cast<uintptr_t>(ws), base};
+    Cov v;
+    const size_t R = 6 * (size_t)Q, Rp = (R + TB - 1) / TB * TB, tiles = (N + CT - 1) / CT;
+    const size_t rows = tiles > (size_t)n_agg ? tiles : (size_t)n_agg;
+    v.x = c.take<double>(6 * N * Rp);
+    v.r = c.take<double>(6 * N * Rp);
+    v.z = c.take<double>(6 * N * Rp);
+    v.p = c.take<double>(6 * N * Rp);
+    v.ap = c.take<double>(6 * N * Rp);
+    v.part_a = c.take<double>(rows * Rp);
+    v.part_rr = c.take<double>(rows * Rp);
+    v.part_rz = c.take<double>(rows * Rp);
+    v.rc = c.take<double>(6 * (size_t)n_agg * Rp);
+    v.hp = c.take<double>(78 * E);
+    v.rz = c.take<double>(2 * Rp);
+    v.bb = c.take<double>(Rp);
+    v.rr = c.take<double>(Rp);
+    v.stop_k = c.take<int>(Rp);
+    v.iters = c.take<int>(Rp);
+    v.R = (int)R;
+    v.R_pad = (int)Rp;
+    v.n_tiles = (int)tiles;
+    v.total = c.o;
+    return v;
+}
+
+// the covariance call's three layouts; false when the coarse space has too many aggregates
+bool cov_layout(void *ws, int N, int E, int Q, int L, Buffers &b, Coarse &c, Cov &v)
+{
+    const long long n_agg = L ? aggregates_of(N, L) : 0;
+    if (n_agg > NSC_POSEGRAPH_MAX_AGGREGATES) return false;
+    b = buffers(ws, N, E);
+    c = coarse_buffers(ws, b.total, N, L, (int)n_agg);
+    v = cov_buffers(ws, L ? c.total : b.total, N, E, Q, (int)n_agg);
+    return true;
+}
+
+bool cov_sizes_ok(int32_t n_poses, int32_t n_edges, int32_t n_nodes, int32_t coarse_block)
+{
+    return n_poses >= 0 && n_edges >= 0 && n_edges <= NSC_POSEGRAPH_MAX_EDGES && n_nodes >= 0 && coarse_block >= 0 &&
+           coarse_block != 1;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t nsc_posegraph_covariance_workspace_bytes(int32_t n_poses, int32_t n_edges, int32_t n_nodes, int32_t coarse_block)
+{
+    if (!cov_sizes_ok(n_poses, n_edges, n_nodes, coarse_block) || n_nodes > NSC_POSEGRAPH_MAX_COV_NODES) return 0;
+    Buffers b;
+    Coarse c;
+    Cov v;
+    return cov_layout(nullptr, n_poses, n_edges, n_nodes, coarse_block, b, c, v) ? v.total : 0;
+}
+
+int nsc_posegraph_covariance(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
+                             const double *information, int32_t n_edges, const uint8_t *fixed,
+                             const NscPoseGraphParams *params, const int64_t *nodes, int32_t n_nodes, double *joint,
+                             double *residual, int32_t *iterations, int64_t *stats, void *ws, size_t ws_bytes,
+                             void *stream, int32_t kernel, const double *edge_scale, int32_t coarse_block,
+                             double *coarse_stats)
+{
+    if (!cov_sizes_ok(n_poses, n_edges, n_nodes, coarse_block) || !params || !params_ok(params) || !kernel_ok(kernel))
+        return NSC_EINVAL;
+    if (!stats) return NSC_EINVAL;
+    if (n_poses > 0 && (!poses || !fixed)) return NSC_EINVAL;
+    if (n_edges > 0 && (!edge_ij || !measurements || !information)) return NSC_EINVAL;
+    if (n_nodes > 0 && (!nodes || !joint || !residual || !iterations)) return NSC_EINVAL;
+    if (n_nodes > NSC_POSEGRAPH_MAX_COV_NODES) return NSC_EUNSUPPORTED;
+    const int L = coarse_block;
+    // per inner iteration 3 launches, 4 with the coarse space; at most 18 around the loop
+    if ((L ? 4LL : 3LL) * params->max_pcg_iterations + 18 > NSC_POSEGRAPH_MAX_LAUNCHES) return NSC_EUNSUPPORTED;
+    Buffers b;
+    Coarse c;
+    Cov v;
+    if (!cov_layout(ws, n_poses, n_edges, n_nodes, L, b, c, v)) return NSC_EUNSUPPORTED;
+    if (!ws || ws_bytes < v.total) return NSC_EWORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int N = n_poses, E = n_edges, Q = n_nodes, gn = blocks_of(N), ge = blocks_of(E), ga = c.n_agg;
+    const double tol2 = params->pcg_tolerance * params->pcg_tolerance;
+    const dim3 tiles(v.n_tiles, v.R_pad / TB), aggs(ga, v.R_pad / TB);
+    const long long *sel = reinterpret_cast<const long long *>(nodes);
+    const bool solve = N > 0 && Q > 0;
+
+    build_lists(s, edge_ij, N, E, b);        // the state zeroed: done = 0 and lambda = 0, the undamped system
+    if (solve) {
+        if (E > 0) {
+            hipLaunchKernelGGL(pg_linearize_kernel, dim3(ge), dim3(TB), 0, s, poses, measurements, information, E, b,
+                               nullptr, 0, kernel, edge_scale, nullptr);
+            hipLaunchKernelGGL(pg_cov_pack_kernel, dim3(ge), dim3(TB), 0, s, E, b, v.hp);
+        }
+        hipLaunchKernelGGL(pg_assemble_kernel, dim3(gn), dim3(TB), 0, s, N, E, fixed, b, b.g, b.blocks, 1);
+        if (L) {
+            nsc_fill_u32(s, c.cs, 0u, (long long)(sizeof(PgCoarse) / 4));
+            hipLaunchKernelGGL(pg_coarse_basis_kernel, dim3(gn), dim3(TB), 0, s, poses, N, b, c);
+            hipLaunchKernelGGL(pg_coarse_galerkin_kernel, dim3(ga * ga), dim3(TB), 0, s, N, E, b, c);
+            hipLaunchKernelGGL(pg_coarse_factor_kernel, dim3(1), dim3(CB), 0, s, b, c);
+            hipLaunchKernelGGL(pg_coarse_invert_kernel, dim3(c.nc), dim3(TB), 0, s, b, c);
+        }
+        hipLaunchKernelGGL(pg_cov_init_kernel, tiles, dim3(VB), 0, s, N, sel, b, v);
+        if (L) {
+            hipLaunchKernelGGL(pg_cov_restrict_kernel, aggs, dim3(VB), 0, s, N, b, c, v, -1);
+            hipLaunchKernelGGL(pg_cov_prolong_kernel, aggs, dim3(VB), 0, s, N, b, c, v, -1);
+        }
+        hipLaunchKernelGGL(pg_cov_begin_kernel, dim3(v.R_pad / TB), dim3(VB), 0, s, L ? ga : v.n_tiles, v);
+        for (int k = 0; k < params->max_pcg_iterations && E > 0; ++k) {
+            hipLaunchKernelGGL(pg_cov_matvec_kernel, tiles, dim3(VB), 0, s, N, b.row_ptr, b.list, b.ei, b.ej, b.free_node,
+                               v.hp, v, k);
+            if (L) {
+                hipLaunchKernelGGL(pg_cov_restrict_kernel, aggs, dim3(VB), 0, s, N, b, c, v, k);
+                hipLaunchKernelGGL(pg_cov_prolong_kernel, aggs, dim3(VB), 0, s, N, b, c, v, k);
+            } else {
+                hipLaunchKernelGGL(pg_cov_step_kernel, tiles, dim3(VB), 0, s, N, b, v, k);
+            }
+            hipLaunchKernelGGL(pg_cov_direction_kernel, tiles, dim3(VB), 0, s, N, b, v, k, tol2, L ? ga : v.n_tiles);
+        }
+    }
+    hipLaunchKernelGGL(pg_cov_final_kernel, dim3(Q > 0 ? Q : 1), dim3(TB), 0, s, N, Q, sel, b, v, solve ? 1 : 0, tol2, joint,
+                       residual, iterations, reinterpret_cast<long long *>(stats), L && solve ? c.cs : nullptr, ga,
+                       coarse_stats);
+    return launch_status();
+}
 
 void nsc_posegraph_default_params(NscPoseGraphParams *p)
 {

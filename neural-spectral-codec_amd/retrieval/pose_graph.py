@@ -22,8 +22,17 @@ Definition (the contract nsc_posegraph_optimize and tests/posegraph_restatement.
                    geman_mcclure  rho = c^2 s / (c^2 + s)                         w = (c^2 / (c^2 + s))^2
                  an edge whose width is not finite and positive is quadratic (rho = s, w = 1): give odometry edges 0
 
+    covariance   Sigma = the inverse, over the free poses, of the undamped H at the given poses (robust weights included):
+                 the covariance of the right perturbations delta_k in X_k Exp(delta_k), in the gauge the fixed poses set.
+                 ``PoseGraphOptimizer.covariance`` returns the joint blocks of selected poses, each column a conjugate-
+                 gradient solve of its own, all columns in one batch on the device
+
 Edges with i == j or an index outside [0, N) are skipped and counted.  Residual rotations beyond 179 degrees are out of
-scope.  Marginal covariances, 2-D graphs and g2o files are not part of this module.
+scope.  2-D graphs and g2o files are not part of this module.
+
+Gating a closure before it enters the graph: ``TwoStageRetrieval.query`` -> ``closure_edges`` (Z, Omega of each verified
+candidate) -> ``PoseGraphOptimizer.covariance`` on the graph so far, with nodes = [query, candidates...] -> per candidate
+``relative_covariance`` of the pair's blocks -> ``closure_mahalanobis`` against a chi^2 quantile at 6 degrees of freedom.
 
 A false closure that passed geometric verification keeps weight 1 under the quadratic cost and bends the whole
 trajectory; with ``kernel="cauchy"`` and a width of about 3 on the closure edges it ends with a weight below 1e-3, and
@@ -109,6 +118,40 @@ def closure_edges(query_index, candidates):
     m = len(e)
     return (np.asarray(e, np.int64).reshape(m, 2), np.asarray(Z, np.float64).reshape(m, 4, 4),
             np.asarray(om, np.float64).reshape(m, 6, 6))
+
+
+def _log_so3(R):
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = float(np.linalg.norm(v))
+    return v if s < 1e-12 else v * (np.arctan2(s, 0.5 * (np.trace(R) - 1.0)) / s)
+
+
+def relative_covariance(joint_pair, X_i, X_j):
+    """The covariance of A = X_i^-1 X_j from the joint marginal of the two poses: ``joint_pair`` (2,2,6,6) is
+    ``PoseGraphOptimizer.covariance``'s ``joint`` restricted to (i, j), in that order, i.e. the covariance of the right
+    perturbations (delta_i, delta_j) in X_k Exp(delta_k).  To first order X_i^-1 X_j moves by the right perturbation
+    delta_A = delta_j - Ad(A^-1) delta_i (this module's Jacobians J_j and J_i with B = I), so Sigma_rel = G Sigma G^T
+    with G = [-Ad(A^-1), I].  The block is symmetrised first.  When one of the two poses is fixed its blocks are zero
+    and Sigma_rel is the other pose's marginal, carried over.  -> (6,6), rotation first"""
+    S = np.asarray(joint_pair, np.float64).reshape(2, 2, 6, 6).transpose(0, 2, 1, 3).reshape(12, 12)
+    S = 0.5 * (S + S.T)
+    A = _inverse(np.asarray(X_i, np.float64).reshape(4, 4)) @ np.asarray(X_j, np.float64).reshape(4, 4)
+    G = np.concatenate([-adjoint(_inverse(A)), np.eye(6)], axis=1)
+    return G @ S @ G.T
+
+
+def closure_mahalanobis(Z, Omega, X_i, X_j, sigma_rel):
+    """The gate of a closure candidate (i, j) with measurement ``Z`` ~ X_i^-1 X_j and information ``Omega`` (6,6), both as
+    ``closure_edges`` returns them, against the graph *without* that closure: with r = [Log_SO3(R_D); t_D], D = Z^-1
+    X_i^-1 X_j, this module's residual, and ``sigma_rel`` = ``relative_covariance`` of the two poses,
+    d^2 = r^T (Omega^-1 + Sigma_rel)^-1 r.  For a true closure d^2 follows a chi^2 distribution with 6 degrees of
+    freedom: compare it with a quantile, 12.59 for 95 %, 16.81 for 99 %, 22.46 for 99.9 %.  -> float"""
+    D = _inverse(np.asarray(Z, np.float64).reshape(4, 4)) @ _inverse(np.asarray(X_i, np.float64).reshape(4, 4)) @ \
+        np.asarray(X_j, np.float64).reshape(4, 4)
+    r = np.concatenate([_log_so3(D[:3, :3]), D[:3, 3]])
+    W = np.asarray(Omega, np.float64).reshape(6, 6)
+    S = np.linalg.inv(0.5 * (W + W.T)) + np.asarray(sigma_rel, np.float64).reshape(6, 6)
+    return float(r @ np.linalg.solve(S, r))
 
 
 def _f64(a, dev, shape):
@@ -214,17 +257,7 @@ class PoseGraphOptimizer:
         dev, X, e, Z, om = self._inputs(poses, edge_ij, measurements, information)
         N, E = int(X.shape[0]), int(e.shape[0])
         c = self._scale(robust_scale, dev, E)
-        if fixed is None:
-            fx = torch.zeros(N, dtype=torch.uint8, device=dev)
-            fx[:1] = 1
-        else:
-            fx = fixed if isinstance(fixed, torch.Tensor) else torch.from_numpy(
-                np.ascontiguousarray((np.asarray(fixed) != 0).astype(np.uint8)))
-            if fx.dtype != torch.uint8:                      # a uint8 device tensor is used as it is: no launch
-                fx = fx != 0
-            fx = fx.to(device=dev, dtype=torch.uint8).reshape(-1).contiguous()
-            if int(fx.numel()) != N:
-                raise _lib.NscError("pose graph: fixed must have one entry per pose")
+        fx = self._fixed(fixed, dev, N)
         f64 = dict(dtype=torch.float64, device=dev)
         out = dict(poses=torch.empty((N, 4, 4), **f64) if poses_out is None else poses_out,
                    stats=torch.empty(_lib.POSEGRAPH_STATS, **f64),
@@ -258,6 +291,87 @@ class PoseGraphOptimizer:
             else:
                 _lib.check(L.nsc_posegraph_optimize_robust(*args), "nsc_posegraph_optimize_robust")
         return out
+
+    def _fixed(self, fixed, dev, N):
+        """the (N,) uint8 mask on the device; None fixes pose 0"""
+        if fixed is None:
+            fx = torch.zeros(N, dtype=torch.uint8, device=dev)
+            fx[:1] = 1
+            return fx
+        fx = fixed if isinstance(fixed, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray((np.asarray(fixed) != 0).astype(np.uint8)))
+        if fx.dtype != torch.uint8:                          # a uint8 device tensor is used as it is: no launch
+            fx = fx != 0
+        fx = fx.to(device=dev, dtype=torch.uint8).reshape(-1).contiguous()
+        if int(fx.numel()) != N:
+            raise _lib.NscError("pose graph: fixed must have one entry per pose")
+        return fx
+
+    def covariance_device(self, poses, edge_ij, measurements, information, nodes, fixed=None, robust_scale=None):
+        """Marginal covariances of the poses ``nodes`` (Q,) at ``poses`` (include/nsc.h nsc_posegraph_covariance): Sigma
+        is the inverse, over the free poses, of the H that ``linearize`` forms with this optimiser's ``kernel`` and the
+        call's ``robust_scale`` -- the covariance of the right perturbations delta_k in X_k Exp(delta_k), rotation first,
+        in the gauge the fixed poses set.  Give it the poses ``optimize`` returned.  -> dict of device tensors: joint
+        (Q,Q,6,6) with joint[a,b] = Sigma[nodes[a], nodes[b]] (from the columns solved for nodes[b]; not symmetrised),
+        residual (Q,6) = |r| of each column's PCG at exit, iterations (Q,6) int32, stats (4,) int64 = [skipped edges, indices outside
+        [0,N), selected poses that are not free, columns above ``pcg_tolerance``], and with ``coarse_block``
+        coarse_stats (2,).  Every column is a conjugate-gradient solve of its own, capped by ``max_pcg_iterations`` and
+        ended at ``pcg_tolerance``: for covariances set the tolerance tight (1e-10) and, on a trajectory, a
+        ``coarse_block``.  ``nodes`` as a device int64 tensor is used as it is; nothing is synchronised, so the call can
+        be captured.  An index outside [0,N) in a device tensor gives zero rows and columns and is counted."""
+        # what the host can refuse, before anything touches the device
+        N = int(poses.numel() if isinstance(poses, torch.Tensor) else np.asarray(poses).size) // 16
+        sel = nodes.reshape(-1) if isinstance(nodes, torch.Tensor) else np.asarray(nodes, np.int64).reshape(-1)
+        Q = int(sel.numel() if isinstance(sel, torch.Tensor) else sel.size)
+        if Q > _lib.POSEGRAPH_MAX_COV_NODES:
+            raise _lib.NscError(f"pose graph: covariances of at most {_lib.POSEGRAPH_MAX_COV_NODES} poses per call "
+                                f"(got {Q})")
+        if not (isinstance(sel, torch.Tensor) and sel.is_cuda) and Q and (int(sel.min()) < 0 or int(sel.max()) >= N):
+            raise _lib.NscError(f"pose graph: covariance nodes must lie in [0, {N}) (got {int(sel.min())} .. "
+                                f"{int(sel.max())})")
+        dev, X, e, Z, om = self._inputs(poses, edge_ij, measurements, information)
+        E = int(e.shape[0])
+        c = self._scale(robust_scale, dev, E)
+        fx = self._fixed(fixed, dev, N)
+        sel = (sel if isinstance(sel, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sel))).to(
+            device=dev, dtype=torch.int64).contiguous()
+        block = self._coarse(N)
+        if block and -(-N // block) > _lib.POSEGRAPH_MAX_AGGREGATES:
+            raise _lib.NscError(f"pose graph: coarse_block {block} gives {-(-N // block)} aggregates of {N} poses; "
+                                f"at most {_lib.POSEGRAPH_MAX_AGGREGATES}")
+        f64 = dict(dtype=torch.float64, device=dev)
+        out = dict(joint=torch.empty((Q, Q, 6, 6), **f64), residual=torch.empty((Q, 6), **f64),
+                   iterations=torch.empty((Q, 6), dtype=torch.int32, device=dev),
+                   stats=torch.empty(_lib.POSEGRAPH_COV_STATS, dtype=torch.int64, device=dev))
+        if block:
+            out["coarse_stats"] = torch.empty(2, **f64)
+        L = _lib.lib()
+        ws = torch.empty(max(int(L.nsc_posegraph_covariance_workspace_bytes(N, E, Q, block)), 1), dtype=torch.uint8,
+                         device=dev)
+        with torch.cuda.device(dev):
+            status = L.nsc_posegraph_covariance(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E, _lib.ptr(fx),
+                                                C.byref(self.params), _lib.ptr(sel), Q, _lib.ptr(out["joint"]),
+                                                _lib.ptr(out["residual"]), _lib.ptr(out["iterations"]),
+                                                _lib.ptr(out["stats"]), _lib.ptr(ws), int(ws.numel()),
+                                                _lib.stream_ptr(dev), self.kernel, _lib.ptr(c), block,
+                                                _lib.ptr(out.get("coarse_stats")))
+        _lib.check(status, "nsc_posegraph_covariance")
+        return out
+
+    def covariance(self, poses, edge_ij, measurements, information, nodes, fixed=None, robust_scale=None):
+        """``covariance_device`` read back -> dict of numpy arrays: joint (Q,Q,6,6), residual (Q,6), iterations (Q,6),
+        converged (Q,6) = residual <= ``pcg_tolerance`` (use only converged columns), and skipped, outside, not_free,
+        not_converged as ints; with ``coarse_block`` also coarse_aggregates and coarse_failed.  The pair block of poses i
+        and j is ``joint[np.ix_([a, b], [a, b])]`` for nodes[a] = i, nodes[b] = j: hand it to ``relative_covariance``,
+        and its result to ``closure_mahalanobis``.  Synchronises."""
+        out = self.covariance_device(poses, edge_ij, measurements, information, nodes, fixed, robust_scale)
+        res = {k: out[k].cpu().numpy() for k in ("joint", "residual", "iterations")}
+        res["converged"] = res["residual"] <= self.params.pcg_tolerance
+        res.update(zip(_lib.POSEGRAPH_COV_STAT_NAMES, (int(s) for s in out["stats"].cpu().numpy())))
+        if "coarse_stats" in out:
+            cs = out["coarse_stats"].cpu().numpy()
+            res.update(coarse_aggregates=int(cs[0]), coarse_failed=int(cs[1]))
+        return res
 
     def optimize(self, poses, edge_ij, measurements, information, fixed=None, robust_scale=None):
         """-> dict: poses (N,4,4) (a device tensor for device poses, numpy for numpy), cost0, cost, iterations, accepted,

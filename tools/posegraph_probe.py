@@ -8,12 +8,16 @@ and, as a host baseline on the same residuals and Jacobians, Gauss-Newton with s
 normal equations (tests/posegraph_restatement.py builds them, edge by edge, in numpy: the linearisation time is
 reported apart from the solve time).  Prints the launch count and the inner iterations per outer step.
 usage: posegraph_probe.py [reps=10] [max_pcg_iterations=100] [max_iteration=20] [graph=1] [kernel=none] [width=3]
-                          [coarse_block=N|auto] [lambda0=X] [lambda_min=X] [host=0]
+                          [coarse_block=N|auto] [lambda0=X] [lambda_min=X] [host=0] [cov=Q]
 ``graph=0`` leaves the capture out (for caps whose launch count makes a graph of several hundred thousand nodes).
 ``kernel`` = huber, cauchy or geman_mcclure puts that robust kernel, with ``width``, on the closure edges (the odometry
 edges stay quadratic) and asks for the per-edge chi2 and weights: one more launch.  The host baseline stays quadratic.
 The arguments written name=value may stand anywhere: ``coarse_block`` switches the two-level preconditioner on (poses per
-aggregate, or auto), ``lambda0`` and ``lambda_min`` set the damping, ``host=0`` leaves the host baseline out."""
+aggregate, or auto), ``lambda0`` and ``lambda_min`` set the damping, ``host=0`` leaves the host baseline out.
+``cov=Q`` times ``covariance_device`` instead (marginal covariances of the newest pose and Q - 1 earlier ones, at the poses
+one ``optimize`` returns, tolerance 1e-10, ``max_pcg_iterations`` as the cap): eager and replayed, iterations per column,
+the worst error against the bar 10 tau |Sigma|_2 of tests/test_posegraph_cov_gpu.py, and as the host row
+scipy.sparse.linalg.splu of the same H plus 6 Q solves."""
 import os
 import sys
 import time
@@ -41,6 +45,7 @@ coarse_block = named.pop("coarse_block", None)
 if coarse_block not in (None, "auto"):
     coarse_block = int(coarse_block)
 with_host = int(named.pop("host", 1)) != 0
+cov_q = int(named.pop("cov", 0))
 damping = {k: float(named.pop(k)) for k in ("lambda0", "lambda_min") if k in named}
 assert not named, f"unknown arguments {sorted(named)}"
 N, CLOSURES = 4541, 200
@@ -79,6 +84,20 @@ def call():
     return opt.optimize_device(*args, fixed=fixed, robust_scale=scale)
 
 
+def capture(fn):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        cap = fn()
+    g.replay()
+    torch.cuda.synchronize()
+    return g, cap
+
+
 def device_times(fn, n):
     for _ in range(3):
         fn()
@@ -93,6 +112,52 @@ def device_times(fn, n):
         out.append(t0.elapsed_time(t1))
     return np.array(out)
 
+
+if cov_q:
+    import posegraph_coarse_restatement as Cr
+    TAU = 1e-10
+    X = call()["poses"]
+    nodes = np.unique(np.concatenate([np.linspace(0.05 * N, 0.95 * N, cov_q - 1).astype(np.int64), [N - 1]]))
+    assert len(nodes) == cov_q
+    sel = torch.from_numpy(nodes).to(dev)
+    cov = PoseGraphOptimizer(kernel=kernel, coarse_block=coarse_block, max_pcg_iterations=max_pcg, pcg_tolerance=TAU)
+
+    def cov_call():
+        return cov.covariance_device(X, *args[1:], sel, fixed=fixed, robust_scale=scale)
+    res = cov_call()
+    torch.cuda.synchronize()
+    its, resid = res["iterations"].cpu().numpy(), res["residual"].cpu().numpy()
+    print(f"covariance of {cov_q} poses ({6 * cov_q} columns): iterations per column {its.min()} .. {its.max()} (mean "
+          f"{its.mean():.1f}), worst residual {resid.max():.3g}, stats {res['stats'].tolist()}; "
+          f"{5 + 3 + (9 if block else 2) + (4 if block else 3) * max_pcg + 1} launches per call")
+    t = device_times(cov_call, reps)
+    print(f"eager: median {np.median(t):.2f} ms (min {t.min():.2f}, max {t.max():.2f}; {reps} calls)")
+    if with_graph:
+        g, cap = capture(cov_call)
+        assert all(torch.equal(cap[k], res[k]) for k in res)
+        t = device_times(g.replay, reps)
+        print(f"replayed hipGraph: median {np.median(t):.2f} ms (min {t.min():.2f}, max {t.max():.2f}); bitwise the eager "
+              "result")
+    if with_host:
+        Xh = X.cpu().numpy()
+        t0 = time.perf_counter()
+        H = Cr.linearize(Xh, e, Z, Om, 0 if kernel is None else L.POSEGRAPH_KERNELS[kernel],
+                         None if scale is None else scale.cpu().numpy())["H"][6:, 6:].tocsc()
+        t1 = time.perf_counter()
+        lu = spl.splu(H)
+        t2 = time.perf_counter()
+        rhs = np.zeros((6 * (N - 1), 6 * cov_q))
+        for b, n in enumerate(nodes):
+            rhs[6 * (n - 1):6 * n, 6 * b:6 * b + 6] = np.eye(6)
+        sol = lu.solve(rhs)
+        t3 = time.perf_counter()
+        ref = np.stack([np.stack([sol[6 * (na - 1):6 * na, 6 * b:6 * b + 6] for b in range(cov_q)]) for na in nodes])
+        lam_min = spl.eigsh(H, k=1, sigma=0.0, which="LM", return_eigenvectors=False)[0]
+        err = np.abs(res["joint"].cpu().numpy() - ref).max() * lam_min / TAU
+        print(f"host: splu {1e3 * (t2 - t1):.0f} ms + {6 * cov_q} solves {1e3 * (t3 - t2):.0f} ms (numpy linearisation "
+              f"{1e3 * (t1 - t0):.0f} ms); |Sigma|_2 = 1 / lambda_min(H) = {1.0 / lam_min:.4g}; device error / (tau "
+              f"|Sigma|_2) = {err:.3g} (bar 10)")
+    sys.exit(0)
 
 out = call()
 torch.cuda.synchronize()
@@ -113,16 +178,7 @@ t = device_times(call, reps)
 print(f"eager: median {np.median(t):.2f} ms (min {t.min():.2f}, max {t.max():.2f}; {reps} calls)")
 
 if with_graph:
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        call()
-    torch.cuda.current_stream().wait_stream(side)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        cap = call()
-    g.replay()
-    torch.cuda.synchronize()
+    g, cap = capture(call)
     assert all(torch.equal(cap[k], out[k]) for k in out)
     t = device_times(g.replay, reps)
     print(f"replayed hipGraph: median {np.median(t):.2f} ms (min {t.min():.2f}, max {t.max():.2f}); bitwise the eager "
