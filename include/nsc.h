@@ -828,6 +828,74 @@ int    nsc_posegraph_covariance(const double *poses, int32_t n_poses, const int6
                                 void *stream, int32_t kernel, const double *edge_scale, int32_t coarse_block,
                                 double *coarse_stats);
 
+/* ------------------------------------------------------------------------------------------
+ * Global voxel map (nsc_map_build; restated in tests/map_restatement.py): the keyframe clouds placed by the optimised
+ * poses and merged into one cloud, one point per occupied voxel.  The consumer of nsc_posegraph_optimize's poses.
+ *
+ * Input.  n_clouds clouds packed as rows, cloud c the rows [offsets[c], offsets[c+1]) of `points`; offsets (n_clouds+1)
+ *   int64.  dtype NSC_MAP_DTYPE_F32: float32 rows of stride_floats 3 or 4, xyz first (as nsc_gicp_register takes them);
+ *   NSC_MAP_DTYPE_F64: float64 rows of 3 (the `points` of an NscGicpCloudSet; stride_floats = 3).  poses (n_poses,4,4)
+ *   float64 row-major, sensor to world, rows 0..2 are read.  pose_ids (n_clouds) int64, or NULL: cloud c uses pose c.
+ *   A cloud whose id lies outside [0, n_poses) is left out and its rows are counted; -1 is the way to leave a cloud out.
+ *   A row of [0, total_rows) that lies in no cloud of `offsets` is counted with them.
+ * A row, in float64, every operation rounded on its own:  w_a = ((R_a0 x + R_a1 y) + R_a2 z) + t_a.  A row whose xyz or w
+ *   is not finite is dropped and counted.  k_a = floor((w_a - origin_a) / voxel_size) + 2^20; a row with a k_a outside
+ *   [0, 2^21) is dropped and counted, not clamped (at 0.5 m: +-524 km).  key = k_x | k_y << 21 | k_z << 42.
+ * Per voxel: count; first_row, the smallest index into the packed rows among the voxel's rows; first_cloud and
+ *   last_cloud, the min and max cloud index among them; exact int64 sums of rint(w_a 2^24);
+ *   centroid_a = (sum_a / 2^24) / count.  |coordinate| x rows per voxel must stay below 2^39 m.
+ * Output, voxels in ascending first_row: out_points (max_voxels,3) float64, info (max_voxels,4) int64 = [count,
+ *   first_row, first_cloud, last_cloud], keys (max_voxels) int64, stats (NSC_MAP_STATS) int64.  Entries past
+ *   stats[NSC_MAP_STAT_WRITTEN] are not defined.
+ * Capacity.  The table has 2 max_voxels slots and lives in the workspace.  A probe visits every slot once at most; a
+ *   row that finds neither its key nor an empty slot is counted as unplaced and nothing else happens.  `found` counts the
+ *   voxels in the table.  The result is complete when found <= max_voxels and unplaced = 0; with unplaced = 0 and
+ *   found > max_voxels the written voxels are the first max_voxels of the complete result.  Nothing is written outside
+ *   the buffers.
+ * Determinism.  Integer atomics only: two calls agree bit for bit, and the order of the clouds changes only the order
+ *   of the output voxels and first_row.
+ * Launches.  6 kernels (clear, insert, mark first rows, count them per word and tile, scan the tiles, write) whose grids
+ *   depend on total_rows and max_voxels alone; no host synchronisation, no memset or memcpy nodes: the call can be
+ *   captured.
+ * ------------------------------------------------------------------------------------------ */
+#define NSC_MAP_DTYPE_F32 0
+#define NSC_MAP_DTYPE_F64 1
+#define NSC_MAP_STATS              7
+#define NSC_MAP_STAT_FOUND         0    /* voxels in the table                                   */
+#define NSC_MAP_STAT_WRITTEN       1    /* min(found, max_voxels)                                */
+#define NSC_MAP_STAT_USED          2    /* rows summed into a voxel                              */
+#define NSC_MAP_STAT_NOT_FINITE    3    /* rows with a non-finite xyz or world coordinate        */
+#define NSC_MAP_STAT_OUTSIDE       4    /* rows outside the 2^21 voxels per axis                 */
+#define NSC_MAP_STAT_NO_POSE       5    /* rows of clouds without a pose (and rows of no cloud)  */
+#define NSC_MAP_STAT_UNPLACED      6    /* rows that found the table full                        */
+/* the shapes of the launches, for tests that walk their boundaries */
+#define NSC_MAP_TILE_ROWS      4096     /* rows whose first-row marks one wave counts: the compaction's tile  */
+#define NSC_MAP_SCAN_THREADS   256      /* the one workgroup that scans the tile counts; a thread takes
+                                           ceil(tiles / this) consecutive tiles                              */
+#define NSC_MAP_INSERT_ROWS    512      /* consecutive rows a workgroup of the insert pass takes at a time   */
+#define NSC_MAP_INSERT_BLOCKS  2048     /* its workgroups at most: beyond INSERT_ROWS x this rows they wrap  */
+#define NSC_MAP_MAX_VOXELS     (1LL << 36)
+#define NSC_MAP_MAX_ROWS       (1LL << 46)
+
+typedef struct NscMapParams {
+    double voxel_size;              /* 0.5    voxel edge (m), finite and positive */
+    double origin[3];               /* 0,0,0  world point where voxel (2^20, 2^20, 2^20) begins */
+} NscMapParams;
+
+void   nsc_map_default_params(NscMapParams *p);
+/* Bytes of workspace for nsc_map_build: 128 per voxel of max_voxels (the table) and about 0.2 per row; monotone in both;
+ * 0 for arguments the call would refuse (a negative size, max_voxels above NSC_MAP_MAX_VOXELS, total_rows above
+ * NSC_MAP_MAX_ROWS). */
+size_t nsc_map_workspace_bytes(int64_t total_rows, int64_t max_voxels);
+/* NSC_EINVAL for a null or negative argument, a dtype other than the two above, stride_floats not 3 or 4, float64 with a
+ * stride other than 3, a voxel_size not finite and positive, an origin not finite; NSC_EUNSUPPORTED for max_voxels above
+ * NSC_MAP_MAX_VOXELS or total_rows above NSC_MAP_MAX_ROWS; NSC_EWORKSPACE for a workspace that is missing or too small:
+ * all before anything is launched.  points may be NULL with total_rows = 0, poses with n_poses = 0, and out_points, info, keys with max_voxels = 0. */
+int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_clouds,
+                     int64_t total_rows, const double *poses, int32_t n_poses, const int64_t *pose_ids,
+                     const NscMapParams *params, int64_t max_voxels, double *out_points, int64_t *info, int64_t *keys,
+                     int64_t *stats, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,19 @@ class PoseGraphParams(C.Structure):
                 ("relative_cost", C.c_double), ("min_step", C.c_double)]
 
 
+class MapParams(C.Structure):
+    """struct NscMapParams"""
+    _fields_ = [("voxel_size", C.c_double), ("origin", C.c_double * 3)]
+
+
+# include/nsc.h NSC_MAP_DTYPE_F32, NSC_MAP_DTYPE_F64, NSC_MAP_STATS and NSC_MAP_STAT_*: the name of each entry of `stats`
+MAP_DTYPE_F32, MAP_DTYPE_F64, MAP_STATS = 0, 1, 7
+MAP_STAT_NAMES = ("voxels_found", "voxels_written", "rows_used", "rows_not_finite", "rows_outside", "rows_without_pose",
+                  "rows_unplaced")
+# include/nsc.h NSC_MAP_TILE_ROWS, NSC_MAP_SCAN_THREADS, NSC_MAP_INSERT_ROWS, NSC_MAP_INSERT_BLOCKS
+MAP_TILE_ROWS, MAP_SCAN_THREADS, MAP_INSERT_ROWS, MAP_INSERT_BLOCKS = 4096, 256, 512, 2048
+MAP_MAX_VOXELS, MAP_MAX_ROWS = 1 << 36, 1 << 46     # include/nsc.h NSC_MAP_MAX_VOXELS, NSC_MAP_MAX_ROWS
+
 # include/nsc.h NSC_POSEGRAPH_MAX_EDGES, NSC_POSEGRAPH_MAX_LAUNCHES, NSC_POSEGRAPH_STATS
 POSEGRAPH_MAX_EDGES, POSEGRAPH_MAX_LAUNCHES, POSEGRAPH_STATS = 1073741823, 1000000, 10
 POSEGRAPH_MAX_AGGREGATES = 128                   # include/nsc.h NSC_POSEGRAPH_MAX_AGGREGATES
@@ -235,6 +248,10 @@ SYMBOLS = {
     "nsc_posegraph_covariance_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "nsc_posegraph_covariance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, C.POINTER(PoseGraphParams), _vp, _i32,
                                            _vp, _vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp, _i32, _vp]),
+    "nsc_map_default_params": (None, [C.POINTER(MapParams)]),
+    "nsc_map_workspace_bytes": (_sz, [_i64, _i64]),
+    "nsc_map_build": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, C.POINTER(MapParams), _i64, _vp, _vp,
+                                _vp, _vp, _vp, _sz, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

@@ -37,10 +37,11 @@
 
 #include "../../include/nsc.h"
 #include "nsc_util.h"
+#include "nsc_voxel_hash.h"             // KEY_BITS, KEY_MAX, FIX_SCALE, mix64, pack_key, next_slot
 
 namespace {
 
-constexpr int GEO_BLOCKS = 64;          // blocks per cloud (down-sampling, covariances) and per pair (linearize)
+constexpr int GEO_BLOCKS = 64;         // blocks per cloud (down-sampling, covariances) and per pair (linearize)
 constexpr int GEO_THREADS = 256;
 // gridDim.y is at most 65 535.  The per-cloud launches put the cloud in y (2 clouds per pair in nsc_gicp_register),
 // the per-pair launches the pair; a larger count is NSC_EUNSUPPORTED before anything is launched, callers chunk.
@@ -48,10 +49,7 @@ constexpr int GRID_Y_MAX = 65535;
 static_assert(2 * NSC_GICP_MAX_PAIRS <= GRID_Y_MAX && NSC_GICP_MAX_CLOUDS <= GRID_Y_MAX &&
                   NSC_GICP_MAX_PREPARED_PAIRS <= GRID_Y_MAX,
               "the batch limits of include/nsc.h must fit gridDim.y");
-constexpr int COMPACT_THREADS = 1024;
-constexpr int KEY_BITS = 21;            // voxel key per axis: 0 .. 2^21-1 voxels from the cloud's min bound
-constexpr long long KEY_MAX = (1LL << KEY_BITS) - 1;
-constexpr double FIX_SCALE = 16777216.0;        // coordinate sums in int64 units of 2^-24 m
+constexpr int COMPACT_THREADS = 1024;   // voxel keys count from the cloud's min bound
 constexpr int SLAB = 50;                // 21 JtWJ + 6 JtWd + n_corr + Sum|d|^2 + 21 information terms
 constexpr int SYS = 29;                 // the first 29 terms: the system of stage output system0
 
@@ -89,21 +87,10 @@ struct Clouds {                         // the 2P clouds of a batch and where ea
 
 __device__ __forceinline__ bool finite3(const float *q) { return isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]); }
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x)
-{
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return x;
-}
-
 __device__ __forceinline__ long long voxel_coord(double p, double lo, double v)
 {
     const double k = floor((p - lo) / v);
     return k < 0.0 ? 0 : (k > (double)KEY_MAX ? KEY_MAX : (long long)k);
-}
-
-__device__ __forceinline__ unsigned long long pack_key(long long x, long long y, long long z)
-{
-    return (unsigned long long)x | ((unsigned long long)y << KEY_BITS) | ((unsigned long long)z << (2 * KEY_BITS));
 }
 
 template <class T>
@@ -119,9 +106,6 @@ struct IndexSlot {                      // one voxel of a stored cloud's index (
 
 __device__ __forceinline__ long long ds_row(const Slot &s) { return s.ds; }
 __device__ __forceinline__ long long ds_row(const IndexSlot &s) { return (long long)s.row; }
-
-// the slot a linear probe visits after h, wrapping at the table's end
-__device__ __forceinline__ long long next_slot(long long h, long long cap) { return h + 1 == cap ? 0 : h + 1; }
 
 // Slot of a voxel key in a table of `cap` slots, or -1.
 template <class S>

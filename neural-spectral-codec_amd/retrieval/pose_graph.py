@@ -37,6 +37,9 @@ candidate) -> ``PoseGraphOptimizer.covariance`` on the graph so far, with nodes 
 A false closure that passed geometric verification keeps weight 1 under the quadratic cost and bends the whole
 trajectory; with ``kernel="cauchy"`` and a width of about 3 on the closure edges it ends with a weight below 1e-3, and
 ``optimize`` returns ``chi2`` and ``weights`` per edge so that the caller can drop it.
+
+The consumer of ``optimize``'s poses is ``GlobalMap`` (global_map.py): it places the stored keyframe clouds by them and
+merges the clouds into one voxel map, whose voxel count says, without ground truth, whether the closures helped.
 """
 import ctypes as C
 
