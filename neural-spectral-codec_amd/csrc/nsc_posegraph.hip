@@ -43,12 +43,18 @@
 // registers), then the restrict and prolong kernels once on the start of PCG.  Per inner iteration the step kernel is
 // replaced by pg_coarse_restrict_kernel (one wave per aggregate: the step, B^-1 r and its six entries of P^T r) and
 // pg_coarse_prolong_kernel (one wave per aggregate: its six rows of A_c^-1 r_c, z += P y, the partials of r.r and r.z,
-// one per aggregate, which pg_coarse_begin_kernel and pg_coarse_direction_kernel sum): five launches per inner iteration.  The same house rules hold: no floating-point atomics, every
-// sum in a fixed order (a lane sums its nodes in ascending order, the wave finishes with the butterfly), no host
+// one per aggregate, which pg_pcg_begin_kernel and pg_pcg_direction_kernel are handed in place of those per workgroup of
+// nodes): five launches per inner iteration.  The same house rules hold: no floating-point atomics, every sum in a
+// fixed order (a lane sums its nodes in ascending order, the wave finishes with the butterfly), no host
 // synchronisation, no memset or memcpy nodes, no cooperative launch or grid barrier, `done` and `stop_k` honoured by
 // every kernel, and a launch sequence that depends only on the parameters, N > 0, E > 0 and coarse_block:
 //   5 (lists) + 1 (copy, unless aliased) + 3 + max_iteration (14 + 5 max_pcg_iterations) + 1 (+ 1 for chi2 / weights).
 // A pivot of A_c that is not positive and finite leaves that outer step with B^-1 alone and is counted.
+//
+// Host.  layout() is the one place that knows the workspace (the graph's regions, then the coarse space's, then the
+// covariance call's), graph_ok() the one check of the graph arguments, build_lists() the five launches of the incident
+// lists (the scan is nsc_util.h's), launch_system() the launches from the linearisation to A_c^-1 that the optimiser runs
+// per outer step and the covariance call once.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -67,17 +73,19 @@ struct PgState {
     int done, converged, stop_k, accept_it, iterations, accepted, rejected, pcg_total, skipped, pad;
 };
 
-struct Buffers {                             // the workspace: typed pointers into it, and its size
-    PgState *st;
-    int *row_ptr, *cursor, *tmp, *list, *ei, *ej, *free_node;
+struct Buffers {                             // the graph's part of the workspace: typed pointers into it
+    PgState *st;                             // the head, head_bytes long: the state, then deg; zeroed as one
+    int *row_ptr, *deg, *tmp, *list, *ei, *ej, *free_node;   // row_ptr (N + 1); deg (N): degrees, then places to hand out
     double *hii, *hjj, *hij;                 // (21,E), (21,E), (36,E)
     double *fe;                              // (E): rho(r^T Omega r)
     double *ge, *ye;                         // (E,12): J^T Omega r and the edge half of H p, node i's six then node j's
-    double *g, *blocks, *chol;               // (N,6), (N,21), (N,21)
+    size_t head_bytes;                       // here, eight bytes like the pointers around it: the struct is the kernels'
+                                             // argument, and with the pointers below eight bytes further up
+                                             // pg_pcg_step_kernel was compiled with its loads one behind the other: 1 us
+    double *blocks, *chol;                   // (N,21), (N,21)
     double *x, *r, *z, *p, *ap;              // (N,6)
     double *cand;                            // (N,4,4), rows 0..2 used
     double *part_e, *part_a, *part_b, *part_s;   // partials, one per workgroup of nodes: cost, p.Ap, (r.r, r.z), |delta|^2
-    size_t total;                            // bytes
 };
 
 struct PgCoarse {
@@ -91,7 +99,6 @@ struct Coarse {                              // the coarse space's part of the w
     double *rc;                              // (nc): P^T r
     double *part;                            // (2 n_agg): partials of r.r and r.z, one per aggregate
     int L, n_agg, nc;                        // nc = 6 n_agg
-    size_t total;                            // bytes, Buffers' included
 };
 
 // the sum of nb partials, the same bits in every lane of every wave that calls it
@@ -292,43 +299,22 @@ __global__ __launch_bounds__(TB) void pg_count_kernel(const long long *__restric
     b.ei[e] = ok ? (int)i : -1;
     b.ej[e] = ok ? (int)j : -1;
     if (ok) {
-        atomicAdd(&b.row_ptr[i + 1], 1);
-        atomicAdd(&b.row_ptr[j + 1], 1);
+        atomicAdd(&b.deg[i], 1);
+        atomicAdd(&b.deg[j], 1);
     } else {
         atomicAdd(&b.st->skipped, 1);
     }
 }
 
-// exclusive scan of the degrees in row_ptr[1 .. N] (row_ptr[0] = 0), in place, by one wave; cursor = row_ptr
-__global__ __launch_bounds__(TB) void pg_scan_kernel(int n_poses, Buffers b)
-{
-    const int lane = threadIdx.x;
-    const int per = (n_poses + TB - 1) / TB;
-    const int lo = min(lane * per, n_poses), hi = min(lo + per, n_poses);
-    int sum = 0;
-    for (int n = lo; n < hi; ++n) sum += b.row_ptr[n + 1];
-    int incl = sum;
-    for (int off = 1; off < TB; off <<= 1) {
-        const int o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    int run = incl - sum;                    // entries of the nodes before this lane's
-    for (int n = lo; n < hi; ++n) {
-        const int d = b.row_ptr[n + 1];
-        b.cursor[n] = run;
-        run += d;
-        b.row_ptr[n + 1] = run;
-    }
-}
-
+// after the scan of the degrees into row_ptr: a node's places are handed out from its last down, until deg is zero again
 __global__ __launch_bounds__(TB) void pg_fill_kernel(int n_edges, Buffers b)
 {
     const int e = blockIdx.x * TB + threadIdx.x;
     if (e >= n_edges) return;
     const int i = b.ei[e], j = b.ej[e];
     if (i < 0) return;
-    b.tmp[atomicAdd(&b.cursor[i], 1)] = 2 * e;
-    b.tmp[atomicAdd(&b.cursor[j], 1)] = 2 * e + 1;
+    b.tmp[b.row_ptr[i] + atomicSub(&b.deg[i], 1) - 1] = 2 * e;
+    b.tmp[b.row_ptr[j] + atomicSub(&b.deg[j], 1) - 1] = 2 * e + 1;
 }
 
 // one wave per node: its entries (2 e + side, all different) into ascending order by rank
@@ -354,13 +340,14 @@ __global__ __launch_bounds__(TB) void pg_copy_kernel(const double *__restrict__ 
 
 // One lane per edge at `poses`, each output where its pointer is given: rho(s) into fe (what the cost sums), s = r^T Omega r
 // into chi2 and w into weight (what a caller drops closures by).  A skipped edge writes nothing to fe, zeros to the others.
+// after_done: the launch that runs whatever `done` says, the chi2 and weights at the final poses.
 __global__ __launch_bounds__(TB) void pg_edge_cost_kernel(const double *poses, const double *__restrict__ Z,
                                                           const double *__restrict__ information, int n_edges, Buffers b,
-                                                          int check_done, int kernel, const double *__restrict__ edge_scale,
+                                                          int after_done, int kernel, const double *__restrict__ edge_scale,
                                                           double *fe, double *__restrict__ chi2,
                                                           double *__restrict__ weight)
 {
-    if (check_done && b.st->done) return;
+    if (!after_done && b.st->done) return;
     const int e = blockIdx.x * TB + threadIdx.x;
     if (e >= n_edges) return;
     const bool counted = b.ei[e] >= 0;
@@ -378,9 +365,10 @@ __global__ __launch_bounds__(TB) void pg_edge_cost_kernel(const double *poses, c
 
 // F: every node sums the edges it is the first end of, in list order; one partial per workgroup.  The sum walks the
 // lists, which hold counted edges only, so where the skipped edges stand among the others does not change a bit of it.
-__global__ __launch_bounds__(TB) void pg_cost_gather_kernel(int n_poses, Buffers b, int check_done)
+// Before the first accept kernel of a call `done` is 0, as build_lists left it, so every launch may test it.
+__global__ __launch_bounds__(TB) void pg_cost_gather_kernel(int n_poses, Buffers b)
 {
-    if (check_done && b.st->done) return;
+    if (b.st->done) return;
     const int n = blockIdx.x * TB + threadIdx.x;
     double f = 0.0;
     if (n < n_poses) {
@@ -393,14 +381,14 @@ __global__ __launch_bounds__(TB) void pg_cost_gather_kernel(int n_poses, Buffers
     write_partial(b.part_e, f);
 }
 
-// residual, weight, the blocks of w J^T Omega J and the halves of w J^T Omega r of every edge
+// residual, weight, the blocks of w J^T Omega J and the halves of w J^T Omega r of every edge (`done` as in the gather)
 __global__ __launch_bounds__(TB) void pg_linearize_kernel(const double *poses, const double *__restrict__ Z,
                                                           const double *__restrict__ information, int n_edges,
-                                                          Buffers b, double *__restrict__ residuals, int check_done,
-                                                          int kernel, const double *__restrict__ edge_scale,
+                                                          Buffers b, double *__restrict__ residuals, int kernel,
+                                                          const double *__restrict__ edge_scale,
                                                           double *__restrict__ weights)
 {
-    if (check_done && b.st->done) return;
+    if (b.st->done) return;
     const int e = blockIdx.x * TB + threadIdx.x;
     if (e >= n_edges) return;
     if (b.ei[e] < 0) {
@@ -569,8 +557,8 @@ __device__ __forceinline__ void cholesky_solve6(const double U[21], const double
     }
 }
 
-// gather of g and the diagonal blocks; with solve != 0 also the damped factor and the start of PCG:
-// x = 0, r = -g, z = M^-1 r, p = z, partials of r.r and r.z
+// gather of g (written where g_out is given) and the diagonal blocks; with solve != 0 also the damped factor and the
+// start of PCG: x = 0, r = -g, z = M^-1 r, p = z, partials of r.r and r.z
 __global__ __launch_bounds__(TB) void pg_assemble_kernel(int n_poses, int n_edges, const uint8_t *__restrict__ fixed,
                                                          Buffers b, double *__restrict__ g_out,
                                                          double *__restrict__ blocks_out, int solve)
@@ -593,7 +581,8 @@ __global__ __launch_bounds__(TB) void pg_assemble_kernel(int n_poses, int n_edge
 #pragma unroll
             for (int k = 0; k < 21; ++k) D[k] += h[k * E + e];
         }
-        for (int k = 0; k < 6; ++k) g_out[6 * (long long)n + k] = g[k];
+        if (g_out)
+            for (int k = 0; k < 6; ++k) g_out[6 * (long long)n + k] = g[k];
         for (int k = 0; k < 21; ++k) blocks_out[21 * (long long)n + k] = D[k];
         if (solve) {
             const double lambda = b.st->lambda;
@@ -629,21 +618,17 @@ __global__ __launch_bounds__(TB) void pg_assemble_kernel(int n_poses, int n_edge
     }
 }
 
-// one wave: |g|^2 and r.z of the start; no inner iteration when the gradient is zero
-__device__ __forceinline__ void pcg_begin(const Buffers &b, const double *part_b, int nb)
+// one wave: |g|^2 and r.z of the start; no inner iteration when the gradient is zero.  part: the nb partials of r.r, then
+// those of r.z, one per workgroup of nodes (part_b) or, behind the prolong kernel, one per aggregate
+__global__ __launch_bounds__(TB) void pg_pcg_begin_kernel(Buffers b, const double *part, int nb)
 {
-    const double bb = finish(part_b, nb), rz = finish(part_b + nb, nb);
+    if (b.st->done) return;
+    const double bb = finish(part, nb), rz = finish(part + nb, nb);
     if (threadIdx.x == 0) {
         b.st->bb = bb;
         b.st->rz[0] = rz;
         b.st->stop_k = bb > 0.0 && rz > 0.0 ? INT_MAX : 0;
     }
-}
-
-__global__ __launch_bounds__(TB) void pg_pcg_begin_kernel(int nb, Buffers b)
-{
-    if (b.st->done) return;
-    pcg_begin(b, b.part_b, nb);
 }
 
 // A p = gather + lambda diag(H) p on the free nodes; partial of p.Ap
@@ -673,7 +658,24 @@ __global__ __launch_bounds__(TB) void pg_node_matvec_kernel(int n_poses, Buffers
     write_partial(b.part_a, pap);
 }
 
-// alpha = r.z / p.Ap;  x += alpha p;  r -= alpha A p;  z = M^-1 r;  partials of r.r and r.z
+// the PCG step on free node n: x += alpha p;  r -= alpha A p;  z = B^-1 r
+__device__ __forceinline__ void pcg_step_node(const Buffers &b, int n, double alpha, double r[6], double z[6])
+{
+    double U[21];
+    for (int c = 0; c < 21; ++c) U[c] = b.chol[21 * (long long)n + c];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        const long long at = 6 * (long long)n + c;
+        b.x[at] += alpha * b.p[at];
+        r[c] = b.r[at] - alpha * b.ap[at];
+        b.r[at] = r[c];
+    }
+    cholesky_solve6(U, r, z);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) b.z[6 * (long long)n + c] = z[c];
+}
+
+// alpha = r.z / p.Ap;  the step;  partials of r.r and r.z
 __global__ __launch_bounds__(TB) void pg_pcg_step_kernel(int n_poses, Buffers b, int k)
 {
     if (b.st->done || k >= b.st->stop_k) return;
@@ -683,19 +685,10 @@ __global__ __launch_bounds__(TB) void pg_pcg_step_kernel(int n_poses, Buffers b,
     const int n = blockIdx.x * TB + threadIdx.x;
     double rr = 0.0, rz = 0.0;
     if (n < n_poses && b.free_node[n]) {
-        double U[21], r[6], z[6];
-        for (int c = 0; c < 21; ++c) U[c] = b.chol[21 * (long long)n + c];
+        double r[6], z[6];
+        pcg_step_node(b, n, alpha, r, z);
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
-            const long long at = 6 * (long long)n + c;
-            b.x[at] += alpha * b.p[at];
-            r[c] = b.r[at] - alpha * b.ap[at];
-            b.r[at] = r[c];
-        }
-        cholesky_solve6(U, r, z);
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            b.z[6 * (long long)n + c] = z[c];
             rr += r[c] * r[c];
             rz += r[c] * z[c];
         }
@@ -705,12 +698,24 @@ __global__ __launch_bounds__(TB) void pg_pcg_step_kernel(int n_poses, Buffers b,
 }
 
 // beta = r.z (new) / r.z (old);  p = z + beta p;  the first lane of the grid counts the iteration and ends the loop at
-// |r| <= tolerance |g|, at p.Ap <= 0 or at r.z <= 0.  part_b: the nb_b partials of r.r, then those of r.z
-__device__ __forceinline__ void pcg_direction(int n_poses, const Buffers &b, int k, double tol2, const double *part_b,
-                                              int nb_b)
+// |r| <= tolerance |g|, at p.Ap <= 0 or at r.z <= 0.  part, nb: as in pg_pcg_begin_kernel
+__global__ __launch_bounds__(TB) void pg_pcg_direction_kernel(int n_poses, Buffers b, int k, double tol2,
+                                                              const double *part, int nb)
 {
-    const int nb = gridDim.x;
-    const double pap = finish(b.part_a, nb), rr = finish(part_b, nb_b), rz = finish(part_b + nb_b, nb_b);
+    if (b.st->done || k >= b.st->stop_k) return;
+    // finish() of p.Ap, r.r and r.z, bit for bit, in one pass: the loads of the three sums are in flight together
+    double pap = 0.0, rr = 0.0, rz = 0.0;
+    const int na = gridDim.x;
+    for (int i = threadIdx.x; i < max(na, nb); i += TB) {
+        if (i < na) pap += b.part_a[i];
+        if (i < nb) {
+            rr += part[i];
+            rz += part[nb + i];
+        }
+    }
+    pap = nsc_wave_sum(pap);
+    rr = nsc_wave_sum(rr);
+    rz = nsc_wave_sum(rz);
     const double beta = rz / b.st->rz[k & 1];
     const int n = blockIdx.x * TB + threadIdx.x;
     if (n < n_poses && b.free_node[n]) {
@@ -725,12 +730,6 @@ __device__ __forceinline__ void pcg_direction(int n_poses, const Buffers &b, int
         b.st->pcg_total += 1;
         if (!(pap > 0.0) || rr <= tol2 * b.st->bb || !(rz > 0.0)) b.st->stop_k = k + 1;
     }
-}
-
-__global__ __launch_bounds__(TB) void pg_pcg_direction_kernel(int n_poses, Buffers b, int k, double tol2)
-{
-    if (b.st->done || k >= b.st->stop_k) return;
-    pcg_direction(n_poses, b, k, tol2, b.part_b, gridDim.x);
 }
 
 // ---- the coarse space ----------------------------------------------------------------------------------------------
@@ -978,18 +977,8 @@ __global__ __launch_bounds__(TB) void pg_coarse_restrict_kernel(int n_poses, int
         if (!b.free_node[n]) continue;
         double r[6];
         if (k >= 0) {
-            double U[21], z[6];
-            for (int q = 0; q < 21; ++q) U[q] = b.chol[21 * (long long)n + q];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) {
-                const long long at = 6 * (long long)n + q;
-                b.x[at] += alpha * b.p[at];
-                r[q] = b.r[at] - alpha * b.ap[at];
-                b.r[at] = r[q];
-            }
-            cholesky_solve6(U, r, z);
-#pragma unroll
-            for (int q = 0; q < 6; ++q) b.z[6 * (long long)n + q] = z[q];
+            double z[6];
+            pcg_step_node(b, n, alpha, r, z);
         } else {
 #pragma unroll
             for (int q = 0; q < 6; ++q) r[q] = b.r[6 * (long long)n + q];
@@ -1046,19 +1035,6 @@ __global__ __launch_bounds__(TB) void pg_coarse_prolong_kernel(int n_poses, Buff
     }
     write_partial(c.part, rr);
     write_partial(c.part + c.n_agg, rz);
-}
-
-// pg_pcg_begin_kernel and pg_pcg_direction_kernel on the partials of the prolong kernel, one per aggregate
-__global__ __launch_bounds__(TB) void pg_coarse_begin_kernel(Buffers b, Coarse c)
-{
-    if (b.st->done) return;
-    pcg_begin(b, c.part, c.n_agg);
-}
-
-__global__ __launch_bounds__(TB) void pg_coarse_direction_kernel(int n_poses, Buffers b, Coarse c, int k, double tol2)
-{
-    if (b.st->done || k >= b.st->stop_k) return;
-    pcg_direction(n_poses, b, k, tol2, c.part, c.n_agg);
 }
 
 // candidate poses X_k [Exp(phi_k) | rho_k]; partial of |delta|^2; the first delta of the call on request
@@ -1215,52 +1191,47 @@ struct Cov {                                 // the covariance call's part of th
     double *rz, *bb, *rr;                    // (2,R_pad), (R_pad), (R_pad)
     int *stop_k, *iters;                     // (R_pad)
     int R, R_pad, n_tiles;
-    size_t total;                            // bytes, everything in front included
 };
 
 __device__ __forceinline__ size_t cov_at(int n, int c, int Rp, int col) { return ((size_t)n * 6 + c) * Rp + col; }
+
+// The sums of K lane-local values over the VW waves, in ascending wave order.  ALL: every wave gets them; otherwise wave 0
+// alone, and the other waves keep what they had.  red: K VW rows of the workgroup's LDS, value q of wave w in row VW q + w.
+template <int K, bool ALL> __device__ __forceinline__ void wave_sums(double (&v)[K], double (*red)[TB])
+{
+    const int wave = threadIdx.x / TB, lane = threadIdx.x % TB;
+    __syncthreads();                                         // whoever still reads red from an earlier sum has finished
+#pragma unroll
+    for (int q = 0; q < K; ++q) red[VW * q + wave][lane] = v[q];
+    __syncthreads();
+    if (!ALL && wave != 0) return;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < VW; ++w) s += red[VW * q + w][lane];
+        v[q] = s;
+    }
+}
 
 // The nb partials of one column, for all VW waves of a workgroup at once (they share their 64 columns), the same bits in
 // every wave of every workgroup of every kernel: wave w sums partials w, w + VW, ... in ascending order (four loads in
 // flight), then every wave sums the VW results in ascending order.  red: VW rows of the workgroup's LDS.
 __device__ __forceinline__ double column_sum(const double *part, int nb, int Rp, int col, double (*red)[TB])
 {
-    const int wave = threadIdx.x / TB, lane = threadIdx.x % TB;
-    double s = 0.0;
-    int t = wave;
+    double s[1] = {0.0};
+    int t = threadIdx.x / TB;
     for (; t + 3 * VW < nb; t += 4 * VW) {
         const double a0 = part[(size_t)t * Rp + col], a1 = part[(size_t)(t + VW) * Rp + col],
                      a2 = part[(size_t)(t + 2 * VW) * Rp + col], a3 = part[(size_t)(t + 3 * VW) * Rp + col];
-        s += a0;
-        s += a1;
-        s += a2;
-        s += a3;
+        s[0] += a0;
+        s[0] += a1;
+        s[0] += a2;
+        s[0] += a3;
     }
-    for (; t < nb; t += VW) s += part[(size_t)t * Rp + col];
-    __syncthreads();                                         // whoever still reads red has finished
-    red[wave][lane] = s;
-    __syncthreads();
-    s = 0.0;
-#pragma unroll
-    for (int w = 0; w < VW; ++w) s += red[w][lane];
-    return s;
-}
-
-// the sums of two lane-local values over the VW waves, in ascending wave order; the result stands in wave 0.  red: 2 VW rows
-__device__ __forceinline__ void wave_sums(double &a, double &b, double (*red)[TB])
-{
-    const int wave = threadIdx.x / TB, lane = threadIdx.x % TB;
-    __syncthreads();
-    red[wave][lane] = a;
-    red[VW + wave][lane] = b;
-    __syncthreads();
-    if (wave != 0) return;
-    a = b = 0.0;
-#pragma unroll
-    for (int w = 0; w < VW; ++w) {
-        a += red[w][lane];
-        b += red[VW + w][lane];
-    }
+    for (; t < nb; t += VW) s[0] += part[(size_t)t * Rp + col];
+    wave_sums<1, true>(s, red);
+    return s[0];
 }
 
 // x = 0, r = e (column 6 q + c is the unit vector of entry c of pose nodes[q]; zero when that index is out of range or
@@ -1275,7 +1246,7 @@ __global__ __launch_bounds__(VB) void pg_cov_init_kernel(int n_poses, const long
         if (node < 0 || node >= n_poses || !b.free_node[node]) node = -1;
     }
     const int comp = col % 6;
-    double rr = 0.0, rz = 0.0;
+    double d[2] = {0.0, 0.0};                                // r.r, r.z
     const int lo = blockIdx.x * CT, hi = min(lo + CT, n_poses);
     for (int n = lo + wave; n < hi; n += VW) {
         double r[6], z[6] = {0, 0, 0, 0, 0, 0};
@@ -1294,14 +1265,14 @@ __global__ __launch_bounds__(VB) void pg_cov_init_kernel(int n_poses, const long
             v.z[at] = z[c];
             v.p[at] = z[c];
             v.ap[at] = 0.0;
-            rr += r[c] * r[c];
-            rz += r[c] * z[c];
+            d[0] += r[c] * r[c];
+            d[1] += r[c] * z[c];
         }
     }
-    wave_sums(rr, rz, red);
+    wave_sums<2, false>(d, red);
     if (wave != 0) return;
-    v.part_rr[(size_t)blockIdx.x * Rp + col] = rr;
-    v.part_rz[(size_t)blockIdx.x * Rp + col] = rz;
+    v.part_rr[(size_t)blockIdx.x * Rp + col] = d[0];
+    v.part_rz[(size_t)blockIdx.x * Rp + col] = d[1];
 }
 
 // one workgroup per chunk: b.b and r.z of the start from nb partials; a column with b = 0 runs no iteration
@@ -1342,12 +1313,12 @@ __global__ __launch_bounds__(VB) void pg_cov_matvec_kernel(int n_poses, const in
                                                            const int *__restrict__ ej, const int *__restrict__ free_node,
                                                            const double *__restrict__ hp, Cov v, int k)
 {
-    __shared__ double red[2 * VW][TB];
+    __shared__ double red[VW][TB];
     const int wave = threadIdx.x / TB, col = blockIdx.y * TB + threadIdx.x % TB, Rp = v.R_pad;
     const bool active = k < v.stop_k[col];
     if (!__any(active)) return;                              // the same columns in every wave: the workgroup leaves as one
     const double *__restrict__ P = v.p;
-    double pap = 0.0, unused = 0.0;
+    double pap[1] = {0.0};
     const int lo = blockIdx.x * CT, hi = min(lo + CT, n_poses);
     for (int n = lo + wave; n < hi; n += VW) {
         if (!free_node[n]) continue;
@@ -1377,11 +1348,11 @@ __global__ __launch_bounds__(VB) void pg_cov_matvec_kernel(int n_poses, const in
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
             if (active) v.ap[cov_at(n, c, Rp, col)] = y[c];
-            pap += pn[c] * y[c];
+            pap[0] += pn[c] * y[c];
         }
     }
-    wave_sums(pap, unused, red);
-    if (wave == 0 && active) v.part_a[(size_t)blockIdx.x * Rp + col] = pap;
+    wave_sums<1, false>(pap, red);
+    if (wave == 0 && active) v.part_a[(size_t)blockIdx.x * Rp + col] = pap[0];
 }
 
 // alpha = r.z / p.Ap;  x += alpha p;  r -= alpha A p;  z = B^-1 r on node n, one column per lane; adds to r.r and r.z
@@ -1422,7 +1393,7 @@ __global__ __launch_bounds__(VB) void pg_cov_step_kernel(int n_poses, Buffers b,
     const bool active = k < v.stop_k[col];
     if (!__any(active)) return;                              // the same columns in every wave: the workgroup leaves as one
     const double alpha = cov_alpha(v, k, col, red);
-    double rr = 0.0, rz = 0.0;
+    double d[2] = {0.0, 0.0};                                // r.r, r.z
     const int lo = blockIdx.x * CT, hi = min(lo + CT, n_poses);
     for (int n = lo + wave; n < hi; n += VW) {
         if (!b.free_node[n]) continue;
@@ -1430,14 +1401,14 @@ __global__ __launch_bounds__(VB) void pg_cov_step_kernel(int n_poses, Buffers b,
         cov_step_node(b, v, n, col, alpha, active, r, z);
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
-            rr += r[c] * r[c];
-            rz += r[c] * z[c];
+            d[0] += r[c] * r[c];
+            d[1] += r[c] * z[c];
         }
     }
-    wave_sums(rr, rz, red);
+    wave_sums<2, false>(d, red);
     if (wave == 0 && active) {
-        v.part_rr[(size_t)blockIdx.x * Rp + col] = rr;
-        v.part_rz[(size_t)blockIdx.x * Rp + col] = rz;
+        v.part_rr[(size_t)blockIdx.x * Rp + col] = d[0];
+        v.part_rz[(size_t)blockIdx.x * Rp + col] = d[1];
     }
 }
 
@@ -1476,12 +1447,12 @@ __global__ __launch_bounds__(VB) void pg_cov_direction_kernel(int n_poses, Buffe
 // wave the VW sums in the LDS in ascending order.
 __global__ __launch_bounds__(VB) void pg_cov_restrict_kernel(int n_poses, Buffers b, Coarse c, Cov v, int k)
 {
-    __shared__ double red[VW][6][TB];
+    __shared__ double red[6 * VW][TB];
     const int wave = threadIdx.x / TB, lane = threadIdx.x % TB;
     const int col = blockIdx.y * TB + lane, Rp = v.R_pad;
     const bool active = k < 0 || k < v.stop_k[col];
     if (!__any(active)) return;                              // the same columns in every wave: the workgroup leaves as one
-    const double alpha = k >= 0 ? cov_alpha(v, k, col, reinterpret_cast<double(*)[TB]>(red)) : 0.0;
+    const double alpha = k >= 0 ? cov_alpha(v, k, col, red) : 0.0;
     double rc[6] = {0, 0, 0, 0, 0, 0};
     const int lo = blockIdx.x * c.L, hi = min(lo + c.L, n_poses);
     for (int n = lo + wave; n < hi; n += VW) {
@@ -1499,18 +1470,10 @@ __global__ __launch_bounds__(VB) void pg_cov_restrict_kernel(int n_poses, Buffer
 #pragma unroll
             for (int q = 0; q < 6; ++q) rc[q] += T[6 * i + q] * r[i];
     }
-    __syncthreads();                                         // the sum for alpha has been read by every wave
-#pragma unroll
-    for (int q = 0; q < 6; ++q) red[wave][q][lane] = rc[q];
-    __syncthreads();
+    wave_sums<6, false>(rc, red);                            // its first barrier: every wave has read the sum for alpha
     if (wave == 0 && active) {
 #pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            double s = 0.0;
-#pragma unroll
-            for (int w = 0; w < VW; ++w) s += red[w][q][lane];
-            v.rc[(6 * (size_t)blockIdx.x + q) * Rp + col] = s;
-        }
+        for (int q = 0; q < 6; ++q) v.rc[(6 * (size_t)blockIdx.x + q) * Rp + col] = rc[q];
     }
 }
 
@@ -1519,7 +1482,7 @@ __global__ __launch_bounds__(VB) void pg_cov_restrict_kernel(int n_poses, Buffer
 // the start (k < 0), and the aggregate's partials of r.r and r.z, summed as the restrict kernel sums
 __global__ __launch_bounds__(VB) void pg_cov_prolong_kernel(int n_poses, Buffers b, Coarse c, Cov v, int k)
 {
-    __shared__ double red[VW][6][TB];
+    __shared__ double red[6 * VW][TB];
     const int wave = threadIdx.x / TB, lane = threadIdx.x % TB;
     const int col = blockIdx.y * TB + lane, Rp = v.R_pad;
     const bool active = k < 0 || k < v.stop_k[col];
@@ -1533,18 +1496,9 @@ __global__ __launch_bounds__(VB) void pg_cov_prolong_kernel(int n_poses, Buffers
 #pragma unroll
             for (int q = 0; q < 6; ++q) y[q] += row[(long long)q * c.nc + i] * rc;
         }
-#pragma unroll
-        for (int q = 0; q < 6; ++q) red[wave][q][lane] = y[q];
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            y[q] = 0.0;
-#pragma unroll
-            for (int w = 0; w < VW; ++w) y[q] += red[w][q][lane];
-        }
-        __syncthreads();                                     // red is used again below
+        wave_sums<6, true>(y, red);
     }
-    double rr = 0.0, rz = 0.0;
+    double d[2] = {0.0, 0.0};                                // r.r, r.z
     const int lo = blockIdx.x * c.L, hi = min(lo + c.L, n_poses);
     for (int n = lo + wave; n < hi; n += VW) {
         if (!b.free_node[n]) continue;
@@ -1562,22 +1516,14 @@ __global__ __launch_bounds__(VB) void pg_cov_prolong_kernel(int n_poses, Buffers
             }
             if (k < 0) v.p[at] = z;
             const double r = v.r[at];
-            rr += r * r;
-            rz += r * z;
+            d[0] += r * r;
+            d[1] += r * z;
         }
     }
-    red[wave][0][lane] = rr;
-    red[wave][1][lane] = rz;
-    __syncthreads();
+    wave_sums<2, false>(d, red);                             // its first barrier: every wave has read the sums for y
     if (wave == 0 && active) {
-        rr = rz = 0.0;
-#pragma unroll
-        for (int w = 0; w < VW; ++w) {
-            rr += red[w][0][lane];
-            rz += red[w][1][lane];
-        }
-        v.part_rr[(size_t)blockIdx.x * Rp + col] = rr;
-        v.part_rz[(size_t)blockIdx.x * Rp + col] = rz;
+        v.part_rr[(size_t)blockIdx.x * Rp + col] = d[0];
+        v.part_rz[(size_t)blockIdx.x * Rp + col] = d[1];
     }
 }
 
@@ -1629,15 +1575,33 @@ __global__ __launch_bounds__(TB) void pg_cov_final_kernel(int n_poses, int n_nod
 
 inline int blocks_of(long long n) { return (int)((n + TB - 1) / TB); }
 
-// the one place that knows the workspace's layout; ws = nullptr: the size only
-Buffers buffers(void *ws, size_t N, size_t E)
-{
-    Carver c = {reinterpret_cast<uintptr_t>(ws), 0};
+struct Layout {
     Buffers b;
-    const size_t nbn = (N + TB - 1) / TB;
-    b.st = c.take<PgState>(1);
+    Coarse c;                                // zeros without the coarse space
+    Cov v;                                   // zeros outside the covariance call
+    size_t total;                            // bytes; 0 where cap_ok is false
+    bool cap_ok;                             // at most NSC_POSEGRAPH_MAX_AGGREGATES aggregates
+};
+
+constexpr int NO_COV = -1;                   // layout()'s Q outside the covariance call, whose own Q may be 0
+
+// The one place that knows the workspace's layout; ws = nullptr: the size only.  The graph's regions, then with L >= 2
+// those of the coarse space (aggregates of L consecutive poses), then with Q >= 0 those of a covariance call on Q poses.
+Layout layout(void *ws, size_t N, size_t E, int L, int Q)
+{
+    Layout y = {};
+    const size_t n_agg = L ? (N + L - 1) / L : 0, nc = 6 * n_agg;
+    y.cap_ok = n_agg <= NSC_POSEGRAPH_MAX_AGGREGATES;
+    if (!y.cap_ok) return y;
+    Carver c = {reinterpret_cast<uintptr_t>(ws), 0};
+
+    Buffers &b = y.b;
+    const size_t nbn = (N + TB - 1) / TB, st_bytes = align256(sizeof(PgState));
+    b.head_bytes = st_bytes + N * sizeof(int);
+    char *head = c.take<char>(b.head_bytes);
+    b.st = reinterpret_cast<PgState *>(head);
+    b.deg = reinterpret_cast<int *>(reinterpret_cast<uintptr_t>(head) + st_bytes);
     b.row_ptr = c.take<int>(N + 1);
-    b.cursor = c.take<int>(N);
     b.tmp = c.take<int>(2 * E);
     b.list = c.take<int>(2 * E);
     b.ei = c.take<int>(E);
@@ -1649,7 +1613,6 @@ Buffers buffers(void *ws, size_t N, size_t E)
     b.fe = c.take<double>(E);
     b.ge = c.take<double>(12 * E);
     b.ye = c.take<double>(12 * E);
-    b.g = c.take<double>(6 * N);
     b.blocks = c.take<double>(21 * N);
     b.chol = c.take<double>(21 * N);
     b.x = c.take<double>(6 * N);
@@ -1662,56 +1625,102 @@ Buffers buffers(void *ws, size_t N, size_t E)
     b.part_a = c.take<double>(nbn);
     b.part_b = c.take<double>(2 * nbn);
     b.part_s = c.take<double>(nbn);
-    b.total = c.o;
-    return b;
-}
 
-// the coarse space's regions, carved behind the `base` bytes of Buffers; ws = nullptr: the size only
-Coarse coarse_buffers(void *ws, size_t base, size_t N, int L, int n_agg)
-{
-    Carver c = {reinterpret_cast<uintptr_t>(ws), base};
-    Coarse q;
-    const size_t nc = 6 * (size_t)n_agg;
-    q.cs = c.take<PgCoarse>(1);
-    q.t = c.take<double>(36 * N);
-    q.ac = c.take<double>(nc * nc);
-    q.lt = c.take<double>(nc * nc);
-    q.ainv = c.take<double>(nc * nc);
-    q.rc = c.take<double>(nc);
-    q.part = c.take<double>(2 * (size_t)n_agg);
-    q.L = L;
-    q.n_agg = n_agg;
-    q.nc = (int)nc;
-    q.total = c.o;
-    return q;
-}
+    if (L) {
+        Coarse &q = y.c;
+        q.cs = c.take<PgCoarse>(1);
+        q.t = c.take<double>(36 * N);
+        q.ac = c.take<double>(nc * nc);
+        q.lt = c.take<double>(nc * nc);
+        q.ainv = c.take<double>(nc * nc);
+        q.rc = c.take<double>(nc);
+        q.part = c.take<double>(2 * n_agg);
+        q.L = L;
+        q.n_agg = (int)n_agg;
+        q.nc = (int)nc;
+    }
 
-// aggregates of L >= 2 consecutive poses
-long long aggregates_of(long long N, long long L) { return (N + L - 1) / L; }
+    if (Q >= 0) {
+        Cov &v = y.v;
+        const size_t R = 6 * (size_t)Q, Rp = (R + TB - 1) / TB * TB, tiles = (N + CT - 1) / CT;
+        const size_t rows = tiles > n_agg ? tiles : n_agg;
+        v.x = c.take<double>(6 * N * Rp);
+        v.r = c.take<double>(6 * N * Rp);
+        v.z = c.take<double>(6 * N * Rp);
+        v.p = c.take<double>(6 * N * Rp);
+        v.ap = c.take<double>(6 * N * Rp);
+        v.part_a = c.take<double>(rows * Rp);
+        v.part_rr = c.take<double>(rows * Rp);
+        v.part_rz = c.take<double>(rows * Rp);
+        v.rc = c.take<double>(nc * Rp);
+        v.hp = c.take<double>(78 * E);
+        v.rz = c.take<double>(2 * Rp);
+        v.bb = c.take<double>(Rp);
+        v.rr = c.take<double>(Rp);
+        v.stop_k = c.take<int>(Rp);
+        v.iters = c.take<int>(Rp);
+        v.R = (int)R;
+        v.R_pad = (int)Rp;
+        v.n_tiles = (int)tiles;
+    }
+    y.total = c.o;
+    return y;
+}
 
 bool params_ok(const NscPoseGraphParams *p)
 {
-    return p->max_iteration >= 0 && p->max_pcg_iterations >= 0 && p->pcg_tolerance >= 0.0 && isfinite(p->pcg_tolerance) &&
-           p->lambda0 > 0.0 && isfinite(p->lambda0) && p->lambda_min > 0.0 && isfinite(p->lambda_min) &&
-           p->lambda_factor > 1.0 && isfinite(p->lambda_factor) && p->relative_cost >= 0.0 && isfinite(p->relative_cost) &&
-           p->min_step >= 0.0 && isfinite(p->min_step);
+    return p && p->max_iteration >= 0 && p->max_pcg_iterations >= 0 && p->pcg_tolerance >= 0.0 &&
+           isfinite(p->pcg_tolerance) && p->lambda0 > 0.0 && isfinite(p->lambda0) && p->lambda_min > 0.0 &&
+           isfinite(p->lambda_min) && p->lambda_factor > 1.0 && isfinite(p->lambda_factor) && p->relative_cost >= 0.0 &&
+           isfinite(p->relative_cost) && p->min_step >= 0.0 && isfinite(p->min_step);
 }
 
-bool kernel_ok(int32_t k) { return k >= NSC_POSEGRAPH_KERNEL_NONE && k <= NSC_POSEGRAPH_KERNEL_GEMAN_MCCLURE; }
+bool sizes_ok(int32_t n_poses, int32_t n_edges, int32_t coarse_block)
+{
+    return n_poses >= 0 && n_edges >= 0 && coarse_block >= 0 && coarse_block != 1;
+}
 
-// state and degrees zeroed, then the lists: 5 launches (2 when there are no edges)
+// what every entry point asks of the graph it is given: the sizes, the kernel id and the pointers n_poses and n_edges imply
+bool graph_ok(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
+              const double *information, int32_t n_edges, int32_t kernel, int32_t coarse_block)
+{
+    return sizes_ok(n_poses, n_edges, coarse_block) && n_edges <= NSC_POSEGRAPH_MAX_EDGES &&
+           kernel >= NSC_POSEGRAPH_KERNEL_NONE && kernel <= NSC_POSEGRAPH_KERNEL_GEMAN_MCCLURE && (n_poses == 0 || poses) &&
+           (n_edges == 0 || (edge_ij && measurements && information));
+}
+
+// the head (state and degrees) zeroed, then the lists: 5 launches (2 when there are no edges)
 void build_lists(hipStream_t s, const int64_t *edge_ij, int N, int E, const Buffers &b)
 {
-    // one fill over what lies from the state up to the cursors: the state and the degree array
-    nsc_fill_u32(s, b.st, 0u, (long long)((reinterpret_cast<char *>(b.cursor) - reinterpret_cast<char *>(b.st)) / 4));
+    nsc_fill_u32(s, b.st, 0u, (long long)(b.head_bytes / 4));
     if (E > 0) {
         hipLaunchKernelGGL(pg_count_kernel, dim3(blocks_of(E)), dim3(TB), 0, s,
                            reinterpret_cast<const long long *>(edge_ij), E, N, b);
     }
-    hipLaunchKernelGGL(pg_scan_kernel, dim3(1), dim3(TB), 0, s, N, b);
+    hipLaunchKernelGGL(nsc_csr_scan_kernel<0>, dim3(1), dim3(1024), 0, s, b.deg, N, b.row_ptr);
     if (E > 0) {
         hipLaunchKernelGGL(pg_fill_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, E, b);
         if (N > 0) hipLaunchKernelGGL(pg_sort_kernel, dim3(N), dim3(TB), 0, s, b);
+    }
+}
+
+// The system at `poses` and the state's lambda, N > 0: linearise, assemble with the start of PCG, and with the coarse
+// space P, A_c, its factor and its inverse.  2 launches (1 without edges), 4 more with the coarse space.
+void launch_system(hipStream_t s, const double *poses, const double *measurements, const double *information,
+                   const uint8_t *fixed, int N, int E, int kernel, const double *edge_scale, const Layout &y)
+{
+    const Buffers &b = y.b;
+    const Coarse &c = y.c;
+    const int gn = blocks_of(N);
+    if (E > 0)
+        hipLaunchKernelGGL(pg_linearize_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b,
+                           nullptr, kernel, edge_scale, nullptr);
+    hipLaunchKernelGGL(pg_assemble_kernel, dim3(gn), dim3(TB), 0, s, N, E, fixed, b, nullptr, b.blocks, 1);
+    if (c.L) {
+        hipLaunchKernelGGL(pg_coarse_basis_kernel, dim3(gn), dim3(TB), 0, s, poses, N, b, c);
+        hipLaunchKernelGGL(pg_coarse_galerkin_kernel, dim3(c.n_agg * c.n_agg), dim3(TB), 0, s, N, E, b, c);
+        hipLaunchKernelGGL(pg_coarse_factor_kernel, dim3(1), dim3(CB), 0, s, b, c);
+        hipLaunchKernelGGL(pg_coarse_invert_kernel, dim3(c.nc), dim3(TB), 0, s, b, c);
     }
 }
 
@@ -1722,26 +1731,27 @@ int optimize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const
              void *stream, int32_t kernel, const double *edge_scale, double *edge_chi2, double *edge_weight,
              int32_t coarse_block, double *coarse_stats)
 {
-    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES || !params || !params_ok(params) ||
-        !kernel_ok(kernel) || coarse_block < 0 || coarse_block == 1)
+    if (!graph_ok(poses, n_poses, edge_ij, measurements, information, n_edges, kernel, coarse_block) || !params_ok(params) ||
+        !stats || !cost_history || (n_poses > 0 && (!poses_out || !fixed)))
         return NSC_EINVAL;
-    if (!stats || !cost_history) return NSC_EINVAL;
-    if (n_poses > 0 && (!poses || !poses_out || !fixed)) return NSC_EINVAL;
-    if (n_edges > 0 && (!edge_ij || !measurements || !information)) return NSC_EINVAL;
     const int L = coarse_block;
-    const long long n_agg = L ? aggregates_of(n_poses, L) : 0;
-    if (n_agg > NSC_POSEGRAPH_MAX_AGGREGATES) return NSC_EUNSUPPORTED;
+    const Layout y = layout(ws, n_poses, n_edges, L, NO_COV);
+    if (!y.cap_ok) return NSC_EUNSUPPORTED;
     // per outer step 8 launches and 4 per inner iteration; with the coarse space 14 and 5
     if ((long long)params->max_iteration * ((L ? 5LL : 4LL) * params->max_pcg_iterations + (L ? 14 : 8)) >
         NSC_POSEGRAPH_MAX_LAUNCHES)
         return NSC_EUNSUPPORTED;
-    const Buffers b = buffers(ws, n_poses, n_edges);
-    const Coarse c = coarse_buffers(ws, b.total, n_poses, L, (int)n_agg);
-    if (!ws || ws_bytes < (L ? c.total : b.total)) return NSC_EWORKSPACE;
+    if (!ws || ws_bytes < y.total) return NSC_EWORKSPACE;
+    const Buffers &b = y.b;
+    const Coarse &c = y.c;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int N = n_poses, E = n_edges, gn = blocks_of(N), ge = blocks_of(E), ga = (int)n_agg;
+    const int N = n_poses, E = n_edges, gn = blocks_of(N), ge = blocks_of(E), ga = c.n_agg;
     const NscPoseGraphParams prm = *params;
     const double tol2 = prm.pcg_tolerance * prm.pcg_tolerance;
+    // r.r and r.z reach the begin and direction kernels as one partial per workgroup of nodes or, with the coarse space, one
+    // per aggregate
+    const double *part = L ? c.part : b.part_b;
+    const int n_part = L ? ga : gn;
 
     build_lists(s, edge_ij, N, E, b);
     if (N > 0 && poses_out != poses)
@@ -1749,98 +1759,41 @@ int optimize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const
     if (E > 0)
         hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0,
                            kernel, edge_scale, b.fe, nullptr, nullptr);
-    if (N > 0) hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 0);
-    hipLaunchKernelGGL(pg_init_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm.lambda0, cost_history, L ? c.cs : nullptr);
+    if (N > 0) hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b);
+    hipLaunchKernelGGL(pg_init_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm.lambda0, cost_history, c.cs);
 
     for (int it = 0; it < prm.max_iteration && N > 0; ++it) {
-        if (E > 0)
-            hipLaunchKernelGGL(pg_linearize_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b,
-                               nullptr, 1, kernel, edge_scale, nullptr);
-        hipLaunchKernelGGL(pg_assemble_kernel, dim3(gn), dim3(TB), 0, s, N, E, fixed, b, b.g, b.blocks, 1);
+        launch_system(s, poses_out, measurements, information, fixed, N, E, kernel, edge_scale, y);
         if (L) {
-            hipLaunchKernelGGL(pg_coarse_basis_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, c);
-            hipLaunchKernelGGL(pg_coarse_galerkin_kernel, dim3(ga * ga), dim3(TB), 0, s, N, E, b, c);
-            hipLaunchKernelGGL(pg_coarse_factor_kernel, dim3(1), dim3(CB), 0, s, b, c);
-            hipLaunchKernelGGL(pg_coarse_invert_kernel, dim3(c.nc), dim3(TB), 0, s, b, c);
             hipLaunchKernelGGL(pg_coarse_restrict_kernel, dim3(ga), dim3(TB), 0, s, N, gn, b, c, -1);
             hipLaunchKernelGGL(pg_coarse_prolong_kernel, dim3(ga), dim3(TB), 0, s, N, b, c, -1);
         }
-        if (L)
-            hipLaunchKernelGGL(pg_coarse_begin_kernel, dim3(1), dim3(TB), 0, s, b, c);
-        else
-            hipLaunchKernelGGL(pg_pcg_begin_kernel, dim3(1), dim3(TB), 0, s, gn, b);
+        hipLaunchKernelGGL(pg_pcg_begin_kernel, dim3(1), dim3(TB), 0, s, b, part, n_part);
         for (int k = 0; k < prm.max_pcg_iterations && E > 0; ++k) {
             hipLaunchKernelGGL(pg_edge_matvec_kernel, dim3(ge), dim3(TB), 0, s, E, b, k);
             hipLaunchKernelGGL(pg_node_matvec_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
             if (L) {
                 hipLaunchKernelGGL(pg_coarse_restrict_kernel, dim3(ga), dim3(TB), 0, s, N, gn, b, c, k);
                 hipLaunchKernelGGL(pg_coarse_prolong_kernel, dim3(ga), dim3(TB), 0, s, N, b, c, k);
-                hipLaunchKernelGGL(pg_coarse_direction_kernel, dim3(gn), dim3(TB), 0, s, N, b, c, k, tol2);
             } else {
                 hipLaunchKernelGGL(pg_pcg_step_kernel, dim3(gn), dim3(TB), 0, s, N, b, k);
-                hipLaunchKernelGGL(pg_pcg_direction_kernel, dim3(gn), dim3(TB), 0, s, N, b, k, tol2);
             }
+            hipLaunchKernelGGL(pg_pcg_direction_kernel, dim3(gn), dim3(TB), 0, s, N, b, k, tol2, part, n_part);
         }
         hipLaunchKernelGGL(pg_update_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it, step0);
         if (E > 0)
-            hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, b.cand, measurements, information, E, b, 1,
+            hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, b.cand, measurements, information, E, b, 0,
                                kernel, edge_scale, b.fe, nullptr, nullptr);
-        hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b, 1);
+        hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(gn), dim3(TB), 0, s, N, b);
         hipLaunchKernelGGL(pg_accept_kernel, dim3(1), dim3(TB), 0, s, gn, b, prm, it, cost_history);
         hipLaunchKernelGGL(pg_commit_kernel, dim3(gn), dim3(TB), 0, s, poses_out, N, b, it);
     }
-    hipLaunchKernelGGL(pg_finalize_kernel, dim3(1), dim3(TB), 0, s, b, prm.max_iteration, stats, cost_history,
-                       L ? c.cs : nullptr, ga, coarse_stats);
+    hipLaunchKernelGGL(pg_finalize_kernel, dim3(1), dim3(TB), 0, s, b, prm.max_iteration, stats, cost_history, c.cs, ga,
+                       coarse_stats);
     if (E > 0 && (edge_chi2 || edge_weight))
-        hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 0,
+        hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(ge), dim3(TB), 0, s, poses_out, measurements, information, E, b, 1,
                            kernel, edge_scale, nullptr, edge_chi2, edge_weight);
     return launch_status();
-}
-
-// the covariance call's regions, carved behind the `base` bytes of Buffers and Coarse; ws = nullptr: the size only
-Cov cov_buffers(void *ws, size_t base, size_t N, size_t E, int Q, int n_agg)
-{
-    Carver c = {reinterpret_cast<uintptr_t>(ws), base};
-    Cov v;
-    const size_t R = 6 * (size_t)Q, Rp = (R + TB - 1) / TB * TB, tiles = (N + CT - 1) / CT;
-    const size_t rows = tiles > (size_t)n_agg ? tiles : (size_t)n_agg;
-    v.x = c.take<double>(6 * N * Rp);
-    v.r = c.take<double>(6 * N * Rp);
-    v.z = c.take<double>(6 * N * Rp);
-    v.p = c.take<double>(6 * N * Rp);
-    v.ap = c.take<double>(6 * N * Rp);
-    v.part_a = c.take<double>(rows * Rp);
-    v.part_rr = c.take<double>(rows * Rp);
-    v.part_rz = c.take<double>(rows * Rp);
-    v.rc = c.take<double>(6 * (size_t)n_agg * Rp);
-    v.hp = c.take<double>(78 * E);
-    v.rz = c.take<double>(2 * Rp);
-    v.bb = c.take<double>(Rp);
-    v.rr = c.take<double>(Rp);
-    v.stop_k = c.take<int>(Rp);
-    v.iters = c.take<int>(Rp);
-    v.R = (int)R;
-    v.R_pad = (int)Rp;
-    v.n_tiles = (int)tiles;
-    v.total = c.o;
-    return v;
-}
-
-// the covariance call's three layouts; false when the coarse space has too many aggregates
-bool cov_layout(void *ws, int N, int E, int Q, int L, Buffers &b, Coarse &c, Cov &v)
-{
-    const long long n_agg = L ? aggregates_of(N, L) : 0;
-    if (n_agg > NSC_POSEGRAPH_MAX_AGGREGATES) return false;
-    b = buffers(ws, N, E);
-    c = coarse_buffers(ws, b.total, N, L, (int)n_agg);
-    v = cov_buffers(ws, L ? c.total : b.total, N, E, Q, (int)n_agg);
-    return true;
-}
-
-bool cov_sizes_ok(int32_t n_poses, int32_t n_edges, int32_t n_nodes, int32_t coarse_block)
-{
-    return n_poses >= 0 && n_edges >= 0 && n_edges <= NSC_POSEGRAPH_MAX_EDGES && n_nodes >= 0 && coarse_block >= 0 &&
-           coarse_block != 1;
 }
 
 }  // namespace
@@ -1849,11 +1802,10 @@ extern "C" {
 
 size_t nsc_posegraph_covariance_workspace_bytes(int32_t n_poses, int32_t n_edges, int32_t n_nodes, int32_t coarse_block)
 {
-    if (!cov_sizes_ok(n_poses, n_edges, n_nodes, coarse_block) || n_nodes > NSC_POSEGRAPH_MAX_COV_NODES) return 0;
-    Buffers b;
-    Coarse c;
-    Cov v;
-    return cov_layout(nullptr, n_poses, n_edges, n_nodes, coarse_block, b, c, v) ? v.total : 0;
+    if (!sizes_ok(n_poses, n_edges, coarse_block) || n_edges > NSC_POSEGRAPH_MAX_EDGES || n_nodes < 0 ||
+        n_nodes > NSC_POSEGRAPH_MAX_COV_NODES)
+        return 0;
+    return layout(nullptr, n_poses, n_edges, coarse_block, n_nodes).total;
 }
 
 int nsc_posegraph_covariance(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
@@ -1863,23 +1815,21 @@ int nsc_posegraph_covariance(const double *poses, int32_t n_poses, const int64_t
                              void *stream, int32_t kernel, const double *edge_scale, int32_t coarse_block,
                              double *coarse_stats)
 {
-    if (!cov_sizes_ok(n_poses, n_edges, n_nodes, coarse_block) || !params || !params_ok(params) || !kernel_ok(kernel))
+    if (!graph_ok(poses, n_poses, edge_ij, measurements, information, n_edges, kernel, coarse_block) || !params_ok(params) ||
+        !stats || (n_poses > 0 && !fixed) || n_nodes < 0 || (n_nodes > 0 && (!nodes || !joint || !residual || !iterations)))
         return NSC_EINVAL;
-    if (!stats) return NSC_EINVAL;
-    if (n_poses > 0 && (!poses || !fixed)) return NSC_EINVAL;
-    if (n_edges > 0 && (!edge_ij || !measurements || !information)) return NSC_EINVAL;
-    if (n_nodes > 0 && (!nodes || !joint || !residual || !iterations)) return NSC_EINVAL;
     if (n_nodes > NSC_POSEGRAPH_MAX_COV_NODES) return NSC_EUNSUPPORTED;
     const int L = coarse_block;
     // per inner iteration 3 launches, 4 with the coarse space; at most 18 around the loop
     if ((L ? 4LL : 3LL) * params->max_pcg_iterations + 18 > NSC_POSEGRAPH_MAX_LAUNCHES) return NSC_EUNSUPPORTED;
-    Buffers b;
-    Coarse c;
-    Cov v;
-    if (!cov_layout(ws, n_poses, n_edges, n_nodes, L, b, c, v)) return NSC_EUNSUPPORTED;
-    if (!ws || ws_bytes < v.total) return NSC_EWORKSPACE;
+    const Layout y = layout(ws, n_poses, n_edges, L, n_nodes);
+    if (!y.cap_ok) return NSC_EUNSUPPORTED;
+    if (!ws || ws_bytes < y.total) return NSC_EWORKSPACE;
+    const Buffers &b = y.b;
+    const Coarse &c = y.c;
+    const Cov &v = y.v;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int N = n_poses, E = n_edges, Q = n_nodes, gn = blocks_of(N), ge = blocks_of(E), ga = c.n_agg;
+    const int N = n_poses, E = n_edges, Q = n_nodes, ga = c.n_agg;
     const double tol2 = params->pcg_tolerance * params->pcg_tolerance;
     const dim3 tiles(v.n_tiles, v.R_pad / TB), aggs(ga, v.R_pad / TB);
     const long long *sel = reinterpret_cast<const long long *>(nodes);
@@ -1887,19 +1837,9 @@ int nsc_posegraph_covariance(const double *poses, int32_t n_poses, const int64_t
 
     build_lists(s, edge_ij, N, E, b);        // the state zeroed: done = 0 and lambda = 0, the undamped system
     if (solve) {
-        if (E > 0) {
-            hipLaunchKernelGGL(pg_linearize_kernel, dim3(ge), dim3(TB), 0, s, poses, measurements, information, E, b,
-                               nullptr, 0, kernel, edge_scale, nullptr);
-            hipLaunchKernelGGL(pg_cov_pack_kernel, dim3(ge), dim3(TB), 0, s, E, b, v.hp);
-        }
-        hipLaunchKernelGGL(pg_assemble_kernel, dim3(gn), dim3(TB), 0, s, N, E, fixed, b, b.g, b.blocks, 1);
-        if (L) {
-            nsc_fill_u32(s, c.cs, 0u, (long long)(sizeof(PgCoarse) / 4));
-            hipLaunchKernelGGL(pg_coarse_basis_kernel, dim3(gn), dim3(TB), 0, s, poses, N, b, c);
-            hipLaunchKernelGGL(pg_coarse_galerkin_kernel, dim3(ga * ga), dim3(TB), 0, s, N, E, b, c);
-            hipLaunchKernelGGL(pg_coarse_factor_kernel, dim3(1), dim3(CB), 0, s, b, c);
-            hipLaunchKernelGGL(pg_coarse_invert_kernel, dim3(c.nc), dim3(TB), 0, s, b, c);
-        }
+        if (L) nsc_fill_u32(s, c.cs, 0u, (long long)(sizeof(PgCoarse) / 4));
+        launch_system(s, poses, measurements, information, fixed, N, E, kernel, edge_scale, y);
+        if (E > 0) hipLaunchKernelGGL(pg_cov_pack_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, E, b, v.hp);
         hipLaunchKernelGGL(pg_cov_init_kernel, tiles, dim3(VB), 0, s, N, sel, b, v);
         if (L) {
             hipLaunchKernelGGL(pg_cov_restrict_kernel, aggs, dim3(VB), 0, s, N, b, c, v, -1);
@@ -1919,8 +1859,7 @@ int nsc_posegraph_covariance(const double *poses, int32_t n_poses, const int64_t
         }
     }
     hipLaunchKernelGGL(pg_cov_final_kernel, dim3(Q > 0 ? Q : 1), dim3(TB), 0, s, N, Q, sel, b, v, solve ? 1 : 0, tol2, joint,
-                       residual, iterations, reinterpret_cast<long long *>(stats), L && solve ? c.cs : nullptr, ga,
-                       coarse_stats);
+                       residual, iterations, reinterpret_cast<long long *>(stats), solve ? c.cs : nullptr, ga, coarse_stats);
     return launch_status();
 }
 
@@ -1940,8 +1879,7 @@ void nsc_posegraph_default_params(NscPoseGraphParams *p)
 size_t nsc_posegraph_workspace_bytes(int32_t n_poses, int32_t n_edges, const NscPoseGraphParams *params)
 {
     (void)params;                            // the layout holds one outer and one inner iteration whatever the caps
-    if (n_poses < 0 || n_edges < 0) return 0;
-    return buffers(nullptr, n_poses, n_edges).total;
+    return nsc_posegraph_coarse_workspace_bytes(n_poses, n_edges, 0);
 }
 
 int nsc_posegraph_linearize(const double *poses, int32_t n_poses, const int64_t *edge_ij, const double *measurements,
@@ -1959,12 +1897,12 @@ int nsc_posegraph_linearize_robust(const double *poses, int32_t n_poses, const i
                                    void *ws, size_t ws_bytes, void *stream, int32_t kernel, const double *edge_scale,
                                    double *weights)
 {
-    if (n_poses < 0 || n_edges < 0 || n_edges > NSC_POSEGRAPH_MAX_EDGES || !kernel_ok(kernel)) return NSC_EINVAL;
-    if (!cost || !skipped) return NSC_EINVAL;
-    if (n_poses > 0 && (!poses || !gradient || !blocks)) return NSC_EINVAL;
-    if (n_edges > 0 && (!edge_ij || !measurements || !information || !residuals)) return NSC_EINVAL;
-    const Buffers b = buffers(ws, n_poses, n_edges);
-    if (!ws || ws_bytes < b.total) return NSC_EWORKSPACE;
+    if (!graph_ok(poses, n_poses, edge_ij, measurements, information, n_edges, kernel, 0) || !cost || !skipped ||
+        (n_poses > 0 && (!gradient || !blocks)) || (n_edges > 0 && !residuals))
+        return NSC_EINVAL;
+    const Layout y = layout(ws, n_poses, n_edges, 0, NO_COV);
+    if (!ws || ws_bytes < y.total) return NSC_EWORKSPACE;
+    const Buffers &b = y.b;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int N = n_poses, E = n_edges;
     build_lists(s, edge_ij, N, E, b);
@@ -1972,10 +1910,10 @@ int nsc_posegraph_linearize_robust(const double *poses, int32_t n_poses, const i
         hipLaunchKernelGGL(pg_edge_cost_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b,
                            0, kernel, edge_scale, b.fe, nullptr, nullptr);
         hipLaunchKernelGGL(pg_linearize_kernel, dim3(blocks_of(E)), dim3(TB), 0, s, poses, measurements, information, E, b,
-                           residuals, 0, kernel, edge_scale, weights);
+                           residuals, kernel, edge_scale, weights);
     }
     if (N > 0) {
-        hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(blocks_of(N)), dim3(TB), 0, s, N, b, 0);
+        hipLaunchKernelGGL(pg_cost_gather_kernel, dim3(blocks_of(N)), dim3(TB), 0, s, N, b);
         hipLaunchKernelGGL(pg_assemble_kernel, dim3(blocks_of(N)), dim3(TB), 0, s, N, E, nullptr, b, gradient, blocks, 0);
     }
     hipLaunchKernelGGL(pg_linearize_out_kernel, dim3(1), dim3(TB), 0, s, blocks_of(N), b, cost,
@@ -2006,12 +1944,8 @@ int nsc_posegraph_optimize_robust(const double *poses, int32_t n_poses, const in
 
 size_t nsc_posegraph_coarse_workspace_bytes(int32_t n_poses, int32_t n_edges, int32_t coarse_block)
 {
-    if (n_poses < 0 || n_edges < 0 || coarse_block < 0 || coarse_block == 1) return 0;
-    const size_t base = buffers(nullptr, n_poses, n_edges).total;
-    if (coarse_block == 0) return base;
-    const long long n_agg = aggregates_of(n_poses, coarse_block);
-    if (n_agg > NSC_POSEGRAPH_MAX_AGGREGATES) return 0;
-    return coarse_buffers(nullptr, base, n_poses, coarse_block, (int)n_agg).total;
+    if (!sizes_ok(n_poses, n_edges, coarse_block)) return 0;
+    return layout(nullptr, n_poses, n_edges, coarse_block, NO_COV).total;
 }
 
 int nsc_posegraph_optimize_coarse(const double *poses, int32_t n_poses, const int64_t *edge_ij,

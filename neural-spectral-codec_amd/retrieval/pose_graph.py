@@ -194,6 +194,22 @@ class PoseGraphOptimizer:
             return 0
         return max(8, -(-N // 64)) if self.coarse_block == "auto" else int(self.coarse_block)
 
+    def _coarse_within_cap(self, N):
+        """``_coarse``, refused where it gives more aggregates than the library takes"""
+        block = self._coarse(N)
+        if block and -(-N // block) > _lib.POSEGRAPH_MAX_AGGREGATES:
+            raise _lib.NscError(f"pose graph: coarse_block {block} gives {-(-N // block)} aggregates of {N} poses; "
+                                f"at most {_lib.POSEGRAPH_MAX_AGGREGATES}")
+        return block
+
+    @staticmethod
+    def _coarse_stats(out, res):
+        """``coarse_stats`` of a device result, where the call had a coarse space, read back into ``res``"""
+        if "coarse_stats" in out:
+            cs = out["coarse_stats"].cpu().numpy()
+            res.update(coarse_aggregates=int(cs[0]), coarse_failed=int(cs[1]))
+        return res
+
     def _inputs(self, poses, edge_ij, measurements, information):
         dev = poses.device if isinstance(poses, torch.Tensor) else self.device
         if dev.type != "cuda":
@@ -273,11 +289,8 @@ class PoseGraphOptimizer:
         if c is not None:
             out["chi2"], out["weights"] = torch.empty(E, **f64), torch.empty(E, **f64)
         L = _lib.lib()
-        block = self._coarse(N)
+        block = self._coarse_within_cap(N)
         if block:
-            if -(-N // block) > _lib.POSEGRAPH_MAX_AGGREGATES:
-                raise _lib.NscError(f"pose graph: coarse_block {block} gives {-(-N // block)} aggregates of {N} poses; "
-                                    f"at most {_lib.POSEGRAPH_MAX_AGGREGATES}")
             out["coarse_stats"] = torch.empty(2, **f64)
             need = L.nsc_posegraph_coarse_workspace_bytes(N, E, block)
         else:
@@ -338,10 +351,7 @@ class PoseGraphOptimizer:
         fx = self._fixed(fixed, dev, N)
         sel = (sel if isinstance(sel, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sel))).to(
             device=dev, dtype=torch.int64).contiguous()
-        block = self._coarse(N)
-        if block and -(-N // block) > _lib.POSEGRAPH_MAX_AGGREGATES:
-            raise _lib.NscError(f"pose graph: coarse_block {block} gives {-(-N // block)} aggregates of {N} poses; "
-                                f"at most {_lib.POSEGRAPH_MAX_AGGREGATES}")
+        block = self._coarse_within_cap(N)
         f64 = dict(dtype=torch.float64, device=dev)
         out = dict(joint=torch.empty((Q, Q, 6, 6), **f64), residual=torch.empty((Q, 6), **f64),
                    iterations=torch.empty((Q, 6), dtype=torch.int32, device=dev),
@@ -371,10 +381,7 @@ class PoseGraphOptimizer:
         res = {k: out[k].cpu().numpy() for k in ("joint", "residual", "iterations")}
         res["converged"] = res["residual"] <= self.params.pcg_tolerance
         res.update(zip(_lib.POSEGRAPH_COV_STAT_NAMES, (int(s) for s in out["stats"].cpu().numpy())))
-        if "coarse_stats" in out:
-            cs = out["coarse_stats"].cpu().numpy()
-            res.update(coarse_aggregates=int(cs[0]), coarse_failed=int(cs[1]))
-        return res
+        return self._coarse_stats(out, res)
 
     def optimize(self, poses, edge_ij, measurements, information, fixed=None, robust_scale=None):
         """-> dict: poses (N,4,4) (a device tensor for device poses, numpy for numpy), cost0, cost, iterations, accepted,
@@ -396,7 +403,4 @@ class PoseGraphOptimizer:
                    step=float(s[L.POSEGRAPH_STAT_STEP]), **{"lambda": float(s[L.POSEGRAPH_STAT_LAMBDA])})
         if robust_scale is not None:
             res.update(chi2=out["chi2"].cpu().numpy(), weights=out["weights"].cpu().numpy())
-        if "coarse_stats" in out:
-            cs = out["coarse_stats"].cpu().numpy()
-            res.update(coarse_aggregates=int(cs[0]), coarse_failed=int(cs[1]))
-        return res
+        return self._coarse_stats(out, res)

@@ -50,3 +50,25 @@ def node_types(cg):
         k = NAMES.get(t.value, f"type {t.value}")
         out[k] = out.get(k, 0) + 1
     return out
+
+
+def capture_replay(step):
+    """``step()`` -> dict of device tensors.  It runs eagerly, once more on a side stream (to warm the allocator outside
+    the capture), and is then captured; the captured outputs are overwritten with -1 (0xbff0...: the replay has to write
+    every output) and the graph is replayed and synchronised.
+    -> (clones of the eager outputs, the captured outputs after the replay, node_types of the graph)"""
+    eager = {k: v.clone() for k, v in step().items()}
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step()
+    torch.cuda.current_stream().wait_stream(s)
+    with keep_graphs() as made:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            captured = step()
+    for v in captured.values():
+        v.fill_(-1)
+    g.replay()
+    torch.cuda.synchronize()
+    return eager, captured, node_types(made[0])

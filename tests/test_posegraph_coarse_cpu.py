@@ -10,16 +10,11 @@ import scipy.sparse as sp
 
 import posegraph_coarse_restatement as Cr
 import posegraph_restatement as P
+from _posegraph import first_fixed
 
 LAMBDA = P.DEFAULTS["lambda0"]
 # inner iterations to |r| <= 1e-12 |g| at lambda = 1e-4 on drift_ring(n): block-Jacobi, and with aggregates of 8 poses
 TABLE = {64: (341, 97), 65: (344, 85), 257: (1210, 79)}
-
-
-def first_fixed(n):
-    fixed = np.zeros(n, bool)
-    fixed[:1] = True
-    return fixed
 
 
 # ---- the basis ------------------------------------------------------------------------------------------------------

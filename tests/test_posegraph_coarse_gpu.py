@@ -3,8 +3,6 @@ float64 restatement (tests/posegraph_coarse_restatement.py) -- the first step ag
 aggregate, the inner iterations it saves, full optimisations (the 1 025-pose ring that block-Jacobi does not close within
 the default caps among them), bitwise equivalence with the robust entry point at coarse_block = 0, determinism, capture,
 aliasing, fixed / skipped / degenerate inputs and a robust kernel."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -12,23 +10,13 @@ import torch
 import posegraph_coarse_restatement as Cr
 import posegraph_restatement as P
 import posegraph_robust_restatement as R
-from test_posegraph_gpu import assert_poses, chain5, graph, host, optimizer
+from _posegraph import abi_optimize, first_fixed, host, optimizer, same_bits
+from test_posegraph_gpu import assert_poses, chain5, graph
 
 pytestmark = pytest.mark.gpu
 
 LAMBDA = P.DEFAULTS["lambda0"]
 BLOCK_JACOBI = {64: 341, 257: 1210}          # the restatement's inner iterations to 1e-12 (test_posegraph_coarse_cpu.py)
-
-
-def first_fixed(n):
-    fixed = np.zeros(n, bool)
-    fixed[:1] = True
-    return fixed
-
-
-def same_bits(a, b, keys=None):
-    for k in (keys or a):
-        assert a[k].tobytes() == b[k].tobytes(), k
 
 
 # ---- the first step -----------------------------------------------------------------------------------------------
@@ -121,34 +109,6 @@ def test_ring_of_1025_converges_where_block_jacobi_is_capped():
 
 # ---- equivalence and determinism --------------------------------------------------------------------------------------
 
-def abi_optimize(entry, X, e, Z, Om, scale, kernel, coarse_block=None, **params):
-    """nsc_posegraph_optimize_robust, or nsc_posegraph_optimize_coarse with ``coarse_block``, as the C ABI has them"""
-    from neural_spectral_codec_amd import _lib
-    L, ptr = _lib.lib(), _lib.ptr
-    prm = optimizer(**params).params
-    dev = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in
-           (np.asarray(X, np.float64), np.asarray(e, np.int64).reshape(-1, 2), np.asarray(Z, np.float64),
-            np.asarray(Om, np.float64), np.asarray(scale, np.float64))]
-    N, E = len(dev[0]), len(dev[1])
-    fixed = torch.from_numpy(first_fixed(N).astype(np.uint8)).cuda()
-    f64 = dict(dtype=torch.float64, device="cuda")
-    out = dict(poses=torch.empty((N, 4, 4), **f64), stats=torch.empty(_lib.POSEGRAPH_STATS, **f64),
-               cost_history=torch.empty(prm.max_iteration + 1, **f64), step0=torch.empty((N, 6), **f64),
-               chi2=torch.empty(E, **f64), weights=torch.empty(E, **f64))
-    need = L.nsc_posegraph_workspace_bytes(N, E, None) if coarse_block is None else \
-        L.nsc_posegraph_coarse_workspace_bytes(N, E, coarse_block)
-    ws = torch.empty(max(int(need), 1), dtype=torch.uint8, device="cuda")
-    args = (ptr(dev[0]), N, ptr(dev[1]), ptr(dev[2]), ptr(dev[3]), E, ptr(fixed), C.byref(prm), ptr(out["poses"]),
-            ptr(out["stats"]), ptr(out["cost_history"]), ptr(out["step0"]), ptr(ws), int(ws.numel()),
-            _lib.stream_ptr(ws.device), kernel, ptr(dev[4]), ptr(out["chi2"]), ptr(out["weights"]))
-    if coarse_block is None:
-        _lib.check(getattr(L, entry)(*args), entry)
-    else:
-        out["coarse_stats"] = torch.empty(2, **f64)
-        _lib.check(getattr(L, entry)(*args, coarse_block, ptr(out["coarse_stats"])), entry)
-    return host(out)
-
-
 def test_coarse_block_zero_is_the_robust_entry_point():
     truth, init, e, Z, Om, closures = R.outlier_ring(0)
     scale = R.closure_scale(len(e), closures, 3.0)
@@ -186,7 +146,7 @@ def test_alias_of_input_and_output(ring64):
 
 
 def test_captured_replay_equals_eager(ring64):
-    from _hipgraph import keep_graphs, node_types
+    from _hipgraph import capture_replay
     _, init, e, Z, Om = ring64
     prm = dict(max_iteration=4, max_pcg_iterations=30)
     opt = optimizer(coarse_block=8, **prm)
@@ -196,25 +156,11 @@ def test_captured_replay_equals_eager(ring64):
 
     def step():
         return opt.optimize_device(*dev, fixed=fixed, step0=True)
-    eager = {k: v.clone() for k, v in step().items()}
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        step()                                               # warm the allocator outside the capture
-    torch.cuda.current_stream().wait_stream(s)
-    with keep_graphs() as made:
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            cap = step()
-    for v in cap.values():
-        v.fill_(-1)                                          # the replay has to write every output
-    g.replay()
-    torch.cuda.synchronize()
+    eager, cap, types = capture_replay(step)
     assert set(eager) == {"poses", "stats", "cost_history", "step0", "coarse_stats"}
     for k in eager:
         assert torch.equal(eager[k], cap[k]), k
     assert eager["stats"][1].item() >= 1 and eager["coarse_stats"].tolist() == [8.0, 0.0]
-    types = node_types(made[0])
     launches = 5 + 1 + 3 + prm["max_iteration"] * (14 + 5 * prm["max_pcg_iterations"]) + 1      # include/nsc.h
     kernels = types.pop("kernel", 0)
     assert types.get("memset", 0) == 0 and types.get("memcpy", 0) == 0, types

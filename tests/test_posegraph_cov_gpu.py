@@ -13,7 +13,8 @@ import torch
 import posegraph_cov_restatement as V
 import posegraph_restatement as P
 import posegraph_robust_restatement as R
-from test_posegraph_gpu import chain5, host, optimizer
+from _posegraph import host, optimizer
+from test_posegraph_gpu import chain5
 
 pytestmark = pytest.mark.gpu
 
@@ -160,7 +161,7 @@ def test_columns_do_not_depend_on_their_neighbours(ring65):
 
 
 def test_captured_replay_equals_eager(ring65):
-    from _hipgraph import keep_graphs, node_types
+    from _hipgraph import capture_replay
     X, e, Z, Om, _ = ring65
     cap = 60
     opt = optimizer(coarse_block=8, max_pcg_iterations=cap, pcg_tolerance=V.TAU)
@@ -171,25 +172,11 @@ def test_captured_replay_equals_eager(ring65):
 
     def step():
         return opt.covariance_device(*dev, nodes, fixed=fixed)
-    eager = {k: v.clone() for k, v in step().items()}
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        step()                                               # warm the allocator outside the capture
-    torch.cuda.current_stream().wait_stream(s)
-    with keep_graphs() as made:
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            captured = step()
-    for v in captured.values():
-        v.fill_(-1)                                          # the replay has to write every output
-    g.replay()
-    torch.cuda.synchronize()
+    eager, captured, types = capture_replay(step)
     assert set(eager) == {"joint", "residual", "iterations", "stats", "coarse_stats"}
     for k in eager:
         assert torch.equal(eager[k], captured[k]), k
     assert eager["iterations"].min().item() >= 1 and eager["coarse_stats"].tolist() == [9.0, 0.0]
-    types = node_types(made[0])
     launches = 5 + 2 + 1 + 5 + 4 + 4 * cap + 1               # include/nsc.h
     kernels = types.pop("kernel", 0)
     assert types.get("memset", 0) == 0 and types.get("memcpy", 0) == 0, types

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import posegraph_restatement as P
+from _posegraph import host, optimizer
 
 pytestmark = pytest.mark.gpu
 
@@ -17,15 +18,6 @@ ANGLES = (0.0, 1e-9, 1e-3, np.pi / 2, np.deg2rad(170.0))
 def _pg():
     from neural_spectral_codec_amd.retrieval import pose_graph as pg
     return pg
-
-
-def optimizer(**params):
-    return _pg().PoseGraphOptimizer(**params)
-
-
-def host(out):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
 
 
 def close(got, want, what):
@@ -292,7 +284,7 @@ def test_alias_of_input_and_output(ring64):
 
 
 def test_captured_replay_equals_eager(ring64):
-    from _hipgraph import keep_graphs, node_types
+    from _hipgraph import capture_replay
     _, init, e, Z, Om = ring64
     prm = dict(max_iteration=4, max_pcg_iterations=30)
     opt = optimizer(**prm)
@@ -302,24 +294,10 @@ def test_captured_replay_equals_eager(ring64):
 
     def step():
         return opt.optimize_device(*dev, fixed=fixed, step0=True)
-    eager = {k: v.clone() for k, v in step().items()}
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        step()                                               # warm the allocator outside the capture
-    torch.cuda.current_stream().wait_stream(s)
-    with keep_graphs() as made:
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            cap = step()
-    for v in cap.values():
-        v.fill_(-1)                                          # 0xbff0...: the replay has to write every output
-    g.replay()
-    torch.cuda.synchronize()
+    eager, cap, types = capture_replay(step)
     for k in eager:
         assert torch.equal(eager[k], cap[k]), k
     assert eager["stats"][1].item() >= 1
-    types = node_types(made[0])
     launches = 5 + 1 + 3 + prm["max_iteration"] * (8 + 4 * prm["max_pcg_iterations"]) + 1     # include/nsc.h
     kernels = types.pop("kernel", 0)
     assert types.get("memset", 0) == 0 and types.get("memcpy", 0) == 0, types

@@ -1,70 +1,18 @@
 """Robust kernels of the pose-graph optimiser on the MI355X: nsc_posegraph_linearize_robust and
 nsc_posegraph_optimize_robust against the float64 restatement (tests/posegraph_robust_restatement.py), bitwise against
 the plain entry points wherever every edge is quadratic, and on a ring with two false closures."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import posegraph_restatement as P
 import posegraph_robust_restatement as R
-from test_posegraph_gpu import assert_poses, chain5, close, graph, host, optimizer
+from _posegraph import first_fixed, host, optimizer, plain_linearize, plain_optimize, same_bits
+from test_posegraph_gpu import assert_poses, chain5, close, graph
 
 pytestmark = pytest.mark.gpu
 
 KERNELS = ("huber", "cauchy", "geman_mcclure")
-
-
-def same_bits(a, b, keys=None):
-    for k in (keys or a):
-        assert a[k].tobytes() == b[k].tobytes(), k
-
-
-def first_fixed(n):
-    fixed = np.zeros(n, bool)
-    fixed[:1] = True
-    return fixed
-
-
-# ---- the plain entry points, called as the C ABI has them ---------------------------------------------------------
-
-def _device(X, e, Z, Om):
-    return [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in
-            (np.asarray(X, np.float64), np.asarray(e, np.int64).reshape(-1, 2), np.asarray(Z, np.float64),
-             np.asarray(Om, np.float64))]
-
-
-def plain_linearize(X, e, Z, Om):
-    from neural_spectral_codec_amd import _lib
-    L, ptr = _lib.lib(), _lib.ptr
-    dX, de, dZ, dOm = _device(X, e, Z, Om)
-    N, E = len(dX), len(de)
-    f64 = dict(dtype=torch.float64, device="cuda")
-    out = dict(residuals=torch.empty((E, 6), **f64), cost=torch.empty(1, **f64), gradient=torch.empty((N, 6), **f64),
-               blocks=torch.empty((N, 21), **f64), skipped=torch.empty(1, dtype=torch.int64, device="cuda"))
-    ws = torch.empty(max(int(L.nsc_posegraph_workspace_bytes(N, E, None)), 1), dtype=torch.uint8, device="cuda")
-    _lib.check(L.nsc_posegraph_linearize(ptr(dX), N, ptr(de), ptr(dZ), ptr(dOm), E, ptr(out["residuals"]),
-                                         ptr(out["cost"]), ptr(out["gradient"]), ptr(out["blocks"]), ptr(out["skipped"]),
-                                         ptr(ws), int(ws.numel()), _lib.stream_ptr(ws.device)), "nsc_posegraph_linearize")
-    return host(out)
-
-
-def plain_optimize(X, e, Z, Om, **params):
-    from neural_spectral_codec_amd import _lib
-    L, ptr = _lib.lib(), _lib.ptr
-    prm = optimizer(**params).params
-    dX, de, dZ, dOm = _device(X, e, Z, Om)
-    N, E = len(dX), len(de)
-    fixed = torch.from_numpy(first_fixed(N).astype(np.uint8)).cuda()
-    f64 = dict(dtype=torch.float64, device="cuda")
-    out = dict(poses=torch.empty((N, 4, 4), **f64), stats=torch.empty(_lib.POSEGRAPH_STATS, **f64),
-               cost_history=torch.empty(prm.max_iteration + 1, **f64), step0=torch.empty((N, 6), **f64))
-    ws = torch.empty(max(int(L.nsc_posegraph_workspace_bytes(N, E, None)), 1), dtype=torch.uint8, device="cuda")
-    _lib.check(L.nsc_posegraph_optimize(ptr(dX), N, ptr(de), ptr(dZ), ptr(dOm), E, ptr(fixed), C.byref(prm),
-                                        ptr(out["poses"]), ptr(out["stats"]), ptr(out["cost_history"]), ptr(out["step0"]),
-                                        ptr(ws), int(ws.numel()), _lib.stream_ptr(ws.device)), "nsc_posegraph_optimize")
-    return host(out)
 
 
 # ---- 1. linearize against the restatement -------------------------------------------------------------------------
@@ -295,7 +243,7 @@ def test_alias_of_input_and_output(outlier_ring):
 
 
 def test_captured_replay_equals_eager(outlier_ring):
-    from _hipgraph import keep_graphs, node_types
+    from _hipgraph import capture_replay
     (_, init, e, Z, Om, closures), _, _ = outlier_ring
     prm = dict(max_iteration=4, max_pcg_iterations=30)
     opt = optimizer(kernel="geman_mcclure", **prm)
@@ -306,25 +254,11 @@ def test_captured_replay_equals_eager(outlier_ring):
 
     def step():
         return opt.optimize_device(*dev, fixed=fixed, step0=True, robust_scale=scale)
-    eager = {k: v.clone() for k, v in step().items()}
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        step()                                               # warm the allocator outside the capture
-    torch.cuda.current_stream().wait_stream(s)
-    with keep_graphs() as made:
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            cap = step()
-    for v in cap.values():
-        v.fill_(-1)                                          # the replay has to write every output
-    g.replay()
-    torch.cuda.synchronize()
+    eager, cap, types = capture_replay(step)
     assert set(eager) == {"poses", "stats", "cost_history", "step0", "chi2", "weights"}
     for k in eager:
         assert torch.equal(eager[k], cap[k]), k
     assert eager["stats"][1].item() >= 1 and (eager["weights"][-2:] < 1.0).all()
-    types = node_types(made[0])
     launches = 5 + 1 + 3 + prm["max_iteration"] * (8 + 4 * prm["max_pcg_iterations"]) + 1 + 1    # include/nsc.h
     kernels = types.pop("kernel", 0)
     assert types.get("memset", 0) == 0 and types.get("memcpy", 0) == 0, types
