@@ -896,6 +896,95 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
                      const NscMapParams *params, int64_t max_voxels, double *out_points, int64_t *info, int64_t *keys,
                      int64_t *stats, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Map localisation (restated in tests/map_localize_restatement.py): a map that keeps a normal distribution per voxel and
+ * a table that outlives the call (nsc_map_build_dist), and the registration of scans against it (nsc_map_register).
+ *
+ * nsc_map_build_dist.  Inputs, validation, row placement, keys, the seven stats, the order of the output voxels (ascending
+ *   first row), the table of 2 max_voxels slots and its full-table rule, `info` and `keys` are nsc_map_build's, bit for bit.
+ * Per voxel, in place of the coordinate sums, exact integer moments of the position inside the voxel:
+ *   f_a = (w_a - origin_a) / voxel_size, k_a = floor(f_a), u_a = f_a - k_a (exact), q_a = rint(u_a 2^16) - 2^15;
+ *   three int64 sums of q_a and six of q_a q_b (xx xy xz yy yz zz).  |q| <= 2^15, so the sums are exact for fewer than
+ *   2^31 rows per voxel.
+ * Output for the first min(found, max_voxels) voxels:
+ *   voxels (max_voxels,16) float64, one 128-byte record per voxel:
+ *     [0..2]   mean_a = origin_a + ((k_a + 1/2) + (sum q_a / n) / 2^16) voxel_size
+ *     [3..8]   C_ab = ((sum q_a q_b) / n - (sum q_a / n)(sum q_b / n)) (voxel_size / 2^16)^2, xx xy xz yy yz zz
+ *     [9..14]  information U diag(1 / l'_i) U^T of C = U diag(l_i) U^T (cyclic Jacobi),
+ *              l'_i = max(l_i, eigen_ratio l_max, sigma_floor^2)
+ *     [15]     1.0 when the voxel is usable (count >= min_points and every entry above finite), else 0.0
+ *   moments (max_voxels,9) int64, or NULL: the raw sums, q first.
+ *   index (2 max_voxels,2) uint64, every entry written: (key + 1, place) at the table's own slot positions, (0, ~0) for
+ *     an empty slot.  A lookup walks the probe sequence the insertion walked: slot mix(key) % (2 max_voxels), then the
+ *     next, wrapping, until the key or an empty slot.  A voxel whose place is >= max_voxels keeps its key (probes
+ *     continue past it) with place ~0: not usable.  Which of two keys that meet in a slot claims it is free, so two
+ *     builds may keep a key in different slots; what a lookup finds is the same.
+ * Launches: the six of nsc_map_build in the same shapes; no host synchronisation, no memset or memcpy nodes.
+ *
+ * nsc_map_register.  n_scans scans packed as rows in the formats of nsc_map_build, offsets (n_scans+1) int64,
+ *   init_transforms (n_scans,4,4) float64 row-major, scan to world.  The target is `voxels` and `index` of a
+ *   nsc_map_build_dist call with the same max_voxels and grid (params).
+ * Cost, point to distribution:  E(T) = sum_i d_i^T Omega_v d_i,  d_i = T p_i - mean_v,  v the voxel that contains
+ *   T p_i = ((R_a0 x + R_a1 y) + R_a2 z) + t_a: its key is looked up in the index, no neighbour and no radius.  A row
+ *   contributes when its voxel is in the index and usable; rows that are not finite, outside the grid or without a usable
+ *   voxel do not.
+ * Rounds, as nsc_gicp_register_prepared: one set-up kernel, then max_iteration + 1 pairs of linearize
+ *   (NSC_MAP_REGISTER_BLOCKS x n_scans workgroups of 256; J = [-[T p]x | I]; per workgroup a float64 slab of 21 J^T Omega J
+ *   + 6 J^T Omega d + n_corr + sum |d|^2 + sum d^T Omega d, reduced in a fixed shape) and finalize (one workgroup per scan:
+ *   slabs summed in order, fitness = n_corr / rows, rmse = sqrt(sum |d|^2 / n_corr), Open3D's convergence test on both,
+ *   6x6 Cholesky, T <- dT T with dT = [Rz Ry Rx of the three angles | translation]; without correspondences or a
+ *   positive-definite system T stays).  1 + 2 (max_iteration + 1) launches and nothing else; a finished scan's later
+ *   rounds are no-ops.
+ * Outputs per scan: transforms (4,4), fitness_rmse (2), cost = sum d^T Omega d at the result, corr_iterations (2) int64,
+ *   information (6,6) = sum J^T Omega J at the result, rotation first; system0 (n_scans,NSC_MAP_REGISTER_SYSTEM) or
+ *   NULL: the sums at init_transforms, the first 29 laid out as NscGicpStages.system0, then sum d^T Omega d.
+ * A scan whose init_transform is not finite gets NaN outputs, n_corr -1 and 0 iterations; none of its rows is read.
+ * Results are bitwise reproducible and a scan's results do not depend on what else is in the batch.
+ * ------------------------------------------------------------------------------------------ */
+#define NSC_MAP_VOXEL_DOUBLES       16
+#define NSC_MAP_REGISTER_BLOCKS     64      /* workgroups of 256 lanes per scan in linearize */
+#define NSC_MAP_REGISTER_SYSTEM     30
+#define NSC_MAP_REGISTER_MAX_SCANS  65535
+
+typedef struct NscMapDistParams {
+    int32_t min_points;             /* 6      rows a voxel needs to be usable, >= 1 */
+    int32_t reserved;               /* 0 */
+    double  eigen_ratio;            /* 1e-2   smallest eigenvalue kept, as a share of the largest; in (0, 1] */
+    double  sigma_floor;            /* 1e-3   smallest standard deviation kept (m), finite and positive */
+} NscMapDistParams;
+
+typedef struct NscMapRegisterParams {
+    int32_t max_iteration;          /* 30     >= 0 */
+    int32_t reserved;               /* 0 */
+    double  relative_fitness;       /* 1e-6   >= 0 */
+    double  relative_rmse;          /* 1e-6   >= 0 */
+} NscMapRegisterParams;
+
+void   nsc_map_dist_default_params(NscMapDistParams *p);
+/* As nsc_map_workspace_bytes, with 256 bytes per voxel of max_voxels (the table of 128-byte slots). */
+size_t nsc_map_dist_workspace_bytes(int64_t total_rows, int64_t max_voxels);
+/* Refusals as nsc_map_build's, with voxels, index, info and keys needed when max_voxels > 0; NSC_EINVAL also for a null
+ * `dist`, min_points < 1, eigen_ratio outside (0, 1] or a sigma_floor not finite and positive. */
+int    nsc_map_build_dist(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets,
+                          int32_t n_clouds, int64_t total_rows, const double *poses, int32_t n_poses,
+                          const int64_t *pose_ids, const NscMapParams *params, const NscMapDistParams *dist,
+                          int64_t max_voxels, double *voxels, uint64_t *index, int64_t *info, int64_t *keys,
+                          int64_t *moments, int64_t *stats, void *ws, size_t ws_bytes, void *stream);
+
+void   nsc_map_register_default_params(NscMapRegisterParams *p);
+/* Bytes of workspace for nsc_map_register: the slabs and the state of n_scans scans; 0 for a negative n_scans. */
+size_t nsc_map_register_workspace_bytes(int32_t n_scans);
+/* NSC_EINVAL for a null or negative argument, a format nsc_map_build would refuse, a grid not finite and positive or
+ * parameters out of range; NSC_EUNSUPPORTED for more than NSC_MAP_REGISTER_MAX_SCANS scans (callers split the batch) or
+ * sizes above nsc_map_build's; NSC_EWORKSPACE for a workspace that is missing or too small: all before anything is
+ * launched.  n_scans = 0 returns NSC_OK and launches nothing.  points may be NULL with total_rows = 0, voxels and index
+ * with max_voxels = 0. */
+int    nsc_map_register(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_scans,
+                        int64_t total_rows, const double *voxels, const uint64_t *index, int64_t max_voxels,
+                        const NscMapParams *params, const NscMapRegisterParams *reg, const double *init_transforms,
+                        double *transforms, double *fitness_rmse, double *cost, int64_t *corr_iterations,
+                        double *information, double *system0, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,18 @@ class MapParams(C.Structure):
     _fields_ = [("voxel_size", C.c_double), ("origin", C.c_double * 3)]
 
 
+class MapDistParams(C.Structure):
+    """struct NscMapDistParams"""
+    _fields_ = [("min_points", C.c_int32), ("reserved", C.c_int32), ("eigen_ratio", C.c_double),
+                ("sigma_floor", C.c_double)]
+
+
+class MapRegisterParams(C.Structure):
+    """struct NscMapRegisterParams"""
+    _fields_ = [("max_iteration", C.c_int32), ("reserved", C.c_int32), ("relative_fitness", C.c_double),
+                ("relative_rmse", C.c_double)]
+
+
 # include/nsc.h NSC_MAP_DTYPE_F32, NSC_MAP_DTYPE_F64, NSC_MAP_STATS and NSC_MAP_STAT_*: the name of each entry of `stats`
 MAP_DTYPE_F32, MAP_DTYPE_F64, MAP_STATS = 0, 1, 7
 MAP_STAT_NAMES = ("voxels_found", "voxels_written", "rows_used", "rows_not_finite", "rows_outside", "rows_without_pose",
@@ -123,6 +135,8 @@ MAP_STAT_NAMES = ("voxels_found", "voxels_written", "rows_used", "rows_not_finit
 # include/nsc.h NSC_MAP_TILE_ROWS, NSC_MAP_SCAN_THREADS, NSC_MAP_INSERT_ROWS, NSC_MAP_INSERT_BLOCKS
 MAP_TILE_ROWS, MAP_SCAN_THREADS, MAP_INSERT_ROWS, MAP_INSERT_BLOCKS = 4096, 256, 512, 2048
 MAP_MAX_VOXELS, MAP_MAX_ROWS = 1 << 36, 1 << 46     # include/nsc.h NSC_MAP_MAX_VOXELS, NSC_MAP_MAX_ROWS
+# include/nsc.h NSC_MAP_VOXEL_DOUBLES, NSC_MAP_REGISTER_BLOCKS, NSC_MAP_REGISTER_SYSTEM, NSC_MAP_REGISTER_MAX_SCANS
+MAP_VOXEL_DOUBLES, MAP_REGISTER_BLOCKS, MAP_REGISTER_SYSTEM, MAP_REGISTER_MAX_SCANS = 16, 64, 30, 65535
 
 # include/nsc.h NSC_POSEGRAPH_MAX_EDGES, NSC_POSEGRAPH_MAX_LAUNCHES, NSC_POSEGRAPH_STATS
 POSEGRAPH_MAX_EDGES, POSEGRAPH_MAX_LAUNCHES, POSEGRAPH_STATS = 1073741823, 1000000, 10
@@ -252,6 +266,14 @@ SYMBOLS = {
     "nsc_map_workspace_bytes": (_sz, [_i64, _i64]),
     "nsc_map_build": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, C.POINTER(MapParams), _i64, _vp, _vp,
                                 _vp, _vp, _vp, _sz, _vp]),
+    "nsc_map_dist_default_params": (None, [C.POINTER(MapDistParams)]),
+    "nsc_map_dist_workspace_bytes": (_sz, [_i64, _i64]),
+    "nsc_map_build_dist": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, C.POINTER(MapParams),
+                                     C.POINTER(MapDistParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nsc_map_register_default_params": (None, [C.POINTER(MapRegisterParams)]),
+    "nsc_map_register_workspace_bytes": (_sz, [_i32]),
+    "nsc_map_register": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _i64, C.POINTER(MapParams),
+                                   C.POINTER(MapRegisterParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

@@ -36,6 +36,8 @@
 #include <stdint.h>
 
 #include "../../include/nsc.h"
+#include "nsc_eig3.h"                   // jacobi_eig3
+#include "nsc_gauss_newton.h"           // gn_solve6, gn_apply
 #include "nsc_util.h"
 #include "nsc_voxel_hash.h"             // KEY_BITS, KEY_MAX, FIX_SCALE, mix64, pack_key, next_slot
 
@@ -269,32 +271,8 @@ __device__ __forceinline__ double dist2(const double *a, const double *b)
 // eigenvector of the smallest eigenvalue of a symmetric 3x3 (cyclic Jacobi)
 __device__ void smallest_eigvec(const double C[6], double u[3])
 {
-    double A[3][3] = {{C[0], C[1], C[2]}, {C[1], C[3], C[4]}, {C[2], C[4], C[5]}};
-    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 32; ++sweep) {
-        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        const double diag = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-        if (!(off > 1e-30 * diag)) break;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                if (A[p][q] == 0.0) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-                for (int r = 0; r < 3; ++r) {            // A <- A J
-                    const double arp = A[r][p], arq = A[r][q];
-                    A[r][p] = cs * arp - sn * arq; A[r][q] = sn * arp + cs * arq;
-                }
-                for (int r = 0; r < 3; ++r) {            // A <- J^T A
-                    const double apr = A[p][r], aqr = A[q][r];
-                    A[p][r] = cs * apr - sn * aqr; A[q][r] = sn * apr + cs * aqr;
-                }
-                for (int r = 0; r < 3; ++r) {
-                    const double vrp = V[r][p], vrq = V[r][q];
-                    V[r][p] = cs * vrp - sn * vrq; V[r][q] = sn * vrp + cs * vrq;
-                }
-            }
-    }
+    double A[3][3], V[3][3];
+    jacobi_eig3(C, A, V);
     int m = 0;
     for (int a = 1; a < 3; ++a) if (A[a][a] < A[m][m]) m = a;
     for (int a = 0; a < 3; ++a) u[a] = V[a][m];
@@ -567,15 +545,6 @@ __global__ __launch_bounds__(GEO_THREADS) void linearize_kernel(Pairs pairs, con
     }
 }
 
-__device__ void rot_zyx(double a, double b, double g, double R[3][3])
-{
-    const double ca = cos(a), sa = sin(a), cb = cos(b), sb = sin(b), cg = cos(g), sg = sin(g);
-    // Rz(g) Ry(b) Rx(a)
-    R[0][0] = cg * cb; R[0][1] = cg * sb * sa - sg * ca; R[0][2] = cg * sb * ca + sg * sa;
-    R[1][0] = sg * cb; R[1][1] = sg * sb * sa + cg * ca; R[1][2] = sg * sb * ca - cg * sa;
-    R[2][0] = -sb;     R[2][1] = cb * sa;                R[2][2] = cb * ca;
-}
-
 __global__ __launch_bounds__(64) void finalize_kernel(const long long *count, const double *slab, PairState *state,
                                                       double *transforms, double *fit_rmse, long long *corr_iters,
                                                       double *information, double *system0, int n_pairs,
@@ -617,42 +586,9 @@ __global__ __launch_bounds__(64) void finalize_kernel(const long long *count, co
     stt.prev_rmse = rmse;
     stt.round = round + 1;
     // (sum JtWJ) x = -sum JtWd by Cholesky; dT = I without correspondences or a positive-definite system
-    double L[6][6], x[6];
-    bool ok = nc > 0.0;
-    {
-        int t = 0;
-        for (int a = 0; a < 6; ++a)
-            for (int b = a; b < 6; ++b) { L[b][a] = sum[t]; ++t; }         // lower triangle of the symmetric H
-    }
-    for (int j = 0; j < 6 && ok; ++j) {
-        double dj = L[j][j];
-        for (int k = 0; k < j; ++k) dj -= L[j][k] * L[j][k];
-        if (!(dj > 0.0) || !isfinite(dj)) { ok = false; break; }
-        L[j][j] = sqrt(dj);
-        for (int i = j + 1; i < 6; ++i) {
-            double v = L[i][j];
-            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-            L[i][j] = v / L[j][j];
-        }
-    }
-    if (!ok) return;
-    for (int i = 0; i < 6; ++i) {                                         // L y = -g
-        double v = -sum[21 + i];
-        for (int k = 0; k < i; ++k) v -= L[i][k] * x[k];
-        x[i] = v / L[i][i];
-    }
-    for (int i = 5; i >= 0; --i) {                                        // L^T x = y
-        double v = x[i];
-        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
-        x[i] = v / L[i][i];
-    }
-    double dR[3][3];
-    rot_zyx(x[0], x[1], x[2], dR);
-    double *T = transforms + 16 * (long long)p, N[12];
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 4; ++b)
-            N[4 * a + b] = dR[a][0] * T[b] + dR[a][1] * T[4 + b] + dR[a][2] * T[8 + b] + (b == 3 ? x[3 + a] : 0.0);
-    for (int e = 0; e < 12; ++e) T[e] = N[e];
+    double x[6];
+    if (!(nc > 0.0) || !gn_solve6(sum, x)) return;
+    gn_apply(x, transforms + 16 * (long long)p);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

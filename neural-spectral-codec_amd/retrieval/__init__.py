@@ -7,6 +7,7 @@ from .planar_alignment import estimate_planar, planar_info, yaw_table
 from .pose_graph import (PoseGraphOptimizer, closure_edges, closure_mahalanobis, information_from_g2o,
                          information_to_g2o, odometry_edges, relative_covariance)
 from .global_map import GlobalMap, revisited
+from .map_localization import MapLocalizer
 from .compressed import CompressedRetriever, quantized_cdf, w1_distances_quantized
 from .wasserstein import (WassersteinRetriever, wasserstein_distance_1d_numpy, wasserstein_distance_1d_torch,
                           wasserstein_distance_batch_numpy, wasserstein_distance_batch_torch,
@@ -15,7 +16,7 @@ from .wasserstein import (WassersteinRetriever, wasserstein_distance_1d_numpy, w
 __all__ = ["CompressedRetriever", "quantized_cdf", "w1_distances_quantized", "GeometricVerifier", "PreparedClouds", "register_batch", "register_prepared", "YawImages", "estimate_yaw",
            "estimate_planar", "planar_info", "yaw_table",
            "PoseGraphOptimizer", "closure_edges", "closure_mahalanobis", "information_from_g2o", "information_to_g2o",
-           "odometry_edges", "relative_covariance", "GlobalMap", "revisited",
+           "odometry_edges", "relative_covariance", "GlobalMap", "revisited", "MapLocalizer",
            "LoopClosureCandidate", "ShardedTwoStageRetrieval", "TwoStageRetrieval", "batch_loop_closing",
            "create_two_stage_retrieval", "WassersteinRetriever", "wasserstein_distance_1d_numpy", "wasserstein_distance_1d_torch",
            "wasserstein_distance_batch_numpy", "wasserstein_distance_batch_torch",

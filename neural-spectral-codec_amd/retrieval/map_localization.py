@@ -1,0 +1,235 @@
+"""Map localisation on the device (csrc/nsc_map.hip nsc_map_build_dist, csrc/nsc_localize.hip nsc_map_register): a map
+that keeps a normal distribution per voxel and a table that outlives the build, and scans registered against it.  The
+consumer of ``GlobalMap``'s input: the same clouds under the same optimised poses, kept in a form a scan can be placed in
+without adding a keyframe and optimising again.
+
+Definition (the contract the two entry points and tests/map_localize_restatement.py share; include/nsc.h), float64:
+
+    map          rows placed, keyed, counted and ordered exactly as ``GlobalMap`` does.  Per voxel exact int64 moments of
+                 q = rint(u 2^16) - 2^15, u the position inside the voxel in [0, 1): mean, covariance C, and the
+                 information U diag(1 / max(l_i, eigen_ratio l_max, sigma_floor^2)) U^T of C = U diag(l) U^T.  A voxel
+                 is usable with at least ``min_points`` rows
+    index        (2 max_voxels, 2) uint64 = (key + 1, place) at the build table's own slots: a lookup walks the probe
+                 sequence the insertion walked
+    cost         E(T) = sum_i d_i^T Omega_v d_i,  d_i = T p_i - mean_v,  v the voxel that contains T p_i; only that voxel
+                 is looked up.  Rows that are not finite, outside the grid or without a usable voxel do not contribute
+    rounds       Gauss-Newton on [rotation | translation], J = [-[T p]x | I]; fitness = n_corr / rows,
+                 rmse = sqrt(sum |d|^2 / n_corr); Open3D's convergence test; at most max_iteration updates
+
+Integer atomics and fixed-shape float64 sums only: two calls agree bit for bit and a scan's result does not depend on what
+else is in the batch.
+
+Not part of this module: source covariances (full VGICP), neighbour-voxel correspondences, robust weights, NDT's
+exponential score, insertion of new scans into the kept table, unary edges in the pose graph.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .geometric_verification import PreparedClouds, _device, _workspace
+from .global_map import GlobalMap, _pack, _tensors
+
+_FORMATS = ((torch.float32, 3), (torch.float32, 4), (torch.float64, 3))
+
+
+def _is_packed(clouds):
+    return isinstance(clouds, tuple) and len(clouds) == 2 and isinstance(clouds[1], torch.Tensor) and clouds[1].ndim == 1
+
+
+def _rows(points, offsets, what):
+    """checked packed rows -> (contiguous rows, int64 offsets, number of clouds, number of rows, dtype code)"""
+    if points.ndim != 2 or (points.dtype, int(points.shape[1])) not in _FORMATS:
+        raise _lib.NscError(f"{what} must be (N,3) or (N,4) float32 or (N,3) float64")
+    pts, off = points.contiguous(), offsets.contiguous().to(torch.int64).reshape(-1)
+    if int(off.numel()) < 1:
+        raise _lib.NscError("offsets must have one entry more than there are clouds")
+    return pts, off, int(off.numel()) - 1, int(pts.shape[0]), \
+        _lib.MAP_DTYPE_F64 if pts.dtype == torch.float64 else _lib.MAP_DTYPE_F32
+
+
+class MapLocalizer:
+    """A distribution voxel map built by nsc_map_build_dist and scans registered against it by nsc_map_register.
+
+    voxel_size        1.0      voxel edge (m)
+    origin            (0,0,0)  world point where voxel (2^20, 2^20, 2^20) begins
+    max_voxels        None     capacity of the map; the build table has twice as many slots.  A voxel of capacity costs
+                               256 bytes of table during the build and 200 bytes kept (record 128, index 32, info and key
+                               40).  None means one voxel per input row, which can never be short
+    min_points        6        rows a voxel needs to take part in a registration
+    eigen_ratio       1e-2     smallest eigenvalue of a voxel's covariance, as a share of its largest
+    sigma_floor       1e-3     smallest standard deviation of a voxel along any axis (m)
+    max_iteration     30       Gauss-Newton updates at most
+    relative_fitness  1e-6     a scan is finished when fitness and rmse both change by less than these
+    relative_rmse     1e-6
+    device            'cuda'   there is no CPU fallback
+
+    After a build the instance keeps ``voxels`` (M,16), ``index`` (2M,2), ``keys`` (M,), ``info`` (M,4), ``stats`` (7,)
+    as device tensors over the full capacity M and, after ``build`` or ``build_prepared``, ``complete``
+    (``build_device`` reads nothing back: ``complete`` is then None).
+    """
+
+    def __init__(self, voxel_size: float = 1.0, origin=(0.0, 0.0, 0.0), max_voxels=None, min_points: int = 6,
+                 eigen_ratio: float = 1e-2, sigma_floor: float = 1e-3, max_iteration: int = 30,
+                 relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, device="cuda"):
+        self._grid = GlobalMap(voxel_size, origin, max_voxels, device)       # its refusals are this class's
+        if int(min_points) < 1 or not 0.0 < float(eigen_ratio) <= 1.0 or \
+                not (np.isfinite(sigma_floor) and float(sigma_floor) > 0.0):
+            raise _lib.NscError("MapLocalizer: min_points >= 1, eigen_ratio in (0, 1] and a finite positive sigma_floor")
+        if int(max_iteration) < 0 or not float(relative_fitness) >= 0.0 or not float(relative_rmse) >= 0.0:
+            raise _lib.NscError("MapLocalizer: max_iteration, relative_fitness and relative_rmse must not be negative")
+        self.params = self._grid.params
+        self.dist = _lib.MapDistParams(min_points=int(min_points), reserved=0, eigen_ratio=float(eigen_ratio),
+                                       sigma_floor=float(sigma_floor))
+        self.reg = _lib.MapRegisterParams(max_iteration=int(max_iteration), reserved=0,
+                                          relative_fitness=float(relative_fitness), relative_rmse=float(relative_rmse))
+        self.max_voxels = self._grid.max_voxels
+        self.device = device
+        self.voxels = self.index = self.keys = self.info = self.stats = self.moments = None
+        self.complete = None
+        self.capacity = None
+
+    # ---- the map ------------------------------------------------------------------------------------------------------
+
+    def build_device(self, points, offsets, poses, pose_ids=None, out=None, moments=False):
+        """The map of packed clouds, on the device and without a synchronisation: with device ``pose_ids`` (or none) a
+        call can be captured.  Arguments as ``GlobalMap.build_device``.  Returns, and keeps, the full buffers: voxels
+        (M,16) float64, index (2M,2) uint64 stored as int64, info (M,4) int64, keys (M,) int64, stats (7,) int64 and, with
+        ``moments=True``, moments (M,9) int64; entries of voxels, info, keys and moments past stats[1] are not defined.
+        ``out``: a dict of those tensors to write into."""
+        for t, name in ((points, "points"), (offsets, "offsets"), (poses, "poses")):
+            _lib.require_cuda(t, name)
+        dev = points.device
+        pts, off, B, N, dtype = _rows(points, offsets, "points")
+        if poses.ndim != 3 or tuple(poses.shape[1:]) != (4, 4):
+            raise _lib.NscError("poses must be (P,4,4)")
+        pose = poses.contiguous().to(torch.float64)
+        P = int(pose.shape[0])
+        ids = GlobalMap._host_ids(pose_ids, B, P)
+        if ids is not None:
+            ids = ids.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
+            if int(ids.numel()) != B:
+                raise _lib.NscError(f"pose_ids must have one entry per cloud ({B}), got {int(ids.numel())}")
+        M = N if self.max_voxels is None else self.max_voxels
+        shapes = dict(voxels=((M, _lib.MAP_VOXEL_DOUBLES), torch.float64), index=((2 * M, 2), torch.int64),
+                      info=((M, 4), torch.int64), keys=((M,), torch.int64), stats=((_lib.MAP_STATS,), torch.int64))
+        if moments or (out is not None and "moments" in out):
+            shapes["moments"] = ((M, 9), torch.int64)
+        if out is None:
+            out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+        for k, (shape, dt) in shapes.items():
+            t = out[k]
+            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise _lib.NscError(f"out[{k!r}] must be a contiguous {shape} {dt} tensor on {dev}")
+        L = _lib.lib()
+        ws = _workspace(L.nsc_map_dist_workspace_bytes(N, M), dev)
+        with torch.cuda.device(dev):
+            status = L.nsc_map_build_dist(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off), B, N, _lib.ptr(pose), P,
+                                          _lib.ptr(ids), C.byref(self.params), C.byref(self.dist), M,
+                                          _lib.ptr(out["voxels"]), _lib.ptr(out["index"]), _lib.ptr(out["info"]),
+                                          _lib.ptr(out["keys"]), _lib.ptr(out.get("moments")), _lib.ptr(out["stats"]),
+                                          _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+        _lib.check(status, "nsc_map_build_dist")
+        self.voxels, self.index, self.keys, self.info, self.stats = (out[k] for k in ("voxels", "index", "keys", "info",
+                                                                                     "stats"))
+        self.moments = out.get("moments")
+        self.capacity, self.complete = M, None
+        return out
+
+    def _result(self, out):
+        """build_device's buffers -> the dict ``build`` returns (one read of the stats)"""
+        stats = dict(zip(_lib.MAP_STAT_NAMES, out["stats"].cpu().tolist()))
+        n = stats["voxels_written"]
+        info, vox = out["info"][:n], out["voxels"][:n]
+        res = dict(mean=vox[:, 0:3], covariance=vox[:, 3:9], information=vox[:, 9:15], usable=vox[:, 15] == 1.0,
+                   count=info[:, 0], first_row=info[:, 1], first_cloud=info[:, 2], last_cloud=info[:, 3],
+                   keys=out["keys"][:n], **stats)
+        res["complete"] = stats["voxels_found"] == stats["voxels_written"] and stats["rows_unplaced"] == 0
+        self.complete = res["complete"]
+        return res
+
+    def build(self, clouds, poses, pose_ids=None):
+        """The map of ``clouds`` -- a sequence of (n,3|4) host arrays or tensors, or a packed ``(points, offsets)`` pair of
+        device tensors -- under ``poses`` (P,4,4), host or device.  Returns device tensors in ascending first_row -- mean
+        (V,3), covariance and information (V,6: xx xy xz yy yz zz) float64, usable (V,) bool, count, first_row,
+        first_cloud, last_cloud, keys (V,) int64 -- the stats by name and ``complete``.  One synchronisation, to read the
+        stats."""
+        packed = _is_packed(clouds)
+        clouds = clouds if packed else _tensors(clouds)
+        pose = GlobalMap._poses(poses)
+        # host ids are refused before anything goes to the device
+        ids = GlobalMap._host_ids(pose_ids, int(clouds[1].numel()) - 1 if packed else len(clouds), int(pose.shape[0]))
+        dev = _device(self.device)
+        pts, off = clouds if packed else _pack(clouds, dev)
+        return self._result(self.build_device(pts, off, pose.to(device=dev, dtype=torch.float64), ids))
+
+    def build_prepared(self, store: PreparedClouds, poses, pose_ids=None):
+        """``build`` on the clouds a ``PreparedClouds`` holds, as ``GlobalMap.build_prepared``."""
+        n = len(store)
+        pose = GlobalMap._poses(poses)
+        ids = GlobalMap._host_ids(pose_ids, n, int(pose.shape[0]))
+        if store._buf is None:
+            store._reserve(0, 0, 0)
+        pts, off = store._buf["points"][:store.n_rows], store._buf["row_offsets"][:n + 1]
+        return self._result(self.build_device(pts, off, pose.to(device=store.device, dtype=torch.float64), ids))
+
+    # ---- registration -------------------------------------------------------------------------------------------------
+
+    def register_device(self, points, offsets, init_poses, system0=False):
+        """Register packed scans against the kept map, on the device and without a synchronisation: a call can be
+        captured.  ``points`` (N,3|4) float32 or (N,3) float64 device tensor, ``offsets`` (S+1,) int64 device tensor,
+        ``init_poses`` (S,4,4) float64 device tensor, scan to world.  Returns a dict of device tensors: transform (S,4,4),
+        fitness, rmse, cost (S,), n_correspondences, iterations (S,) int64, information (S,6,6); with ``system0=True``
+        also system0 (S,30), the sums at ``init_poses`` (include/nsc.h).  More than ``_lib.MAP_REGISTER_MAX_SCANS`` scans
+        go to the library in several calls, the outputs are those of one call."""
+        if self.voxels is None:
+            raise _lib.NscError("MapLocalizer.register: build a map first")
+        for t, name in ((points, "points"), (offsets, "offsets"), (init_poses, "init_poses")):
+            _lib.require_cuda(t, name)
+        dev = self.voxels.device
+        pts, off, S, N, dtype = _rows(points, offsets, "scan points")
+        if pts.device != dev:
+            raise _lib.NscError(f"the scans must be on the map's device ({dev})")
+        if init_poses.ndim != 3 or tuple(init_poses.shape) != (S, 4, 4):
+            raise _lib.NscError(f"init_poses must be ({S},4,4), got {tuple(init_poses.shape)}")
+        init = init_poses.contiguous().to(torch.float64)
+        f64 = dict(dtype=torch.float64, device=dev)
+        T, fr, cost = torch.empty((S, 4, 4), **f64), torch.empty((S, 2), **f64), torch.empty((S,), **f64)
+        ci = torch.empty((S, 2), dtype=torch.int64, device=dev)
+        info = torch.empty((S, 6, 6), **f64)
+        sys0 = torch.empty((S, _lib.MAP_REGISTER_SYSTEM), **f64) if system0 else None
+        L = _lib.lib()
+        most = _lib.MAP_REGISTER_MAX_SCANS
+        ws = _workspace(L.nsc_map_register_workspace_bytes(min(S, most)), dev)
+        with torch.cuda.device(dev):
+            for a in range(0, S, most):
+                b = min(a + most, S)
+                status = L.nsc_map_register(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off[a:]), b - a, N,
+                                            _lib.ptr(self.voxels), _lib.ptr(self.index), self.capacity,
+                                            C.byref(self.params), C.byref(self.reg), _lib.ptr(init[a:]), _lib.ptr(T[a:]),
+                                            _lib.ptr(fr[a:]), _lib.ptr(cost[a:]), _lib.ptr(ci[a:]), _lib.ptr(info[a:]),
+                                            None if sys0 is None else _lib.ptr(sys0[a:]), _lib.ptr(ws),
+                                            int(ws.numel()), _lib.stream_ptr(dev))
+                _lib.check(status, "nsc_map_register")
+        out = dict(transform=T, fitness=fr[:, 0], rmse=fr[:, 1], cost=cost, n_correspondences=ci[:, 0],
+                   iterations=ci[:, 1], information=info)
+        if sys0 is not None:
+            out["system0"] = sys0
+        return out
+
+    def register(self, scans, init_poses, system0=False):
+        """Register ``scans`` -- a sequence of (n,3|4) host arrays or tensors, or a packed ``(points, offsets)`` pair of
+        device tensors -- from ``init_poses`` (S,4,4), host or device, scan to world.  Returns ``register_device``'s dict
+        of device tensors."""
+        if self.voxels is None:
+            raise _lib.NscError("MapLocalizer.register: build a map first")
+        packed = _is_packed(scans)
+        scans = scans if packed else _tensors(scans)
+        pose = GlobalMap._poses(init_poses)
+        S = int(scans[1].numel()) - 1 if packed else len(scans)
+        if int(pose.shape[0]) != S:              # refused before anything goes to the device
+            raise _lib.NscError(f"init_poses must have one (4,4) pose per scan ({S}), got {int(pose.shape[0])}")
+        dev = self.voxels.device
+        pts, off = scans if packed else _pack(scans, dev)
+        return self.register_device(pts, off, pose.to(device=dev, dtype=torch.float64), system0=system0)
