@@ -921,6 +921,33 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
  *     builds may keep a key in different slots; what a lookup finds is the same.
  * Launches: the six of nsc_map_build in the same shapes; no host synchronisation, no memset or memcpy nodes.
  *
+ * nsc_map_insert_dist (restated in tests/map_insert_restatement.py).  Rows added to a kept map without a rebuild.
+ *   Given the kept tensors of a nsc_map_build_dist call with the same max_voxels, grid and dist -- voxels, index, info,
+ *   keys, moments, stats -- and `cursor` (2) int64 = [rows taken so far, clouds taken so far] (after a build: its
+ *   total_rows and n_clouds), and n_clouds new clouds in the formats of nsc_map_build: after the call the kept tensors
+ *   hold, bit for bit, what nsc_map_build_dist produces over the old clouds followed by the new ones with the same
+ *   max_voxels: voxels, info, keys, moments, the seven stats, and the index read as a mapping key -> place.  The order of
+ *   the voxels too: new voxels take the places after stats[NSC_MAP_STAT_WRITTEN], in ascending first row.  A record is
+ *   a function of count, moments and key alone, so adding rows is integer arithmetic and one evaluation of that function.
+ *   This holds while the voxels found stay at most 2 max_voxels, the table's slots; with a full table, which rows are
+ *   unplaced is as free as it is in the build.
+ * Numbers.  Row `r` of the call is row cursor[0] + r of the map and cloud `c` cloud cursor[1] + c: these enter first_row,
+ *   first_cloud and last_cloud.  The pose of cloud c is poses[pose_ids[c]], or poses[c]: indexed within the call.
+ * Stats accumulate: rows without a pose (id outside [0, n_poses), rows of no cloud), rows not finite, rows outside the
+ *   grid, rows that find all 2 max_voxels slots keyed (unplaced), rows used.  A new voxel whose place would be >=
+ *   max_voxels keeps its key in the index with place ~0, as in the build; its rows count as used, found counts it,
+ *   written = min(found, max_voxels).
+ * Cursor.  The last launch advances cursor by (total_rows, n_clouds): a captured call can be replayed with new contents
+ *   in the same buffers, and every replay is a further insertion.
+ * Cost.  Work and workspace scale with total_rows, not with max_voxels: no launch walks the slots or the records, and
+ *   only voxels that received a row have their record computed again.
+ * Launches.  NSC_MAP_INSERT_LAUNCHES kernels (clear the call's bitmap and counters; claim: probe the kept index, 64-bit
+ *   CAS for new keys, the smallest row of each new voxel; mark those rows; count; scan; assign places to new voxels;
+ *   accumulate: integer atomics on info and moments, a list of the places reached; refresh their records, fold the new
+ *   voxels into the stats, advance the cursor) whose grids depend on total_rows alone, on the caller's stream; integer
+ *   atomics only; no host synchronisation, no memset or memcpy nodes.  While a call runs, bits 61 and 62 of an index
+ *   place word are in use; they are clear when it ends.
+ *
  * nsc_map_register.  n_scans scans packed as rows in the formats of nsc_map_build, offsets (n_scans+1) int64,
  *   init_transforms (n_scans,4,4) float64 row-major, scan to world.  The target is `voxels` and `index` of a
  *   nsc_map_build_dist call with the same max_voxels and grid (params).
@@ -942,6 +969,7 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
  * Results are bitwise reproducible and a scan's results do not depend on what else is in the batch.
  * ------------------------------------------------------------------------------------------ */
 #define NSC_MAP_VOXEL_DOUBLES       16
+#define NSC_MAP_INSERT_LAUNCHES     8       /* kernels of one nsc_map_insert_dist call */
 #define NSC_MAP_REGISTER_BLOCKS     64      /* workgroups of 256 lanes per scan in linearize */
 #define NSC_MAP_REGISTER_SYSTEM     30
 #define NSC_MAP_REGISTER_MAX_SCANS  65535
@@ -970,6 +998,17 @@ int    nsc_map_build_dist(const void *points, int32_t dtype, int32_t stride_floa
                           const int64_t *pose_ids, const NscMapParams *params, const NscMapDistParams *dist,
                           int64_t max_voxels, double *voxels, uint64_t *index, int64_t *info, int64_t *keys,
                           int64_t *moments, int64_t *stats, void *ws, size_t ws_bytes, void *stream);
+
+/* Bytes of workspace for nsc_map_insert_dist: about 16.2 per row (a slot and a list entry per row, the bitmap and its
+ * prefixes) and nothing per voxel; monotone; 0 for a total_rows the call would refuse. */
+size_t nsc_map_insert_workspace_bytes(int64_t total_rows);
+/* Refusals as nsc_map_build_dist's; NSC_EINVAL also for a null `moments` or `cursor`; NSC_EWORKSPACE for a workspace that
+ * is missing or too small: all before anything is launched. */
+int    nsc_map_insert_dist(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets,
+                           int32_t n_clouds, int64_t total_rows, const double *poses, int32_t n_poses,
+                           const int64_t *pose_ids, const NscMapParams *params, const NscMapDistParams *dist,
+                           int64_t max_voxels, double *voxels, uint64_t *index, int64_t *info, int64_t *keys,
+                           int64_t *moments, int64_t *stats, int64_t *cursor, void *ws, size_t ws_bytes, void *stream);
 
 void   nsc_map_register_default_params(NscMapRegisterParams *p);
 /* Bytes of workspace for nsc_map_register: the slabs and the state of n_scans scans; 0 for a negative n_scans. */

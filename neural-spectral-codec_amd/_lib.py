@@ -137,6 +137,7 @@ MAP_TILE_ROWS, MAP_SCAN_THREADS, MAP_INSERT_ROWS, MAP_INSERT_BLOCKS = 4096, 256,
 MAP_MAX_VOXELS, MAP_MAX_ROWS = 1 << 36, 1 << 46     # include/nsc.h NSC_MAP_MAX_VOXELS, NSC_MAP_MAX_ROWS
 # include/nsc.h NSC_MAP_VOXEL_DOUBLES, NSC_MAP_REGISTER_BLOCKS, NSC_MAP_REGISTER_SYSTEM, NSC_MAP_REGISTER_MAX_SCANS
 MAP_VOXEL_DOUBLES, MAP_REGISTER_BLOCKS, MAP_REGISTER_SYSTEM, MAP_REGISTER_MAX_SCANS = 16, 64, 30, 65535
+MAP_INSERT_LAUNCHES = 8                 # include/nsc.h NSC_MAP_INSERT_LAUNCHES
 
 # include/nsc.h NSC_POSEGRAPH_MAX_EDGES, NSC_POSEGRAPH_MAX_LAUNCHES, NSC_POSEGRAPH_STATS
 POSEGRAPH_MAX_EDGES, POSEGRAPH_MAX_LAUNCHES, POSEGRAPH_STATS = 1073741823, 1000000, 10
@@ -270,6 +271,9 @@ SYMBOLS = {
     "nsc_map_dist_workspace_bytes": (_sz, [_i64, _i64]),
     "nsc_map_build_dist": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, C.POINTER(MapParams),
                                      C.POINTER(MapDistParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nsc_map_insert_workspace_bytes": (_sz, [_i64]),
+    "nsc_map_insert_dist": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, C.POINTER(MapParams),
+                                      C.POINTER(MapDistParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nsc_map_register_default_params": (None, [C.POINTER(MapRegisterParams)]),
     "nsc_map_register_workspace_bytes": (_sz, [_i32]),
     "nsc_map_register": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _i64, C.POINTER(MapParams),

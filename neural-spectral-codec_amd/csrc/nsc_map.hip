@@ -24,6 +24,9 @@
 // second moments.  Its write pass turns them into the record nsc_localize.hip reads (mean, covariance, information,
 // usable flag) and writes the index (key + 1, place) at the table's own slot positions, for every slot.
 //
+// nsc_map_insert_dist adds rows to the kept tensors of such a build, with the result of a build over all rows; its eight
+// launches are described where they stand, below the builds.
+//
 // No float atomics anywhere: results are bitwise reproducible and do not depend on arrival order.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -110,62 +113,116 @@ __device__ __forceinline__ void add_row(MapSlot &s, const double w[3], const dou
         atomicAdd(reinterpret_cast<u64 *>(&s.sum[a]), (u64)__double2ll_rn(w[a] * FIX_SCALE));
 }
 
-__device__ __forceinline__ void add_row(DistSlot &s, const double w[3], const double u[3])
+// The nine integers a row adds to its distribution voxel, each handed to add(t, value) as it is made: q of the row's
+// position u inside the voxel (t = 0 .. 2), then the six products xx xy xz yy yz zz (t = 3 .. 8)
+template <class Add>
+__device__ __forceinline__ void row_moments(const double u[3], Add add)
 {
     long long q[3];
     for (int a = 0; a < 3; ++a) q[a] = __double2ll_rn(u[a] * MOMENT_SCALE) - (long long)MOMENT_HALF;
-    for (int a = 0; a < 3; ++a) atomicAdd(reinterpret_cast<u64 *>(&s.sum[a]), (u64)q[a]);
-    int t = 0;
+    for (int a = 0; a < 3; ++a) add(a, q[a]);
+    int t = 3;
     for (int a = 0; a < 3; ++a)
-        for (int b = a; b < 3; ++b) atomicAdd(reinterpret_cast<u64 *>(&s.sq[t++]), (u64)(q[a] * q[b]));
+        for (int b = a; b < 3; ++b) add(t++, q[a] * q[b]);
 }
 
+__device__ __forceinline__ void add_row(DistSlot &s, const double w[3], const double u[3])
+{
+    row_moments(u, [&s](int t, long long v) { atomicAdd(reinterpret_cast<u64 *>(t < 3 ? &s.sum[t] : &s.sq[t - 3]), (u64)v); });
+}
+
+// the rows of one call, as the two builds and the insertion take them
+template <class T>
+struct InsertRows {
+    const T *pts; int stride; const long long *off; int n_clouds; long long total;
+    const double *poses; int n_poses; const long long *ids;
+    MapGrid g;
+};
+
+struct CloudSpan {                      // the rows [lo, hi) of cloud c, while c >= 0: kept while a lane's rows stay in it
+    long long lo = 0, hi = 0;
+    int c = -1;
+};
+
+// Row -> its cloud (in `span`), world point w, position u inside its voxel and key.  The one place that decides what
+// becomes of a row: C_USED when it has a voxel, else the counter it falls into, the checks in this order
+template <class T>
+__device__ __forceinline__ int locate_row(const InsertRows<T> &in, long long row, CloudSpan &span, double w[3], double u[3],
+                                          u64 &key)
+{
+    if (span.c < 0 || row < span.lo || row >= span.hi) span.c = cloud_of(in.off, in.n_clouds, row, span.lo, span.hi);
+    const long long id = span.c < 0 ? -1 : (in.ids ? in.ids[span.c] : (long long)span.c);
+    if (id < 0 || id >= in.n_poses) return C_NO_POSE;
+    const T *q = in.pts + row * in.stride;
+    const double p[3] = {(double)q[0], (double)q[1], (double)q[2]};
+    place_row(in.poses + 16 * id, p, w);
+    if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && isfinite(w[0]) && isfinite(w[1]) && isfinite(w[2])))
+        return C_NOT_FINITE;
+    return world_voxel(w, in.g, u, key) ? C_USED : C_OUTSIDE;
+}
+
+// The slot of `key` in a table of `cap` slots whose slot h keeps key + 1 in keys[h * words] (0 = empty): found, or
+// claimed with a 64-bit CAS (`claimed`); the probe visits every slot once at most; -1 when all hold other keys
+__device__ __forceinline__ long long claim_slot(u64 *keys, int words, long long cap, u64 key, bool &claimed)
+{
+    claimed = false;
+    long long h = cap > 0 ? (long long)(mix64(key) % (u64)cap) : 0;
+    for (long long probe = 0; probe < cap; ++probe) {
+        u64 e = peek(&keys[h * words]);
+        if (e == 0) {
+            e = atomicCAS(&keys[h * words], 0ULL, key + 1);
+            if (e == 0) { e = key + 1; claimed = true; }
+        }
+        if (e == key + 1) return h;
+        h = next_slot(h, cap);
+    }
+    return -1;
+}
+
+struct RowCounters {                    // a lane's counts of what became of its rows, summed per workgroup into the stats
+    long long n[N_COUNTERS] = {0, 0, 0, 0, 0};
+    __device__ __forceinline__ void count(int kind)
+    {
+        for (int k = 0; k < N_COUNTERS; ++k) n[k] += kind == k;
+    }
+    __device__ __forceinline__ void add_to(long long *stats) const
+    {
+        __shared__ long long red[N_COUNTERS][MAP_THREADS / 64];
+        const int tid = threadIdx.x;
+        for (int k = 0; k < N_COUNTERS; ++k) {
+            const long long v = nsc_wave_sum(n[k]);
+            if ((tid & 63) == 0) red[k][tid >> 6] = v;
+        }
+        __syncthreads();
+        if (tid < N_COUNTERS) {
+            long long v = 0;
+            for (int w = 0; w < MAP_THREADS / 64; ++w) v += red[tid][w];
+            if (v) atomicAdd(reinterpret_cast<u64 *>(&stats[NSC_MAP_STAT_USED + tid]), (u64)v);
+        }
+    }
+};
+
 template <class T, class S>
-__global__ __launch_bounds__(MAP_THREADS) void map_insert_kernel(const T *pts, int stride, const long long *off,
-                                                                 int n_clouds, long long total, const double *poses,
-                                                                 int n_poses, const long long *ids, MapGrid g,
-                                                                 S *tab, long long cap, long long *stats)
+__global__ __launch_bounds__(MAP_THREADS) void map_insert_kernel(InsertRows<T> in, S *tab, long long cap, long long *stats)
 {
     const int tid = threadIdx.x;
-    long long cnt[N_COUNTERS] = {0, 0, 0, 0, 0};
-    const long long n_sweeps = (total + INSERT_ROWS - 1) / INSERT_ROWS;
+    RowCounters cnt;
+    const long long n_sweeps = (in.total + INSERT_ROWS - 1) / INSERT_ROWS;
     for (long long sweep = blockIdx.x; sweep < n_sweeps; sweep += gridDim.x) {
-        long long lo = 0, hi = 0;       // the rows of cloud c, while c >= 0
-        int c = -1;
+        CloudSpan span;
         for (int k = 0; k < INSERT_ROWS / MAP_THREADS; ++k) {
             const long long row = sweep * INSERT_ROWS + (long long)k * MAP_THREADS + tid;
-            if (row >= total) break;
-            if (c < 0 || row < lo || row >= hi) c = cloud_of(off, n_clouds, row, lo, hi);
-            const long long id = c < 0 ? -1 : (ids ? ids[c] : (long long)c);
-            if (id < 0 || id >= n_poses) { ++cnt[C_NO_POSE]; continue; }
-            const T *q = pts + row * stride;
-            const double p[3] = {(double)q[0], (double)q[1], (double)q[2]};
-            double w[3];
-            place_row(poses + 16 * id, p, w);
-            if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && isfinite(w[0]) && isfinite(w[1]) && isfinite(w[2]))) {
-                ++cnt[C_NOT_FINITE];
-                continue;
-            }
-            double u[3];
+            if (row >= in.total) break;
+            double w[3], u[3];
             u64 key;
-            if (!world_voxel(w, g, u, key)) {
-                ++cnt[C_OUTSIDE];
-                continue;
-            }
-            long long h = cap > 0 ? (long long)(mix64(key) % (u64)cap) : 0;
-            bool placed = false;
-            for (long long probe = 0; probe < cap; ++probe) {          // every slot once at most
-                u64 e = peek(&tab[h].key);
-                if (e == 0) {
-                    e = atomicCAS(&tab[h].key, 0ULL, key + 1);
-                    if (e == 0) e = key + 1;
-                }
-                if (e == key + 1) { placed = true; break; }
-                h = next_slot(h, cap);
-            }
-            if (!placed) { ++cnt[C_UNPLACED]; continue; }
-            ++cnt[C_USED];
+            int kind = locate_row(in, row, span, w, u, key);
+            long long h = -1;
+            bool claimed;
+            if (kind == C_USED && (h = claim_slot(&tab[0].key, slot_words<S>(), cap, key, claimed)) < 0) kind = C_UNPLACED;
+            cnt.count(kind);
+            if (kind != C_USED) continue;
             S &s = tab[h];
+            const int c = span.c;
             // min and max only move one way: a value read before the atomic that already beats ours stays beaten
             if (peek(&s.first) > (u64)row) atomicMin(&s.first, (u64)row);
             if (peek(&s.cloud_min) > (u64)c) atomicMin(&s.cloud_min, (u64)c);
@@ -174,17 +231,7 @@ __global__ __launch_bounds__(MAP_THREADS) void map_insert_kernel(const T *pts, i
             add_row(s, w, u);
         }
     }
-    __shared__ long long red[N_COUNTERS][MAP_THREADS / 64];
-    for (int k = 0; k < N_COUNTERS; ++k) {
-        const long long v = nsc_wave_sum(cnt[k]);
-        if ((tid & 63) == 0) red[k][tid >> 6] = v;
-    }
-    __syncthreads();
-    if (tid < N_COUNTERS) {
-        long long v = 0;
-        for (int w = 0; w < MAP_THREADS / 64; ++w) v += red[tid][w];
-        if (v) atomicAdd(reinterpret_cast<u64 *>(&stats[NSC_MAP_STAT_USED + tid]), (u64)v);
-    }
+    cnt.add_to(stats);
 }
 static_assert(NSC_MAP_STAT_NOT_FINITE == NSC_MAP_STAT_USED + C_NOT_FINITE && NSC_MAP_STAT_OUTSIDE == NSC_MAP_STAT_USED + C_OUTSIDE &&
                   NSC_MAP_STAT_NO_POSE == NSC_MAP_STAT_USED + C_NO_POSE && NSC_MAP_STAT_UNPLACED == NSC_MAP_STAT_USED + C_UNPLACED,
@@ -281,11 +328,45 @@ struct CentroidOut {                     // nsc_map_build: one centroid per voxe
     }
 };
 
-struct DistOut {                         // nsc_map_build_dist: a distribution record per voxel, and the kept index
-    double *voxels; u64 *index; long long *moments;
+struct DistRule {                        // what turns a voxel's integers into its record
     MapGrid g;
     double eigen_ratio, floor2;
     long long min_points;
+};
+
+// The record of a voxel (include/nsc.h): a function of its count, its nine sums (q first) and its key alone.  The one
+// copy of this arithmetic: the build's write pass and the insertion's refresh pass call it, so their records agree bit
+// for bit
+__device__ inline void dist_record(u64 count, const long long sum[3], const long long sq[6], u64 key, const DistRule &r,
+                                   double rec[16])
+{
+    const double n = (double)count;
+    double m[3];
+    for (int a = 0; a < 3; ++a) {
+        const double k = (double)(long long)((key >> (a * KEY_BITS)) & (u64)KEY_MAX) - KEY_OFFSET;
+        m[a] = (double)sum[a] / n;                             // mean of q
+        rec[a] = r.g.origin[a] + ((k + 0.5) + m[a] / MOMENT_SCALE) * r.g.voxel;
+    }
+    const double unit = r.g.voxel / MOMENT_SCALE, unit2 = unit * unit;
+    int t = 0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = a; b < 3; ++b, ++t) rec[3 + t] = ((double)sq[t] / n - m[a] * m[b]) * unit2;
+    double A[3][3], V[3][3], inv[3];
+    jacobi_eig3(rec + 3, A, V);
+    const double top = fmax(A[0][0], fmax(A[1][1], A[2][2]));
+    for (int i = 0; i < 3; ++i) inv[i] = 1.0 / fmax(fmax(A[i][i], r.eigen_ratio * top), r.floor2);
+    t = 0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = a; b < 3; ++b, ++t)
+            rec[9 + t] = (V[a][0] * V[b][0] * inv[0] + V[a][1] * V[b][1] * inv[1]) + V[a][2] * V[b][2] * inv[2];
+    bool usable = (long long)count >= r.min_points;
+    for (int e = 0; e < 15; ++e) usable = usable && isfinite(rec[e]);
+    rec[15] = usable ? 1.0 : 0.0;
+}
+
+struct DistOut {                         // nsc_map_build_dist: a distribution record per voxel, and the kept index
+    double *voxels; u64 *index; long long *moments;
+    DistRule rule;
     __device__ void empty(long long h) const { index[2 * h] = 0ULL; index[2 * h + 1] = ~0ULL; }
     // a voxel past the outputs keeps its key, so that probes continue past it
     __device__ void overflow(long long h, const DistSlot &s) const { index[2 * h] = s.key; index[2 * h + 1] = ~0ULL; }
@@ -297,29 +378,8 @@ struct DistOut {                         // nsc_map_build_dist: a distribution r
             for (int a = 0; a < 3; ++a) moments[9 * pos + a] = s.sum[a];
             for (int t = 0; t < 6; ++t) moments[9 * pos + 3 + t] = s.sq[t];
         }
-        const double n = (double)s.count;
-        const u64 key = s.key - 1;
-        double rec[16], m[3];
-        for (int a = 0; a < 3; ++a) {
-            const double k = (double)(long long)((key >> (a * KEY_BITS)) & (u64)KEY_MAX) - KEY_OFFSET;
-            m[a] = (double)s.sum[a] / n;                       // mean of q
-            rec[a] = g.origin[a] + ((k + 0.5) + m[a] / MOMENT_SCALE) * g.voxel;
-        }
-        const double unit = g.voxel / MOMENT_SCALE, unit2 = unit * unit;
-        int t = 0;
-        for (int a = 0; a < 3; ++a)
-            for (int b = a; b < 3; ++b, ++t) rec[3 + t] = ((double)s.sq[t] / n - m[a] * m[b]) * unit2;
-        double A[3][3], V[3][3], inv[3];
-        jacobi_eig3(rec + 3, A, V);
-        const double top = fmax(A[0][0], fmax(A[1][1], A[2][2]));
-        for (int i = 0; i < 3; ++i) inv[i] = 1.0 / fmax(fmax(A[i][i], eigen_ratio * top), floor2);
-        t = 0;
-        for (int a = 0; a < 3; ++a)
-            for (int b = a; b < 3; ++b, ++t)
-                rec[9 + t] = (V[a][0] * V[b][0] * inv[0] + V[a][1] * V[b][1] * inv[1]) + V[a][2] * V[b][2] * inv[2];
-        bool usable = (long long)s.count >= min_points;
-        for (int e = 0; e < 15; ++e) usable = usable && isfinite(rec[e]);
-        rec[15] = usable ? 1.0 : 0.0;
+        double rec[16];
+        dist_record(s.count, s.sum, s.sq, s.key - 1, rule, rec);
         for (int e = 0; e < 16; ++e) voxels[16 * pos + e] = rec[e];
     }
 };
@@ -408,11 +468,15 @@ int launch_build(const void *points, int32_t dtype, int32_t stride_floats, const
     hipLaunchKernelGGL(map_clear_kernel, dim3(blocks_for(n_slot_words > r.n_words ? n_slot_words : r.n_words, MAP_THREADS, MAP_SLOT_BLOCKS)),
                        threads, 0, s, reinterpret_cast<u64 *>(r.slots), n_slot_words, slot_words<S>(), r.bits, r.n_words, st);
     if (dtype == NSC_MAP_DTYPE_F32)
-        hipLaunchKernelGGL((map_insert_kernel<float, S>), per_rows, threads, 0, s, static_cast<const float *>(points),
-                           stride_floats, off, n_clouds, (long long)total_rows, poses, n_poses, ids, g, r.slots, r.cap, st);
+        hipLaunchKernelGGL((map_insert_kernel<float, S>), per_rows, threads, 0, s,
+                           InsertRows<float>{static_cast<const float *>(points), stride_floats, off, n_clouds,
+                                             (long long)total_rows, poses, n_poses, ids, g},
+                           r.slots, r.cap, st);
     else
-        hipLaunchKernelGGL((map_insert_kernel<double, S>), per_rows, threads, 0, s, static_cast<const double *>(points),
-                           stride_floats, off, n_clouds, (long long)total_rows, poses, n_poses, ids, g, r.slots, r.cap, st);
+        hipLaunchKernelGGL((map_insert_kernel<double, S>), per_rows, threads, 0, s,
+                           InsertRows<double>{static_cast<const double *>(points), stride_floats, off, n_clouds,
+                                              (long long)total_rows, poses, n_poses, ids, g},
+                           r.slots, r.cap, st);
     const dim3 per_slot(blocks_for(r.cap, MAP_THREADS, MAP_SLOT_BLOCKS));
     hipLaunchKernelGGL(map_mark_kernel<S>, per_slot, threads, 0, s, r.slots, r.cap, r.bits, r.n_words);
     hipLaunchKernelGGL(map_count_kernel, dim3(blocks_for(r.n_tiles, MAP_THREADS / 64, MAP_SLOT_BLOCKS)), threads, 0, s,
@@ -422,6 +486,217 @@ int launch_build(const void *points, int32_t dtype, int32_t stride_floats, const
                        MapPlaces{r.bits, r.prefix, r.tile, r.n_words}, (long long)max_voxels,
                        reinterpret_cast<long long *>(info), reinterpret_cast<long long *>(keys), out);
     return launch_status();
+}
+
+bool dist_ok(const NscMapDistParams *dist)
+{
+    return dist && dist->min_points >= 1 && dist->eigen_ratio > 0.0 && dist->eigen_ratio <= 1.0 && dist->sigma_floor > 0.0 &&
+           isfinite(dist->sigma_floor);
+}
+
+DistRule dist_rule(const NscMapParams *params, const NscMapDistParams *dist)
+{
+    return DistRule{MapGrid{params->voxel_size, {params->origin[0], params->origin[1], params->origin[2]}},
+                    dist->eigen_ratio, dist->sigma_floor * dist->sigma_floor, (long long)dist->min_points};
+}
+
+// ---- nsc_map_insert_dist: rows added to a kept map ---------------------------------------------------------------------
+// The kept index is the build's table: (key + 1, place) at the slots the build's probes walked, so new keys are claimed in
+// it as the build claims them.  Nothing below walks the 2 max_voxels slots or the max_voxels records: every pass is over
+// the call's rows, or over the places they reached.
+//
+// Launch sequence (8; the grids depend on total_rows alone):
+//   clear       map_clear_kernel on the call's first-row bitmap and its counters
+//   claim       per row: the row's slot, found or claimed (64-bit CAS) along the build's probe sequence and kept in the
+//               workspace; in the place word of a slot claimed in this call the smallest local row, PLACE_NEW | row
+//               (atomic min); the counters of dropped, unplaced and used rows into the kept stats
+//   mark        per row: the row a new slot's place word names sets its bit
+//   count, scan map_count_kernel and map_scan_kernel as they are, on the call's bitmap: the new voxels in first-row order
+//   assign      per first row of a new voxel: place = voxels written before the call + its rank; below max_voxels the
+//               place word, the key and an empty info and moments row, else place ~0 as the build's overflow
+//   accumulate  per row: integer atomics on info and moments of its place; the first row to reach a place in this call
+//               (PLACE_TOUCHED, an atomic or on the place word) appends the slot to the touched list
+//   refresh     per touched slot: PLACE_TOUCHED off, the record from dist_record; one thread folds the new voxels into
+//               the kept stats and advances the cursor
+// A map whose outputs are full (written == max_voxels before the call) can hold keyed slots with place ~0 from an
+// earlier overflow, which a place word cannot tell from a slot claimed a moment ago.  No new voxel gets a place then, so
+// only their number matters: the thread whose CAS claims the slot sets its own row's bit, and mark and assign do nothing.
+constexpr u64 PLACE_NEW = 1ULL << 62;        // no place reaches these bits: places stay below NSC_MAP_MAX_VOXELS
+constexpr u64 PLACE_TOUCHED = 1ULL << 61;
+static_assert(NSC_MAP_MAX_VOXELS <= (1LL << 61) && NSC_MAP_MAX_ROWS <= (1LL << 61), "the flags lie above places and rows");
+enum { CALL_FOUND = NSC_MAP_STAT_FOUND, CALL_WRITTEN = NSC_MAP_STAT_WRITTEN, CALL_TOUCHED, CALL_WORDS = NSC_MAP_STATS };
+
+struct KeptMap {
+    double *voxels; u64 *index; long long *info, *keys, *moments, *stats, *cursor;
+    long long max_voxels;
+    // the outputs were full before this call; the stats' voxel counts stay as they were until the refresh pass
+    __device__ bool full() const { return stats[NSC_MAP_STAT_WRITTEN] >= max_voxels; }
+};
+
+struct InsertRegions {
+    u64 *bits; unsigned *prefix; long long *tile, *slot, *touched, *call;
+    long long n_words, n_tiles;
+    size_t total;
+};
+
+InsertRegions insert_regions(void *ws, long long total_rows)
+{
+    Carver c = {reinterpret_cast<uintptr_t>(ws), 0};
+    InsertRegions r;
+    r.n_words = (total_rows + 63) / 64;
+    r.n_tiles = (total_rows + TILE_ROWS - 1) / TILE_ROWS;
+    r.bits = c.take<u64>(r.n_words);
+    r.prefix = c.take<unsigned>(r.n_words);
+    r.tile = c.take<long long>(r.n_tiles);
+    r.slot = c.take<long long>(total_rows);
+    r.touched = c.take<long long>(total_rows);
+    r.call = c.take<long long>(CALL_WORDS);
+    r.total = c.o;
+    return r;
+}
+
+template <class T>
+__global__ __launch_bounds__(MAP_THREADS) void ins_claim_kernel(InsertRows<T> in, KeptMap m, u64 *bits, long long *slot)
+{
+    const int tid = threadIdx.x;
+    const long long cap = 2 * m.max_voxels;
+    const bool full = m.full();
+    RowCounters cnt;
+    const long long n_sweeps = (in.total + INSERT_ROWS - 1) / INSERT_ROWS;
+    for (long long sweep = blockIdx.x; sweep < n_sweeps; sweep += gridDim.x) {
+        CloudSpan span;
+        for (int k = 0; k < INSERT_ROWS / MAP_THREADS; ++k) {
+            const long long row = sweep * INSERT_ROWS + (long long)k * MAP_THREADS + tid;
+            if (row >= in.total) break;
+            double w[3], u[3];
+            u64 key;
+            int kind = locate_row(in, row, span, w, u, key);
+            long long h = -1;
+            bool claimed = false;
+            if (kind == C_USED && (h = claim_slot(m.index, 2, cap, key, claimed)) < 0) kind = C_UNPLACED;
+            cnt.count(kind);
+            slot[row] = h;
+            if (h < 0) continue;
+            if (full) {
+                if (claimed) atomicOr(&bits[row >> 6], 1ULL << (row & 63));
+                continue;
+            }
+            // an empty slot's place word is ~0, which has PLACE_NEW set and is above every PLACE_NEW | row
+            const u64 mine = PLACE_NEW | (u64)row, there = peek(&m.index[2 * h + 1]);
+            if ((there & PLACE_NEW) && there > mine) atomicMin(&m.index[2 * h + 1], mine);
+        }
+    }
+    cnt.add_to(m.stats);
+}
+
+__global__ __launch_bounds__(MAP_THREADS) void ins_mark_kernel(KeptMap m, const long long *slot, long long total, u64 *bits)
+{
+    if (m.full()) return;
+    for (long long row = (long long)blockIdx.x * MAP_THREADS + threadIdx.x; row < total; row += (long long)gridDim.x * MAP_THREADS) {
+        const long long h = slot[row];
+        if (h >= 0 && m.index[2 * h + 1] == (PLACE_NEW | (u64)row)) atomicOr(&bits[row >> 6], 1ULL << (row & 63));
+    }
+}
+
+__global__ __launch_bounds__(MAP_THREADS) void ins_assign_kernel(KeptMap m, const long long *slot, long long total,
+                                                                 MapPlaces places)
+{
+    if (m.full()) return;
+    const long long written = m.stats[NSC_MAP_STAT_WRITTEN], row0 = m.cursor[0];
+    for (long long row = (long long)blockIdx.x * MAP_THREADS + threadIdx.x; row < total; row += (long long)gridDim.x * MAP_THREADS) {
+        const long long h = slot[row];
+        if (h < 0 || m.index[2 * h + 1] != (PLACE_NEW | (u64)row)) continue;
+        const long long pos = written + places.of((u64)row);
+        if (pos >= m.max_voxels) { m.index[2 * h + 1] = ~0ULL; continue; }
+        m.index[2 * h + 1] = (u64)pos;
+        m.keys[pos] = (long long)(m.index[2 * h] - 1);
+        m.info[4 * pos] = 0;
+        m.info[4 * pos + 1] = row0 + row;
+        m.info[4 * pos + 2] = INT64_MAX;
+        m.info[4 * pos + 3] = -1;
+        for (int t = 0; t < 9; ++t) m.moments[9 * pos + t] = 0;
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(MAP_THREADS) void ins_accumulate_kernel(InsertRows<T> in, KeptMap m, const long long *slot,
+                                                                     long long *touched, long long *call)
+{
+    const int tid = threadIdx.x;
+    const long long cloud0 = m.cursor[1];
+    const long long n_sweeps = (in.total + INSERT_ROWS - 1) / INSERT_ROWS;
+    for (long long sweep = blockIdx.x; sweep < n_sweeps; sweep += gridDim.x) {
+        CloudSpan span;
+        for (int k = 0; k < INSERT_ROWS / MAP_THREADS; ++k) {
+            const long long row = sweep * INSERT_ROWS + (long long)k * MAP_THREADS + tid;
+            if (row >= in.total) break;
+            const long long h = slot[row];
+            if (h < 0) continue;
+            u64 there = peek(&m.index[2 * h + 1]);
+            if (there & PLACE_NEW) continue;                           // ~0, a voxel past the outputs: its rows are counted, no more
+            if (!(there & PLACE_TOUCHED)) {
+                there = atomicOr(&m.index[2 * h + 1], PLACE_TOUCHED);
+                if (!(there & PLACE_TOUCHED))
+                    touched[atomicAdd(reinterpret_cast<u64 *>(&call[CALL_TOUCHED]), 1ULL)] = h;
+            }
+            const long long pos = (long long)(there & ~PLACE_TOUCHED);
+            // a row with a slot has a cloud, a pose, finite coordinates and a voxel: the claim pass found C_USED
+            double w[3], u[3];
+            u64 key;
+            locate_row(in, row, span, w, u, key);
+            const int c = span.c;
+            long long *info = m.info + 4 * pos;
+            const long long cloud = cloud0 + c;
+            atomicAdd(reinterpret_cast<u64 *>(info), 1ULL);
+            // min and max only move one way: a value read before the atomic that already beats ours stays beaten
+            if ((long long)peek(reinterpret_cast<u64 *>(info + 2)) > cloud)
+                __hip_atomic_fetch_min(info + 2, cloud, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((long long)peek(reinterpret_cast<u64 *>(info + 3)) < cloud)
+                __hip_atomic_fetch_max(info + 3, cloud, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            long long *mo = m.moments + 9 * pos;
+            row_moments(u, [mo](int t, long long v) { atomicAdd(reinterpret_cast<u64 *>(mo + t), (u64)v); });
+        }
+    }
+}
+
+__global__ __launch_bounds__(MAP_THREADS) void ins_refresh_kernel(KeptMap m, const long long *touched, const long long *call,
+                                                                  DistRule rule, long long total, long long n_clouds)
+{
+    const long long n = call[CALL_TOUCHED];
+    for (long long i = (long long)blockIdx.x * MAP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * MAP_THREADS) {
+        const long long h = touched[i];
+        const long long pos = (long long)(m.index[2 * h + 1] & ~PLACE_TOUCHED);
+        m.index[2 * h + 1] = (u64)pos;
+        double rec[16];
+        dist_record((u64)m.info[4 * pos], m.moments + 9 * pos, m.moments + 9 * pos + 3, m.index[2 * h] - 1, rule, rec);
+        for (int e = 0; e < 16; ++e) m.voxels[16 * pos + e] = rec[e];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const long long found = m.stats[NSC_MAP_STAT_FOUND] + call[CALL_FOUND];
+        m.stats[NSC_MAP_STAT_FOUND] = found;
+        m.stats[NSC_MAP_STAT_WRITTEN] = min(found, m.max_voxels);
+        m.cursor[0] += total;
+        m.cursor[1] += n_clouds;
+    }
+}
+
+template <class T>
+void launch_insert_rows(const InsertRows<T> &in, const KeptMap &m, const DistRule &rule, const InsertRegions &r, hipStream_t s)
+{
+    const dim3 threads(MAP_THREADS), sweeps(blocks_for(in.total, INSERT_ROWS, NSC_MAP_INSERT_BLOCKS)),
+        per_row(blocks_for(in.total, MAP_THREADS, MAP_SLOT_BLOCKS));
+    hipLaunchKernelGGL(map_clear_kernel, dim3(blocks_for(r.n_words, MAP_THREADS, MAP_SLOT_BLOCKS)), threads, 0, s,
+                       static_cast<u64 *>(nullptr), 0LL, 1, r.bits, r.n_words, r.call);
+    hipLaunchKernelGGL(ins_claim_kernel<T>, sweeps, threads, 0, s, in, m, r.bits, r.slot);
+    hipLaunchKernelGGL(ins_mark_kernel, per_row, threads, 0, s, m, r.slot, in.total, r.bits);
+    hipLaunchKernelGGL(map_count_kernel, dim3(blocks_for(r.n_tiles, MAP_THREADS / 64, MAP_SLOT_BLOCKS)), threads, 0, s,
+                       r.bits, r.n_words, r.n_tiles, r.prefix, r.tile);
+    hipLaunchKernelGGL(map_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, r.tile, r.n_tiles, m.max_voxels, r.call);
+    hipLaunchKernelGGL(ins_assign_kernel, per_row, threads, 0, s, m, r.slot, in.total,
+                       MapPlaces{r.bits, r.prefix, r.tile, r.n_words});
+    hipLaunchKernelGGL(ins_accumulate_kernel<T>, sweeps, threads, 0, s, in, m, r.slot, r.touched, r.call);
+    hipLaunchKernelGGL(ins_refresh_kernel, per_row, threads, 0, s, m, r.touched, r.call, rule, in.total,
+                       (long long)in.n_clouds);
 }
 
 }  // namespace
@@ -477,16 +752,47 @@ int nsc_map_build_dist(const void *points, int32_t dtype, int32_t stride_floats,
     if (const int st = check_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, params,
                                    max_voxels, voxels && index && info && keys, stats))
         return st;
-    if (!dist || dist->min_points < 1 || !(dist->eigen_ratio > 0.0) || !(dist->eigen_ratio <= 1.0) ||
-        !(dist->sigma_floor > 0.0) || !isfinite(dist->sigma_floor))
-        return NSC_EINVAL;
+    if (!dist_ok(dist)) return NSC_EINVAL;
     const MapRegions<DistSlot> r = map_regions<DistSlot>(ws, total_rows, max_voxels);
     if (r.total > 0 && (!ws || ws_bytes < r.total)) return NSC_EWORKSPACE;
-    const DistOut out{voxels, reinterpret_cast<u64 *>(index), reinterpret_cast<long long *>(moments),
-                      MapGrid{params->voxel_size, {params->origin[0], params->origin[1], params->origin[2]}},
-                      dist->eigen_ratio, dist->sigma_floor * dist->sigma_floor, (long long)dist->min_points};
+    const DistOut out{voxels, reinterpret_cast<u64 *>(index), reinterpret_cast<long long *>(moments), dist_rule(params, dist)};
     return launch_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params,
                         max_voxels, info, keys, stats, out, r, stream);
+}
+
+size_t nsc_map_insert_workspace_bytes(int64_t total_rows)
+{
+    if (total_rows < 0 || total_rows > NSC_MAP_MAX_ROWS) return 0;
+    return insert_regions(nullptr, total_rows).total;
+}
+
+int nsc_map_insert_dist(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_clouds,
+                        int64_t total_rows, const double *poses, int32_t n_poses, const int64_t *pose_ids,
+                        const NscMapParams *params, const NscMapDistParams *dist, int64_t max_voxels, double *voxels,
+                        uint64_t *index, int64_t *info, int64_t *keys, int64_t *moments, int64_t *stats, int64_t *cursor,
+                        void *ws, size_t ws_bytes, void *stream)
+{
+    if (const int st = check_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, params,
+                                   max_voxels, voxels && index && info && keys, stats))
+        return st;
+    if (!dist_ok(dist) || !moments || !cursor) return NSC_EINVAL;
+    const InsertRegions r = insert_regions(ws, total_rows);
+    if (!ws || ws_bytes < r.total) return NSC_EWORKSPACE;
+    const KeptMap m{voxels, reinterpret_cast<u64 *>(index), reinterpret_cast<long long *>(info),
+                    reinterpret_cast<long long *>(keys), reinterpret_cast<long long *>(moments),
+                    reinterpret_cast<long long *>(stats), reinterpret_cast<long long *>(cursor), (long long)max_voxels};
+    const MapGrid g{params->voxel_size, {params->origin[0], params->origin[1], params->origin[2]}};
+    const long long *off = reinterpret_cast<const long long *>(offsets), *ids = reinterpret_cast<const long long *>(pose_ids);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dtype == NSC_MAP_DTYPE_F32)
+        launch_insert_rows(InsertRows<float>{static_cast<const float *>(points), stride_floats, off, n_clouds,
+                                             (long long)total_rows, poses, n_poses, ids, g},
+                           m, dist_rule(params, dist), r, s);
+    else
+        launch_insert_rows(InsertRows<double>{static_cast<const double *>(points), stride_floats, off, n_clouds,
+                                              (long long)total_rows, poses, n_poses, ids, g},
+                           m, dist_rule(params, dist), r, s);
+    return launch_status();
 }
 
 }  // extern "C"

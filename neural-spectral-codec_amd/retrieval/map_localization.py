@@ -15,12 +15,17 @@ Definition (the contract the two entry points and tests/map_localize_restatement
                  is looked up.  Rows that are not finite, outside the grid or without a usable voxel do not contribute
     rounds       Gauss-Newton on [rotation | translation], J = [-[T p]x | I]; fitness = n_corr / rows,
                  rmse = sqrt(sum |d|^2 / n_corr); Open3D's convergence test; at most max_iteration updates
+    insertion    (nsc_map_insert_dist) a map built ``insertable`` keeps its int64 moments and a cursor [rows, clouds taken
+                 so far]; new clouds are added to the kept tensors in work proportional to their rows, and the map is
+                 then, bit for bit, the map a build over all clouds would give.  Rows and clouds of an insertion are
+                 numbered on from the cursor; poses and ``pose_ids`` are indexed within the call
 
 Integer atomics and fixed-shape float64 sums only: two calls agree bit for bit and a scan's result does not depend on what
 else is in the batch.
 
 Not part of this module: source covariances (full VGICP), neighbour-voxel correspondences, robust weights, NDT's
-exponential score, insertion of new scans into the kept table, unary edges in the pose graph.
+exponential score, removal or re-placing of clouds (first_row and the cloud range are minima and maxima: they do not
+subtract), growing the capacity of a kept map, unary edges in the pose graph.
 """
 import ctypes as C
 
@@ -64,15 +69,20 @@ class MapLocalizer:
     relative_fitness  1e-6     a scan is finished when fitness and rmse both change by less than these
     relative_rmse     1e-6
     device            'cuda'   there is no CPU fallback
+    insertable        False    every build keeps ``moments`` (M,9) and ``cursor`` (2,) int64 = [rows, clouds taken so
+                               far], so that ``insert*`` and ``extend`` can add scans to the kept map.  The capacity does
+                               not grow: with ``max_voxels=None`` it is the first build's row count, so a map that is
+                               meant to grow needs an explicit ``max_voxels``
 
     After a build the instance keeps ``voxels`` (M,16), ``index`` (2M,2), ``keys`` (M,), ``info`` (M,4), ``stats`` (7,)
-    as device tensors over the full capacity M and, after ``build`` or ``build_prepared``, ``complete``
-    (``build_device`` reads nothing back: ``complete`` is then None).
+    as device tensors over the full capacity M and, after ``build``, ``build_prepared``, ``insert`` or
+    ``insert_prepared``, ``complete`` (``build_device``, ``insert_device`` and ``extend`` read nothing back:
+    ``complete`` is then None).
     """
 
     def __init__(self, voxel_size: float = 1.0, origin=(0.0, 0.0, 0.0), max_voxels=None, min_points: int = 6,
                  eigen_ratio: float = 1e-2, sigma_floor: float = 1e-3, max_iteration: int = 30,
-                 relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, device="cuda"):
+                 relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, device="cuda", insertable: bool = False):
         self._grid = GlobalMap(voxel_size, origin, max_voxels, device)       # its refusals are this class's
         if int(min_points) < 1 or not 0.0 < float(eigen_ratio) <= 1.0 or \
                 not (np.isfinite(sigma_floor) and float(sigma_floor) > 0.0):
@@ -86,7 +96,8 @@ class MapLocalizer:
                                           relative_fitness=float(relative_fitness), relative_rmse=float(relative_rmse))
         self.max_voxels = self._grid.max_voxels
         self.device = device
-        self.voxels = self.index = self.keys = self.info = self.stats = self.moments = None
+        self.insertable = bool(insertable)
+        self.voxels = self.index = self.keys = self.info = self.stats = self.moments = self.cursor = None
         self.complete = None
         self.capacity = None
 
@@ -97,25 +108,17 @@ class MapLocalizer:
         call can be captured.  Arguments as ``GlobalMap.build_device``.  Returns, and keeps, the full buffers: voxels
         (M,16) float64, index (2M,2) uint64 stored as int64, info (M,4) int64, keys (M,) int64, stats (7,) int64 and, with
         ``moments=True``, moments (M,9) int64; entries of voxels, info, keys and moments past stats[1] are not defined.
+        An insertable map always keeps moments, and cursor (2,) int64, set to this build's rows and clouds by two fills.
         ``out``: a dict of those tensors to write into."""
-        for t, name in ((points, "points"), (offsets, "offsets"), (poses, "poses")):
-            _lib.require_cuda(t, name)
         dev = points.device
-        pts, off, B, N, dtype = _rows(points, offsets, "points")
-        if poses.ndim != 3 or tuple(poses.shape[1:]) != (4, 4):
-            raise _lib.NscError("poses must be (P,4,4)")
-        pose = poses.contiguous().to(torch.float64)
-        P = int(pose.shape[0])
-        ids = GlobalMap._host_ids(pose_ids, B, P)
-        if ids is not None:
-            ids = ids.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
-            if int(ids.numel()) != B:
-                raise _lib.NscError(f"pose_ids must have one entry per cloud ({B}), got {int(ids.numel())}")
+        pts, off, B, N, dtype, pose, P, ids = self._clouds(points, offsets, poses, pose_ids)
         M = N if self.max_voxels is None else self.max_voxels
         shapes = dict(voxels=((M, _lib.MAP_VOXEL_DOUBLES), torch.float64), index=((2 * M, 2), torch.int64),
                       info=((M, 4), torch.int64), keys=((M,), torch.int64), stats=((_lib.MAP_STATS,), torch.int64))
-        if moments or (out is not None and "moments" in out):
+        if moments or self.insertable or (out is not None and "moments" in out):
             shapes["moments"] = ((M, 9), torch.int64)
+        if self.insertable:
+            shapes["cursor"] = ((2,), torch.int64)
         if out is None:
             out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
         for k, (shape, dt) in shapes.items():
@@ -133,8 +136,115 @@ class MapLocalizer:
         _lib.check(status, "nsc_map_build_dist")
         self.voxels, self.index, self.keys, self.info, self.stats = (out[k] for k in ("voxels", "index", "keys", "info",
                                                                                      "stats"))
-        self.moments = out.get("moments")
+        self.moments, self.cursor = out.get("moments"), out.get("cursor") if self.insertable else None
+        if self.cursor is not None:
+            self.cursor[0].fill_(N)
+            self.cursor[1].fill_(B)
         self.capacity, self.complete = M, None
+        return out
+
+    def _clouds(self, points, offsets, poses, pose_ids):
+        """checked device input of a build or an insertion -> (rows, offsets, clouds, rows, dtype code, float64 poses,
+        poses, device ids or None)"""
+        for t, name in ((points, "points"), (offsets, "offsets"), (poses, "poses")):
+            _lib.require_cuda(t, name)
+        dev = points.device
+        pts, off, B, N, dtype = _rows(points, offsets, "points")
+        if poses.ndim != 3 or tuple(poses.shape[1:]) != (4, 4):
+            raise _lib.NscError("poses must be (P,4,4)")
+        pose = poses.contiguous().to(torch.float64)
+        P = int(pose.shape[0])
+        ids = GlobalMap._host_ids(pose_ids, B, P)
+        if ids is not None:
+            ids = ids.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
+            if int(ids.numel()) != B:
+                raise _lib.NscError(f"pose_ids must have one entry per cloud ({B}), got {int(ids.numel())}")
+        return pts, off, B, N, dtype, pose, P, ids
+
+    # ---- insertion ----------------------------------------------------------------------------------------------------
+
+    def _kept(self):
+        return {k: getattr(self, k) for k in ("voxels", "index", "info", "keys", "moments", "stats", "cursor")}
+
+    def _insertable_map(self, what):
+        """the host-side refusals every insertion starts with"""
+        if self.voxels is None:
+            raise _lib.NscError(f"MapLocalizer.{what}: build a map first")
+        if not self.insertable or self.moments is None or self.cursor is None:
+            raise _lib.NscError(f"MapLocalizer.{what}: the map was not built insertable (MapLocalizer(insertable=True))")
+
+    def insert_device(self, points, offsets, poses, pose_ids=None):
+        """Add packed clouds to the kept map (nsc_map_insert_dist), on the device and without a synchronisation: with
+        device ``pose_ids`` (or none) a call can be captured, and every replay is a further insertion of what the buffers
+        then hold.  Arguments as ``build_device``; poses and ``pose_ids`` are indexed within the call, rows and clouds are
+        numbered on from ``cursor``.  The kept tensors are then those of a build over all clouds so far with the same
+        capacity, bit for bit.  Returns the kept tensors (``build_device``'s dict and cursor); nothing is read back and
+        ``complete`` is None."""
+        self._insertable_map("insert_device")
+        dev = self.voxels.device
+        if points.device != dev:
+            raise _lib.NscError(f"the scans must be on the map's device ({dev})")
+        pts, off, B, N, dtype, pose, P, ids = self._clouds(points, offsets, poses, pose_ids)
+        L = _lib.lib()
+        ws = _workspace(L.nsc_map_insert_workspace_bytes(N), dev)
+        with torch.cuda.device(dev):
+            status = L.nsc_map_insert_dist(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off), B, N, _lib.ptr(pose), P,
+                                           _lib.ptr(ids), C.byref(self.params), C.byref(self.dist), self.capacity,
+                                           _lib.ptr(self.voxels), _lib.ptr(self.index), _lib.ptr(self.info),
+                                           _lib.ptr(self.keys), _lib.ptr(self.moments), _lib.ptr(self.stats),
+                                           _lib.ptr(self.cursor), _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+        _lib.check(status, "nsc_map_insert_dist")
+        self.complete = None
+        return self._kept()
+
+    def insert(self, clouds, poses, pose_ids=None):
+        """``insert_device`` on the input forms of ``build``.  Returns ``build``'s dict over the whole map; one
+        synchronisation, to read the stats."""
+        self._insertable_map("insert")
+        packed = _is_packed(clouds)
+        clouds = clouds if packed else _tensors(clouds)
+        pose = GlobalMap._poses(poses)
+        # host ids are refused before anything goes to the device
+        ids = GlobalMap._host_ids(pose_ids, int(clouds[1].numel()) - 1 if packed else len(clouds), int(pose.shape[0]))
+        dev = self.voxels.device
+        pts, off = clouds if packed else _pack(clouds, dev)
+        return self._result(self.insert_device(pts, off, pose.to(device=dev, dtype=torch.float64), ids))
+
+    def insert_prepared(self, store: PreparedClouds, poses, pose_ids=None, start=0):
+        """``insert`` on the clouds of a ``PreparedClouds`` from index ``start`` on: the clouds added to the store since
+        the map was built or last extended.  ``poses`` and ``pose_ids`` have one entry per inserted cloud."""
+        self._insertable_map("insert_prepared")
+        n = len(store)
+        if not 0 <= int(start) <= n:
+            raise _lib.NscError(f"start must lie in [0, {n}], got {start}")
+        start = int(start)
+        pose = GlobalMap._poses(poses)
+        ids = GlobalMap._host_ids(pose_ids, n - start, int(pose.shape[0]))
+        if store._buf is None:
+            store._reserve(0, 0, 0)
+        r0 = int(store._row_host[start])
+        pts, off = store._buf["points"][r0:store.n_rows], store._buf["row_offsets"][start:n + 1] - r0
+        return self._result(self.insert_device(pts, off, pose.to(device=store.device, dtype=torch.float64), ids))
+
+    def extend(self, scans, init_poses, min_fitness: float):
+        """Register ``scans`` (as ``register`` takes them) and insert those whose fitness reaches ``min_fitness`` under
+        their registered transforms: the map grows with the vehicle.  The choice is made on the device --
+        pose_ids = where(fitness >= min_fitness, scan, -1) -- so nothing is read back and, with packed device scans, the
+        pair of calls can be captured; the rows of the other scans are counted in rows_without_pose.  Returns
+        ``register_device``'s dict."""
+        self._insertable_map("extend")
+        packed = _is_packed(scans)
+        scans = scans if packed else _tensors(scans)
+        pose = GlobalMap._poses(init_poses)
+        S = int(scans[1].numel()) - 1 if packed else len(scans)
+        if int(pose.shape[0]) != S:              # refused before anything goes to the device
+            raise _lib.NscError(f"init_poses must have one (4,4) pose per scan ({S}), got {int(pose.shape[0])}")
+        dev = self.voxels.device
+        pts, off = scans if packed else _pack(scans, dev)
+        out = self.register_device(pts, off, pose.to(device=dev, dtype=torch.float64))
+        scan = torch.arange(S, dtype=torch.int64, device=dev)
+        ids = torch.where(out["fitness"] >= float(min_fitness), scan, -1)         # four launches: arange, >=, the -1 (a fill), where
+        self.insert_device(pts, off, out["transform"], ids)
         return out
 
     def _result(self, out):
