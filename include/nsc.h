@@ -967,12 +967,44 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
  *   NULL: the sums at init_transforms, the first 29 laid out as NscGicpStages.system0, then sum d^T Omega d.
  * A scan whose init_transform is not finite gets NaN outputs, n_corr -1 and 0 iterations; none of its rows is read.
  * Results are bitwise reproducible and a scan's results do not depend on what else is in the batch.
+ *
+ * nsc_map_register_robust (restated in tests/map_robust_restatement.py).  nsc_map_register with robust weights and face-
+ *   neighbour voxels; with NSC_MAP_KERNEL_NONE and neighbours = 1 it is nsc_map_register, bit for bit.  Float64:
+ * Voxels.  For a row with w = T p finite and inside the grid the candidates are its own voxel k and, with neighbours = 7,
+ *   k -+ e_x, k -+ e_y, k -+ e_z, in the fixed order (0, -x, +x, -y, +y, -z, +z).  A neighbour whose coordinate leaves
+ *   [0, 2^21) on its axis is skipped: a packed key never borrows from or carries into another axis' bits.
+ * Pairs.  A pair (row, voxel) exists when the voxel is in the index, has a place below max_voxels and is usable
+ *   (record[15] == 1.0), as nsc_map_register decides for the own voxel.
+ * Per pair.  d = w - mean_v, s = d^T Omega_v d, J = [-[w]x | I], and the weight w = rho'(s) of the pose graph's kernels
+ *   (the table at nsc_posegraph_optimize_robust) with one width c = `scale` per call, in units of sqrt(chi^2):
+ *   Huber w = 1 for s <= c^2 else c / sqrt(s); Cauchy w = 1 / (1 + s / c^2); Geman-McClure w = (c^2 / (c^2 + s))^2;
+ *   NONE rho = s, w = 1.
+ * System.  H = sum_pairs w J^T Omega J, g = sum_pairs w J^T Omega d, cost = sum_pairs rho(s).
+ * Counts.  n_correspondences = rows with at least one pair (fitness = that / rows stays <= 1), n_pairs = the number of
+ *   pairs, weight_sum = sum w.  rmse = sqrt(sum w |d|^2 / sum w), 0 when sum w = 0.
+ * Rounds.  Convergence test, update, NaN initial transforms and scans without correspondences as nsc_map_register;
+ *   information = H at the result.  A row's pairs are added in the fixed order and the reduction keeps its fixed shape:
+ *   two calls agree bit for bit and a scan's result does not depend on what else is in the batch.
+ * Outputs.  nsc_map_register's, with system0 (n_scans,NSC_MAP_REGISTER_ROBUST_SYSTEM) or NULL: the 30 sums of
+ *   nsc_map_register in their places (sum w |d|^2 at 28, sum rho at 29), then sum w and n_pairs; and weight_pairs
+ *   (n_scans,2) float64 = [weight_sum, n_pairs] at the result.  A scan whose init_transform is not finite gets
+ *   weight_pairs = [NaN, -1] and a system0 of NaN.
+ * Launches.  1 + 2 (max_iteration + 1), in nsc_map_register's shapes; NONE with one voxel launches nsc_map_register's
+ *   own kernels.  Neighbours without a kernel pull every row towards up to seven means at full weight and bias the result:
+ *   neighbours = 7 is meant to be used with a kernel.  Geman-McClure refines from a good start; Cauchy suits wide starts.
  * ------------------------------------------------------------------------------------------ */
 #define NSC_MAP_VOXEL_DOUBLES       16
 #define NSC_MAP_INSERT_LAUNCHES     8       /* kernels of one nsc_map_insert_dist call */
 #define NSC_MAP_REGISTER_BLOCKS     64      /* workgroups of 256 lanes per scan in linearize */
 #define NSC_MAP_REGISTER_SYSTEM     30
 #define NSC_MAP_REGISTER_MAX_SCANS  65535
+#define NSC_MAP_REGISTER_ROBUST_SYSTEM  32  /* the NSC_MAP_REGISTER_SYSTEM sums, then sum w and n_pairs */
+
+/* NscMapRobustParams.kernel: the values of NSC_POSEGRAPH_KERNEL_* */
+#define NSC_MAP_KERNEL_NONE           0
+#define NSC_MAP_KERNEL_HUBER          1
+#define NSC_MAP_KERNEL_CAUCHY         2
+#define NSC_MAP_KERNEL_GEMAN_MCCLURE  3
 
 typedef struct NscMapDistParams {
     int32_t min_points;             /* 6      rows a voxel needs to be usable, >= 1 */
@@ -987,6 +1019,12 @@ typedef struct NscMapRegisterParams {
     double  relative_fitness;       /* 1e-6   >= 0 */
     double  relative_rmse;          /* 1e-6   >= 0 */
 } NscMapRegisterParams;
+
+typedef struct NscMapRobustParams {
+    int32_t kernel;                 /* NSC_MAP_KERNEL_NONE */
+    int32_t neighbours;             /* 1      voxels a row is paired with: 1 (its own) or 7 (and the six face neighbours) */
+    double  scale;                  /* 0      the kernel's width c, finite and positive with a kernel; not read with NONE */
+} NscMapRobustParams;
 
 void   nsc_map_dist_default_params(NscMapDistParams *p);
 /* As nsc_map_workspace_bytes, with 256 bytes per voxel of max_voxels (the table of 128-byte slots). */
@@ -1023,6 +1061,20 @@ int    nsc_map_register(const void *points, int32_t dtype, int32_t stride_floats
                         const NscMapParams *params, const NscMapRegisterParams *reg, const double *init_transforms,
                         double *transforms, double *fitness_rmse, double *cost, int64_t *corr_iterations,
                         double *information, double *system0, void *ws, size_t ws_bytes, void *stream);
+
+void   nsc_map_robust_default_params(NscMapRobustParams *p);
+/* Bytes of workspace for nsc_map_register_robust: nsc_map_register's layout with slabs of NSC_MAP_REGISTER_ROBUST_SYSTEM
+ * sums; monotone; 0 for a negative n_scans.  It is enough for every kernel and neighbourhood. */
+size_t nsc_map_register_robust_workspace_bytes(int32_t n_scans);
+/* NSC_EINVAL for a null `robust`, a kernel outside 0..3, neighbours other than 1 or 7, or a kernel other than NONE with a
+ * scale that is not finite and positive: checked first, whatever else is passed.  Then nsc_map_register's refusals, and
+ * NSC_EINVAL for a null weight_pairs with n_scans > 0. */
+int    nsc_map_register_robust(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets,
+                               int32_t n_scans, int64_t total_rows, const double *voxels, const uint64_t *index,
+                               int64_t max_voxels, const NscMapParams *params, const NscMapRegisterParams *reg,
+                               const NscMapRobustParams *robust, const double *init_transforms, double *transforms,
+                               double *fitness_rmse, double *cost, int64_t *corr_iterations, double *information,
+                               double *system0, double *weight_pairs, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

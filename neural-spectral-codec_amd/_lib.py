@@ -128,6 +128,11 @@ class MapRegisterParams(C.Structure):
                 ("relative_rmse", C.c_double)]
 
 
+class MapRobustParams(C.Structure):
+    """struct NscMapRobustParams"""
+    _fields_ = [("kernel", C.c_int32), ("neighbours", C.c_int32), ("scale", C.c_double)]
+
+
 # include/nsc.h NSC_MAP_DTYPE_F32, NSC_MAP_DTYPE_F64, NSC_MAP_STATS and NSC_MAP_STAT_*: the name of each entry of `stats`
 MAP_DTYPE_F32, MAP_DTYPE_F64, MAP_STATS = 0, 1, 7
 MAP_STAT_NAMES = ("voxels_found", "voxels_written", "rows_used", "rows_not_finite", "rows_outside", "rows_without_pose",
@@ -138,6 +143,9 @@ MAP_MAX_VOXELS, MAP_MAX_ROWS = 1 << 36, 1 << 46     # include/nsc.h NSC_MAP_MAX_
 # include/nsc.h NSC_MAP_VOXEL_DOUBLES, NSC_MAP_REGISTER_BLOCKS, NSC_MAP_REGISTER_SYSTEM, NSC_MAP_REGISTER_MAX_SCANS
 MAP_VOXEL_DOUBLES, MAP_REGISTER_BLOCKS, MAP_REGISTER_SYSTEM, MAP_REGISTER_MAX_SCANS = 16, 64, 30, 65535
 MAP_INSERT_LAUNCHES = 8                 # include/nsc.h NSC_MAP_INSERT_LAUNCHES
+MAP_REGISTER_ROBUST_SYSTEM = 32         # include/nsc.h NSC_MAP_REGISTER_ROBUST_SYSTEM
+# include/nsc.h NSC_MAP_KERNEL_*: the pose graph's names and numbers
+MAP_KERNELS = {None: 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
 
 # include/nsc.h NSC_POSEGRAPH_MAX_EDGES, NSC_POSEGRAPH_MAX_LAUNCHES, NSC_POSEGRAPH_STATS
 POSEGRAPH_MAX_EDGES, POSEGRAPH_MAX_LAUNCHES, POSEGRAPH_STATS = 1073741823, 1000000, 10
@@ -278,6 +286,11 @@ SYMBOLS = {
     "nsc_map_register_workspace_bytes": (_sz, [_i32]),
     "nsc_map_register": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _i64, C.POINTER(MapParams),
                                    C.POINTER(MapRegisterParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nsc_map_robust_default_params": (None, [C.POINTER(MapRobustParams)]),
+    "nsc_map_register_robust_workspace_bytes": (_sz, [_i32]),
+    "nsc_map_register_robust": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _i64, C.POINTER(MapParams),
+                                          C.POINTER(MapRegisterParams), C.POINTER(MapRobustParams), _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

@@ -62,6 +62,7 @@
 
 #include "../../include/nsc.h"
 #include "nsc_fill.h"
+#include "nsc_robust.h"                 // Robust, robust_rho_w
 #include "nsc_util.h"
 
 namespace {
@@ -242,34 +243,13 @@ __device__ __forceinline__ double quad_form(const double W[36], const double r[6
     return f;
 }
 
-// rho(s) and w = rho'(s) of one edge (include/nsc.h has the table).  The edge is quadratic, rho = s and w = 1 exactly, for
-// kernel 0, without widths, for a width c that is not finite and positive or whose square is not, and for s <= 0 or NaN.
-struct Robust {
-    double rho, w;
-};
-
+// rho(s) and w = rho'(s) of one edge (nsc_robust.h; include/nsc.h has the table).  The edge is quadratic, rho = s and
+// w = 1 exactly, for kernel 0, without widths, for a width c that is not finite and positive or whose square is not, and
+// for s <= 0 or NaN.
 __device__ __forceinline__ Robust robust_kernel(int kernel, const double *__restrict__ edge_scale, long long e, double s)
 {
-    Robust out{s, 1.0};
-    if (kernel == NSC_POSEGRAPH_KERNEL_NONE || !edge_scale) return out;
-    const double c = edge_scale[e], c2 = c * c;
-    if (!(c > 0.0) || !(c2 > 0.0) || !isfinite(c2) || !(s > 0.0)) return out;
-    if (kernel == NSC_POSEGRAPH_KERNEL_HUBER) {
-        if (s > c2) {
-            const double q = sqrt(s);
-            out.rho = 2.0 * c * q - c2;
-            out.w = c / q;
-        }
-    } else if (kernel == NSC_POSEGRAPH_KERNEL_CAUCHY) {
-        const double u = s / c2;
-        out.rho = c2 * log1p(u);
-        out.w = 1.0 / (1.0 + u);
-    } else {                                 // Geman-McClure
-        const double t = c2 / (c2 + s);
-        out.rho = t * s;
-        out.w = t * t;
-    }
-    return out;
+    if (kernel == NSC_POSEGRAPH_KERNEL_NONE || !edge_scale) return Robust{s, 1.0};
+    return robust_rho_w(kernel, edge_scale[e], s);
 }
 
 // One edge at `poses`: its geometry, Omega as given, s = r^T Omega r, and rho(s) and w.  Every kernel that needs any of

@@ -20,12 +20,21 @@ Definition (the contract the two entry points and tests/map_localize_restatement
                  then, bit for bit, the map a build over all clouds would give.  Rows and clouds of an insertion are
                  numbered on from the cursor; poses and ``pose_ids`` are indexed within the call
 
+    robust       (nsc_map_register_robust; ``kernel``, ``robust_scale``, ``neighbours``) every pair (row, voxel) is weighted
+                 by w = rho'(s), s = d^T Omega_v d, with the pose graph's kernels and one width c in units of sqrt(chi^2):
+                 H = sum w J^T Omega J, g = sum w J^T Omega d, cost = sum rho(s), rmse = sqrt(sum w |d|^2 / sum w).  With
+                 ``neighbours=7`` a row pairs with its own voxel and the six face neighbours, in the fixed order
+                 (0, -x, +x, -y, +y, -z, +z); n_correspondences counts rows with at least one pair, n_pairs the pairs.
+                 Geman-McClure refines from a good start (clutter in front of walls); Cauchy with seven voxels widens the
+                 basin (starts a metre off at 0.5 m voxels).  Seven voxels without a kernel bias the result: a far voxel
+                 pulls at full weight
+
 Integer atomics and fixed-shape float64 sums only: two calls agree bit for bit and a scan's result does not depend on what
 else is in the batch.
 
-Not part of this module: source covariances (full VGICP), neighbour-voxel correspondences, robust weights, NDT's
-exponential score, removal or re-placing of clouds (first_row and the cloud range are minima and maxima: they do not
-subtract), growing the capacity of a kept map, unary edges in the pose graph.
+Not part of this module: source covariances (full VGICP), 27-voxel neighbourhoods, a width per scan, a step-acceptance
+test, NDT's exponential score, removal or re-placing of clouds (first_row and the cloud range are minima and maxima: they
+do not subtract), growing the capacity of a kept map, unary edges in the pose graph.
 """
 import ctypes as C
 
@@ -73,6 +82,12 @@ class MapLocalizer:
                                far], so that ``insert*`` and ``extend`` can add scans to the kept map.  The capacity does
                                not grow: with ``max_voxels=None`` it is the first build's row count, so a map that is
                                meant to grow needs an explicit ``max_voxels``
+    kernel            None     robust kernel of the registration: None (quadratic), "huber", "cauchy" or "geman_mcclure"
+    robust_scale      None     the kernel's width c, in units of sqrt(chi^2); needed with a kernel, refused without one
+    neighbours        1        voxels a row is paired with: 1 (its own) or 7 (and the six face neighbours)
+
+    With the defaults ``register*`` and ``extend`` call nsc_map_register; with a kernel or seven voxels they call
+    nsc_map_register_robust, and ``extend`` still gates on ``fitness``.
 
     After a build the instance keeps ``voxels`` (M,16), ``index`` (2M,2), ``keys`` (M,), ``info`` (M,4), ``stats`` (7,)
     as device tensors over the full capacity M and, after ``build``, ``build_prepared``, ``insert`` or
@@ -82,8 +97,20 @@ class MapLocalizer:
 
     def __init__(self, voxel_size: float = 1.0, origin=(0.0, 0.0, 0.0), max_voxels=None, min_points: int = 6,
                  eigen_ratio: float = 1e-2, sigma_floor: float = 1e-3, max_iteration: int = 30,
-                 relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, device="cuda", insertable: bool = False):
+                 relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, device="cuda", insertable: bool = False,
+                 kernel=None, robust_scale=None, neighbours: int = 1):
         self._grid = GlobalMap(voxel_size, origin, max_voxels, device)       # its refusals are this class's
+        if kernel not in _lib.MAP_KERNELS:
+            raise _lib.NscError(f"MapLocalizer: unknown kernel {kernel!r}")
+        if neighbours not in (1, 7):
+            raise _lib.NscError(f"MapLocalizer: neighbours is 1 or 7, got {neighbours!r}")
+        if kernel is None and robust_scale is not None:
+            raise _lib.NscError("MapLocalizer: robust_scale is the width of a kernel; give one")
+        if kernel is not None and not (robust_scale is not None and np.isfinite(robust_scale) and
+                                       float(robust_scale) > 0.0):
+            raise _lib.NscError(f"MapLocalizer: kernel {kernel!r} needs a finite positive robust_scale")
+        self.robust = _lib.MapRobustParams(kernel=_lib.MAP_KERNELS[kernel], neighbours=int(neighbours),
+                                           scale=0.0 if kernel is None else float(robust_scale))
         if int(min_points) < 1 or not 0.0 < float(eigen_ratio) <= 1.0 or \
                 not (np.isfinite(sigma_floor) and float(sigma_floor) > 0.0):
             raise _lib.NscError("MapLocalizer: min_points >= 1, eigen_ratio in (0, 1] and a finite positive sigma_floor")
@@ -291,7 +318,9 @@ class MapLocalizer:
         captured.  ``points`` (N,3|4) float32 or (N,3) float64 device tensor, ``offsets`` (S+1,) int64 device tensor,
         ``init_poses`` (S,4,4) float64 device tensor, scan to world.  Returns a dict of device tensors: transform (S,4,4),
         fitness, rmse, cost (S,), n_correspondences, iterations (S,) int64, information (S,6,6); with ``system0=True``
-        also system0 (S,30), the sums at ``init_poses`` (include/nsc.h).  More than ``_lib.MAP_REGISTER_MAX_SCANS`` scans
+        also system0 (S,30), the sums at ``init_poses`` (include/nsc.h).  With a kernel or seven voxels the dict also has
+        weight_sum (S,) float64 and n_pairs (S,) int64 (one conversion launch after the library's), and system0 is
+        (S,32): the 30 sums, then sum w and n_pairs.  More than ``_lib.MAP_REGISTER_MAX_SCANS`` scans
         go to the library in several calls, the outputs are those of one call."""
         if self.voxels is None:
             raise _lib.NscError("MapLocalizer.register: build a map first")
@@ -308,22 +337,32 @@ class MapLocalizer:
         T, fr, cost = torch.empty((S, 4, 4), **f64), torch.empty((S, 2), **f64), torch.empty((S,), **f64)
         ci = torch.empty((S, 2), dtype=torch.int64, device=dev)
         info = torch.empty((S, 6, 6), **f64)
-        sys0 = torch.empty((S, _lib.MAP_REGISTER_SYSTEM), **f64) if system0 else None
+        plain = self.robust.kernel == 0 and self.robust.neighbours == 1
+        width = _lib.MAP_REGISTER_SYSTEM if plain else _lib.MAP_REGISTER_ROBUST_SYSTEM
+        sys0 = torch.empty((S, width), **f64) if system0 else None
+        wp = None if plain else torch.empty((S, 2), **f64)
         L = _lib.lib()
         most = _lib.MAP_REGISTER_MAX_SCANS
-        ws = _workspace(L.nsc_map_register_workspace_bytes(min(S, most)), dev)
+        need = L.nsc_map_register_workspace_bytes if plain else L.nsc_map_register_robust_workspace_bytes
+        ws = _workspace(need(min(S, most)), dev)
         with torch.cuda.device(dev):
             for a in range(0, S, most):
                 b = min(a + most, S)
-                status = L.nsc_map_register(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off[a:]), b - a, N,
-                                            _lib.ptr(self.voxels), _lib.ptr(self.index), self.capacity,
-                                            C.byref(self.params), C.byref(self.reg), _lib.ptr(init[a:]), _lib.ptr(T[a:]),
-                                            _lib.ptr(fr[a:]), _lib.ptr(cost[a:]), _lib.ptr(ci[a:]), _lib.ptr(info[a:]),
-                                            None if sys0 is None else _lib.ptr(sys0[a:]), _lib.ptr(ws),
-                                            int(ws.numel()), _lib.stream_ptr(dev))
-                _lib.check(status, "nsc_map_register")
+                head = (_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off[a:]), b - a, N, _lib.ptr(self.voxels),
+                        _lib.ptr(self.index), self.capacity, C.byref(self.params), C.byref(self.reg))
+                outs = (_lib.ptr(init[a:]), _lib.ptr(T[a:]), _lib.ptr(fr[a:]), _lib.ptr(cost[a:]), _lib.ptr(ci[a:]),
+                        _lib.ptr(info[a:]), None if sys0 is None else _lib.ptr(sys0[a:]))
+                tail = (_lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+                if plain:
+                    _lib.check(L.nsc_map_register(*head, *outs, *tail), "nsc_map_register")
+                else:
+                    _lib.check(L.nsc_map_register_robust(*head, C.byref(self.robust), *outs, _lib.ptr(wp[a:]), *tail),
+                               "nsc_map_register_robust")
         out = dict(transform=T, fitness=fr[:, 0], rmse=fr[:, 1], cost=cost, n_correspondences=ci[:, 0],
                    iterations=ci[:, 1], information=info)
+        if wp is not None:
+            out["weight_sum"] = wp[:, 0]
+            out["n_pairs"] = wp[:, 1].to(torch.int64)
         if sys0 is not None:
             out["system0"] = sys0
         return out
