@@ -948,6 +948,52 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
  *   atomics only; no host synchronisation, no memset or memcpy nodes.  While a call runs, bits 61 and 62 of an index
  *   place word are in use; they are clear when it ends.
  *
+ * nsc_map_remove_dist and nsc_map_replace_dist (restated in tests/map_replace_restatement.py).  Rows taken out of a kept
+ *   map, and clouds moved from one pose to another, in work proportional to their rows.
+ * Matched removal.  A removal is matched when every row it is given was added earlier by a build or an insertion, with
+ *   the same bits of xyz and of the pose: the row then has the key, the position inside its voxel and the nine integers it
+ *   had then.  It finds its voxel by the build's probe (a lookup that claims nothing) and subtracts: -1 on the count, the
+ *   negated integers on the moments.
+ * Contract.  Let M be a kept map after any sequence of builds, insertions, matched removals and replacements, and B
+ *   nsc_map_build_dist over the rows that remain, in any cloud order, with the same grid, dist and max_voxels, while the
+ *   voxels found stay at most max_voxels in both.  Then
+ *   - for every key of B, M holds the key with a place, and info[place][0] (the count), moments[place] and the 16 doubles
+ *     of voxels[place] equal B's by bits;
+ *   - every other keyed slot of M is an emptied voxel: count 0, nine zero moments, a record of 16 zeros (written as
+ *     zeros: the record function is not evaluated for a count of 0), hence not usable.  It keeps its key, its slot and its
+ *     place; places are never reused or compacted.  A later insertion into it adds to the zeros and makes its record again;
+ *   - nsc_map_register and nsc_map_register_robust (every kernel, 1 and 7 voxels) against M give the bits they give
+ *     against B: an emptied voxel is found and skipped by its usable flag exactly where B's lookup finds nothing;
+ *   - info[:,1] is the row that made the voxel; info[:,2] and info[:,3] become a lower and an upper bound of the cloud
+ *     numbers present, no longer attained; keys and the order of places never change for voxels that exist.
+ * removed (NSC_MAP_REMOVE_STATS int64), written, not accumulated, by every call: rows removed, rows not finite, rows
+ *   outside the grid, rows without a pose, rows missing (their voxel is not in the index, or it has place ~0), voxels
+ *   touched, voxels emptied, voxels inconsistent.  In a replacement these are the removal half's: a voxel it emptied may
+ *   be filled again by the insertion half.
+ * Inconsistent voxels.  A touched voxel whose count ends below 0, or at 0 with a moment that is not 0, is inconsistent:
+ *   it gets the zero record and keeps its integers (so adding the rows again restores it), and it is not counted as
+ *   emptied.  The call writes nowhere but to the places the index names.  An unmatched removal that leaves a positive
+ *   count cannot be detected: the voxel then has the record of integers no set of rows gives.
+ * Kept stats.  stats[NSC_MAP_STAT_USED] goes down by the rows removed; a removal changes no other entry (found and
+ *   written keep counting emptied voxels).
+ * Replacement.  clouds, old_poses and new_poses (both (n_poses,4,4)) and one pose_ids: a cloud with an id is removed
+ *   under old_poses[id] and inserted under new_poses[id]; a cloud with id -1 (or past n_poses) is left alone.  The
+ *   insertion half is nsc_map_insert_dist's with two differences: rows and clouds are numbered from first_row and
+ *   first_cloud, so that a store's numbering survives, and no cursor is read or advanced; and what became of the call's rows
+ *   goes into placed (NSC_MAP_STATS int64 in the layout of stats: new voxels, written after the call, used, not finite,
+ *   outside, no pose, unplaced), of which only found, written, used and unplaced are folded into the kept stats, so that
+ *   leaving clouds out does not inflate the map's rows without pose.  New voxels take the places after
+ *   stats[NSC_MAP_STAT_WRITTEN] in ascending call row; overflow and the full-table rule are the insertion's.  With
+ *   first_row and first_cloud equal to the cursor a replacement leaves what nsc_map_remove_dist followed by
+ *   nsc_map_insert_dist leaves, bit for bit, apart from the cursor.
+ * Launches.  NSC_MAP_REMOVE_LAUNCHES kernels (clear the call's counters; rows: lookup, integer atomics, the list of
+ *   places reached; refresh: their records, the counters) and NSC_MAP_REPLACE_LAUNCHES (one clear for both halves, the
+ *   removal's rows and refresh, the insertion's seven passes).  No launch walks the slots or the records; the grids depend
+ *   on total_rows alone; integer atomics only, so two identical sequences of calls leave identical bits in every kept
+ *   tensor (the index as a mapping) and a cloud's effect does not depend on what else is in the call; no host
+ *   synchronisation, no memset or memcpy nodes.  Bits 61 and 62 of a place word may be in use during a call and are clear
+ *   at its end.
+ *
  * nsc_map_register.  n_scans scans packed as rows in the formats of nsc_map_build, offsets (n_scans+1) int64,
  *   init_transforms (n_scans,4,4) float64 row-major, scan to world.  The target is `voxels` and `index` of a
  *   nsc_map_build_dist call with the same max_voxels and grid (params).
@@ -995,6 +1041,17 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
  * ------------------------------------------------------------------------------------------ */
 #define NSC_MAP_VOXEL_DOUBLES       16
 #define NSC_MAP_INSERT_LAUNCHES     8       /* kernels of one nsc_map_insert_dist call */
+#define NSC_MAP_REMOVE_LAUNCHES     3       /* kernels of one nsc_map_remove_dist call */
+#define NSC_MAP_REPLACE_LAUNCHES    10      /* of one nsc_map_replace_dist call: one clear, 2 of the removal, 7 of the insertion */
+#define NSC_MAP_REMOVE_STATS            8   /* entries of `removed` */
+#define NSC_MAP_REMOVE_STAT_REMOVED     0   /* rows taken out of a voxel                             */
+#define NSC_MAP_REMOVE_STAT_NOT_FINITE  1   /* rows with a non-finite xyz or world coordinate        */
+#define NSC_MAP_REMOVE_STAT_OUTSIDE     2   /* rows outside the 2^21 voxels per axis                 */
+#define NSC_MAP_REMOVE_STAT_NO_POSE     3   /* rows of clouds without a pose (and rows of no cloud)  */
+#define NSC_MAP_REMOVE_STAT_MISSING     4   /* rows whose voxel is not in the index or has place ~0  */
+#define NSC_MAP_REMOVE_STAT_TOUCHED     5   /* voxels a row was taken out of                         */
+#define NSC_MAP_REMOVE_STAT_EMPTIED     6   /* of those: count 0 and nine zero moments afterwards    */
+#define NSC_MAP_REMOVE_STAT_INCONSISTENT 7  /* of those: count below 0, or 0 with a moment left      */
 #define NSC_MAP_REGISTER_BLOCKS     64      /* workgroups of 256 lanes per scan in linearize */
 #define NSC_MAP_REGISTER_SYSTEM     30
 #define NSC_MAP_REGISTER_MAX_SCANS  65535
@@ -1047,6 +1104,27 @@ int    nsc_map_insert_dist(const void *points, int32_t dtype, int32_t stride_flo
                            const int64_t *pose_ids, const NscMapParams *params, const NscMapDistParams *dist,
                            int64_t max_voxels, double *voxels, uint64_t *index, int64_t *info, int64_t *keys,
                            int64_t *moments, int64_t *stats, int64_t *cursor, void *ws, size_t ws_bytes, void *stream);
+
+/* Bytes of workspace for nsc_map_remove_dist (about 8 per row: a list entry) and for nsc_map_replace_dist (the sum of the
+ * insertion's and the removal's); nothing per voxel; monotone; 0 for a total_rows the call would refuse. */
+size_t nsc_map_remove_workspace_bytes(int64_t total_rows);
+size_t nsc_map_replace_workspace_bytes(int64_t total_rows);
+/* Refusals as nsc_map_build_dist's; NSC_EINVAL also for a null `moments` or `removed`; NSC_EWORKSPACE for a workspace that
+ * is missing or too small (one is needed even for no rows): all before anything is launched. */
+int    nsc_map_remove_dist(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets,
+                           int32_t n_clouds, int64_t total_rows, const double *poses, int32_t n_poses,
+                           const int64_t *pose_ids, const NscMapParams *params, const NscMapDistParams *dist,
+                           int64_t max_voxels, double *voxels, uint64_t *index, int64_t *info, int64_t *keys,
+                           int64_t *moments, int64_t *stats, int64_t *removed, void *ws, size_t ws_bytes, void *stream);
+/* Refusals as nsc_map_remove_dist's; NSC_EINVAL also for a null new_poses with n_poses > 0, a null `placed` and a
+ * negative first_row or first_cloud. */
+int    nsc_map_replace_dist(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets,
+                            int32_t n_clouds, int64_t total_rows, const double *old_poses, const double *new_poses,
+                            int32_t n_poses, const int64_t *pose_ids, const NscMapParams *params,
+                            const NscMapDistParams *dist, int64_t max_voxels, double *voxels, uint64_t *index,
+                            int64_t *info, int64_t *keys, int64_t *moments, int64_t *stats, int64_t first_row,
+                            int64_t first_cloud, int64_t *removed, int64_t *placed, void *ws, size_t ws_bytes,
+                            void *stream);
 
 void   nsc_map_register_default_params(NscMapRegisterParams *p);
 /* Bytes of workspace for nsc_map_register: the slabs and the state of n_scans scans; 0 for a negative n_scans. */

@@ -143,6 +143,11 @@ MAP_MAX_VOXELS, MAP_MAX_ROWS = 1 << 36, 1 << 46     # include/nsc.h NSC_MAP_MAX_
 # include/nsc.h NSC_MAP_VOXEL_DOUBLES, NSC_MAP_REGISTER_BLOCKS, NSC_MAP_REGISTER_SYSTEM, NSC_MAP_REGISTER_MAX_SCANS
 MAP_VOXEL_DOUBLES, MAP_REGISTER_BLOCKS, MAP_REGISTER_SYSTEM, MAP_REGISTER_MAX_SCANS = 16, 64, 30, 65535
 MAP_INSERT_LAUNCHES = 8                 # include/nsc.h NSC_MAP_INSERT_LAUNCHES
+MAP_REMOVE_LAUNCHES, MAP_REPLACE_LAUNCHES = 3, 10      # include/nsc.h NSC_MAP_REMOVE_LAUNCHES, NSC_MAP_REPLACE_LAUNCHES
+# include/nsc.h NSC_MAP_REMOVE_STATS and NSC_MAP_REMOVE_STAT_*: the name of each entry of `removed`
+MAP_REMOVE_STATS = 8
+MAP_REMOVE_STAT_NAMES = ("rows_removed", "removed_not_finite", "removed_outside", "removed_without_pose", "rows_missing",
+                         "voxels_touched", "voxels_emptied", "voxels_inconsistent")
 MAP_REGISTER_ROBUST_SYSTEM = 32         # include/nsc.h NSC_MAP_REGISTER_ROBUST_SYSTEM
 # include/nsc.h NSC_MAP_KERNEL_*: the pose graph's names and numbers
 MAP_KERNELS = {None: 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
@@ -282,6 +287,13 @@ SYMBOLS = {
     "nsc_map_insert_workspace_bytes": (_sz, [_i64]),
     "nsc_map_insert_dist": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, C.POINTER(MapParams),
                                       C.POINTER(MapDistParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nsc_map_remove_workspace_bytes": (_sz, [_i64]),
+    "nsc_map_replace_workspace_bytes": (_sz, [_i64]),
+    "nsc_map_remove_dist": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, C.POINTER(MapParams),
+                                      C.POINTER(MapDistParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nsc_map_replace_dist": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _vp, C.POINTER(MapParams),
+                                       C.POINTER(MapDistParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
+                                       _vp, _sz, _vp]),
     "nsc_map_register_default_params": (None, [C.POINTER(MapRegisterParams)]),
     "nsc_map_register_workspace_bytes": (_sz, [_i32]),
     "nsc_map_register": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _i64, C.POINTER(MapParams),

@@ -25,7 +25,8 @@
 // usable flag) and writes the index (key + 1, place) at the table's own slot positions, for every slot.
 //
 // nsc_map_insert_dist adds rows to the kept tensors of such a build, with the result of a build over all rows; its eight
-// launches are described where they stand, below the builds.
+// launches are described where they stand, below the builds.  nsc_map_remove_dist takes rows out again and
+// nsc_map_replace_dist moves clouds from one pose to another; their launches stand below the insertion's.
 //
 // No float atomics anywhere: results are bitwise reproducible and do not depend on arrival order.
 #include <hip/hip_runtime.h>
@@ -185,7 +186,9 @@ struct RowCounters {                    // a lane's counts of what became of its
     {
         for (int k = 0; k < N_COUNTERS; ++k) n[k] += kind == k;
     }
-    __device__ __forceinline__ void add_to(long long *stats) const
+    __device__ __forceinline__ void add_to(long long *stats) const { add_from(stats + NSC_MAP_STAT_USED); }
+    // first[k] += the workgroup's count of kind k
+    __device__ __forceinline__ void add_from(long long *first) const
     {
         __shared__ long long red[N_COUNTERS][MAP_THREADS / 64];
         const int tid = threadIdx.x;
@@ -197,7 +200,7 @@ struct RowCounters {                    // a lane's counts of what became of its
         if (tid < N_COUNTERS) {
             long long v = 0;
             for (int w = 0; w < MAP_THREADS / 64; ++w) v += red[tid][w];
-            if (v) atomicAdd(reinterpret_cast<u64 *>(&stats[NSC_MAP_STAT_USED + tid]), (u64)v);
+            if (v) atomicAdd(reinterpret_cast<u64 *>(&first[tid]), (u64)v);
         }
     }
 };
@@ -529,6 +532,7 @@ enum { CALL_FOUND = NSC_MAP_STAT_FOUND, CALL_WRITTEN = NSC_MAP_STAT_WRITTEN, CAL
 struct KeptMap {
     double *voxels; u64 *index; long long *info, *keys, *moments, *stats, *cursor;
     long long max_voxels;
+    long long *counters;                // where the claim pass counts its rows: stats, or `placed` of a replacement
     // the outputs were full before this call; the stats' voxel counts stay as they were until the refresh pass
     __device__ bool full() const { return stats[NSC_MAP_STAT_WRITTEN] >= max_voxels; }
 };
@@ -586,7 +590,7 @@ __global__ __launch_bounds__(MAP_THREADS) void ins_claim_kernel(InsertRows<T> in
             if ((there & PLACE_NEW) && there > mine) atomicMin(&m.index[2 * h + 1], mine);
         }
     }
-    cnt.add_to(m.stats);
+    cnt.add_to(m.counters);
 }
 
 __global__ __launch_bounds__(MAP_THREADS) void ins_mark_kernel(KeptMap m, const long long *slot, long long total, u64 *bits)
@@ -659,34 +663,59 @@ __global__ __launch_bounds__(MAP_THREADS) void ins_accumulate_kernel(InsertRows<
     }
 }
 
+enum { PLACE_RECORD, PLACE_EMPTIED, PLACE_INCONSISTENT };
+
+// The refresh of one touched slot, of an insertion and of a removal: PLACE_TOUCHED off, and the record of what the place
+// now holds.  A positive count gives dist_record's record.  A count of 0 with nine zero moments is an emptied voxel, any
+// other count below 1 an inconsistent one (an unmatched removal): both get the zero record, written as zeros, and keep
+// their integers
+__device__ __forceinline__ int refresh_place(const KeptMap &m, long long h, const DistRule &rule)
+{
+    const long long pos = (long long)(m.index[2 * h + 1] & ~PLACE_TOUCHED);
+    m.index[2 * h + 1] = (u64)pos;
+    const long long count = m.info[4 * pos], *mo = m.moments + 9 * pos;
+    double rec[16];
+    int kind = PLACE_RECORD;
+    if (count > 0) {
+        dist_record((u64)count, mo, mo + 3, m.index[2 * h] - 1, rule, rec);
+    } else {
+        bool zero = count == 0;
+        for (int t = 0; t < 9; ++t) zero = zero && mo[t] == 0;
+        kind = zero ? PLACE_EMPTIED : PLACE_INCONSISTENT;
+        for (int e = 0; e < 16; ++e) rec[e] = 0.0;
+    }
+    for (int e = 0; e < 16; ++e) m.voxels[16 * pos + e] = rec[e];
+    return kind;
+}
+
 __global__ __launch_bounds__(MAP_THREADS) void ins_refresh_kernel(KeptMap m, const long long *touched, const long long *call,
                                                                   DistRule rule, long long total, long long n_clouds)
 {
     const long long n = call[CALL_TOUCHED];
-    for (long long i = (long long)blockIdx.x * MAP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * MAP_THREADS) {
-        const long long h = touched[i];
-        const long long pos = (long long)(m.index[2 * h + 1] & ~PLACE_TOUCHED);
-        m.index[2 * h + 1] = (u64)pos;
-        double rec[16];
-        dist_record((u64)m.info[4 * pos], m.moments + 9 * pos, m.moments + 9 * pos + 3, m.index[2 * h] - 1, rule, rec);
-        for (int e = 0; e < 16; ++e) m.voxels[16 * pos + e] = rec[e];
-    }
+    for (long long i = (long long)blockIdx.x * MAP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * MAP_THREADS)
+        refresh_place(m, touched[i], rule);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const long long found = m.stats[NSC_MAP_STAT_FOUND] + call[CALL_FOUND];
         m.stats[NSC_MAP_STAT_FOUND] = found;
         m.stats[NSC_MAP_STAT_WRITTEN] = min(found, m.max_voxels);
+        if (m.counters != m.stats) {
+            // a replacement: what became of the call's rows stays in `placed`; the map takes the rows it holds or lacks
+            m.counters[NSC_MAP_STAT_FOUND] = call[CALL_FOUND];
+            m.counters[NSC_MAP_STAT_WRITTEN] = min(found, m.max_voxels);
+            m.stats[NSC_MAP_STAT_USED] += m.counters[NSC_MAP_STAT_USED];
+            m.stats[NSC_MAP_STAT_UNPLACED] += m.counters[NSC_MAP_STAT_UNPLACED];
+        }
         m.cursor[0] += total;
         m.cursor[1] += n_clouds;
     }
 }
 
+// the insertion's launches after its clear
 template <class T>
-void launch_insert_rows(const InsertRows<T> &in, const KeptMap &m, const DistRule &rule, const InsertRegions &r, hipStream_t s)
+void launch_insert_passes(const InsertRows<T> &in, const KeptMap &m, const DistRule &rule, const InsertRegions &r, hipStream_t s)
 {
     const dim3 threads(MAP_THREADS), sweeps(blocks_for(in.total, INSERT_ROWS, NSC_MAP_INSERT_BLOCKS)),
         per_row(blocks_for(in.total, MAP_THREADS, MAP_SLOT_BLOCKS));
-    hipLaunchKernelGGL(map_clear_kernel, dim3(blocks_for(r.n_words, MAP_THREADS, MAP_SLOT_BLOCKS)), threads, 0, s,
-                       static_cast<u64 *>(nullptr), 0LL, 1, r.bits, r.n_words, r.call);
     hipLaunchKernelGGL(ins_claim_kernel<T>, sweeps, threads, 0, s, in, m, r.bits, r.slot);
     hipLaunchKernelGGL(ins_mark_kernel, per_row, threads, 0, s, m, r.slot, in.total, r.bits);
     hipLaunchKernelGGL(map_count_kernel, dim3(blocks_for(r.n_tiles, MAP_THREADS / 64, MAP_SLOT_BLOCKS)), threads, 0, s,
@@ -698,6 +727,211 @@ void launch_insert_rows(const InsertRows<T> &in, const KeptMap &m, const DistRul
     hipLaunchKernelGGL(ins_refresh_kernel, per_row, threads, 0, s, m, r.touched, r.call, rule, in.total,
                        (long long)in.n_clouds);
 }
+
+template <class T>
+void launch_insert_rows(const InsertRows<T> &in, const KeptMap &m, const DistRule &rule, const InsertRegions &r, hipStream_t s)
+{
+    hipLaunchKernelGGL(map_clear_kernel, dim3(blocks_for(r.n_words, MAP_THREADS, MAP_SLOT_BLOCKS)), dim3(MAP_THREADS), 0, s,
+                       static_cast<u64 *>(nullptr), 0LL, 1, r.bits, r.n_words, r.call);
+    launch_insert_passes(in, m, rule, r, s);
+}
+
+// ---- nsc_map_remove_dist and nsc_map_replace_dist: rows taken out of a kept map, and clouds moved to other poses ---------
+// A row finds the voxel it once went into by the build's probe, and what it added then is subtracted as integers: the
+// record of a voxel that keeps rows is dist_record of what is left, as a build over the remaining rows gives it.  Nothing
+// walks the slots or the records here either.
+//
+// Removal (NSC_MAP_REMOVE_LAUNCHES = 3; the grids depend on total_rows alone):
+//   clear    the call's counters and `removed`
+//   rows     per row: locate_row, a lookup of the kept index that claims nothing; a row whose key is absent or has place
+//            ~0 is missing.  Else -1 on the count and the negated integers of row_moments on the moments; the first row to
+//            reach a place in this call (PLACE_TOUCHED) appends the slot to the touched list
+//   refresh  per touched slot: refresh_place; emptied and inconsistent voxels counted; one thread takes the removed rows
+//            from the kept stats
+// Replacement (NSC_MAP_REPLACE_LAUNCHES = 10): one clear for both halves, which also sets the workspace's own cursor to the
+// caller's bases; rows and refresh of the removal under the old poses; the insertion's seven passes under the new poses,
+// numbering from that cursor and counting into `placed`.
+constexpr int REM_TOUCHED = NSC_MAP_REMOVE_STAT_TOUCHED, REM_EMPTIED = NSC_MAP_REMOVE_STAT_EMPTIED,
+              REM_INCONSISTENT = NSC_MAP_REMOVE_STAT_INCONSISTENT;
+static_assert(NSC_MAP_REMOVE_STAT_REMOVED == C_USED && NSC_MAP_REMOVE_STAT_NOT_FINITE == C_NOT_FINITE &&
+                  NSC_MAP_REMOVE_STAT_OUTSIDE == C_OUTSIDE && NSC_MAP_REMOVE_STAT_NO_POSE == C_NO_POSE &&
+                  NSC_MAP_REMOVE_STAT_MISSING == C_UNPLACED && NSC_MAP_REMOVE_STATS <= MAP_THREADS,
+              "the row pass's counters are the first five entries of `removed`, which the clear's first threads zero");
+
+struct RemoveRegions {
+    long long *touched, *call, *cursor;
+    size_t total;
+};
+
+// `with_cursor`: a replacement, whose insertion half numbers from two words of the workspace
+RemoveRegions remove_regions(void *ws, size_t at, long long total_rows, bool with_cursor)
+{
+    Carver c = {reinterpret_cast<uintptr_t>(ws), at};
+    RemoveRegions r;
+    r.touched = c.take<long long>(total_rows);
+    r.call = c.take<long long>(CALL_WORDS);
+    r.cursor = with_cursor ? c.take<long long>(2) : nullptr;
+    r.total = c.o;
+    return r;
+}
+
+// the slot of `key` in the kept index, or -1: the build's probe sequence, read only
+__device__ __forceinline__ long long find_slot(const u64 *index, long long cap, u64 key)
+{
+    long long h = cap > 0 ? (long long)(mix64(key) % (u64)cap) : 0;
+    for (long long probe = 0; probe < cap; ++probe) {
+        const u64 e = index[2 * h];
+        if (e == key + 1) return h;
+        if (e == 0) return -1;
+        h = next_slot(h, cap);
+    }
+    return -1;
+}
+
+// bits, ins_call, placed and cursor may be null (a removal alone)
+__global__ __launch_bounds__(MAP_THREADS) void call_clear_kernel(u64 *bits, long long n_words, long long *ins_call,
+                                                                 long long *rem_call, long long *removed, long long *placed,
+                                                                 long long *cursor, long long first_row, long long first_cloud)
+{
+    const long long i0 = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
+    for (long long i = i0; i < n_words; i += (long long)gridDim.x * MAP_THREADS) bits[i] = 0ULL;
+    if (i0 < CALL_WORDS) {
+        rem_call[i0] = 0;
+        if (ins_call) ins_call[i0] = 0;
+        if (placed) placed[i0] = 0;
+    }
+    if (i0 < NSC_MAP_REMOVE_STATS) removed[i0] = 0;
+    if (i0 == 0 && cursor) { cursor[0] = first_row; cursor[1] = first_cloud; }
+}
+
+template <class T>
+__global__ __launch_bounds__(MAP_THREADS) void rem_rows_kernel(InsertRows<T> in, KeptMap m, long long *touched, long long *call,
+                                                               long long *removed)
+{
+    const int tid = threadIdx.x;
+    const long long cap = 2 * m.max_voxels;
+    RowCounters cnt;
+    const long long n_sweeps = (in.total + INSERT_ROWS - 1) / INSERT_ROWS;
+    for (long long sweep = blockIdx.x; sweep < n_sweeps; sweep += gridDim.x) {
+        CloudSpan span;
+        for (int k = 0; k < INSERT_ROWS / MAP_THREADS; ++k) {
+            const long long row = sweep * INSERT_ROWS + (long long)k * MAP_THREADS + tid;
+            if (row >= in.total) break;
+            double w[3], u[3];
+            u64 key;
+            int kind = locate_row(in, row, span, w, u, key);
+            long long pos = -1;
+            if (kind == C_USED) {
+                const long long h = find_slot(m.index, cap, key);
+                u64 there = h < 0 ? ~0ULL : peek(&m.index[2 * h + 1]);
+                // ~0 has PLACE_NEW set: a voxel past the outputs holds no sums to take the row from
+                if (!(there & PLACE_NEW) && (long long)(there & ~PLACE_TOUCHED) < m.max_voxels) {
+                    pos = (long long)(there & ~PLACE_TOUCHED);
+                    if (!(there & PLACE_TOUCHED)) {
+                        there = atomicOr(&m.index[2 * h + 1], PLACE_TOUCHED);
+                        if (!(there & PLACE_TOUCHED))
+                            touched[atomicAdd(reinterpret_cast<u64 *>(&call[CALL_TOUCHED]), 1ULL)] = h;
+                    }
+                } else {
+                    kind = C_UNPLACED;                                  // counted as missing
+                }
+            }
+            cnt.count(kind);
+            if (kind != C_USED) continue;
+            atomicAdd(reinterpret_cast<u64 *>(m.info + 4 * pos), ~0ULL);              // count - 1
+            long long *mo = m.moments + 9 * pos;
+            row_moments(u, [mo](int t, long long v) { atomicAdd(reinterpret_cast<u64 *>(mo + t), (u64)(-v)); });
+        }
+    }
+    cnt.add_from(removed);
+}
+
+__global__ __launch_bounds__(MAP_THREADS) void rem_refresh_kernel(KeptMap m, const long long *touched, const long long *call,
+                                                                  DistRule rule, long long *removed)
+{
+    const long long n = call[CALL_TOUCHED];
+    long long emptied = 0, inconsistent = 0;
+    for (long long i = (long long)blockIdx.x * MAP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * MAP_THREADS) {
+        const int kind = refresh_place(m, touched[i], rule);
+        emptied += kind == PLACE_EMPTIED;
+        inconsistent += kind == PLACE_INCONSISTENT;
+    }
+    emptied = nsc_wave_sum(emptied);
+    inconsistent = nsc_wave_sum(inconsistent);
+    if ((threadIdx.x & 63) == 0) {
+        if (emptied) atomicAdd(reinterpret_cast<u64 *>(&removed[REM_EMPTIED]), (u64)emptied);
+        if (inconsistent) atomicAdd(reinterpret_cast<u64 *>(&removed[REM_INCONSISTENT]), (u64)inconsistent);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        removed[REM_TOUCHED] = n;
+        m.stats[NSC_MAP_STAT_USED] -= removed[NSC_MAP_REMOVE_STAT_REMOVED];       // final: the row pass has ended
+    }
+}
+
+// the removal's launches after the clear
+template <class T>
+void launch_remove_passes(const InsertRows<T> &in, const KeptMap &m, const DistRule &rule, const RemoveRegions &r,
+                          long long *removed, hipStream_t s)
+{
+    const dim3 threads(MAP_THREADS);
+    hipLaunchKernelGGL(rem_rows_kernel<T>, dim3(blocks_for(in.total, INSERT_ROWS, NSC_MAP_INSERT_BLOCKS)), threads, 0, s, in, m,
+                       r.touched, r.call, removed);
+    hipLaunchKernelGGL(rem_refresh_kernel, dim3(blocks_for(in.total, MAP_THREADS, MAP_SLOT_BLOCKS)), threads, 0, s, m,
+                       r.touched, r.call, rule, removed);
+}
+
+template <class T>
+void launch_remove_rows(const InsertRows<T> &in, const KeptMap &m, const DistRule &rule, const RemoveRegions &r,
+                        long long *removed, hipStream_t s)
+{
+    hipLaunchKernelGGL(call_clear_kernel, dim3(1), dim3(MAP_THREADS), 0, s, static_cast<u64 *>(nullptr), 0LL,
+                       static_cast<long long *>(nullptr), r.call, removed, static_cast<long long *>(nullptr),
+                       static_cast<long long *>(nullptr), 0LL, 0LL);
+    launch_remove_passes(in, m, rule, r, removed, s);
+}
+
+template <class T>
+void launch_replace_rows(const InsertRows<T> &old_rows, const double *new_poses, KeptMap m, const DistRule &rule,
+                         const InsertRegions &ins, const RemoveRegions &rem, long long first_row, long long first_cloud,
+                         long long *removed, long long *placed, hipStream_t s)
+{
+    hipLaunchKernelGGL(call_clear_kernel, dim3(blocks_for(ins.n_words, MAP_THREADS, MAP_SLOT_BLOCKS)), dim3(MAP_THREADS), 0, s,
+                       ins.bits, ins.n_words, ins.call, rem.call, removed, placed, rem.cursor, first_row, first_cloud);
+    launch_remove_passes(old_rows, m, rule, rem, removed, s);
+    InsertRows<T> new_rows = old_rows;
+    new_rows.poses = new_poses;
+    m.cursor = rem.cursor;
+    m.counters = placed;
+    launch_insert_passes(new_rows, m, rule, ins, s);
+}
+
+// what the three calls on a kept map take alike
+struct KeptArgs {
+    const void *points; int32_t dtype, stride_floats; const int64_t *offsets; int32_t n_clouds; int64_t total_rows;
+    const double *poses; int32_t n_poses; const int64_t *pose_ids; const NscMapParams *params; const NscMapDistParams *dist;
+    int64_t max_voxels; double *voxels; uint64_t *index; int64_t *info, *keys, *moments, *stats;
+    // NSC_OK, or the refusal of nsc_map_build_dist and of a missing `moments`
+    int check() const
+    {
+        if (const int st = check_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, params,
+                                       max_voxels, voxels && index && info && keys, stats))
+            return st;
+        return dist_ok(dist) && moments ? NSC_OK : NSC_EINVAL;
+    }
+    KeptMap map(int64_t *cursor) const
+    {
+        return KeptMap{voxels, reinterpret_cast<u64 *>(index), reinterpret_cast<long long *>(info),
+                       reinterpret_cast<long long *>(keys), reinterpret_cast<long long *>(moments),
+                       reinterpret_cast<long long *>(stats), reinterpret_cast<long long *>(cursor), (long long)max_voxels,
+                       reinterpret_cast<long long *>(stats)};
+    }
+    template <class T> InsertRows<T> rows() const
+    {
+        return InsertRows<T>{static_cast<const T *>(points), stride_floats, reinterpret_cast<const long long *>(offsets),
+                             n_clouds, (long long)total_rows, poses, n_poses, reinterpret_cast<const long long *>(pose_ids),
+                             MapGrid{params->voxel_size, {params->origin[0], params->origin[1], params->origin[2]}}};
+    }
+};
 
 }  // namespace
 
@@ -772,26 +1006,75 @@ int nsc_map_insert_dist(const void *points, int32_t dtype, int32_t stride_floats
                         uint64_t *index, int64_t *info, int64_t *keys, int64_t *moments, int64_t *stats, int64_t *cursor,
                         void *ws, size_t ws_bytes, void *stream)
 {
-    if (const int st = check_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, params,
-                                   max_voxels, voxels && index && info && keys, stats))
-        return st;
-    if (!dist_ok(dist) || !moments || !cursor) return NSC_EINVAL;
+    const KeptArgs a{points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params, dist,
+                     max_voxels, voxels, index, info, keys, moments, stats};
+    if (const int st = a.check()) return st;
+    if (!cursor) return NSC_EINVAL;
     const InsertRegions r = insert_regions(ws, total_rows);
     if (!ws || ws_bytes < r.total) return NSC_EWORKSPACE;
-    const KeptMap m{voxels, reinterpret_cast<u64 *>(index), reinterpret_cast<long long *>(info),
-                    reinterpret_cast<long long *>(keys), reinterpret_cast<long long *>(moments),
-                    reinterpret_cast<long long *>(stats), reinterpret_cast<long long *>(cursor), (long long)max_voxels};
-    const MapGrid g{params->voxel_size, {params->origin[0], params->origin[1], params->origin[2]}};
-    const long long *off = reinterpret_cast<const long long *>(offsets), *ids = reinterpret_cast<const long long *>(pose_ids);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == NSC_MAP_DTYPE_F32)
-        launch_insert_rows(InsertRows<float>{static_cast<const float *>(points), stride_floats, off, n_clouds,
-                                             (long long)total_rows, poses, n_poses, ids, g},
-                           m, dist_rule(params, dist), r, s);
+        launch_insert_rows(a.rows<float>(), a.map(cursor), dist_rule(params, dist), r, s);
     else
-        launch_insert_rows(InsertRows<double>{static_cast<const double *>(points), stride_floats, off, n_clouds,
-                                              (long long)total_rows, poses, n_poses, ids, g},
-                           m, dist_rule(params, dist), r, s);
+        launch_insert_rows(a.rows<double>(), a.map(cursor), dist_rule(params, dist), r, s);
+    return launch_status();
+}
+
+size_t nsc_map_remove_workspace_bytes(int64_t total_rows)
+{
+    if (total_rows < 0 || total_rows > NSC_MAP_MAX_ROWS) return 0;
+    return remove_regions(nullptr, 0, total_rows, false).total;
+}
+
+size_t nsc_map_replace_workspace_bytes(int64_t total_rows)
+{
+    if (total_rows < 0 || total_rows > NSC_MAP_MAX_ROWS) return 0;
+    return remove_regions(nullptr, insert_regions(nullptr, total_rows).total, total_rows, true).total;
+}
+
+int nsc_map_remove_dist(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_clouds,
+                        int64_t total_rows, const double *poses, int32_t n_poses, const int64_t *pose_ids,
+                        const NscMapParams *params, const NscMapDistParams *dist, int64_t max_voxels, double *voxels,
+                        uint64_t *index, int64_t *info, int64_t *keys, int64_t *moments, int64_t *stats, int64_t *removed,
+                        void *ws, size_t ws_bytes, void *stream)
+{
+    const KeptArgs a{points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params, dist,
+                     max_voxels, voxels, index, info, keys, moments, stats};
+    if (const int st = a.check()) return st;
+    if (!removed) return NSC_EINVAL;
+    const RemoveRegions r = remove_regions(ws, 0, total_rows, false);
+    if (!ws || ws_bytes < r.total) return NSC_EWORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    long long *rem = reinterpret_cast<long long *>(removed);
+    if (dtype == NSC_MAP_DTYPE_F32)
+        launch_remove_rows(a.rows<float>(), a.map(nullptr), dist_rule(params, dist), r, rem, s);
+    else
+        launch_remove_rows(a.rows<double>(), a.map(nullptr), dist_rule(params, dist), r, rem, s);
+    return launch_status();
+}
+
+int nsc_map_replace_dist(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_clouds,
+                         int64_t total_rows, const double *old_poses, const double *new_poses, int32_t n_poses,
+                         const int64_t *pose_ids, const NscMapParams *params, const NscMapDistParams *dist,
+                         int64_t max_voxels, double *voxels, uint64_t *index, int64_t *info, int64_t *keys, int64_t *moments,
+                         int64_t *stats, int64_t first_row, int64_t first_cloud, int64_t *removed, int64_t *placed, void *ws,
+                         size_t ws_bytes, void *stream)
+{
+    const KeptArgs a{points, dtype, stride_floats, offsets, n_clouds, total_rows, old_poses, n_poses, pose_ids, params, dist,
+                     max_voxels, voxels, index, info, keys, moments, stats};
+    if (const int st = a.check()) return st;
+    if ((n_poses > 0 && !new_poses) || !removed || !placed || first_row < 0 || first_cloud < 0) return NSC_EINVAL;
+    const InsertRegions ins = insert_regions(ws, total_rows);
+    const RemoveRegions rem = remove_regions(ws, ins.total, total_rows, true);
+    if (!ws || ws_bytes < rem.total) return NSC_EWORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    long long *rm = reinterpret_cast<long long *>(removed), *pl = reinterpret_cast<long long *>(placed);
+    if (dtype == NSC_MAP_DTYPE_F32)
+        launch_replace_rows(a.rows<float>(), new_poses, a.map(nullptr), dist_rule(params, dist), ins, rem,
+                            (long long)first_row, (long long)first_cloud, rm, pl, s);
+    else
+        launch_replace_rows(a.rows<double>(), new_poses, a.map(nullptr), dist_rule(params, dist), ins, rem,
+                            (long long)first_row, (long long)first_cloud, rm, pl, s);
     return launch_status();
 }
 

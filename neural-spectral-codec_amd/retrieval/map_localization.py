@@ -19,6 +19,20 @@ Definition (the contract the two entry points and tests/map_localize_restatement
                  so far]; new clouds are added to the kept tensors in work proportional to their rows, and the map is
                  then, bit for bit, the map a build over all clouds would give.  Rows and clouds of an insertion are
                  numbered on from the cursor; poses and ``pose_ids`` are indexed within the call
+    removal      (nsc_map_remove_dist) a removal is matched when every row it is given was added earlier with the same
+                 bits of xyz and of its pose.  The row finds its voxel by the build's probe and its nine integers and its
+                 count are subtracted, in work proportional to the rows.  After any sequence of builds, insertions,
+                 matched removals and replacements the map holds, for every voxel of a build over the rows that remain,
+                 that build's count, moments and record by bits, and ``register`` gives the bits it gives against that
+                 build.  Every other keyed voxel is emptied: count 0, zero moments, a record of 16 zeros, not usable; it
+                 keeps its key and its place, and a later insertion fills it again.  first_row stays the row that made the
+                 voxel, first_cloud and last_cloud become bounds; ``rows_used`` goes down by the rows removed.  A voxel
+                 whose count ends below 0, or at 0 with a moment left, is inconsistent (an unmatched removal): it gets
+                 the zero record and is counted in ``removed``
+    replacement  (nsc_map_replace_dist) clouds removed under ``old_poses`` and inserted under ``new_poses`` in one call;
+                 rows and clouds are numbered from ``first_row`` and ``first_cloud``, the cursor stays as it is, and what
+                 became of the rows goes into ``placed``.  ``update_prepared`` is the call to make after
+                 ``PoseGraphOptimizer.optimize``: it chooses the clouds whose poses moved, on the device
 
     robust       (nsc_map_register_robust; ``kernel``, ``robust_scale``, ``neighbours``) every pair (row, voxel) is weighted
                  by w = rho'(s), s = d^T Omega_v d, with the pose graph's kernels and one width c in units of sqrt(chi^2):
@@ -33,8 +47,8 @@ Integer atomics and fixed-shape float64 sums only: two calls agree bit for bit a
 else is in the batch.
 
 Not part of this module: source covariances (full VGICP), 27-voxel neighbourhoods, a width per scan, a step-acceptance
-test, NDT's exponential score, removal or re-placing of clouds (first_row and the cloud range are minima and maxima: they
-do not subtract), growing the capacity of a kept map, unary edges in the pose graph.
+test, NDT's exponential score, reuse or compaction of emptied places, detection of an unmatched removal that leaves a
+positive count, growing the capacity of a kept map, unary edges in the pose graph.
 """
 import ctypes as C
 
@@ -79,7 +93,8 @@ class MapLocalizer:
     relative_rmse     1e-6
     device            'cuda'   there is no CPU fallback
     insertable        False    every build keeps ``moments`` (M,9) and ``cursor`` (2,) int64 = [rows, clouds taken so
-                               far], so that ``insert*`` and ``extend`` can add scans to the kept map.  The capacity does
+                               far], so that ``insert*`` and ``extend`` can add scans to the kept map, and ``remove*``,
+                               ``replace*`` and ``update_prepared`` take clouds out or move them.  The capacity does
                                not grow: with ``max_voxels=None`` it is the first build's row count, so a map that is
                                meant to grow needs an explicit ``max_voxels``
     kernel            None     robust kernel of the registration: None (quadratic), "huber", "cauchy" or "geman_mcclure"
@@ -272,6 +287,165 @@ class MapLocalizer:
         scan = torch.arange(S, dtype=torch.int64, device=dev)
         ids = torch.where(out["fitness"] >= float(min_fitness), scan, -1)         # four launches: arange, >=, the -1 (a fill), where
         self.insert_device(pts, off, out["transform"], ids)
+        return out
+
+    # ---- removal and re-placing --------------------------------------------------------------------------------------
+
+    def remove_device(self, points, offsets, poses, pose_ids=None):
+        """Take packed clouds out of the kept map (nsc_map_remove_dist), on the device and without a synchronisation:
+        with device ``pose_ids`` (or none) a call can be captured.  Arguments as ``insert_device``; the removal is matched
+        when every row was added earlier with the same bits of xyz and of its pose, and the map is then, voxel by voxel,
+        the build over the rows that remain (include/nsc.h).  Returns the kept tensors and ``removed`` (8,) int64
+        (``_lib.MAP_REMOVE_STAT_NAMES``); nothing is read back and ``complete`` is None."""
+        self._insertable_map("remove_device")
+        dev = self.voxels.device
+        if points.device != dev:
+            raise _lib.NscError(f"the clouds must be on the map's device ({dev})")
+        pts, off, B, N, dtype, pose, P, ids = self._clouds(points, offsets, poses, pose_ids)
+        L = _lib.lib()
+        ws = _workspace(L.nsc_map_remove_workspace_bytes(N), dev)
+        removed = torch.empty((_lib.MAP_REMOVE_STATS,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            status = L.nsc_map_remove_dist(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off), B, N, _lib.ptr(pose), P,
+                                           _lib.ptr(ids), C.byref(self.params), C.byref(self.dist), self.capacity,
+                                           _lib.ptr(self.voxels), _lib.ptr(self.index), _lib.ptr(self.info),
+                                           _lib.ptr(self.keys), _lib.ptr(self.moments), _lib.ptr(self.stats),
+                                           _lib.ptr(removed), _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+        _lib.check(status, "nsc_map_remove_dist")
+        self.complete = None
+        return dict(self._kept(), removed=removed)
+
+    def _removed(self, out):
+        """remove_device's or replace_device's dict -> ``_result``'s dict and the eight counts by name"""
+        removed = out["removed"]
+        res = self._result(out)                                  # the one synchronisation
+        res.update(zip(_lib.MAP_REMOVE_STAT_NAMES, removed.cpu().tolist()))
+        return res
+
+    def remove(self, clouds, poses, pose_ids=None):
+        """``remove_device`` on the input forms of ``build``.  Returns ``build``'s dict over the whole map (emptied voxels
+        included: count 0, not usable) and the eight counts of ``removed`` by name; one synchronisation."""
+        self._insertable_map("remove")
+        packed = _is_packed(clouds)
+        clouds = clouds if packed else _tensors(clouds)
+        pose = GlobalMap._poses(poses)
+        # host ids are refused before anything goes to the device
+        ids = GlobalMap._host_ids(pose_ids, int(clouds[1].numel()) - 1 if packed else len(clouds), int(pose.shape[0]))
+        dev = self.voxels.device
+        pts, off = clouds if packed else _pack(clouds, dev)
+        return self._removed(self.remove_device(pts, off, pose.to(device=dev, dtype=torch.float64), ids))
+
+    def remove_prepared(self, store: PreparedClouds, poses, pose_ids=None, start=0, stop=None):
+        """``remove`` on the clouds ``start`` to ``stop`` (the end, if None) of a ``PreparedClouds``, under the poses they
+        were placed by.  ``poses`` and ``pose_ids`` have one entry per cloud of that range."""
+        self._insertable_map("remove_prepared")
+        n = len(store)
+        stop = n if stop is None else stop
+        if not 0 <= int(start) <= int(stop) <= n:
+            raise _lib.NscError(f"start and stop must satisfy 0 <= start <= stop <= {n}, got {start} and {stop}")
+        start, stop = int(start), int(stop)
+        pose = GlobalMap._poses(poses)
+        ids = GlobalMap._host_ids(pose_ids, stop - start, int(pose.shape[0]))
+        if store._buf is None:
+            store._reserve(0, 0, 0)
+        r0, r1 = int(store._row_host[start]), int(store._row_host[stop])
+        pts, off = store._buf["points"][r0:r1], store._buf["row_offsets"][start:stop + 1] - r0
+        return self._removed(self.remove_device(pts, off, pose.to(device=store.device, dtype=torch.float64), ids))
+
+    def replace_device(self, points, offsets, old_poses, new_poses, pose_ids=None, first_row=0, first_cloud=0):
+        """Move packed clouds of the kept map from ``old_poses`` to ``new_poses`` (nsc_map_replace_dist; both (P,4,4)), on
+        the device and without a synchronisation: cloud c is removed under old_poses[pose_ids[c]] and inserted under
+        new_poses[pose_ids[c]], a cloud with id -1 is left alone.  Rows and clouds are numbered from ``first_row`` and
+        ``first_cloud`` (the place of ``points`` in the store the map was built from), and ``cursor`` is neither read
+        nor advanced.  Returns the kept tensors, ``removed`` (8,) and ``placed`` (7,) int64: what became of the call's rows
+        in the layout of ``stats`` (new voxels, written after the call, used, not finite, outside, without pose,
+        unplaced)."""
+        self._insertable_map("replace_device")
+        dev = self.voxels.device
+        if points.device != dev:
+            raise _lib.NscError(f"the clouds must be on the map's device ({dev})")
+        if int(first_row) < 0 or int(first_cloud) < 0:
+            raise _lib.NscError(f"first_row and first_cloud must not be negative, got {first_row} and {first_cloud}")
+        _lib.require_cuda(new_poses, "new_poses")
+        pts, off, B, N, dtype, old, P, ids = self._clouds(points, offsets, old_poses, pose_ids)
+        if new_poses.ndim != 3 or tuple(new_poses.shape) != (P, 4, 4):
+            raise _lib.NscError(f"new_poses must be ({P},4,4) as old_poses, got {tuple(new_poses.shape)}")
+        new = new_poses.contiguous().to(torch.float64)
+        L = _lib.lib()
+        ws = _workspace(L.nsc_map_replace_workspace_bytes(N), dev)
+        removed = torch.empty((_lib.MAP_REMOVE_STATS,), dtype=torch.int64, device=dev)
+        placed = torch.empty((_lib.MAP_STATS,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            status = L.nsc_map_replace_dist(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off), B, N, _lib.ptr(old),
+                                            _lib.ptr(new), P, _lib.ptr(ids), C.byref(self.params), C.byref(self.dist),
+                                            self.capacity, _lib.ptr(self.voxels), _lib.ptr(self.index), _lib.ptr(self.info),
+                                            _lib.ptr(self.keys), _lib.ptr(self.moments), _lib.ptr(self.stats),
+                                            int(first_row), int(first_cloud), _lib.ptr(removed), _lib.ptr(placed),
+                                            _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+        _lib.check(status, "nsc_map_replace_dist")
+        self.complete = None
+        return dict(self._kept(), removed=removed, placed=placed)
+
+    def replace(self, clouds, old_poses, new_poses, pose_ids=None, first_row=0, first_cloud=0):
+        """``replace_device`` on the input forms of ``build``.  Returns ``remove``'s dict and ``placed`` (7,) as a device
+        tensor; one synchronisation."""
+        self._insertable_map("replace")
+        packed = _is_packed(clouds)
+        clouds = clouds if packed else _tensors(clouds)
+        old, new = GlobalMap._poses(old_poses), GlobalMap._poses(new_poses)
+        if tuple(old.shape) != tuple(new.shape):
+            raise _lib.NscError(f"old_poses and new_poses must have one pose each per id, got {int(old.shape[0])} and "
+                                f"{int(new.shape[0])}")
+        if int(first_row) < 0 or int(first_cloud) < 0:
+            raise _lib.NscError(f"first_row and first_cloud must not be negative, got {first_row} and {first_cloud}")
+        # host ids are refused before anything goes to the device
+        ids = GlobalMap._host_ids(pose_ids, int(clouds[1].numel()) - 1 if packed else len(clouds), int(old.shape[0]))
+        dev = self.voxels.device
+        pts, off = clouds if packed else _pack(clouds, dev)
+        out = self.replace_device(pts, off, old.to(device=dev, dtype=torch.float64), new.to(device=dev, dtype=torch.float64),
+                                  ids, first_row, first_cloud)
+        return dict(self._removed(out), placed=out["placed"])
+
+    def update_prepared(self, store: PreparedClouds, old_poses, new_poses, min_translation: float = 0.0,
+                        min_rotation: float = 0.0):
+        """Make the kept map follow the pose graph: after ``PoseGraphOptimizer.optimize`` has moved keyframes from
+        ``old_poses`` to ``new_poses`` (one (4,4) pose per cloud of ``store``, the map's input), re-place the clouds that
+        moved.  A cloud is re-placed when its two poses differ in any of the twelve entries, both are finite, and
+        |t_new - t_old| >= ``min_translation`` (m) or the angle of R_old^T R_new (atan2 of the skew part's norm and
+        (trace - 1) / 2, as the pose graph's Log) >= ``min_rotation`` (rad).  A cloud below both thresholds stays under its
+        old pose: the caller keeps the poses the map holds, which are ``new_poses`` where ``moved`` >= 0 and
+        ``old_poses`` elsewhere.  The choice is made on the device into ``pose_ids``, as ``extend`` does, so nothing is
+        read back and the call can be captured.  Rows and clouds keep the store's numbering.  Returns
+        ``replace_device``'s dict and ``moved`` (clouds,) int64: the cloud's own number, or -1.
+        A replacement is two scattered-atomic passes over the moved clouds' rows and costs about two insertions of them
+        (measured 1.85).  On the map of profiles/map_localize.md (4 541 clouds, 90.8 M rows) re-placing every second cloud
+        took what ``build_prepared`` over all of them takes (44.9 ms each): from about half of all clouds moved a rebuild is
+        cheaper.  The call walks the whole store to find the rows that moved (3.0 ms there for 64 moved clouds);
+        ``replace_device`` on a contiguous range of clouds with its ``first_row`` and ``first_cloud`` pays for that range
+        alone."""
+        self._insertable_map("update_prepared")
+        n = len(store)
+        old, new = GlobalMap._poses(old_poses), GlobalMap._poses(new_poses)
+        if int(old.shape[0]) != n or int(new.shape[0]) != n:          # refused before anything goes to the device
+            raise _lib.NscError(f"old_poses and new_poses must have one (4,4) pose per cloud of the store ({n}), got "
+                                f"{int(old.shape[0])} and {int(new.shape[0])}")
+        if not (float(min_translation) >= 0.0 and float(min_rotation) >= 0.0):
+            raise _lib.NscError("min_translation and min_rotation must not be negative")
+        if store._buf is None:
+            store._reserve(0, 0, 0)
+        dev = store.device
+        old, new = old.to(device=dev, dtype=torch.float64), new.to(device=dev, dtype=torch.float64)
+        A, B = old[:, :3, :], new[:, :3, :]
+        differ = (A != B).flatten(1).any(1)
+        finite = torch.isfinite(A).flatten(1).all(1) & torch.isfinite(B).flatten(1).all(1)
+        D = (A[:, :, :3].unsqueeze(3) * B[:, :, :3].unsqueeze(2)).sum(1)      # R_old^T R_new, elementwise: no BLAS call to capture
+        v = 0.5 * torch.stack([D[:, 2, 1] - D[:, 1, 2], D[:, 0, 2] - D[:, 2, 0], D[:, 1, 0] - D[:, 0, 1]], 1)
+        angle = torch.atan2(v.norm(dim=1), 0.5 * (D[:, 0, 0] + D[:, 1, 1] + D[:, 2, 2] - 1.0))
+        far = ((B[:, :, 3] - A[:, :, 3]).norm(dim=1) >= float(min_translation)) | (angle >= float(min_rotation))
+        moved = torch.where(differ & finite & far, torch.arange(n, dtype=torch.int64, device=dev), -1)
+        pts, off = store._buf["points"][:store.n_rows], store._buf["row_offsets"][:n + 1]
+        out = self.replace_device(pts, off, old, new, moved, 0, 0)
+        out["moved"] = moved
         return out
 
     def _result(self, out):
