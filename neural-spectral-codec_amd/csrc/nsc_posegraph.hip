@@ -1253,6 +1253,9 @@ __global__ __launch_bounds__(VB) void pg_cov_init_kernel(int n_poses, const long
     if (wave != 0) return;
     v.part_rr[(size_t)blockIdx.x * Rp + col] = d[0];
     v.part_rz[(size_t)blockIdx.x * Rp + col] = d[1];
+    // the matvec kernel writes p.Ap for the columns that run; a column that never runs has its alpha formed all the same
+    // (cov_alpha) and dropped: it sums zeros then, not what the caller's workspace happened to hold
+    v.part_a[(size_t)blockIdx.x * Rp + col] = 0.0;
 }
 
 // one workgroup per chunk: b.b and r.z of the start from nb partials; a column with b = 0 runs no iteration

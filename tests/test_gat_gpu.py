@@ -62,7 +62,7 @@ def test_no_edge_attr_paths():
     _check(out2, m_edge, g2)
 
 
-def test_irregular_graph_self_loops_and_hubs():
+def irregular_graph():
     """random multigraph-free graph with explicit self loops, isolated nodes and a hub of degree 200."""
     rng = np.random.default_rng(0)
     n = 300
@@ -77,7 +77,11 @@ def test_irregular_graph_self_loops_and_hubs():
     ei = torch.tensor(edges, dtype=torch.long).t().contiguous()
     ea = torch.rand(ei.shape[1], 2)
     x = torch.rand(n, 800)
-    g = gm.Data(x=x.cuda(), edge_index=ei.cuda(), edge_attr=ea.cuda(), num_nodes=n)
+    return gm.Data(x=x.cuda(), edge_index=ei.cuda(), edge_attr=ea.cuda(), num_nodes=n)
+
+
+def test_irregular_graph_self_loops_and_hubs():
+    g = irregular_graph()
     m = _model()
     with torch.no_grad():
         out = m(g)
