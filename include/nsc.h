@@ -961,7 +961,7 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
  *     of voxels[place] equal B's by bits;
  *   - every other keyed slot of M is an emptied voxel: count 0, nine zero moments, a record of 16 zeros (written as
  *     zeros: the record function is not evaluated for a count of 0), hence not usable.  It keeps its key, its slot and its
- *     place; places are never reused or compacted.  A later insertion into it adds to the zeros and makes its record again;
+ *     place (places are never reused; nsc_map_rehash_dist moves the map without them).  A later insertion into it adds to the zeros and makes its record again;
  *   - nsc_map_register and nsc_map_register_robust (every kernel, 1 and 7 voxels) against M give the bits they give
  *     against B: an emptied voxel is found and skipped by its usable flag exactly where B's lookup finds nothing;
  *   - info[:,1] is the row that made the voxel; info[:,2] and info[:,3] become a lower and an upper bound of the cloud
@@ -993,6 +993,43 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
  *   tensor (the index as a mapping) and a cloud's effect does not depend on what else is in the call; no host
  *   synchronisation, no memset or memcpy nodes.  Bits 61 and 62 of a place word may be in use during a call and are clear
  *   at its end.
+ *
+ * nsc_map_rehash_dist (restated in tests/map_rehash_restatement.py).  A kept map moved to another capacity, with or
+ *   without its emptied voxels, in work proportional to its voxels: a record is a function of count, moments and key
+ *   alone, so the integers and the record are copied by bits (the record function is not evaluated) and a new index is
+ *   keyed by the build's probe.  No row is read: the clouds need not exist any more.  The source -- voxels, info, keys,
+ *   moments, stats, cursor of capacity max_voxels -- is read only (its index is not needed: `keys` holds the key of every
+ *   place); the destination tensors of capacity new_max_voxels are other memory, and both maps exist while the call runs.
+ *   moments and new_moments are both given or both NULL (a map that is not insertable can be moved too), cursor and
+ *   new_cursor likewise.
+ * Kept voxels.  Place p < stats[NSC_MAP_STAT_WRITTEN] is dropped iff keep_emptied == 0, its count is 0 and its nine moments
+ *   are 0 (with moments == NULL the count alone decides).  Every other place is kept, an inconsistent one too (count below
+ *   0, or 0 with a moment left): it keeps its integers and its zero record, so adding the rows again still restores it.
+ * Order.  Kept voxels take the new places 0, 1, ... in ascending old place: ascending first_row survives.
+ * new_place (max_voxels) int64, every entry written: the new place of old place p; -1 where p was dropped, where
+ *   p >= written, and where the new place would be >= new_max_voxels.  For side data a caller keeps by place.
+ * tile_base (n_tiles + 1) int64, n_tiles = ceil(max_voxels / NSC_MAP_TILE_ROWS), every entry written: entry t is the number
+ *   of kept places before old place t NSC_MAP_TILE_ROWS, the last entry the number kept.  The call's own scan, and an
+ *   output.
+ * Copies.  For every kept voxel with new place q < new_max_voxels: the 16 doubles of its record, its 4 info entries, its 9
+ *   moments and its key, by bits.  Entries of the destination at and past new_stats[NSC_MAP_STAT_WRITTEN] are not defined.
+ * new_index (2 new_max_voxels,2) uint64, every entry written: (0, ~0) for an empty slot; each kept key claimed along the
+ *   build's probe sequence (mix(key) % (2 new_max_voxels), linear, 64-bit CAS) with its new place, or with place ~0 when
+ *   q >= new_max_voxels (the build's overflow rule).  Bits 61 and 62 of every place word are clear.  Which of two keys
+ *   that meet in a slot claims it is free, as in the build; the index read as a mapping key -> place is fixed.  With
+ *   kept <= new_max_voxels the destination is, bit for bit, what nsc_map_build_dist gives at new_max_voxels over the rows
+ *   the source holds (voxels, info, keys, moments, stats, the index as a mapping), provided the source never overflowed.
+ * new_stats: found = voxels kept, written = min(kept, new_max_voxels), entries 2 to 6 copied.  new_cursor: copied.
+ * rehashed (NSC_MAP_REHASH_STATS int64), written, not accumulated: voxels kept; voxels dropped as emptied; source keys
+ *   without a place (found - written of the source: they never had a record and cannot be carried); inconsistent voxels
+ *   kept; kept voxels without a place in the destination (kept - written); kept voxels that found all 2 new_max_voxels
+ *   slots keyed (only with kept > 2 new_max_voxels; which voxels these are is as free as in a full build table).
+ * No workspace: the two arrays the call needs beyond the map, new_place and tile_base, are typed outputs with a defined
+ *   value in every element.
+ * Launches.  NSC_MAP_REHASH_LAUNCHES kernels (clear new_index and rehashed; count the kept places per tile; scan: one
+ *   workgroup, also the stats, the cursor and rehashed; move: per tile the kept places listed in LDS, the four tensors
+ *   copied as flat ranges, the keys claimed) whose grids depend on max_voxels and new_max_voxels alone; the source's
+ *   stats are read on the device; integer atomics only; no host synchronisation, no memset or memcpy nodes.
  *
  * nsc_map_register.  n_scans scans packed as rows in the formats of nsc_map_build, offsets (n_scans+1) int64,
  *   init_transforms (n_scans,4,4) float64 row-major, scan to world.  The target is `voxels` and `index` of a
@@ -1052,6 +1089,14 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
 #define NSC_MAP_REMOVE_STAT_TOUCHED     5   /* voxels a row was taken out of                         */
 #define NSC_MAP_REMOVE_STAT_EMPTIED     6   /* of those: count 0 and nine zero moments afterwards    */
 #define NSC_MAP_REMOVE_STAT_INCONSISTENT 7  /* of those: count below 0, or 0 with a moment left      */
+#define NSC_MAP_REHASH_LAUNCHES     4       /* kernels of one nsc_map_rehash_dist call */
+#define NSC_MAP_REHASH_STATS            6   /* entries of `rehashed` */
+#define NSC_MAP_REHASH_STAT_KEPT        0   /* voxels kept                                            */
+#define NSC_MAP_REHASH_STAT_EMPTIED     1   /* voxels dropped as emptied                              */
+#define NSC_MAP_REHASH_STAT_SOURCE_UNPLACED 2 /* source keys without a place: found - written          */
+#define NSC_MAP_REHASH_STAT_INCONSISTENT 3  /* inconsistent voxels kept                               */
+#define NSC_MAP_REHASH_STAT_UNPLACED    4   /* kept voxels without a place in the destination         */
+#define NSC_MAP_REHASH_STAT_TABLE_FULL  5   /* kept voxels that found all 2 new_max_voxels slots keyed */
 #define NSC_MAP_REGISTER_BLOCKS     64      /* workgroups of 256 lanes per scan in linearize */
 #define NSC_MAP_REGISTER_SYSTEM     30
 #define NSC_MAP_REGISTER_MAX_SCANS  65535
@@ -1125,6 +1170,15 @@ int    nsc_map_replace_dist(const void *points, int32_t dtype, int32_t stride_fl
                             int64_t *info, int64_t *keys, int64_t *moments, int64_t *stats, int64_t first_row,
                             int64_t first_cloud, int64_t *removed, int64_t *placed, void *ws, size_t ws_bytes,
                             void *stream);
+/* NSC_EINVAL for a negative max_voxels, new_max_voxels < 1, a null stats, tile_base, rehashed or destination tensor
+ * (new_voxels, new_index, new_info, new_keys, new_stats), with max_voxels > 0 a null voxels, info, keys or new_place,
+ * moments or cursor given on one side only, or a destination pointer equal to its source pointer (the call is out of
+ * place); NSC_EUNSUPPORTED for a size above NSC_MAP_MAX_VOXELS: all before anything is launched.  No workspace. */
+int    nsc_map_rehash_dist(const double *voxels, const int64_t *info, const int64_t *keys, const int64_t *moments,
+                           const int64_t *stats, const int64_t *cursor, int64_t max_voxels, int32_t keep_emptied,
+                           double *new_voxels, uint64_t *new_index, int64_t *new_info, int64_t *new_keys,
+                           int64_t *new_moments, int64_t *new_stats, int64_t *new_cursor, int64_t new_max_voxels,
+                           int64_t *new_place, int64_t *tile_base, int64_t *rehashed, void *stream);
 
 void   nsc_map_register_default_params(NscMapRegisterParams *p);
 /* Bytes of workspace for nsc_map_register: the slabs and the state of n_scans scans; 0 for a negative n_scans. */

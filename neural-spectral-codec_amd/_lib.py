@@ -148,6 +148,10 @@ MAP_REMOVE_LAUNCHES, MAP_REPLACE_LAUNCHES = 3, 10      # include/nsc.h NSC_MAP_R
 MAP_REMOVE_STATS = 8
 MAP_REMOVE_STAT_NAMES = ("rows_removed", "removed_not_finite", "removed_outside", "removed_without_pose", "rows_missing",
                          "voxels_touched", "voxels_emptied", "voxels_inconsistent")
+# include/nsc.h NSC_MAP_REHASH_LAUNCHES, NSC_MAP_REHASH_STATS and NSC_MAP_REHASH_STAT_*: the name of each entry of `rehashed`
+MAP_REHASH_LAUNCHES, MAP_REHASH_STATS = 4, 6
+MAP_REHASH_STAT_NAMES = ("voxels_kept", "voxels_dropped", "source_keys_unplaced", "inconsistent_kept", "kept_unplaced",
+                         "kept_table_full")
 MAP_REGISTER_ROBUST_SYSTEM = 32         # include/nsc.h NSC_MAP_REGISTER_ROBUST_SYSTEM
 # include/nsc.h NSC_MAP_KERNEL_*: the pose graph's names and numbers
 MAP_KERNELS = {None: 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
@@ -294,6 +298,8 @@ SYMBOLS = {
     "nsc_map_replace_dist": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _vp, C.POINTER(MapParams),
                                        C.POINTER(MapDistParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
                                        _vp, _sz, _vp]),
+    "nsc_map_rehash_dist": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                      _vp, _vp, _vp, _vp]),
     "nsc_map_register_default_params": (None, [C.POINTER(MapRegisterParams)]),
     "nsc_map_register_workspace_bytes": (_sz, [_i32]),
     "nsc_map_register": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _i64, C.POINTER(MapParams),

@@ -27,6 +27,7 @@
 // nsc_map_insert_dist adds rows to the kept tensors of such a build, with the result of a build over all rows; its eight
 // launches are described where they stand, below the builds.  nsc_map_remove_dist takes rows out again and
 // nsc_map_replace_dist moves clouds from one pose to another; their launches stand below the insertion's.
+// nsc_map_rehash_dist moves a kept map to another capacity, without its emptied voxels; its four launches stand last.
 //
 // No float atomics anywhere: results are bitwise reproducible and do not depend on arrival order.
 #include <hip/hip_runtime.h>
@@ -271,9 +272,9 @@ __global__ __launch_bounds__(MAP_THREADS) void map_count_kernel(const u64 *bits,
     }
 }
 
-// exclusive scan of tile[0 .. n_tiles) in place; a thread takes ceil(n_tiles / SCAN_THREADS) consecutive tiles
-__global__ __launch_bounds__(SCAN_THREADS) void map_scan_kernel(long long *tile, long long n_tiles, long long max_voxels,
-                                                                long long *stats)
+// exclusive scan of tile[0 .. n_tiles) in place by one workgroup of SCAN_THREADS -> the total, in every thread; a thread
+// takes ceil(n_tiles / SCAN_THREADS) consecutive tiles
+__device__ __forceinline__ long long scan_tiles(long long *tile, long long n_tiles)
 {
     __shared__ long long part[SCAN_THREADS];
     const int tid = threadIdx.x;
@@ -291,8 +292,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void map_scan_kernel(long long *tile,
     }
     long long run = part[tid] - s;
     for (long long i = b; i < e; ++i) { const long long v = tile[i]; tile[i] = run; run += v; }
-    if (tid == SCAN_THREADS - 1) {
-        const long long found = part[tid];
+    return part[SCAN_THREADS - 1];
+}
+
+__global__ __launch_bounds__(SCAN_THREADS) void map_scan_kernel(long long *tile, long long n_tiles, long long max_voxels,
+                                                                long long *stats)
+{
+    const long long found = scan_tiles(tile, n_tiles);
+    if (threadIdx.x == SCAN_THREADS - 1) {
         stats[NSC_MAP_STAT_FOUND] = found;
         stats[NSC_MAP_STAT_WRITTEN] = min(found, max_voxels);
     }
@@ -905,6 +912,165 @@ void launch_replace_rows(const InsertRows<T> &old_rows, const double *new_poses,
     launch_insert_passes(new_rows, m, rule, ins, s);
 }
 
+// ---- nsc_map_rehash_dist: a kept map moved to another capacity, its emptied voxels left behind ------------------------
+// A record is a function of count, moments and key alone, so the map at another capacity is its voxels copied by bits and
+// an index keyed anew by the build's probe: passes over the max_voxels places, no row read and no record evaluated.
+//
+// Launch sequence (NSC_MAP_REHASH_LAUNCHES = 4; the grids depend on max_voxels and new_max_voxels alone):
+//   clear   new_index to (0, ~0) and `rehashed` to 0
+//   count   per tile of NSC_MAP_TILE_ROWS old places: which are kept (a ballot and its popcount per wave of 64 places), the
+//           tile's number into tile_base; the inconsistent voxels among them counted
+//   scan    one workgroup: tile_base scanned in place, the total behind it; new_stats, new_cursor and `rehashed`
+//   move    one workgroup per tile: the kept flags again, ranks by ballot prefix, the tile's kept places as a list in LDS
+//           and new_place of every place of the tile.  The tile's destination is the range [tile_base[t], tile_base[t+1])
+//           of each tensor: records, info, moments and keys are copied as flat arrays, lane i taking word i of the range,
+//           so stores are contiguous and loads come in whole records.  Then one lane per kept voxel claims its key's slot
+//           in new_index (claim_slot, as the build) and stores the place
+constexpr int TILE_ROUNDS = NSC_MAP_TILE_ROWS / MAP_THREADS;        // sweeps of a workgroup over the places of a tile
+constexpr int MAP_WAVES = MAP_THREADS / 64;
+constexpr int TILE_SEGMENTS = TILE_ROUNDS * MAP_WAVES;             // runs of 64 places, one ballot each, in ascending place
+static_assert(TILE_SEGMENTS == 64, "one lane of a wave per segment of a tile");
+
+enum { OLD_DROPPED, OLD_KEPT, OLD_INCONSISTENT };
+
+struct RehashSource {
+    const u64 *voxels; const long long *info, *keys, *moments, *stats;
+    long long max_voxels;
+    int keep_emptied;
+    // the places that hold a voxel: read on the device, and held inside the tensors whatever the stats say
+    __device__ long long written() const { return max(0LL, min((long long)stats[NSC_MAP_STAT_WRITTEN], max_voxels)); }
+    // what becomes of old place p: nothing is read at or past `written`
+    __device__ int kind(long long p, long long written) const
+    {
+        if (p >= written) return OLD_DROPPED;
+        const long long count = info[4 * p];
+        if (count > 0) return OLD_KEPT;
+        bool zero = count == 0;
+        if (moments)
+            for (int t = 0; t < 9; ++t) zero = zero && moments[9 * p + t] == 0;
+        if (!zero) return OLD_INCONSISTENT;
+        return keep_emptied ? OLD_KEPT : OLD_DROPPED;
+    }
+};
+
+struct RehashDest {
+    u64 *voxels, *index; long long *info, *keys, *moments;
+    long long max_voxels;
+};
+
+__global__ __launch_bounds__(MAP_THREADS) void rehash_clear_kernel(u64 *index, long long index_words, long long *rehashed)
+{
+    const long long i0 = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
+    for (long long i = i0; i < index_words; i += (long long)gridDim.x * MAP_THREADS) index[i] = (i & 1) ? ~0ULL : 0ULL;
+    if (i0 < NSC_MAP_REHASH_STATS) rehashed[i0] = 0;
+}
+
+__global__ __launch_bounds__(MAP_THREADS) void rehash_count_kernel(RehashSource src, long long n_tiles, long long *tile_base,
+                                                                   long long *rehashed)
+{
+    __shared__ int part[2][MAP_WAVES];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const long long written = src.written();
+    for (long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        int kept = 0, bad = 0;                                           // the same in every lane of a wave
+        for (int r = 0; r < TILE_ROUNDS; ++r) {
+            const int k = src.kind(t * TILE_ROWS + r * MAP_THREADS + tid, written);
+            kept += __popcll(__ballot(k != OLD_DROPPED));
+            bad += __popcll(__ballot(k == OLD_INCONSISTENT));
+        }
+        if ((tid & 63) == 0) { part[0][wave] = kept; part[1][wave] = bad; }
+        __syncthreads();
+        if (tid == 0) {
+            int n = 0, b = 0;
+            for (int w = 0; w < MAP_WAVES; ++w) { n += part[0][w]; b += part[1][w]; }
+            tile_base[t] = n;
+            if (b) atomicAdd(reinterpret_cast<u64 *>(&rehashed[NSC_MAP_REHASH_STAT_INCONSISTENT]), (u64)b);
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(SCAN_THREADS) void rehash_scan_kernel(RehashSource src, const long long *cursor, long long n_tiles,
+                                                                   long long new_max_voxels, long long *tile_base,
+                                                                   long long *new_stats, long long *new_cursor,
+                                                                   long long *rehashed)
+{
+    const long long kept = scan_tiles(tile_base, n_tiles);
+    const int tid = threadIdx.x;
+    if (tid == SCAN_THREADS - 1) {
+        const long long written = src.written(), placed = min(kept, new_max_voxels);
+        tile_base[n_tiles] = kept;
+        new_stats[NSC_MAP_STAT_FOUND] = kept;
+        new_stats[NSC_MAP_STAT_WRITTEN] = placed;
+        rehashed[NSC_MAP_REHASH_STAT_KEPT] = kept;
+        rehashed[NSC_MAP_REHASH_STAT_EMPTIED] = written - kept;
+        rehashed[NSC_MAP_REHASH_STAT_SOURCE_UNPLACED] = src.stats[NSC_MAP_STAT_FOUND] - written;
+        rehashed[NSC_MAP_REHASH_STAT_UNPLACED] = kept - placed;
+    }
+    if (tid >= NSC_MAP_STAT_USED && tid < NSC_MAP_STATS) new_stats[tid] = src.stats[tid];
+    if (cursor && tid < 2) new_cursor[tid] = cursor[tid];
+}
+
+__global__ __launch_bounds__(MAP_THREADS) void rehash_move_kernel(RehashSource src, RehashDest dst, long long n_tiles,
+                                                                  const long long *tile_base, long long *new_place,
+                                                                  long long *rehashed)
+{
+    __shared__ int list[NSC_MAP_TILE_ROWS];                              // the tile's kept places, counted from its first
+    __shared__ int seg[TILE_SEGMENTS + 1];                              // kept places in front of each segment; the tile's
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long written = src.written(), cap = 2 * dst.max_voxels;
+    long long full = 0;
+    for (long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const long long p0 = t * TILE_ROWS, q0 = tile_base[t];
+        unsigned flags = 0;                                              // bit r: this lane's place of sweep r is kept
+        for (int r = 0; r < TILE_ROUNDS; ++r) {
+            const bool keep = src.kind(p0 + r * MAP_THREADS + tid, written) != OLD_DROPPED;
+            const u64 b = __ballot(keep);
+            flags |= (unsigned)keep << r;
+            if (lane == 0) seg[r * MAP_WAVES + wave] = __popcll(b);
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const int v = seg[lane];
+            int inc = v;
+            for (int o = 1; o < 64; o <<= 1) {
+                const int u = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += u;
+            }
+            seg[lane] = inc - v;
+            if (lane == 63) seg[TILE_SEGMENTS] = inc;
+        }
+        __syncthreads();
+        for (int r = 0; r < TILE_ROUNDS; ++r) {
+            const bool keep = (flags >> r) & 1u;
+            const u64 b = __ballot(keep);
+            const int j = seg[r * MAP_WAVES + wave] + __popcll(b & ((1ULL << lane) - 1ULL));
+            if (keep) list[j] = r * MAP_THREADS + tid;
+            const long long p = p0 + r * MAP_THREADS + tid;
+            if (p < src.max_voxels) new_place[p] = keep && q0 + j < dst.max_voxels ? q0 + j : -1;
+        }
+        __syncthreads();
+        // k kept places in this tile, the first `fit` of them with a place in the destination
+        const int k = seg[TILE_SEGMENTS];
+        const int fit = (int)max(0LL, min((long long)k, dst.max_voxels - q0));
+        for (int i = tid; i < 16 * fit; i += MAP_THREADS) dst.voxels[16 * q0 + i] = src.voxels[16 * (p0 + list[i >> 4]) + (i & 15)];
+        for (int i = tid; i < 4 * fit; i += MAP_THREADS) dst.info[4 * q0 + i] = src.info[4 * (p0 + list[i >> 2]) + (i & 3)];
+        if (src.moments)
+            for (int i = tid; i < 9 * fit; i += MAP_THREADS) dst.moments[9 * q0 + i] = src.moments[9 * (p0 + list[i / 9]) + i % 9];
+        for (int j = tid; j < k; j += MAP_THREADS) {
+            const long long key = src.keys[p0 + list[j]];
+            if (j < fit) dst.keys[q0 + j] = key;
+            bool claimed;
+            const long long h = claim_slot(dst.index, 2, cap, (u64)key, claimed);
+            // a voxel past the outputs keeps its key with place ~0, the build's overflow rule
+            if (h < 0) ++full; else dst.index[2 * h + 1] = j < fit ? (u64)(q0 + j) : ~0ULL;
+        }
+        __syncthreads();                                                 // list and seg are the next tile's
+    }
+    full = nsc_wave_sum(full);
+    if (lane == 0 && full) atomicAdd(reinterpret_cast<u64 *>(&rehashed[NSC_MAP_REHASH_STAT_TABLE_FULL]), (u64)full);
+}
+
 // what the three calls on a kept map take alike
 struct KeptArgs {
     const void *points; int32_t dtype, stride_floats; const int64_t *offsets; int32_t n_clouds; int64_t total_rows;
@@ -1075,6 +1241,42 @@ int nsc_map_replace_dist(const void *points, int32_t dtype, int32_t stride_float
     else
         launch_replace_rows(a.rows<double>(), new_poses, a.map(nullptr), dist_rule(params, dist), ins, rem,
                             (long long)first_row, (long long)first_cloud, rm, pl, s);
+    return launch_status();
+}
+
+int nsc_map_rehash_dist(const double *voxels, const int64_t *info, const int64_t *keys, const int64_t *moments,
+                        const int64_t *stats, const int64_t *cursor, int64_t max_voxels, int32_t keep_emptied,
+                        double *new_voxels, uint64_t *new_index, int64_t *new_info, int64_t *new_keys, int64_t *new_moments,
+                        int64_t *new_stats, int64_t *new_cursor, int64_t new_max_voxels, int64_t *new_place,
+                        int64_t *tile_base, int64_t *rehashed, void *stream)
+{
+    if (max_voxels < 0 || new_max_voxels < 1) return NSC_EINVAL;
+    if (!stats || !new_voxels || !new_index || !new_info || !new_keys || !new_stats || !tile_base || !rehashed) return NSC_EINVAL;
+    if (max_voxels > 0 && !(voxels && info && keys && new_place)) return NSC_EINVAL;
+    if (!moments != !new_moments || !cursor != !new_cursor) return NSC_EINVAL;
+    // out of place: both maps exist while the call runs
+    if (new_voxels == voxels || new_info == info || new_keys == keys || new_stats == stats ||
+        (moments && new_moments == moments) || (cursor && new_cursor == cursor))
+        return NSC_EINVAL;
+    if (max_voxels > NSC_MAP_MAX_VOXELS || new_max_voxels > NSC_MAP_MAX_VOXELS) return NSC_EUNSUPPORTED;
+    const RehashSource src{reinterpret_cast<const u64 *>(voxels), reinterpret_cast<const long long *>(info),
+                           reinterpret_cast<const long long *>(keys), reinterpret_cast<const long long *>(moments),
+                           reinterpret_cast<const long long *>(stats), (long long)max_voxels, keep_emptied != 0};
+    const RehashDest dst{reinterpret_cast<u64 *>(new_voxels), reinterpret_cast<u64 *>(new_index),
+                         reinterpret_cast<long long *>(new_info), reinterpret_cast<long long *>(new_keys),
+                         reinterpret_cast<long long *>(new_moments), (long long)new_max_voxels};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long n_tiles = (max_voxels + TILE_ROWS - 1) / TILE_ROWS, index_words = 4 * (long long)new_max_voxels;
+    long long *base = reinterpret_cast<long long *>(tile_base), *re = reinterpret_cast<long long *>(rehashed);
+    const dim3 threads(MAP_THREADS), per_tile(blocks_for(n_tiles, 1, MAP_SLOT_BLOCKS));
+    hipLaunchKernelGGL(rehash_clear_kernel, dim3(blocks_for(index_words, MAP_THREADS, MAP_SLOT_BLOCKS)), threads, 0, s,
+                       dst.index, index_words, re);
+    hipLaunchKernelGGL(rehash_count_kernel, per_tile, threads, 0, s, src, n_tiles, base, re);
+    hipLaunchKernelGGL(rehash_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, src, reinterpret_cast<const long long *>(cursor),
+                       n_tiles, (long long)new_max_voxels, base, reinterpret_cast<long long *>(new_stats),
+                       reinterpret_cast<long long *>(new_cursor), re);
+    hipLaunchKernelGGL(rehash_move_kernel, per_tile, threads, 0, s, src, dst, n_tiles, base,
+                       reinterpret_cast<long long *>(new_place), re);
     return launch_status();
 }
 

@@ -33,8 +33,17 @@ Definition (the contract the two entry points and tests/map_localize_restatement
                  rows and clouds are numbered from ``first_row`` and ``first_cloud``, the cursor stays as it is, and what
                  became of the rows goes into ``placed``.  ``update_prepared`` is the call to make after
                  ``PoseGraphOptimizer.optimize``: it chooses the clouds whose poses moved, on the device
+    resize       (nsc_map_rehash_dist; ``resize*``, ``fit``) the kept map moved to another capacity, with or without its
+                 emptied voxels, in one pass over its voxels: count, moments, key and record are copied by bits, the kept
+                 voxels take the places 0, 1, ... in their old order (ascending first_row survives), and a new index is keyed
+                 by the build's probe.  No row is read, so the clouds need not exist any more.  While the voxels kept fit
+                 into the new capacity the result is, bit for bit, the build at that capacity over the rows the map holds
+                 (after a compaction: voxel by voxel, under places of its own), and ``register`` gives the same bits before
+                 and after.  A destination that is too small follows the build's overflow rule: the kept voxels in front
+                 take the places, the others keep their key with place ~0.  ``new_place`` tells a caller who keeps side data
+                 by place where every old place went.  An inconsistent voxel is kept with its integers
 
-    robust       (nsc_map_register_robust; ``kernel``, ``robust_scale``, ``neighbours``) every pair (row, voxel) is weighted
+    robust      (nsc_map_register_robust; ``kernel``, ``robust_scale``, ``neighbours``) every pair (row, voxel) is weighted
                  by w = rho'(s), s = d^T Omega_v d, with the pose graph's kernels and one width c in units of sqrt(chi^2):
                  H = sum w J^T Omega J, g = sum w J^T Omega d, cost = sum rho(s), rmse = sqrt(sum w |d|^2 / sum w).  With
                  ``neighbours=7`` a row pairs with its own voxel and the six face neighbours, in the fixed order
@@ -47,8 +56,8 @@ Integer atomics and fixed-shape float64 sums only: two calls agree bit for bit a
 else is in the batch.
 
 Not part of this module: source covariances (full VGICP), 27-voxel neighbourhoods, a width per scan, a step-acceptance
-test, NDT's exponential score, reuse or compaction of emptied places, detection of an unmatched removal that leaves a
-positive count, growing the capacity of a kept map, unary edges in the pose graph.
+test, NDT's exponential score, detection of an unmatched removal that leaves a positive count, a resize in place or one
+that ``extend`` starts by itself (it would need a read-back), unary edges in the pose graph.
 """
 import ctypes as C
 
@@ -84,7 +93,9 @@ class MapLocalizer:
     origin            (0,0,0)  world point where voxel (2^20, 2^20, 2^20) begins
     max_voxels        None     capacity of the map; the build table has twice as many slots.  A voxel of capacity costs
                                256 bytes of table during the build and 200 bytes kept (record 128, index 32, info and key
-                               40).  None means one voxel per input row, which can never be short
+                               40).  None means one voxel per input row of the first build, which can never be short
+                               for that build; ``fit`` then gives back what the voxels do not need, and ``resize*`` sets
+                               any other capacity later
     min_points        6        rows a voxel needs to take part in a registration
     eigen_ratio       1e-2     smallest eigenvalue of a voxel's covariance, as a share of its largest
     sigma_floor       1e-3     smallest standard deviation of a voxel along any axis (m)
@@ -95,8 +106,10 @@ class MapLocalizer:
     insertable        False    every build keeps ``moments`` (M,9) and ``cursor`` (2,) int64 = [rows, clouds taken so
                                far], so that ``insert*`` and ``extend`` can add scans to the kept map, and ``remove*``,
                                ``replace*`` and ``update_prepared`` take clouds out or move them.  The capacity does
-                               not grow: with ``max_voxels=None`` it is the first build's row count, so a map that is
-                               meant to grow needs an explicit ``max_voxels``
+                               not grow by itself: with ``max_voxels=None`` it is the first build's row count.  ``resize*``
+                               moves the map to a larger one, and leaves behind the voxels that removals emptied, before
+                               it fills up: a voxel found past the capacity (voxels_found > voxels_written) never had a
+                               record, cannot be carried and is counted in ``source_keys_unplaced``
     kernel            None     robust kernel of the registration: None (quadratic), "huber", "cauchy" or "geman_mcclure"
     robust_scale      None     the kernel's width c, in units of sqrt(chi^2); needed with a kernel, refused without one
     neighbours        1        voxels a row is paired with: 1 (its own) or 7 (and the six face neighbours)
@@ -447,6 +460,90 @@ class MapLocalizer:
         out = self.replace_device(pts, off, old, new, moved, 0, 0)
         out["moved"] = moved
         return out
+
+    # ---- resizing and compaction -------------------------------------------------------------------------------------
+
+    def _resizable(self, what, max_voxels):
+        """the host-side refusals of a resize -> the new capacity"""
+        if self.voxels is None:
+            raise _lib.NscError(f"MapLocalizer.{what}: build a map first")
+        M = self.capacity if max_voxels is None else int(max_voxels)
+        if not 1 <= M <= _lib.MAP_MAX_VOXELS:
+            raise _lib.NscError(f"MapLocalizer.{what}: max_voxels must lie in [1, {_lib.MAP_MAX_VOXELS}], got {M}")
+        return M
+
+    def resize_device(self, max_voxels=None, compact=True, out=None):
+        """Move the kept map to the capacity ``max_voxels`` (nsc_map_rehash_dist; None keeps the capacity), on the device
+        and without a synchronisation.  With ``compact`` the emptied voxels (count 0, zero moments) are left behind; the
+        kept voxels take the places 0, 1, ... in their old order, records and integers copied by bits, and the index is
+        keyed anew.  While the voxels kept fit, the map is then the build at the new capacity over the rows it holds, bit
+        for bit, and the clouds are not needed for it.  ``out``: a dict of the destination tensors as ``build_device``
+        takes them (moments and cursor when the map keeps them), with new_place (old capacity,), tile_base
+        (ceil(old capacity / ``_lib.MAP_TILE_ROWS``) + 1,) and rehashed (6,) int64; with it a call can be captured (the
+        graph reads the tensors that were kept when it was captured: the caller keeps them alive).
+        The kept tensors are then the destination's, ``capacity`` and ``max_voxels`` the new size -- a later
+        ``build_device`` and every ``insert*``, ``remove*``, ``replace*`` and ``register*`` use it -- and ``complete`` is
+        None.  Returns the kept tensors, new_place (the new place of every old place, or -1), tile_base and rehashed
+        (``_lib.MAP_REHASH_STAT_NAMES``).
+        Measured on the map of profiles/map_localize.md (90.8 M rows, 484 681 voxels, capacity 4 194 304): 0.358 ms to
+        the same capacity and 0.390 ms to twice the capacity, against 44.85 and 45.99 ms for ``build_prepared`` at the new
+        capacity over the same clouds (1/125 and 1/118); 0.399 ms for a fit after every second cloud was removed, against
+        22.48 ms (1/56).  The copy pass reaches a quarter of a flat device copy's rate there, because the voxels of a map
+        far below its capacity stand in few tiles (profiles/map_localize.md, "Resizing the kept map")."""
+        M = self._resizable("resize_device", max_voxels)
+        dev, old = self.voxels.device, self.capacity
+        tiles = -(-old // _lib.MAP_TILE_ROWS)
+        shapes = dict(voxels=((M, _lib.MAP_VOXEL_DOUBLES), torch.float64), index=((2 * M, 2), torch.int64),
+                      info=((M, 4), torch.int64), keys=((M,), torch.int64), stats=((_lib.MAP_STATS,), torch.int64))
+        if self.moments is not None:
+            shapes["moments"] = ((M, 9), torch.int64)
+        if self.cursor is not None:
+            shapes["cursor"] = ((2,), torch.int64)
+        shapes.update(new_place=((old,), torch.int64), tile_base=((tiles + 1,), torch.int64),
+                      rehashed=((_lib.MAP_REHASH_STATS,), torch.int64))
+        if out is None:
+            out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+        for k, (shape, dt) in shapes.items():
+            t = out.get(k)
+            if t is None or tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise _lib.NscError(f"out[{k!r}] must be a contiguous {shape} {dt} tensor on {dev}")
+        with torch.cuda.device(dev):
+            status = _lib.lib().nsc_map_rehash_dist(
+                _lib.ptr(self.voxels), _lib.ptr(self.info), _lib.ptr(self.keys), _lib.ptr(self.moments),
+                _lib.ptr(self.stats), _lib.ptr(self.cursor), old, 0 if compact else 1, _lib.ptr(out["voxels"]),
+                _lib.ptr(out["index"]), _lib.ptr(out["info"]), _lib.ptr(out["keys"]), _lib.ptr(out.get("moments")),
+                _lib.ptr(out["stats"]), _lib.ptr(out.get("cursor")), M, _lib.ptr(out["new_place"]),
+                _lib.ptr(out["tile_base"]), _lib.ptr(out["rehashed"]), _lib.stream_ptr(dev))
+        _lib.check(status, "nsc_map_rehash_dist")
+        self.voxels, self.index, self.keys, self.info, self.stats = (out[k] for k in ("voxels", "index", "keys", "info",
+                                                                                     "stats"))
+        if self.moments is not None:
+            self.moments = out["moments"]
+        if self.cursor is not None:
+            self.cursor = out["cursor"]
+        self.capacity = self.max_voxels = M
+        self.complete = None
+        return dict(self._kept(), new_place=out["new_place"], tile_base=out["tile_base"], rehashed=out["rehashed"])
+
+    def resize(self, max_voxels=None, compact=True):
+        """``resize_device`` in its host form.  Returns ``build``'s dict over the whole map and the six counts of
+        ``rehashed`` by name; one synchronisation."""
+        out = self.resize_device(max_voxels, compact)
+        rehashed = out["rehashed"]
+        res = self._result(out)                                  # the one synchronisation
+        res.update(zip(_lib.MAP_REHASH_STAT_NAMES, rehashed.cpu().tolist()))
+        return res
+
+    def fit(self, headroom: float = 1.0, compact=True):
+        """``resize`` to max(1, ceil(``headroom`` x voxels_written)): the way to give back the memory of a build with
+        ``max_voxels=None``, whose capacity is its row count.  Reads the stats once before the resize, so with
+        ``compact`` the voxels dropped come off the new capacity only at the next ``fit``."""
+        if self.voxels is None:
+            raise _lib.NscError("MapLocalizer.fit: build a map first")
+        if not (np.isfinite(headroom) and float(headroom) >= 1.0):
+            raise _lib.NscError(f"MapLocalizer.fit: headroom must be finite and at least 1, got {headroom!r}")
+        written = int(self.stats[1])                             # voxels_written
+        return self.resize(max(1, int(np.ceil(float(headroom) * written))), compact)
 
     def _result(self, out):
         """build_device's buffers -> the dict ``build`` returns (one read of the stats)"""
