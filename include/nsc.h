@@ -961,7 +961,10 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
  *     of voxels[place] equal B's by bits;
  *   - every other keyed slot of M is an emptied voxel: count 0, nine zero moments, a record of 16 zeros (written as
  *     zeros: the record function is not evaluated for a count of 0), hence not usable.  It keeps its key, its slot and its
- *     place (places are never reused; nsc_map_rehash_dist moves the map without them).  A later insertion into it adds to the zeros and makes its record again;
+ *     place (places are never reused; nsc_map_rehash_dist moves the map without them).  A later insertion into it adds to the zeros and makes its record again:
+ *     the voxel keeps its place and info[place][1], the row that first made it, and info[place][2] and info[place][3]
+ *     become the min and the max of the bounds it kept and the numbers of the clouds now added.  An insertion into an
+ *     inconsistent voxel adds to its integers in the same way, and the record stays zero while the count is below 1;
  *   - nsc_map_register and nsc_map_register_robust (every kernel, 1 and 7 voxels) against M give the bits they give
  *     against B: an emptied voxel is found and skipped by its usable flag exactly where B's lookup finds nothing;
  *   - info[:,1] is the row that made the voxel; info[:,2] and info[:,3] become a lower and an upper bound of the cloud

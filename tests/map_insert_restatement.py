@@ -61,8 +61,9 @@ def insert(s, points, offsets, poses, pose_ids=None):
             mo[a] += qq[a]
         for t, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
             mo[3 + t] += qq[a] * qq[b]
-    for at in touched:
-        s["voxels"][at] = R.record(s["moments"][at], s["info"][at][0], key_voxel(s["keys"][at]), voxel, origin, *s["rule"])
+    for at in touched:                   # a place an unmatched removal left below one row keeps the zero record until it has one
+        s["voxels"][at] = R.record(s["moments"][at], s["info"][at][0], key_voxel(s["keys"][at]), voxel, origin, *s["rule"]) \
+            if s["info"][at][0] > 0 else np.zeros(16)
     st = s["stats"]
     st[0] = len(s["keys"])
     st[1] = min(st[0], s["capacity"])
