@@ -29,6 +29,11 @@
 // nsc_map_replace_dist moves clouds from one pose to another; their launches stand below the insertion's.
 // nsc_map_rehash_dist moves a kept map to another capacity, without its emptied voxels; its four launches stand last.
 //
+// What the calls share stands once: for_each_row deals a call's rows to the lanes (the build's insert pass, the
+// insertion's claim and accumulate passes, the removal's row pass), locate_row decides what becomes of a row, claim_slot
+// and find_slot walk the probe sequence, touch_place keeps the touched list, dist_record makes a record, and on the host
+// MapArgs / KeptArgs hold an entry point's arguments, their checks and the float32 / float64 dispatch.
+//
 // No float atomics anywhere: results are bitwise reproducible and do not depend on arrival order.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -79,7 +84,8 @@ __device__ __forceinline__ u64 peek(const u64 *p)        // a value other workgr
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// per_slot: the words of a slot, a power of two; words 1 (first) and 6 (cloud_min) of a slot start at ~0
+// The clear of a build: its table, its first-row bitmap and the stats.  per_slot: the words of a slot, a power of two;
+// words 1 (first) and 6 (cloud_min) of a slot start at ~0
 __global__ __launch_bounds__(MAP_THREADS) void map_clear_kernel(u64 *slots, long long slot_words, int per_slot, u64 *bits,
                                                                 long long n_words, long long *stats)
 {
@@ -136,6 +142,7 @@ __device__ __forceinline__ void add_row(DistSlot &s, const double w[3], const do
 // the rows of one call, as the two builds and the insertion take them
 template <class T>
 struct InsertRows {
+    typedef T scalar;
     const T *pts; int stride; const long long *off; int n_clouds; long long total;
     const double *poses; int n_poses; const long long *ids;
     MapGrid g;
@@ -145,6 +152,22 @@ struct CloudSpan {                      // the rows [lo, hi) of cloud c, while c
     long long lo = 0, hi = 0;
     int c = -1;
 };
+
+// The one pass over the rows of a call: a workgroup takes INSERT_ROWS consecutive rows per sweep, a lane every
+// MAP_THREADS-th of them, and body(row, span) runs per row, with a span of its own per sweep
+template <class Body>
+__device__ __forceinline__ void for_each_row(long long total, Body body)
+{
+    const long long n_sweeps = (total + INSERT_ROWS - 1) / INSERT_ROWS;
+    for (long long sweep = blockIdx.x; sweep < n_sweeps; sweep += gridDim.x) {
+        CloudSpan span;
+        for (int k = 0; k < INSERT_ROWS / MAP_THREADS; ++k) {
+            const long long row = sweep * INSERT_ROWS + (long long)k * MAP_THREADS + threadIdx.x;
+            if (row >= total) break;
+            body(row, span);
+        }
+    }
+}
 
 // Row -> its cloud (in `span`), world point w, position u inside its voxel and key.  The one place that decides what
 // becomes of a row: C_USED when it has a voxel, else the counter it falls into, the checks in this order
@@ -209,32 +232,25 @@ struct RowCounters {                    // a lane's counts of what became of its
 template <class T, class S>
 __global__ __launch_bounds__(MAP_THREADS) void map_insert_kernel(InsertRows<T> in, S *tab, long long cap, long long *stats)
 {
-    const int tid = threadIdx.x;
     RowCounters cnt;
-    const long long n_sweeps = (in.total + INSERT_ROWS - 1) / INSERT_ROWS;
-    for (long long sweep = blockIdx.x; sweep < n_sweeps; sweep += gridDim.x) {
-        CloudSpan span;
-        for (int k = 0; k < INSERT_ROWS / MAP_THREADS; ++k) {
-            const long long row = sweep * INSERT_ROWS + (long long)k * MAP_THREADS + tid;
-            if (row >= in.total) break;
-            double w[3], u[3];
-            u64 key;
-            int kind = locate_row(in, row, span, w, u, key);
-            long long h = -1;
-            bool claimed;
-            if (kind == C_USED && (h = claim_slot(&tab[0].key, slot_words<S>(), cap, key, claimed)) < 0) kind = C_UNPLACED;
-            cnt.count(kind);
-            if (kind != C_USED) continue;
-            S &s = tab[h];
-            const int c = span.c;
-            // min and max only move one way: a value read before the atomic that already beats ours stays beaten
-            if (peek(&s.first) > (u64)row) atomicMin(&s.first, (u64)row);
-            if (peek(&s.cloud_min) > (u64)c) atomicMin(&s.cloud_min, (u64)c);
-            if (peek(&s.cloud_max) < (u64)c + 1) atomicMax(&s.cloud_max, (u64)c + 1);
-            atomicAdd(&s.count, 1ULL);
-            add_row(s, w, u);
-        }
-    }
+    for_each_row(in.total, [&](long long row, CloudSpan &span) {
+        double w[3], u[3];
+        u64 key;
+        int kind = locate_row(in, row, span, w, u, key);
+        long long h = -1;
+        bool claimed;
+        if (kind == C_USED && (h = claim_slot(&tab[0].key, slot_words<S>(), cap, key, claimed)) < 0) kind = C_UNPLACED;
+        cnt.count(kind);
+        if (kind != C_USED) return;
+        S &s = tab[h];
+        const int c = span.c;
+        // min and max only move one way: a value read before the atomic that already beats ours stays beaten
+        if (peek(&s.first) > (u64)row) atomicMin(&s.first, (u64)row);
+        if (peek(&s.cloud_min) > (u64)c) atomicMin(&s.cloud_min, (u64)c);
+        if (peek(&s.cloud_max) < (u64)c + 1) atomicMax(&s.cloud_max, (u64)c + 1);
+        atomicAdd(&s.count, 1ULL);
+        add_row(s, w, u);
+    });
     cnt.add_to(stats);
 }
 static_assert(NSC_MAP_STAT_NOT_FINITE == NSC_MAP_STAT_USED + C_NOT_FINITE && NSC_MAP_STAT_OUTSIDE == NSC_MAP_STAT_USED + C_OUTSIDE &&
@@ -261,12 +277,7 @@ __global__ __launch_bounds__(MAP_THREADS) void map_count_kernel(const u64 *bits,
     const long long waves = (long long)gridDim.x * (MAP_THREADS / 64);
     for (long long t = (long long)blockIdx.x * (MAP_THREADS / 64) + (threadIdx.x >> 6); t < n_tiles; t += waves) {
         const long long w = t * TILE_WORDS + lane;
-        const int v = w < n_words ? __popcll(bits[w]) : 0;
-        int inc = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += u;
-        }
+        const int v = w < n_words ? __popcll(bits[w]) : 0, inc = nsc_wave_scan(v);
         if (w < n_words) prefix[w] = (unsigned)(inc - v);
         if (lane == 63) tile[t] = inc;
     }
@@ -439,21 +450,37 @@ inline unsigned blocks_for(long long n, long long per_block, long long most)
     return (unsigned)(b < 1 ? 1 : (b > most ? most : b));
 }
 
-// The arguments both builds take: NSC_OK, or what the call returns before anything is launched
-int check_build(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_clouds,
-                int64_t total_rows, const double *poses, int32_t n_poses, const NscMapParams *params, int64_t max_voxels,
-                bool outputs, const int64_t *stats)
-{
-    if (n_clouds < 0 || n_poses < 0 || total_rows < 0 || max_voxels < 0 || !params || !stats || !offsets) return NSC_EINVAL;
-    if (dtype != NSC_MAP_DTYPE_F32 && dtype != NSC_MAP_DTYPE_F64) return NSC_EINVAL;
-    if (stride_floats != 3 && !(stride_floats == 4 && dtype == NSC_MAP_DTYPE_F32)) return NSC_EINVAL;
-    if (!(params->voxel_size > 0.0) || !isfinite(params->voxel_size) || !isfinite(params->origin[0]) ||
-        !isfinite(params->origin[1]) || !isfinite(params->origin[2]))
-        return NSC_EINVAL;
-    if ((total_rows > 0 && !points) || (n_poses > 0 && !poses) || (max_voxels > 0 && !outputs)) return NSC_EINVAL;
-    if (total_rows > NSC_MAP_MAX_ROWS || max_voxels > NSC_MAP_MAX_VOXELS) return NSC_EUNSUPPORTED;
-    return NSC_OK;
-}
+// What the two builds and the three calls on a kept map take alike: the rows, their poses, the grid, the capacity, the stats
+struct MapArgs {
+    const void *points; int32_t dtype, stride_floats; const int64_t *offsets; int32_t n_clouds; int64_t total_rows;
+    const double *poses; int32_t n_poses; const int64_t *pose_ids; const NscMapParams *params; int64_t max_voxels;
+    int64_t *stats;
+    // NSC_OK, or what the call returns before anything is launched; `outputs`: the call's output tensors are all there
+    int check(bool outputs) const
+    {
+        if (n_clouds < 0 || n_poses < 0 || total_rows < 0 || max_voxels < 0 || !params || !stats || !offsets) return NSC_EINVAL;
+        if (dtype != NSC_MAP_DTYPE_F32 && dtype != NSC_MAP_DTYPE_F64) return NSC_EINVAL;
+        if (stride_floats != 3 && !(stride_floats == 4 && dtype == NSC_MAP_DTYPE_F32)) return NSC_EINVAL;
+        if (!(params->voxel_size > 0.0) || !isfinite(params->voxel_size) || !isfinite(params->origin[0]) ||
+            !isfinite(params->origin[1]) || !isfinite(params->origin[2]))
+            return NSC_EINVAL;
+        if ((total_rows > 0 && !points) || (n_poses > 0 && !poses) || (max_voxels > 0 && !outputs)) return NSC_EINVAL;
+        if (total_rows > NSC_MAP_MAX_ROWS || max_voxels > NSC_MAP_MAX_VOXELS) return NSC_EUNSUPPORTED;
+        return NSC_OK;
+    }
+    MapGrid grid() const { return MapGrid{params->voxel_size, {params->origin[0], params->origin[1], params->origin[2]}}; }
+    template <class T> InsertRows<T> rows() const
+    {
+        return InsertRows<T>{static_cast<const T *>(points), stride_floats, reinterpret_cast<const long long *>(offsets),
+                             n_clouds, (long long)total_rows, poses, n_poses, reinterpret_cast<const long long *>(pose_ids),
+                             grid()};
+    }
+    // launch(rows), the rows being float32 or float64 as `dtype` says
+    template <class Launch> void with_rows(Launch launch) const
+    {
+        if (dtype == NSC_MAP_DTYPE_F32) launch(rows<float>()); else launch(rows<double>());
+    }
+};
 
 template <class S>
 size_t workspace_bytes(int64_t total_rows, int64_t max_voxels)
@@ -464,36 +491,24 @@ size_t workspace_bytes(int64_t total_rows, int64_t max_voxels)
 
 // The six launches of a build over slots of type S; `out` is what the write pass writes per voxel beside info and keys
 template <class S, class Out>
-int launch_build(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_clouds,
-                 int64_t total_rows, const double *poses, int32_t n_poses, const int64_t *pose_ids,
-                 const NscMapParams *params, int64_t max_voxels, int64_t *info, int64_t *keys, int64_t *stats, const Out &out,
-                 const MapRegions<S> &r, void *stream)
+int launch_build(const MapArgs &a, int64_t *info, int64_t *keys, const Out &out, const MapRegions<S> &r, void *stream)
 {
-    const MapGrid g{params->voxel_size, {params->origin[0], params->origin[1], params->origin[2]}};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 threads(MAP_THREADS), per_rows(blocks_for(total_rows, INSERT_ROWS, NSC_MAP_INSERT_BLOCKS));
-    const long long *off = reinterpret_cast<const long long *>(offsets), *ids = reinterpret_cast<const long long *>(pose_ids);
-    long long *st = reinterpret_cast<long long *>(stats);
+    const dim3 threads(MAP_THREADS), per_rows(blocks_for(a.total_rows, INSERT_ROWS, NSC_MAP_INSERT_BLOCKS));
+    long long *st = reinterpret_cast<long long *>(a.stats);
     const long long n_slot_words = r.cap * slot_words<S>();
     hipLaunchKernelGGL(map_clear_kernel, dim3(blocks_for(n_slot_words > r.n_words ? n_slot_words : r.n_words, MAP_THREADS, MAP_SLOT_BLOCKS)),
                        threads, 0, s, reinterpret_cast<u64 *>(r.slots), n_slot_words, slot_words<S>(), r.bits, r.n_words, st);
-    if (dtype == NSC_MAP_DTYPE_F32)
-        hipLaunchKernelGGL((map_insert_kernel<float, S>), per_rows, threads, 0, s,
-                           InsertRows<float>{static_cast<const float *>(points), stride_floats, off, n_clouds,
-                                             (long long)total_rows, poses, n_poses, ids, g},
-                           r.slots, r.cap, st);
-    else
-        hipLaunchKernelGGL((map_insert_kernel<double, S>), per_rows, threads, 0, s,
-                           InsertRows<double>{static_cast<const double *>(points), stride_floats, off, n_clouds,
-                                              (long long)total_rows, poses, n_poses, ids, g},
-                           r.slots, r.cap, st);
+    a.with_rows([&](auto in) {
+        hipLaunchKernelGGL((map_insert_kernel<typename decltype(in)::scalar, S>), per_rows, threads, 0, s, in, r.slots, r.cap, st);
+    });
     const dim3 per_slot(blocks_for(r.cap, MAP_THREADS, MAP_SLOT_BLOCKS));
     hipLaunchKernelGGL(map_mark_kernel<S>, per_slot, threads, 0, s, r.slots, r.cap, r.bits, r.n_words);
     hipLaunchKernelGGL(map_count_kernel, dim3(blocks_for(r.n_tiles, MAP_THREADS / 64, MAP_SLOT_BLOCKS)), threads, 0, s,
                        r.bits, r.n_words, r.n_tiles, r.prefix, r.tile);
-    hipLaunchKernelGGL(map_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, r.tile, r.n_tiles, (long long)max_voxels, st);
+    hipLaunchKernelGGL(map_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, r.tile, r.n_tiles, (long long)a.max_voxels, st);
     hipLaunchKernelGGL((map_write_kernel<S, Out>), per_slot, threads, 0, s, r.slots, r.cap,
-                       MapPlaces{r.bits, r.prefix, r.tile, r.n_words}, (long long)max_voxels,
+                       MapPlaces{r.bits, r.prefix, r.tile, r.n_words}, (long long)a.max_voxels,
                        reinterpret_cast<long long *>(info), reinterpret_cast<long long *>(keys), out);
     return launch_status();
 }
@@ -504,19 +519,13 @@ bool dist_ok(const NscMapDistParams *dist)
            isfinite(dist->sigma_floor);
 }
 
-DistRule dist_rule(const NscMapParams *params, const NscMapDistParams *dist)
-{
-    return DistRule{MapGrid{params->voxel_size, {params->origin[0], params->origin[1], params->origin[2]}},
-                    dist->eigen_ratio, dist->sigma_floor * dist->sigma_floor, (long long)dist->min_points};
-}
-
 // ---- nsc_map_insert_dist: rows added to a kept map ---------------------------------------------------------------------
 // The kept index is the build's table: (key + 1, place) at the slots the build's probes walked, so new keys are claimed in
 // it as the build claims them.  Nothing below walks the 2 max_voxels slots or the max_voxels records: every pass is over
 // the call's rows, or over the places they reached.
 //
 // Launch sequence (8; the grids depend on total_rows alone):
-//   clear       map_clear_kernel on the call's first-row bitmap and its counters
+//   clear       call_clear_kernel, the clear of every call on a kept map, on the call's first-row bitmap and its counters
 //   claim       per row: the row's slot, found or claimed (64-bit CAS) along the build's probe sequence and kept in the
 //               workspace; in the place word of a slot claimed in this call the smallest local row, PLACE_NEW | row
 //               (atomic min); the counters of dropped, unplaced and used rows into the kept stats
@@ -535,6 +544,18 @@ constexpr u64 PLACE_NEW = 1ULL << 62;        // no place reaches these bits: pla
 constexpr u64 PLACE_TOUCHED = 1ULL << 61;
 static_assert(NSC_MAP_MAX_VOXELS <= (1LL << 61) && NSC_MAP_MAX_ROWS <= (1LL << 61), "the flags lie above places and rows");
 enum { CALL_FOUND = NSC_MAP_STAT_FOUND, CALL_WRITTEN = NSC_MAP_STAT_WRITTEN, CALL_TOUCHED, CALL_WORDS = NSC_MAP_STATS };
+
+// The touched list of a call, of an insertion and of a removal: the first row to reach a place in this call (an atomic or
+// of PLACE_TOUCHED on the place word decides which) appends the place's slot h.  `there` is the place word as the caller's
+// guard read it: the one load serves both.  Returns the place, the flag stripped
+__device__ __forceinline__ long long touch_place(u64 *place_word, u64 there, long long h, long long *touched, long long *call)
+{
+    if (!(there & PLACE_TOUCHED)) {
+        there = atomicOr(place_word, PLACE_TOUCHED);
+        if (!(there & PLACE_TOUCHED)) touched[atomicAdd(reinterpret_cast<u64 *>(&call[CALL_TOUCHED]), 1ULL)] = h;
+    }
+    return (long long)(there & ~PLACE_TOUCHED);
+}
 
 struct KeptMap {
     double *voxels; u64 *index; long long *info, *keys, *moments, *stats, *cursor;
@@ -569,34 +590,27 @@ InsertRegions insert_regions(void *ws, long long total_rows)
 template <class T>
 __global__ __launch_bounds__(MAP_THREADS) void ins_claim_kernel(InsertRows<T> in, KeptMap m, u64 *bits, long long *slot)
 {
-    const int tid = threadIdx.x;
     const long long cap = 2 * m.max_voxels;
     const bool full = m.full();
     RowCounters cnt;
-    const long long n_sweeps = (in.total + INSERT_ROWS - 1) / INSERT_ROWS;
-    for (long long sweep = blockIdx.x; sweep < n_sweeps; sweep += gridDim.x) {
-        CloudSpan span;
-        for (int k = 0; k < INSERT_ROWS / MAP_THREADS; ++k) {
-            const long long row = sweep * INSERT_ROWS + (long long)k * MAP_THREADS + tid;
-            if (row >= in.total) break;
-            double w[3], u[3];
-            u64 key;
-            int kind = locate_row(in, row, span, w, u, key);
-            long long h = -1;
-            bool claimed = false;
-            if (kind == C_USED && (h = claim_slot(m.index, 2, cap, key, claimed)) < 0) kind = C_UNPLACED;
-            cnt.count(kind);
-            slot[row] = h;
-            if (h < 0) continue;
-            if (full) {
-                if (claimed) atomicOr(&bits[row >> 6], 1ULL << (row & 63));
-                continue;
-            }
-            // an empty slot's place word is ~0, which has PLACE_NEW set and is above every PLACE_NEW | row
-            const u64 mine = PLACE_NEW | (u64)row, there = peek(&m.index[2 * h + 1]);
-            if ((there & PLACE_NEW) && there > mine) atomicMin(&m.index[2 * h + 1], mine);
+    for_each_row(in.total, [&](long long row, CloudSpan &span) {
+        double w[3], u[3];
+        u64 key;
+        int kind = locate_row(in, row, span, w, u, key);
+        long long h = -1;
+        bool claimed = false;
+        if (kind == C_USED && (h = claim_slot(m.index, 2, cap, key, claimed)) < 0) kind = C_UNPLACED;
+        cnt.count(kind);
+        slot[row] = h;
+        if (h < 0) return;
+        if (full) {
+            if (claimed) atomicOr(&bits[row >> 6], 1ULL << (row & 63));
+            return;
         }
-    }
+        // an empty slot's place word is ~0, which has PLACE_NEW set and is above every PLACE_NEW | row
+        const u64 mine = PLACE_NEW | (u64)row, there = peek(&m.index[2 * h + 1]);
+        if ((there & PLACE_NEW) && there > mine) atomicMin(&m.index[2 * h + 1], mine);
+    });
     cnt.add_to(m.counters);
 }
 
@@ -633,41 +647,29 @@ template <class T>
 __global__ __launch_bounds__(MAP_THREADS) void ins_accumulate_kernel(InsertRows<T> in, KeptMap m, const long long *slot,
                                                                      long long *touched, long long *call)
 {
-    const int tid = threadIdx.x;
     const long long cloud0 = m.cursor[1];
-    const long long n_sweeps = (in.total + INSERT_ROWS - 1) / INSERT_ROWS;
-    for (long long sweep = blockIdx.x; sweep < n_sweeps; sweep += gridDim.x) {
-        CloudSpan span;
-        for (int k = 0; k < INSERT_ROWS / MAP_THREADS; ++k) {
-            const long long row = sweep * INSERT_ROWS + (long long)k * MAP_THREADS + tid;
-            if (row >= in.total) break;
-            const long long h = slot[row];
-            if (h < 0) continue;
-            u64 there = peek(&m.index[2 * h + 1]);
-            if (there & PLACE_NEW) continue;                           // ~0, a voxel past the outputs: its rows are counted, no more
-            if (!(there & PLACE_TOUCHED)) {
-                there = atomicOr(&m.index[2 * h + 1], PLACE_TOUCHED);
-                if (!(there & PLACE_TOUCHED))
-                    touched[atomicAdd(reinterpret_cast<u64 *>(&call[CALL_TOUCHED]), 1ULL)] = h;
-            }
-            const long long pos = (long long)(there & ~PLACE_TOUCHED);
-            // a row with a slot has a cloud, a pose, finite coordinates and a voxel: the claim pass found C_USED
-            double w[3], u[3];
-            u64 key;
-            locate_row(in, row, span, w, u, key);
-            const int c = span.c;
-            long long *info = m.info + 4 * pos;
-            const long long cloud = cloud0 + c;
-            atomicAdd(reinterpret_cast<u64 *>(info), 1ULL);
-            // min and max only move one way: a value read before the atomic that already beats ours stays beaten
-            if ((long long)peek(reinterpret_cast<u64 *>(info + 2)) > cloud)
-                __hip_atomic_fetch_min(info + 2, cloud, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((long long)peek(reinterpret_cast<u64 *>(info + 3)) < cloud)
-                __hip_atomic_fetch_max(info + 3, cloud, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            long long *mo = m.moments + 9 * pos;
-            row_moments(u, [mo](int t, long long v) { atomicAdd(reinterpret_cast<u64 *>(mo + t), (u64)v); });
-        }
-    }
+    for_each_row(in.total, [&](long long row, CloudSpan &span) {
+        const long long h = slot[row];
+        if (h < 0) return;
+        const u64 there = peek(&m.index[2 * h + 1]);
+        if (there & PLACE_NEW) return;                                 // ~0, a voxel past the outputs: its rows are counted, no more
+        const long long pos = touch_place(&m.index[2 * h + 1], there, h, touched, call);
+        // a row with a slot has a cloud, a pose, finite coordinates and a voxel: the claim pass found C_USED
+        double w[3], u[3];
+        u64 key;
+        locate_row(in, row, span, w, u, key);
+        const int c = span.c;
+        long long *info = m.info + 4 * pos;
+        const long long cloud = cloud0 + c;
+        atomicAdd(reinterpret_cast<u64 *>(info), 1ULL);
+        // min and max only move one way: a value read before the atomic that already beats ours stays beaten
+        if ((long long)peek(reinterpret_cast<u64 *>(info + 2)) > cloud)
+            __hip_atomic_fetch_min(info + 2, cloud, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((long long)peek(reinterpret_cast<u64 *>(info + 3)) < cloud)
+            __hip_atomic_fetch_max(info + 3, cloud, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        long long *mo = m.moments + 9 * pos;
+        row_moments(u, [mo](int t, long long v) { atomicAdd(reinterpret_cast<u64 *>(mo + t), (u64)v); });
+    });
 }
 
 enum { PLACE_RECORD, PLACE_EMPTIED, PLACE_INCONSISTENT };
@@ -717,6 +719,24 @@ __global__ __launch_bounds__(MAP_THREADS) void ins_refresh_kernel(KeptMap m, con
     }
 }
 
+// The clear of every call on a kept map: the first-row bitmap and the counters of the insertion (bits, ins_call), the
+// counters of the removal (rem_call, removed), and for a replacement `placed` and its cursor, set to the caller's bases.
+// What a call does not have is null: an insertion alone has the first two, a removal alone the second two
+__global__ __launch_bounds__(MAP_THREADS) void call_clear_kernel(u64 *bits, long long n_words, long long *ins_call,
+                                                                 long long *rem_call, long long *removed, long long *placed,
+                                                                 long long *cursor, long long first_row, long long first_cloud)
+{
+    const long long i0 = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
+    for (long long i = i0; i < n_words; i += (long long)gridDim.x * MAP_THREADS) bits[i] = 0ULL;
+    if (i0 < CALL_WORDS) {
+        if (rem_call) rem_call[i0] = 0;
+        if (ins_call) ins_call[i0] = 0;
+        if (placed) placed[i0] = 0;
+    }
+    if (removed && i0 < NSC_MAP_REMOVE_STATS) removed[i0] = 0;
+    if (i0 == 0 && cursor) { cursor[0] = first_row; cursor[1] = first_cloud; }
+}
+
 // the insertion's launches after its clear
 template <class T>
 void launch_insert_passes(const InsertRows<T> &in, const KeptMap &m, const DistRule &rule, const InsertRegions &r, hipStream_t s)
@@ -738,8 +758,9 @@ void launch_insert_passes(const InsertRows<T> &in, const KeptMap &m, const DistR
 template <class T>
 void launch_insert_rows(const InsertRows<T> &in, const KeptMap &m, const DistRule &rule, const InsertRegions &r, hipStream_t s)
 {
-    hipLaunchKernelGGL(map_clear_kernel, dim3(blocks_for(r.n_words, MAP_THREADS, MAP_SLOT_BLOCKS)), dim3(MAP_THREADS), 0, s,
-                       static_cast<u64 *>(nullptr), 0LL, 1, r.bits, r.n_words, r.call);
+    long long *const none = nullptr;
+    hipLaunchKernelGGL(call_clear_kernel, dim3(blocks_for(r.n_words, MAP_THREADS, MAP_SLOT_BLOCKS)), dim3(MAP_THREADS), 0, s,
+                       r.bits, r.n_words, r.call, none, none, none, none, 0LL, 0LL);
     launch_insert_passes(in, m, rule, r, s);
 }
 
@@ -795,61 +816,32 @@ __device__ __forceinline__ long long find_slot(const u64 *index, long long cap, 
     return -1;
 }
 
-// bits, ins_call, placed and cursor may be null (a removal alone)
-__global__ __launch_bounds__(MAP_THREADS) void call_clear_kernel(u64 *bits, long long n_words, long long *ins_call,
-                                                                 long long *rem_call, long long *removed, long long *placed,
-                                                                 long long *cursor, long long first_row, long long first_cloud)
-{
-    const long long i0 = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
-    for (long long i = i0; i < n_words; i += (long long)gridDim.x * MAP_THREADS) bits[i] = 0ULL;
-    if (i0 < CALL_WORDS) {
-        rem_call[i0] = 0;
-        if (ins_call) ins_call[i0] = 0;
-        if (placed) placed[i0] = 0;
-    }
-    if (i0 < NSC_MAP_REMOVE_STATS) removed[i0] = 0;
-    if (i0 == 0 && cursor) { cursor[0] = first_row; cursor[1] = first_cloud; }
-}
-
 template <class T>
 __global__ __launch_bounds__(MAP_THREADS) void rem_rows_kernel(InsertRows<T> in, KeptMap m, long long *touched, long long *call,
                                                                long long *removed)
 {
-    const int tid = threadIdx.x;
     const long long cap = 2 * m.max_voxels;
     RowCounters cnt;
-    const long long n_sweeps = (in.total + INSERT_ROWS - 1) / INSERT_ROWS;
-    for (long long sweep = blockIdx.x; sweep < n_sweeps; sweep += gridDim.x) {
-        CloudSpan span;
-        for (int k = 0; k < INSERT_ROWS / MAP_THREADS; ++k) {
-            const long long row = sweep * INSERT_ROWS + (long long)k * MAP_THREADS + tid;
-            if (row >= in.total) break;
-            double w[3], u[3];
-            u64 key;
-            int kind = locate_row(in, row, span, w, u, key);
-            long long pos = -1;
-            if (kind == C_USED) {
-                const long long h = find_slot(m.index, cap, key);
-                u64 there = h < 0 ? ~0ULL : peek(&m.index[2 * h + 1]);
-                // ~0 has PLACE_NEW set: a voxel past the outputs holds no sums to take the row from
-                if (!(there & PLACE_NEW) && (long long)(there & ~PLACE_TOUCHED) < m.max_voxels) {
-                    pos = (long long)(there & ~PLACE_TOUCHED);
-                    if (!(there & PLACE_TOUCHED)) {
-                        there = atomicOr(&m.index[2 * h + 1], PLACE_TOUCHED);
-                        if (!(there & PLACE_TOUCHED))
-                            touched[atomicAdd(reinterpret_cast<u64 *>(&call[CALL_TOUCHED]), 1ULL)] = h;
-                    }
-                } else {
-                    kind = C_UNPLACED;                                  // counted as missing
-                }
-            }
-            cnt.count(kind);
-            if (kind != C_USED) continue;
-            atomicAdd(reinterpret_cast<u64 *>(m.info + 4 * pos), ~0ULL);              // count - 1
-            long long *mo = m.moments + 9 * pos;
-            row_moments(u, [mo](int t, long long v) { atomicAdd(reinterpret_cast<u64 *>(mo + t), (u64)(-v)); });
+    for_each_row(in.total, [&](long long row, CloudSpan &span) {
+        double w[3], u[3];
+        u64 key;
+        int kind = locate_row(in, row, span, w, u, key);
+        long long pos = -1;
+        if (kind == C_USED) {
+            const long long h = find_slot(m.index, cap, key);
+            const u64 there = h < 0 ? ~0ULL : peek(&m.index[2 * h + 1]);
+            // ~0 has PLACE_NEW set: a voxel past the outputs holds no sums to take the row from
+            if (!(there & PLACE_NEW) && (long long)(there & ~PLACE_TOUCHED) < m.max_voxels)
+                pos = touch_place(&m.index[2 * h + 1], there, h, touched, call);
+            else
+                kind = C_UNPLACED;                                      // counted as missing
         }
-    }
+        cnt.count(kind);
+        if (kind != C_USED) return;
+        atomicAdd(reinterpret_cast<u64 *>(m.info + 4 * pos), ~0ULL);                  // count - 1
+        long long *mo = m.moments + 9 * pos;
+        row_moments(u, [mo](int t, long long v) { atomicAdd(reinterpret_cast<u64 *>(mo + t), (u64)(-v)); });
+    });
     cnt.add_from(removed);
 }
 
@@ -891,9 +883,9 @@ template <class T>
 void launch_remove_rows(const InsertRows<T> &in, const KeptMap &m, const DistRule &rule, const RemoveRegions &r,
                         long long *removed, hipStream_t s)
 {
-    hipLaunchKernelGGL(call_clear_kernel, dim3(1), dim3(MAP_THREADS), 0, s, static_cast<u64 *>(nullptr), 0LL,
-                       static_cast<long long *>(nullptr), r.call, removed, static_cast<long long *>(nullptr),
-                       static_cast<long long *>(nullptr), 0LL, 0LL);
+    long long *const none = nullptr;
+    hipLaunchKernelGGL(call_clear_kernel, dim3(1), dim3(MAP_THREADS), 0, s, static_cast<u64 *>(nullptr), 0LL, none, r.call,
+                       removed, none, none, 0LL, 0LL);
     launch_remove_passes(in, m, rule, r, removed, s);
 }
 
@@ -1031,12 +1023,7 @@ __global__ __launch_bounds__(MAP_THREADS) void rehash_move_kernel(RehashSource s
         }
         __syncthreads();
         if (wave == 0) {
-            const int v = seg[lane];
-            int inc = v;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int u = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += u;
-            }
+            const int v = seg[lane], inc = nsc_wave_scan(v);
             seg[lane] = inc - v;
             if (lane == 63) seg[TILE_SEGMENTS] = inc;
         }
@@ -1071,18 +1058,19 @@ __global__ __launch_bounds__(MAP_THREADS) void rehash_move_kernel(RehashSource s
     if (lane == 0 && full) atomicAdd(reinterpret_cast<u64 *>(&rehashed[NSC_MAP_REHASH_STAT_TABLE_FULL]), (u64)full);
 }
 
-// what the three calls on a kept map take alike
-struct KeptArgs {
-    const void *points; int32_t dtype, stride_floats; const int64_t *offsets; int32_t n_clouds; int64_t total_rows;
-    const double *poses; int32_t n_poses; const int64_t *pose_ids; const NscMapParams *params; const NscMapDistParams *dist;
-    int64_t max_voxels; double *voxels; uint64_t *index; int64_t *info, *keys, *moments, *stats;
-    // NSC_OK, or the refusal of nsc_map_build_dist and of a missing `moments`
-    int check() const
+// MapArgs and the kept tensors: what nsc_map_build_dist makes and the three calls on a kept map change
+struct KeptArgs : MapArgs {
+    const NscMapDistParams *dist;
+    double *voxels; uint64_t *index; int64_t *info, *keys, *moments;
+    // NSC_OK, or the refusal of nsc_map_build_dist, and of a missing `moments` where the call needs them
+    int check(bool need_moments) const
     {
-        if (const int st = check_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, params,
-                                       max_voxels, voxels && index && info && keys, stats))
-            return st;
-        return dist_ok(dist) && moments ? NSC_OK : NSC_EINVAL;
+        if (const int st = MapArgs::check(voxels && index && info && keys)) return st;
+        return dist_ok(dist) && (moments || !need_moments) ? NSC_OK : NSC_EINVAL;
+    }
+    DistRule rule() const
+    {
+        return DistRule{grid(), dist->eigen_ratio, dist->sigma_floor * dist->sigma_floor, (long long)dist->min_points};
     }
     KeptMap map(int64_t *cursor) const
     {
@@ -1090,12 +1078,6 @@ struct KeptArgs {
                        reinterpret_cast<long long *>(keys), reinterpret_cast<long long *>(moments),
                        reinterpret_cast<long long *>(stats), reinterpret_cast<long long *>(cursor), (long long)max_voxels,
                        reinterpret_cast<long long *>(stats)};
-    }
-    template <class T> InsertRows<T> rows() const
-    {
-        return InsertRows<T>{static_cast<const T *>(points), stride_floats, reinterpret_cast<const long long *>(offsets),
-                             n_clouds, (long long)total_rows, poses, n_poses, reinterpret_cast<const long long *>(pose_ids),
-                             MapGrid{params->voxel_size, {params->origin[0], params->origin[1], params->origin[2]}}};
     }
 };
 
@@ -1134,13 +1116,12 @@ int nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, cons
                   const NscMapParams *params, int64_t max_voxels, double *out_points, int64_t *info, int64_t *keys,
                   int64_t *stats, void *ws, size_t ws_bytes, void *stream)
 {
-    if (const int st = check_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, params,
-                                   max_voxels, out_points && info && keys, stats))
-        return st;
+    const MapArgs a{points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params, max_voxels,
+                    stats};
+    if (const int st = a.check(out_points && info && keys)) return st;
     const MapRegions<MapSlot> r = map_regions<MapSlot>(ws, total_rows, max_voxels);
     if (r.total > 0 && (!ws || ws_bytes < r.total)) return NSC_EWORKSPACE;
-    return launch_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params,
-                        max_voxels, info, keys, stats, CentroidOut{out_points}, r, stream);
+    return launch_build(a, info, keys, CentroidOut{out_points}, r, stream);
 }
 
 int nsc_map_build_dist(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_clouds,
@@ -1149,15 +1130,13 @@ int nsc_map_build_dist(const void *points, int32_t dtype, int32_t stride_floats,
                        uint64_t *index, int64_t *info, int64_t *keys, int64_t *moments, int64_t *stats, void *ws,
                        size_t ws_bytes, void *stream)
 {
-    if (const int st = check_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, params,
-                                   max_voxels, voxels && index && info && keys, stats))
-        return st;
-    if (!dist_ok(dist)) return NSC_EINVAL;
+    const KeptArgs a{{points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params,
+                      max_voxels, stats}, dist, voxels, index, info, keys, moments};
+    if (const int st = a.check(false)) return st;
     const MapRegions<DistSlot> r = map_regions<DistSlot>(ws, total_rows, max_voxels);
     if (r.total > 0 && (!ws || ws_bytes < r.total)) return NSC_EWORKSPACE;
-    const DistOut out{voxels, reinterpret_cast<u64 *>(index), reinterpret_cast<long long *>(moments), dist_rule(params, dist)};
-    return launch_build(points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params,
-                        max_voxels, info, keys, stats, out, r, stream);
+    const DistOut out{voxels, reinterpret_cast<u64 *>(index), reinterpret_cast<long long *>(moments), a.rule()};
+    return launch_build(a, info, keys, out, r, stream);
 }
 
 size_t nsc_map_insert_workspace_bytes(int64_t total_rows)
@@ -1172,17 +1151,14 @@ int nsc_map_insert_dist(const void *points, int32_t dtype, int32_t stride_floats
                         uint64_t *index, int64_t *info, int64_t *keys, int64_t *moments, int64_t *stats, int64_t *cursor,
                         void *ws, size_t ws_bytes, void *stream)
 {
-    const KeptArgs a{points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params, dist,
-                     max_voxels, voxels, index, info, keys, moments, stats};
-    if (const int st = a.check()) return st;
+    const KeptArgs a{{points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params,
+                      max_voxels, stats}, dist, voxels, index, info, keys, moments};
+    if (const int st = a.check(true)) return st;
     if (!cursor) return NSC_EINVAL;
     const InsertRegions r = insert_regions(ws, total_rows);
     if (!ws || ws_bytes < r.total) return NSC_EWORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == NSC_MAP_DTYPE_F32)
-        launch_insert_rows(a.rows<float>(), a.map(cursor), dist_rule(params, dist), r, s);
-    else
-        launch_insert_rows(a.rows<double>(), a.map(cursor), dist_rule(params, dist), r, s);
+    a.with_rows([&](auto in) { launch_insert_rows(in, a.map(cursor), a.rule(), r, s); });
     return launch_status();
 }
 
@@ -1204,18 +1180,15 @@ int nsc_map_remove_dist(const void *points, int32_t dtype, int32_t stride_floats
                         uint64_t *index, int64_t *info, int64_t *keys, int64_t *moments, int64_t *stats, int64_t *removed,
                         void *ws, size_t ws_bytes, void *stream)
 {
-    const KeptArgs a{points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params, dist,
-                     max_voxels, voxels, index, info, keys, moments, stats};
-    if (const int st = a.check()) return st;
+    const KeptArgs a{{points, dtype, stride_floats, offsets, n_clouds, total_rows, poses, n_poses, pose_ids, params,
+                      max_voxels, stats}, dist, voxels, index, info, keys, moments};
+    if (const int st = a.check(true)) return st;
     if (!removed) return NSC_EINVAL;
     const RemoveRegions r = remove_regions(ws, 0, total_rows, false);
     if (!ws || ws_bytes < r.total) return NSC_EWORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     long long *rem = reinterpret_cast<long long *>(removed);
-    if (dtype == NSC_MAP_DTYPE_F32)
-        launch_remove_rows(a.rows<float>(), a.map(nullptr), dist_rule(params, dist), r, rem, s);
-    else
-        launch_remove_rows(a.rows<double>(), a.map(nullptr), dist_rule(params, dist), r, rem, s);
+    a.with_rows([&](auto in) { launch_remove_rows(in, a.map(nullptr), a.rule(), r, rem, s); });
     return launch_status();
 }
 
@@ -1226,21 +1199,19 @@ int nsc_map_replace_dist(const void *points, int32_t dtype, int32_t stride_float
                          int64_t *stats, int64_t first_row, int64_t first_cloud, int64_t *removed, int64_t *placed, void *ws,
                          size_t ws_bytes, void *stream)
 {
-    const KeptArgs a{points, dtype, stride_floats, offsets, n_clouds, total_rows, old_poses, n_poses, pose_ids, params, dist,
-                     max_voxels, voxels, index, info, keys, moments, stats};
-    if (const int st = a.check()) return st;
+    const KeptArgs a{{points, dtype, stride_floats, offsets, n_clouds, total_rows, old_poses, n_poses, pose_ids, params,
+                      max_voxels, stats}, dist, voxels, index, info, keys, moments};
+    if (const int st = a.check(true)) return st;
     if ((n_poses > 0 && !new_poses) || !removed || !placed || first_row < 0 || first_cloud < 0) return NSC_EINVAL;
     const InsertRegions ins = insert_regions(ws, total_rows);
     const RemoveRegions rem = remove_regions(ws, ins.total, total_rows, true);
     if (!ws || ws_bytes < rem.total) return NSC_EWORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     long long *rm = reinterpret_cast<long long *>(removed), *pl = reinterpret_cast<long long *>(placed);
-    if (dtype == NSC_MAP_DTYPE_F32)
-        launch_replace_rows(a.rows<float>(), new_poses, a.map(nullptr), dist_rule(params, dist), ins, rem,
-                            (long long)first_row, (long long)first_cloud, rm, pl, s);
-    else
-        launch_replace_rows(a.rows<double>(), new_poses, a.map(nullptr), dist_rule(params, dist), ins, rem,
-                            (long long)first_row, (long long)first_cloud, rm, pl, s);
+    a.with_rows([&](auto old_rows) {
+        launch_replace_rows(old_rows, new_poses, a.map(nullptr), a.rule(), ins, rem, (long long)first_row, (long long)first_cloud,
+                            rm, pl, s);
+    });
     return launch_status();
 }
 

@@ -19,6 +19,17 @@ template <class T> __device__ __forceinline__ T nsc_wave_sum(T v)
     return v;
 }
 
+// the inclusive scan of an integer over the 64 lanes of a wave: lane l gets the sum of lanes 0 .. l
+__device__ __forceinline__ int nsc_wave_scan(int v)
+{
+    const int lane = threadIdx.x & 63;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
 // ---- workspaces.  A workspace is laid out by ONE function that maps (base or null, shape) to a struct of typed pointers
 // plus `total`: the size query calls it with a null base, the entry points with the caller's pointer.
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }

@@ -318,6 +318,20 @@ class PreparedClouds:
         r0, r1 = int(self._row_host[i]), int(self._row_host[i + 1])
         return dict(points=self._buf["points"][r0:r1], covariances=self._buf["covariances"][r0:r1])
 
+    def packed(self, start: int = 0, stop: Optional[int] = None):
+        """The stored clouds ``start`` to ``stop`` (the end, if None) as packed rows -> (points (m,3) float64, offsets
+        (stop - start + 1,) int64 counted from 0): device views of the store; the offsets are a tensor of their own (one
+        launch) unless the range begins at the store's row 0.  An empty store gives (0,3) rows and the offsets [0]."""
+        n = len(self)
+        stop = n if stop is None else stop
+        if not 0 <= int(start) <= int(stop) <= n:
+            raise _lib.NscError(f"start and stop must satisfy 0 <= start <= stop <= {n}, got {start} and {stop}")
+        if self._buf is None:
+            self._reserve(0, 0, 0)
+        r0, r1 = int(self._row_host[int(start)]), int(self._row_host[int(stop)])
+        off = self._buf["row_offsets"][int(start):int(stop) + 1]
+        return self._buf["points"][r0:r1], off if r0 == 0 else off - r0
+
 
 def _ids(ids, device):
     t = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids, np.int64).reshape(-1))

@@ -28,6 +28,7 @@ Not part of this module: insertion into a kept table, free space or ray casting,
 colour, meshes.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -62,6 +63,117 @@ def _pack(ts, device):
     off[1:] = np.cumsum([int(t.shape[0]) for t in ts])
     pts = torch.cat(ts, 0).contiguous() if ts else torch.zeros((0, 3), dtype=dtype, device=device)
     return pts, torch.from_numpy(off).to(device)
+
+
+def _is_packed(clouds):
+    return isinstance(clouds, tuple) and len(clouds) == 2 and isinstance(clouds[1], torch.Tensor) and clouds[1].ndim == 1
+
+
+def _host_rows(clouds, poses, device, check):
+    """The host form of a call's input -> what its ``*_device`` form takes: ``clouds`` a sequence of (n,3|4) host arrays
+    or tensors, or a packed ``(points, offsets)`` pair of device tensors; ``poses`` (P,4,4), host or device.  Returns
+    (points, offsets, float64 poses on ``device``, check(number of clouds, number of poses)); ``check`` is where the
+    caller refuses what it can on the host, before anything goes to the device."""
+    packed = _is_packed(clouds)
+    clouds = clouds if packed else _tensors(clouds)
+    pose = GlobalMap._poses(poses)
+    checked = check(int(clouds[1].numel()) - 1 if packed else len(clouds), int(pose.shape[0]))
+    dev = _device(device)
+    pts, off = clouds if packed else _pack(clouds, dev)
+    return pts, off, pose.to(device=dev, dtype=torch.float64), checked
+
+
+def _host_clouds(clouds, poses, pose_ids, device):
+    """_host_rows for clouds with a pose per id -> (points, offsets, poses, ids); host ids are refused before anything
+    goes to the device and stay on the host"""
+    return _host_rows(clouds, poses, device, lambda B, P: GlobalMap._host_ids(pose_ids, B, P))
+
+
+def _host_scans(scans, init_poses, device):
+    """_host_rows for scans with one pose each -> (points, offsets, poses, number of scans)"""
+    def one_each(S, P):
+        if P != S:
+            raise _lib.NscError(f"init_poses must have one (4,4) pose per scan ({S}), got {P}")
+        return S
+    return _host_rows(scans, init_poses, device, one_each)
+
+
+def _prepared_clouds(store, poses, pose_ids, start=0, stop=None):
+    """_host_clouds for the clouds ``start`` to ``stop`` (the end, if None) of a ``PreparedClouds``, on the store's
+    device; the caller has checked the range"""
+    stop = len(store) if stop is None else stop
+    pose = GlobalMap._poses(poses)
+    ids = GlobalMap._host_ids(pose_ids, stop - start, int(pose.shape[0]))
+    pts, off = store.packed(start, stop)
+    return pts, off, pose.to(device=store.device, dtype=torch.float64), ids
+
+
+_FORMATS = ((torch.float32, 3), (torch.float32, 4), (torch.float64, 3))
+
+
+def _rows(points, offsets, what):
+    """checked packed rows -> (contiguous rows, int64 offsets, number of clouds, number of rows, dtype code)"""
+    if points.ndim != 2 or (points.dtype, int(points.shape[1])) not in _FORMATS:
+        raise _lib.NscError(f"{what} must be (N,3) or (N,4) float32 or (N,3) float64")
+    pts, off = points.contiguous(), offsets.contiguous().to(torch.int64).reshape(-1)
+    if int(off.numel()) < 1:
+        raise _lib.NscError("offsets must have one entry more than there are clouds")
+    return pts, off, int(off.numel()) - 1, int(pts.shape[0]), \
+        _lib.MAP_DTYPE_F64 if pts.dtype == torch.float64 else _lib.MAP_DTYPE_F32
+
+
+_Clouds = namedtuple("_Clouds", "pts off B N dtype pose P ids")
+
+
+def _clouds(points, offsets, poses, pose_ids):
+    """checked device input of a build, an insertion or a removal -> (rows, offsets, clouds, rows, dtype code, float64
+    poses, poses, device ids or None)"""
+    for t, name in ((points, "points"), (offsets, "offsets"), (poses, "poses")):
+        _lib.require_cuda(t, name)
+    dev = points.device
+    pts, off, B, N, dtype = _rows(points, offsets, "points")
+    if poses.ndim != 3 or tuple(poses.shape[1:]) != (4, 4):
+        raise _lib.NscError("poses must be (P,4,4)")
+    pose = poses.contiguous().to(torch.float64)
+    P = int(pose.shape[0])
+    ids = GlobalMap._host_ids(pose_ids, B, P)
+    if ids is not None:
+        ids = ids.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
+        if int(ids.numel()) != B:
+            raise _lib.NscError(f"pose_ids must have one entry per cloud ({B}), got {int(ids.numel())}")
+    return _Clouds(pts, off, B, N, dtype, pose, P, ids)
+
+
+def _row_args(c, params, new_poses=None):
+    """the ctypes arguments every map call starts with, from _clouds' tuple: the rows, the poses (the old and the new of a
+    replacement), the ids and the grid"""
+    poses = (_lib.ptr(c.pose),) if new_poses is None else (_lib.ptr(c.pose), _lib.ptr(new_poses))
+    return (_lib.ptr(c.pts), c.dtype, int(c.pts.shape[1]), _lib.ptr(c.off), c.B, c.N, *poses, c.P, _lib.ptr(c.ids),
+            C.byref(params))
+
+
+def _outputs(shapes, out, device):
+    """The output tensors of a ``*_device`` call, name -> (shape, dtype) in ``shapes``: allocated, or the caller's
+    ``out``, each checked"""
+    if out is None:
+        return {k: torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
+    for k, (shape, dt) in shapes.items():
+        t = out.get(k)
+        if t is None or tuple(t.shape) != shape or t.dtype != dt or t.device != device or not t.is_contiguous():
+            raise _lib.NscError(f"out[{k!r}] must be a contiguous {shape} {dt} tensor on {device}")
+    return out
+
+
+def _result(out, per_voxel):
+    """A call's buffers -> the dict its host form returns, in one read of the stats: per_voxel(n)'s entries for the n
+    voxels written, their info columns and keys, the stats by name and ``complete``"""
+    stats = dict(zip(_lib.MAP_STAT_NAMES, out["stats"].cpu().tolist()))
+    n = stats["voxels_written"]
+    info = out["info"][:n]
+    res = dict(per_voxel(n), count=info[:, 0], first_row=info[:, 1], first_cloud=info[:, 2], last_cloud=info[:, 3],
+               keys=out["keys"][:n], **stats)
+    res["complete"] = stats["voxels_found"] == stats["voxels_written"] and stats["rows_unplaced"] == 0
+    return res
 
 
 class GlobalMap:
@@ -109,53 +221,23 @@ class GlobalMap:
         (max_voxels,4) int64 = [count, first_row, first_cloud, last_cloud], keys (max_voxels,) int64 and stats
         (``_lib.MAP_STAT_NAMES``) int64; entries past stats[1] = voxels_written are not defined.  ``out``: a dict of
         those four tensors to write into, for a map that is rebuilt after every closure."""
-        for t, name in ((points, "points"), (offsets, "offsets"), (poses, "poses")):
-            _lib.require_cuda(t, name)
-        dev = points.device
-        if points.ndim != 2 or (points.dtype, int(points.shape[1])) not in (
-                (torch.float32, 3), (torch.float32, 4), (torch.float64, 3)):
-            raise _lib.NscError("points must be (N,3) or (N,4) float32 or (N,3) float64")
-        if poses.ndim != 3 or tuple(poses.shape[1:]) != (4, 4):
-            raise _lib.NscError("poses must be (P,4,4)")
-        pts, off = points.contiguous(), offsets.contiguous().to(torch.int64).reshape(-1)
-        pose = poses.contiguous().to(torch.float64)
-        B, N, P = int(off.numel()) - 1, int(pts.shape[0]), int(pose.shape[0])
-        if B < 0:
-            raise _lib.NscError("offsets must have one entry more than there are clouds")
-        ids = self._host_ids(pose_ids, B, P)
-        if ids is not None:
-            ids = ids.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
-            if int(ids.numel()) != B:
-                raise _lib.NscError(f"pose_ids must have one entry per cloud ({B}), got {int(ids.numel())}")
+        c = _clouds(points, offsets, poses, pose_ids)
+        dev, N = c.pts.device, c.N
         M = N if self.max_voxels is None else self.max_voxels
-        shapes = dict(points=((M, 3), torch.float64), info=((M, 4), torch.int64), keys=((M,), torch.int64),
-                      stats=((_lib.MAP_STATS,), torch.int64))
-        if out is None:
-            out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
-        for k, (shape, dt) in shapes.items():
-            t = out[k]
-            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise _lib.NscError(f"out[{k!r}] must be a contiguous {shape} {dt} tensor on {dev}")
+        out = _outputs(dict(points=((M, 3), torch.float64), info=((M, 4), torch.int64), keys=((M,), torch.int64),
+                            stats=((_lib.MAP_STATS,), torch.int64)), out, dev)
         L = _lib.lib()
         ws = _workspace(L.nsc_map_workspace_bytes(N, M), dev)
-        dtype = _lib.MAP_DTYPE_F64 if pts.dtype == torch.float64 else _lib.MAP_DTYPE_F32
         with torch.cuda.device(dev):
-            status = L.nsc_map_build(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off), B, N, _lib.ptr(pose), P,
-                                     _lib.ptr(ids), C.byref(self.params), M, _lib.ptr(out["points"]),
-                                     _lib.ptr(out["info"]), _lib.ptr(out["keys"]), _lib.ptr(out["stats"]),
-                                     _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+            status = L.nsc_map_build(*_row_args(c, self.params), M, _lib.ptr(out["points"]), _lib.ptr(out["info"]),
+                                     _lib.ptr(out["keys"]), _lib.ptr(out["stats"]), _lib.ptr(ws), int(ws.numel()),
+                                     _lib.stream_ptr(dev))
         _lib.check(status, "nsc_map_build")
         return out
 
     def _result(self, out):
         """build_device's buffers -> the dict ``build`` returns (one read of the stats)"""
-        stats = dict(zip(_lib.MAP_STAT_NAMES, out["stats"].cpu().tolist()))
-        n = stats["voxels_written"]
-        info = out["info"][:n]
-        res = dict(points=out["points"][:n], count=info[:, 0], first_row=info[:, 1], first_cloud=info[:, 2],
-                   last_cloud=info[:, 3], keys=out["keys"][:n], **stats)
-        res["complete"] = stats["voxels_found"] == stats["voxels_written"] and stats["rows_unplaced"] == 0
-        return res
+        return _result(out, lambda n: dict(points=out["points"][:n]))
 
     @staticmethod
     def _poses(poses):
@@ -171,23 +253,9 @@ class GlobalMap:
         points (V,3) float64, count, first_row, first_cloud, last_cloud, keys (V,) int64 -- the stats by name
         (voxels_found, voxels_written, rows_used, rows_not_finite, rows_outside, rows_without_pose, rows_unplaced) and
         ``complete``.  One synchronisation, to read the stats."""
-        packed = isinstance(clouds, tuple) and len(clouds) == 2 and isinstance(clouds[1], torch.Tensor) and \
-            clouds[1].ndim == 1
-        clouds = clouds if packed else _tensors(clouds)
-        pose = self._poses(poses)
-        # host ids are refused before anything goes to the device
-        ids = self._host_ids(pose_ids, int(clouds[1].numel()) - 1 if packed else len(clouds), int(pose.shape[0]))
-        dev = _device(self.device)
-        pts, off = clouds if packed else _pack(clouds, dev)
-        return self._result(self.build_device(pts, off, pose.to(device=dev, dtype=torch.float64), ids))
+        return self._result(self.build_device(*_host_clouds(clouds, poses, pose_ids, self.device)))
 
     def build_prepared(self, store: PreparedClouds, poses, pose_ids=None):
         """``build`` on the clouds a ``PreparedClouds`` holds: its float64 points and row offsets are the input as they
         stand, so the clouds stage 2 keeps are the map's clouds (one point per voxel of the store's own voxel size)."""
-        n = len(store)
-        pose = self._poses(poses)
-        ids = self._host_ids(pose_ids, n, int(pose.shape[0]))
-        if store._buf is None:
-            store._reserve(0, 0, 0)
-        pts, off = store._buf["points"][:store.n_rows], store._buf["row_offsets"][:n + 1]
-        return self._result(self.build_device(pts, off, pose.to(device=store.device, dtype=torch.float64), ids))
+        return self._result(self.build_device(*_prepared_clouds(store, poses, pose_ids)))

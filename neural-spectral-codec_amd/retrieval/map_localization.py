@@ -65,25 +65,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .geometric_verification import PreparedClouds, _device, _workspace
-from .global_map import GlobalMap, _pack, _tensors
-
-_FORMATS = ((torch.float32, 3), (torch.float32, 4), (torch.float64, 3))
-
-
-def _is_packed(clouds):
-    return isinstance(clouds, tuple) and len(clouds) == 2 and isinstance(clouds[1], torch.Tensor) and clouds[1].ndim == 1
-
-
-def _rows(points, offsets, what):
-    """checked packed rows -> (contiguous rows, int64 offsets, number of clouds, number of rows, dtype code)"""
-    if points.ndim != 2 or (points.dtype, int(points.shape[1])) not in _FORMATS:
-        raise _lib.NscError(f"{what} must be (N,3) or (N,4) float32 or (N,3) float64")
-    pts, off = points.contiguous(), offsets.contiguous().to(torch.int64).reshape(-1)
-    if int(off.numel()) < 1:
-        raise _lib.NscError("offsets must have one entry more than there are clouds")
-    return pts, off, int(off.numel()) - 1, int(pts.shape[0]), \
-        _lib.MAP_DTYPE_F64 if pts.dtype == torch.float64 else _lib.MAP_DTYPE_F32
+from .geometric_verification import PreparedClouds, _workspace
+from .global_map import (GlobalMap, _clouds, _host_clouds, _host_rows, _host_scans, _outputs, _prepared_clouds, _result,
+                         _row_args, _rows)
 
 
 class MapLocalizer:
@@ -166,60 +150,52 @@ class MapLocalizer:
         An insertable map always keeps moments, and cursor (2,) int64, set to this build's rows and clouds by two fills.
         ``out``: a dict of those tensors to write into."""
         dev = points.device
-        pts, off, B, N, dtype, pose, P, ids = self._clouds(points, offsets, poses, pose_ids)
+        c = _clouds(points, offsets, poses, pose_ids)
+        B, N = c.B, c.N
         M = N if self.max_voxels is None else self.max_voxels
-        shapes = dict(voxels=((M, _lib.MAP_VOXEL_DOUBLES), torch.float64), index=((2 * M, 2), torch.int64),
-                      info=((M, 4), torch.int64), keys=((M,), torch.int64), stats=((_lib.MAP_STATS,), torch.int64))
-        if moments or self.insertable or (out is not None and "moments" in out):
-            shapes["moments"] = ((M, 9), torch.int64)
-        if self.insertable:
-            shapes["cursor"] = ((2,), torch.int64)
-        if out is None:
-            out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
-        for k, (shape, dt) in shapes.items():
-            t = out[k]
-            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise _lib.NscError(f"out[{k!r}] must be a contiguous {shape} {dt} tensor on {dev}")
+        keeps_moments = moments or self.insertable or (out is not None and "moments" in out)
+        out = _outputs(self._shapes(M, keeps_moments, self.insertable), out, dev)
         L = _lib.lib()
         ws = _workspace(L.nsc_map_dist_workspace_bytes(N, M), dev)
         with torch.cuda.device(dev):
-            status = L.nsc_map_build_dist(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off), B, N, _lib.ptr(pose), P,
-                                          _lib.ptr(ids), C.byref(self.params), C.byref(self.dist), M,
-                                          _lib.ptr(out["voxels"]), _lib.ptr(out["index"]), _lib.ptr(out["info"]),
-                                          _lib.ptr(out["keys"]), _lib.ptr(out.get("moments")), _lib.ptr(out["stats"]),
-                                          _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+            status = L.nsc_map_build_dist(*_row_args(c, self.params), C.byref(self.dist), M, _lib.ptr(out["voxels"]),
+                                          _lib.ptr(out["index"]), _lib.ptr(out["info"]), _lib.ptr(out["keys"]),
+                                          _lib.ptr(out.get("moments")), _lib.ptr(out["stats"]), _lib.ptr(ws),
+                                          int(ws.numel()), _lib.stream_ptr(dev))
         _lib.check(status, "nsc_map_build_dist")
-        self.voxels, self.index, self.keys, self.info, self.stats = (out[k] for k in ("voxels", "index", "keys", "info",
-                                                                                     "stats"))
-        self.moments, self.cursor = out.get("moments"), out.get("cursor") if self.insertable else None
+        self._keep(out, M, out.get("moments"), out.get("cursor") if self.insertable else None)
         if self.cursor is not None:
             self.cursor[0].fill_(N)
             self.cursor[1].fill_(B)
-        self.capacity, self.complete = M, None
         return out
 
-    def _clouds(self, points, offsets, poses, pose_ids):
-        """checked device input of a build or an insertion -> (rows, offsets, clouds, rows, dtype code, float64 poses,
-        poses, device ids or None)"""
-        for t, name in ((points, "points"), (offsets, "offsets"), (poses, "poses")):
-            _lib.require_cuda(t, name)
-        dev = points.device
-        pts, off, B, N, dtype = _rows(points, offsets, "points")
-        if poses.ndim != 3 or tuple(poses.shape[1:]) != (4, 4):
-            raise _lib.NscError("poses must be (P,4,4)")
-        pose = poses.contiguous().to(torch.float64)
-        P = int(pose.shape[0])
-        ids = GlobalMap._host_ids(pose_ids, B, P)
-        if ids is not None:
-            ids = ids.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
-            if int(ids.numel()) != B:
-                raise _lib.NscError(f"pose_ids must have one entry per cloud ({B}), got {int(ids.numel())}")
-        return pts, off, B, N, dtype, pose, P, ids
+    @staticmethod
+    def _shapes(M, moments, cursor):
+        """name -> (shape, dtype) of the kept tensors of a map of capacity M"""
+        shapes = dict(voxels=((M, _lib.MAP_VOXEL_DOUBLES), torch.float64), index=((2 * M, 2), torch.int64),
+                      info=((M, 4), torch.int64), keys=((M,), torch.int64), stats=((_lib.MAP_STATS,), torch.int64))
+        if moments:
+            shapes["moments"] = ((M, 9), torch.int64)
+        if cursor:
+            shapes["cursor"] = ((2,), torch.int64)
+        return shapes
+
+    def _keep(self, out, M, moments, cursor):
+        """the kept tensors are ``out``'s from here on, over the capacity M"""
+        self.voxels, self.index, self.keys, self.info, self.stats = (out[k] for k in ("voxels", "index", "keys", "info",
+                                                                                     "stats"))
+        self.moments, self.cursor = moments, cursor
+        self.capacity, self.complete = M, None
 
     # ---- insertion ----------------------------------------------------------------------------------------------------
 
     def _kept(self):
         return {k: getattr(self, k) for k in ("voxels", "index", "info", "keys", "moments", "stats", "cursor")}
+
+    def _kept_args(self):
+        """the ctypes arguments of the kept map, as every call on it takes them after the rows"""
+        return (C.byref(self.dist), self.capacity, _lib.ptr(self.voxels), _lib.ptr(self.index), _lib.ptr(self.info),
+                _lib.ptr(self.keys), _lib.ptr(self.moments), _lib.ptr(self.stats))
 
     def _insertable_map(self, what):
         """the host-side refusals every insertion starts with"""
@@ -239,15 +215,12 @@ class MapLocalizer:
         dev = self.voxels.device
         if points.device != dev:
             raise _lib.NscError(f"the scans must be on the map's device ({dev})")
-        pts, off, B, N, dtype, pose, P, ids = self._clouds(points, offsets, poses, pose_ids)
+        c = _clouds(points, offsets, poses, pose_ids)
         L = _lib.lib()
-        ws = _workspace(L.nsc_map_insert_workspace_bytes(N), dev)
+        ws = _workspace(L.nsc_map_insert_workspace_bytes(c.N), dev)
         with torch.cuda.device(dev):
-            status = L.nsc_map_insert_dist(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off), B, N, _lib.ptr(pose), P,
-                                           _lib.ptr(ids), C.byref(self.params), C.byref(self.dist), self.capacity,
-                                           _lib.ptr(self.voxels), _lib.ptr(self.index), _lib.ptr(self.info),
-                                           _lib.ptr(self.keys), _lib.ptr(self.moments), _lib.ptr(self.stats),
-                                           _lib.ptr(self.cursor), _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+            status = L.nsc_map_insert_dist(*_row_args(c, self.params), *self._kept_args(), _lib.ptr(self.cursor),
+                                           _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
         _lib.check(status, "nsc_map_insert_dist")
         self.complete = None
         return self._kept()
@@ -256,14 +229,7 @@ class MapLocalizer:
         """``insert_device`` on the input forms of ``build``.  Returns ``build``'s dict over the whole map; one
         synchronisation, to read the stats."""
         self._insertable_map("insert")
-        packed = _is_packed(clouds)
-        clouds = clouds if packed else _tensors(clouds)
-        pose = GlobalMap._poses(poses)
-        # host ids are refused before anything goes to the device
-        ids = GlobalMap._host_ids(pose_ids, int(clouds[1].numel()) - 1 if packed else len(clouds), int(pose.shape[0]))
-        dev = self.voxels.device
-        pts, off = clouds if packed else _pack(clouds, dev)
-        return self._result(self.insert_device(pts, off, pose.to(device=dev, dtype=torch.float64), ids))
+        return self._result(self.insert_device(*_host_clouds(clouds, poses, pose_ids, self.voxels.device)))
 
     def insert_prepared(self, store: PreparedClouds, poses, pose_ids=None, start=0):
         """``insert`` on the clouds of a ``PreparedClouds`` from index ``start`` on: the clouds added to the store since
@@ -272,14 +238,7 @@ class MapLocalizer:
         n = len(store)
         if not 0 <= int(start) <= n:
             raise _lib.NscError(f"start must lie in [0, {n}], got {start}")
-        start = int(start)
-        pose = GlobalMap._poses(poses)
-        ids = GlobalMap._host_ids(pose_ids, n - start, int(pose.shape[0]))
-        if store._buf is None:
-            store._reserve(0, 0, 0)
-        r0 = int(store._row_host[start])
-        pts, off = store._buf["points"][r0:store.n_rows], store._buf["row_offsets"][start:n + 1] - r0
-        return self._result(self.insert_device(pts, off, pose.to(device=store.device, dtype=torch.float64), ids))
+        return self._result(self.insert_device(*_prepared_clouds(store, poses, pose_ids, int(start))))
 
     def extend(self, scans, init_poses, min_fitness: float):
         """Register ``scans`` (as ``register`` takes them) and insert those whose fitness reaches ``min_fitness`` under
@@ -288,15 +247,9 @@ class MapLocalizer:
         pair of calls can be captured; the rows of the other scans are counted in rows_without_pose.  Returns
         ``register_device``'s dict."""
         self._insertable_map("extend")
-        packed = _is_packed(scans)
-        scans = scans if packed else _tensors(scans)
-        pose = GlobalMap._poses(init_poses)
-        S = int(scans[1].numel()) - 1 if packed else len(scans)
-        if int(pose.shape[0]) != S:              # refused before anything goes to the device
-            raise _lib.NscError(f"init_poses must have one (4,4) pose per scan ({S}), got {int(pose.shape[0])}")
         dev = self.voxels.device
-        pts, off = scans if packed else _pack(scans, dev)
-        out = self.register_device(pts, off, pose.to(device=dev, dtype=torch.float64))
+        pts, off, pose, S = _host_scans(scans, init_poses, dev)
+        out = self.register_device(pts, off, pose)
         scan = torch.arange(S, dtype=torch.int64, device=dev)
         ids = torch.where(out["fitness"] >= float(min_fitness), scan, -1)         # four launches: arange, >=, the -1 (a fill), where
         self.insert_device(pts, off, out["transform"], ids)
@@ -314,16 +267,13 @@ class MapLocalizer:
         dev = self.voxels.device
         if points.device != dev:
             raise _lib.NscError(f"the clouds must be on the map's device ({dev})")
-        pts, off, B, N, dtype, pose, P, ids = self._clouds(points, offsets, poses, pose_ids)
+        c = _clouds(points, offsets, poses, pose_ids)
         L = _lib.lib()
-        ws = _workspace(L.nsc_map_remove_workspace_bytes(N), dev)
+        ws = _workspace(L.nsc_map_remove_workspace_bytes(c.N), dev)
         removed = torch.empty((_lib.MAP_REMOVE_STATS,), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
-            status = L.nsc_map_remove_dist(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off), B, N, _lib.ptr(pose), P,
-                                           _lib.ptr(ids), C.byref(self.params), C.byref(self.dist), self.capacity,
-                                           _lib.ptr(self.voxels), _lib.ptr(self.index), _lib.ptr(self.info),
-                                           _lib.ptr(self.keys), _lib.ptr(self.moments), _lib.ptr(self.stats),
-                                           _lib.ptr(removed), _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+            status = L.nsc_map_remove_dist(*_row_args(c, self.params), *self._kept_args(), _lib.ptr(removed), _lib.ptr(ws),
+                                           int(ws.numel()), _lib.stream_ptr(dev))
         _lib.check(status, "nsc_map_remove_dist")
         self.complete = None
         return dict(self._kept(), removed=removed)
@@ -339,14 +289,7 @@ class MapLocalizer:
         """``remove_device`` on the input forms of ``build``.  Returns ``build``'s dict over the whole map (emptied voxels
         included: count 0, not usable) and the eight counts of ``removed`` by name; one synchronisation."""
         self._insertable_map("remove")
-        packed = _is_packed(clouds)
-        clouds = clouds if packed else _tensors(clouds)
-        pose = GlobalMap._poses(poses)
-        # host ids are refused before anything goes to the device
-        ids = GlobalMap._host_ids(pose_ids, int(clouds[1].numel()) - 1 if packed else len(clouds), int(pose.shape[0]))
-        dev = self.voxels.device
-        pts, off = clouds if packed else _pack(clouds, dev)
-        return self._removed(self.remove_device(pts, off, pose.to(device=dev, dtype=torch.float64), ids))
+        return self._removed(self.remove_device(*_host_clouds(clouds, poses, pose_ids, self.voxels.device)))
 
     def remove_prepared(self, store: PreparedClouds, poses, pose_ids=None, start=0, stop=None):
         """``remove`` on the clouds ``start`` to ``stop`` (the end, if None) of a ``PreparedClouds``, under the poses they
@@ -356,14 +299,7 @@ class MapLocalizer:
         stop = n if stop is None else stop
         if not 0 <= int(start) <= int(stop) <= n:
             raise _lib.NscError(f"start and stop must satisfy 0 <= start <= stop <= {n}, got {start} and {stop}")
-        start, stop = int(start), int(stop)
-        pose = GlobalMap._poses(poses)
-        ids = GlobalMap._host_ids(pose_ids, stop - start, int(pose.shape[0]))
-        if store._buf is None:
-            store._reserve(0, 0, 0)
-        r0, r1 = int(store._row_host[start]), int(store._row_host[stop])
-        pts, off = store._buf["points"][r0:r1], store._buf["row_offsets"][start:stop + 1] - r0
-        return self._removed(self.remove_device(pts, off, pose.to(device=store.device, dtype=torch.float64), ids))
+        return self._removed(self.remove_device(*_prepared_clouds(store, poses, pose_ids, int(start), int(stop))))
 
     def replace_device(self, points, offsets, old_poses, new_poses, pose_ids=None, first_row=0, first_cloud=0):
         """Move packed clouds of the kept map from ``old_poses`` to ``new_poses`` (nsc_map_replace_dist; both (P,4,4)), on
@@ -380,21 +316,19 @@ class MapLocalizer:
         if int(first_row) < 0 or int(first_cloud) < 0:
             raise _lib.NscError(f"first_row and first_cloud must not be negative, got {first_row} and {first_cloud}")
         _lib.require_cuda(new_poses, "new_poses")
-        pts, off, B, N, dtype, old, P, ids = self._clouds(points, offsets, old_poses, pose_ids)
+        c = _clouds(points, offsets, old_poses, pose_ids)
+        P = c.P
         if new_poses.ndim != 3 or tuple(new_poses.shape) != (P, 4, 4):
             raise _lib.NscError(f"new_poses must be ({P},4,4) as old_poses, got {tuple(new_poses.shape)}")
         new = new_poses.contiguous().to(torch.float64)
         L = _lib.lib()
-        ws = _workspace(L.nsc_map_replace_workspace_bytes(N), dev)
+        ws = _workspace(L.nsc_map_replace_workspace_bytes(c.N), dev)
         removed = torch.empty((_lib.MAP_REMOVE_STATS,), dtype=torch.int64, device=dev)
         placed = torch.empty((_lib.MAP_STATS,), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
-            status = L.nsc_map_replace_dist(_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off), B, N, _lib.ptr(old),
-                                            _lib.ptr(new), P, _lib.ptr(ids), C.byref(self.params), C.byref(self.dist),
-                                            self.capacity, _lib.ptr(self.voxels), _lib.ptr(self.index), _lib.ptr(self.info),
-                                            _lib.ptr(self.keys), _lib.ptr(self.moments), _lib.ptr(self.stats),
-                                            int(first_row), int(first_cloud), _lib.ptr(removed), _lib.ptr(placed),
-                                            _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
+            status = L.nsc_map_replace_dist(*_row_args(c, self.params, new), *self._kept_args(), int(first_row),
+                                            int(first_cloud), _lib.ptr(removed), _lib.ptr(placed), _lib.ptr(ws),
+                                            int(ws.numel()), _lib.stream_ptr(dev))
         _lib.check(status, "nsc_map_replace_dist")
         self.complete = None
         return dict(self._kept(), removed=removed, placed=placed)
@@ -403,20 +337,17 @@ class MapLocalizer:
         """``replace_device`` on the input forms of ``build``.  Returns ``remove``'s dict and ``placed`` (7,) as a device
         tensor; one synchronisation."""
         self._insertable_map("replace")
-        packed = _is_packed(clouds)
-        clouds = clouds if packed else _tensors(clouds)
-        old, new = GlobalMap._poses(old_poses), GlobalMap._poses(new_poses)
-        if tuple(old.shape) != tuple(new.shape):
-            raise _lib.NscError(f"old_poses and new_poses must have one pose each per id, got {int(old.shape[0])} and "
-                                f"{int(new.shape[0])}")
-        if int(first_row) < 0 or int(first_cloud) < 0:
-            raise _lib.NscError(f"first_row and first_cloud must not be negative, got {first_row} and {first_cloud}")
-        # host ids are refused before anything goes to the device
-        ids = GlobalMap._host_ids(pose_ids, int(clouds[1].numel()) - 1 if packed else len(clouds), int(old.shape[0]))
+        def check(B, P):                          # after the clouds and old_poses, and before anything goes to the device
+            new = GlobalMap._poses(new_poses)
+            if P != int(new.shape[0]):
+                raise _lib.NscError(f"old_poses and new_poses must have one pose each per id, got {P} and "
+                                    f"{int(new.shape[0])}")
+            if int(first_row) < 0 or int(first_cloud) < 0:
+                raise _lib.NscError(f"first_row and first_cloud must not be negative, got {first_row} and {first_cloud}")
+            return GlobalMap._host_ids(pose_ids, B, P), new
         dev = self.voxels.device
-        pts, off = clouds if packed else _pack(clouds, dev)
-        out = self.replace_device(pts, off, old.to(device=dev, dtype=torch.float64), new.to(device=dev, dtype=torch.float64),
-                                  ids, first_row, first_cloud)
+        pts, off, old, (ids, new) = _host_rows(clouds, old_poses, dev, check)
+        out = self.replace_device(pts, off, old, new.to(device=dev, dtype=torch.float64), ids, first_row, first_cloud)
         return dict(self._removed(out), placed=out["placed"])
 
     def update_prepared(self, store: PreparedClouds, old_poses, new_poses, min_translation: float = 0.0,
@@ -444,8 +375,6 @@ class MapLocalizer:
                                 f"{int(old.shape[0])} and {int(new.shape[0])}")
         if not (float(min_translation) >= 0.0 and float(min_rotation) >= 0.0):
             raise _lib.NscError("min_translation and min_rotation must not be negative")
-        if store._buf is None:
-            store._reserve(0, 0, 0)
         dev = store.device
         old, new = old.to(device=dev, dtype=torch.float64), new.to(device=dev, dtype=torch.float64)
         A, B = old[:, :3, :], new[:, :3, :]
@@ -456,8 +385,7 @@ class MapLocalizer:
         angle = torch.atan2(v.norm(dim=1), 0.5 * (D[:, 0, 0] + D[:, 1, 1] + D[:, 2, 2] - 1.0))
         far = ((B[:, :, 3] - A[:, :, 3]).norm(dim=1) >= float(min_translation)) | (angle >= float(min_rotation))
         moved = torch.where(differ & finite & far, torch.arange(n, dtype=torch.int64, device=dev), -1)
-        pts, off = store._buf["points"][:store.n_rows], store._buf["row_offsets"][:n + 1]
-        out = self.replace_device(pts, off, old, new, moved, 0, 0)
+        out = self.replace_device(*store.packed(), old, new, moved, 0, 0)
         out["moved"] = moved
         return out
 
@@ -493,20 +421,10 @@ class MapLocalizer:
         M = self._resizable("resize_device", max_voxels)
         dev, old = self.voxels.device, self.capacity
         tiles = -(-old // _lib.MAP_TILE_ROWS)
-        shapes = dict(voxels=((M, _lib.MAP_VOXEL_DOUBLES), torch.float64), index=((2 * M, 2), torch.int64),
-                      info=((M, 4), torch.int64), keys=((M,), torch.int64), stats=((_lib.MAP_STATS,), torch.int64))
-        if self.moments is not None:
-            shapes["moments"] = ((M, 9), torch.int64)
-        if self.cursor is not None:
-            shapes["cursor"] = ((2,), torch.int64)
+        shapes = self._shapes(M, self.moments is not None, self.cursor is not None)
         shapes.update(new_place=((old,), torch.int64), tile_base=((tiles + 1,), torch.int64),
                       rehashed=((_lib.MAP_REHASH_STATS,), torch.int64))
-        if out is None:
-            out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
-        for k, (shape, dt) in shapes.items():
-            t = out.get(k)
-            if t is None or tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise _lib.NscError(f"out[{k!r}] must be a contiguous {shape} {dt} tensor on {dev}")
+        out = _outputs(shapes, out, dev)
         with torch.cuda.device(dev):
             status = _lib.lib().nsc_map_rehash_dist(
                 _lib.ptr(self.voxels), _lib.ptr(self.info), _lib.ptr(self.keys), _lib.ptr(self.moments),
@@ -515,14 +433,9 @@ class MapLocalizer:
                 _lib.ptr(out["stats"]), _lib.ptr(out.get("cursor")), M, _lib.ptr(out["new_place"]),
                 _lib.ptr(out["tile_base"]), _lib.ptr(out["rehashed"]), _lib.stream_ptr(dev))
         _lib.check(status, "nsc_map_rehash_dist")
-        self.voxels, self.index, self.keys, self.info, self.stats = (out[k] for k in ("voxels", "index", "keys", "info",
-                                                                                     "stats"))
-        if self.moments is not None:
-            self.moments = out["moments"]
-        if self.cursor is not None:
-            self.cursor = out["cursor"]
-        self.capacity = self.max_voxels = M
-        self.complete = None
+        self._keep(out, M, out["moments"] if self.moments is not None else None,
+                   out["cursor"] if self.cursor is not None else None)
+        self.max_voxels = M
         return dict(self._kept(), new_place=out["new_place"], tile_base=out["tile_base"], rehashed=out["rehashed"])
 
     def resize(self, max_voxels=None, compact=True):
@@ -547,13 +460,9 @@ class MapLocalizer:
 
     def _result(self, out):
         """build_device's buffers -> the dict ``build`` returns (one read of the stats)"""
-        stats = dict(zip(_lib.MAP_STAT_NAMES, out["stats"].cpu().tolist()))
-        n = stats["voxels_written"]
-        info, vox = out["info"][:n], out["voxels"][:n]
-        res = dict(mean=vox[:, 0:3], covariance=vox[:, 3:9], information=vox[:, 9:15], usable=vox[:, 15] == 1.0,
-                   count=info[:, 0], first_row=info[:, 1], first_cloud=info[:, 2], last_cloud=info[:, 3],
-                   keys=out["keys"][:n], **stats)
-        res["complete"] = stats["voxels_found"] == stats["voxels_written"] and stats["rows_unplaced"] == 0
+        vox = out["voxels"]
+        res = _result(out, lambda n: dict(mean=vox[:n, 0:3], covariance=vox[:n, 3:9], information=vox[:n, 9:15],
+                                          usable=vox[:n, 15] == 1.0))
         self.complete = res["complete"]
         return res
 
@@ -563,24 +472,11 @@ class MapLocalizer:
         (V,3), covariance and information (V,6: xx xy xz yy yz zz) float64, usable (V,) bool, count, first_row,
         first_cloud, last_cloud, keys (V,) int64 -- the stats by name and ``complete``.  One synchronisation, to read the
         stats."""
-        packed = _is_packed(clouds)
-        clouds = clouds if packed else _tensors(clouds)
-        pose = GlobalMap._poses(poses)
-        # host ids are refused before anything goes to the device
-        ids = GlobalMap._host_ids(pose_ids, int(clouds[1].numel()) - 1 if packed else len(clouds), int(pose.shape[0]))
-        dev = _device(self.device)
-        pts, off = clouds if packed else _pack(clouds, dev)
-        return self._result(self.build_device(pts, off, pose.to(device=dev, dtype=torch.float64), ids))
+        return self._result(self.build_device(*_host_clouds(clouds, poses, pose_ids, self.device)))
 
     def build_prepared(self, store: PreparedClouds, poses, pose_ids=None):
         """``build`` on the clouds a ``PreparedClouds`` holds, as ``GlobalMap.build_prepared``."""
-        n = len(store)
-        pose = GlobalMap._poses(poses)
-        ids = GlobalMap._host_ids(pose_ids, n, int(pose.shape[0]))
-        if store._buf is None:
-            store._reserve(0, 0, 0)
-        pts, off = store._buf["points"][:store.n_rows], store._buf["row_offsets"][:n + 1]
-        return self._result(self.build_device(pts, off, pose.to(device=store.device, dtype=torch.float64), ids))
+        return self._result(self.build_device(*_prepared_clouds(store, poses, pose_ids)))
 
     # ---- registration -------------------------------------------------------------------------------------------------
 
@@ -644,12 +540,5 @@ class MapLocalizer:
         of device tensors."""
         if self.voxels is None:
             raise _lib.NscError("MapLocalizer.register: build a map first")
-        packed = _is_packed(scans)
-        scans = scans if packed else _tensors(scans)
-        pose = GlobalMap._poses(init_poses)
-        S = int(scans[1].numel()) - 1 if packed else len(scans)
-        if int(pose.shape[0]) != S:              # refused before anything goes to the device
-            raise _lib.NscError(f"init_poses must have one (4,4) pose per scan ({S}), got {int(pose.shape[0])}")
-        dev = self.voxels.device
-        pts, off = scans if packed else _pack(scans, dev)
-        return self.register_device(pts, off, pose.to(device=dev, dtype=torch.float64), system0=system0)
+        pts, off, pose, _ = _host_scans(scans, init_poses, self.voxels.device)
+        return self.register_device(pts, off, pose, system0=system0)

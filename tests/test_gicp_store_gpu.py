@@ -78,6 +78,38 @@ def test_stage_parity(pairs, other):
     assert store.n_rows == int(out["counts"][:len(clouds)].sum())
 
 
+def test_packed_ranges():
+    """``PreparedClouds.packed``: every range of a store of three clouds of 0, 5 and 300 rows (one row per voxel, so the
+    store keeps them all) is the clouds' points by bits under offsets counted from 0; an empty store gives no rows and the
+    offsets [0]; a bad range is refused."""
+    from neural_spectral_codec_amd import _lib
+    lattice = np.stack(np.meshgrid(np.arange(10.0), np.arange(10.0), np.arange(3.0), indexing="ij"), -1).reshape(-1, 3)
+    sizes = [0, 5, 300]
+    store, ids = store_of([np.zeros((0, 3)), lattice[:5] + 100.0, lattice], stride=3)
+    stored = [store.cloud(i)["points"].cpu().numpy() for i in ids]
+    assert [len(p) for p in stored] == sizes and store.n_rows == 305
+    for start in range(4):
+        for stop in range(start, 4):
+            pts, off = store.packed(start, stop)
+            assert pts.is_cuda and off.is_cuda and pts.dtype == torch.float64 and off.dtype == torch.int64
+            want = np.concatenate(stored[start:stop] + [np.zeros((0, 3))])
+            assert tuple(pts.shape) == want.shape and pts.cpu().numpy().tobytes() == want.tobytes(), (start, stop)
+            assert off.cpu().tolist() == np.concatenate([[0], np.cumsum(sizes[start:stop])]).tolist(), (start, stop)
+    for got in (store.packed(), store.packed(0), store.packed(0, None)):
+        assert got[0].data_ptr() == store.packed(0, 3)[0].data_ptr() and tuple(got[0].shape) == (305, 3)
+        assert got[1].cpu().tolist() == [0, 0, 5, 305]
+    assert store.packed(2)[1].cpu().tolist() == [0, 300]
+    for start, stop in ((-1, None), (4, None), (2, 1), (0, 4), (-2, -1)):
+        with pytest.raises(_lib.NscError, match="start and stop must satisfy"):
+            store.packed(start, stop)
+    for empty in (_gv().PreparedClouds(), store):
+        empty.clear()
+        pts, off = empty.packed()
+        assert tuple(pts.shape) == (0, 3) and pts.dtype == torch.float64 and pts.is_cuda and off.cpu().tolist() == [0]
+        with pytest.raises(_lib.NscError, match="start and stop must satisfy"):
+            empty.packed(0, 1)
+
+
 @pytest.mark.parametrize("stride", [3, 4])
 def test_registration_parity(pairs, other, stride):
     srcs = [p[0] for p in pairs] + [pairs[0][0]]

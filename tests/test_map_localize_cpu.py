@@ -2,15 +2,12 @@
 claims of the constructed inputs (tests/map_localize_cases.py) that tests/test_map_localize_gpu.py relies on, the host-side
 refusals of ``MapLocalizer`` and the argument checks of the C ABI."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import kernel_budget as KB
 import map_localize_cases as K
 import map_localize_restatement as R
 import map_restatement as M
@@ -277,24 +274,9 @@ def test_abi_defaults_workspace_and_guards(lib):
 def test_linearize_keeps_its_sums_in_registers(lib, tmp_path):
     """loc_linearize_kernel adds 30 float64 terms per row into per-lane accumulators: they must stay in registers (no
     scratch) and leave room for four waves per SIMD (at most 128 VGPRs), read from the gfx950 code object."""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not (os.path.exists(f"{llvm}/llvm-objdump") and os.path.exists(f"{llvm}/llvm-readelf")):
+    if not KB.binutils():
         pytest.skip("llvm binutils of the ROCm image not found")
-    from neural_spectral_codec_amd import build
-    so = shutil.copy(build.LIB, tmp_path / "libnsc_hip.so")
-    subprocess.run([f"{llvm}/llvm-objdump", "--offloading", str(so)], check=True, capture_output=True, cwd=tmp_path)
-    found = {}
-    for f in sorted(os.listdir(tmp_path)):
-        if "amdgcn" not in f:
-            continue
-        notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", str(tmp_path / f)], check=True, capture_output=True,
-                               text=True).stdout
-        for blk in notes.split(".agpr_count")[1:]:              # one metadata map per kernel, keys in alphabetical order
-            name = re.search(r"\.name:\s+(\S+)", blk)
-            vg = re.search(r"\.vgpr_count:\s+(\d+)", blk)
-            sc = re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
-            if name and vg and sc and "loc_linearize_kernel" in name.group(1):
-                found[name.group(1)] = (int(vg.group(1)), int(sc.group(1)))
+    found = KB.kernels("loc_linearize_kernel")
     assert len(found) == 2, sorted(found)                        # float32 and float64 rows
     for k, (vg, sc) in found.items():
         assert vg <= 128 and sc == 0, f"{k}: {vg} VGPRs, {sc} B scratch"

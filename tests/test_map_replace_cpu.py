@@ -319,28 +319,10 @@ def test_remove_and_replace_kernels_use_no_scratch(lib, tmp_path):
     insertion's refresh, whose loop body the removal's shares, keep everything in registers (no scratch) and leave room
     for four waves per SIMD (at most 128 VGPRs); read from the gfx950 code object as test_insert_kernels_use_no_scratch
     does"""
-    import os
-    import re
-    import shutil
-    import subprocess
-    llvm = "/opt/rocm/lib/llvm/bin"
+    import kernel_budget as KB
     # the binutils stand beside the hipcc that built the library: their absence is a failure, not a reason to skip
-    assert os.path.exists(f"{llvm}/llvm-objdump") and os.path.exists(f"{llvm}/llvm-readelf"), f"no llvm binutils in {llvm}"
-    from neural_spectral_codec_amd import build
-    so = shutil.copy(build.LIB, tmp_path / "libnsc_hip.so")
-    subprocess.run([f"{llvm}/llvm-objdump", "--offloading", str(so)], check=True, capture_output=True, cwd=tmp_path)
-    found = {}
-    for f in sorted(os.listdir(tmp_path)):
-        if "amdgcn" not in f:
-            continue
-        notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", str(tmp_path / f)], check=True, capture_output=True,
-                               text=True).stdout
-        for blk in notes.split(".agpr_count")[1:]:              # one metadata map per kernel, keys in alphabetical order
-            name = re.search(r"\.name:\s+(\S+)", blk)
-            vg = re.search(r"\.vgpr_count:\s+(\d+)", blk)
-            sc = re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
-            if name and vg and sc and re.search(r"call_clear_kernel|rem_(rows|refresh)_kernel|ins_refresh_kernel", name.group(1)):
-                found[name.group(1)] = (int(vg.group(1)), int(sc.group(1)))
+    assert KB.binutils(), f"no llvm binutils in {KB.LLVM}"
+    found = KB.kernels(r"call_clear_kernel|rem_(rows|refresh)_kernel|ins_refresh_kernel")
     assert len(found) == 5, sorted(found)
     for k, (vg, sc) in found.items():
         print(f"{k}: {vg} VGPRs, {sc} B scratch")

@@ -3,14 +3,11 @@ refusals, the restatement (tests/map_robust_restatement.py) against map_localize
 differences, and the claims of the constructed inputs (tests/map_robust_cases.py) that tests/test_map_robust_gpu.py relies
 on."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_budget as KB
 import map_localize_cases as K
 import map_localize_restatement as R
 import map_robust_cases as KR
@@ -81,23 +78,8 @@ def test_localizer_refusals():
 def test_new_linearize_kernels_use_no_scratch(lib, tmp_path):
     """the six instantiations of loc_linearize_robust_kernel (float32 and float64 rows x {kernel over one voxel, seven
     voxels without a kernel, kernel over seven voxels}) keep their 32 sums in registers; read from the gfx950 code object"""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    assert os.path.exists(f"{llvm}/llvm-objdump") and os.path.exists(f"{llvm}/llvm-readelf"), f"no llvm binutils in {llvm}"
-    from neural_spectral_codec_amd import build
-    so = shutil.copy(build.LIB, tmp_path / "libnsc_hip.so")
-    subprocess.run([f"{llvm}/llvm-objdump", "--offloading", str(so)], check=True, capture_output=True, cwd=tmp_path)
-    found = {}
-    for f in sorted(os.listdir(tmp_path)):
-        if "amdgcn" not in f:
-            continue
-        notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", str(tmp_path / f)], check=True, capture_output=True,
-                               text=True).stdout
-        for blk in notes.split(".agpr_count")[1:]:              # one metadata map per kernel, keys in alphabetical order
-            name = re.search(r"\.name:\s+(\S+)", blk)
-            vg = re.search(r"\.vgpr_count:\s+(\d+)", blk)
-            sc = re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
-            if name and vg and sc and "loc_linearize_robust_kernel" in name.group(1):
-                found[name.group(1)] = (int(vg.group(1)), int(sc.group(1)))
+    assert KB.binutils(), f"no llvm binutils in {KB.LLVM}"
+    found = KB.kernels("loc_linearize_robust_kernel")
     assert len(found) == 6, sorted(found)
     for k, (vg, sc) in found.items():
         print(f"{k}: {vg} VGPRs, {sc} B scratch")

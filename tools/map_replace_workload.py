@@ -43,15 +43,13 @@ class StoreView:
 
     def __init__(self, pts, off):
         self.device = pts.device
-        self._buf = dict(points=pts, row_offsets=off)
-        self._row_host = off.cpu().numpy()
+        self._packed = (pts, off)
 
     def __len__(self):
-        return len(self._row_host) - 1
+        return int(self._packed[1].numel()) - 1
 
-    @property
-    def n_rows(self):
-        return int(self._row_host[-1])
+    def packed(self):
+        return self._packed
 
 
 def moved(poses):
