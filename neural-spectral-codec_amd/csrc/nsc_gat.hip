@@ -18,8 +18,10 @@
 //   gemm_nt_direct_kernel / gat_aggregate_kernel<1,4,false>
 //                        the NSC_GAT_CORESIDENT set: no LDS, < 64 VGPRs, bit-identical output -- fits beside a
 //                        resident encoder grid so that the GNN of batch k runs under the encoder of batch k+1
+// Every kernel set gives the same bits: each output element is the same MFMA chain, and the epilogue arithmetic (BatchNorm
+// fold, projection value, aux columns) is nsc_gat_epilogue.h's in all six kernels; the LDS opt-in and the wave reductions
+// are nsc_util.h's.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -30,6 +32,7 @@
 
 namespace {
 
+#include "nsc_gat_epilogue.h"
 #include "nsc_gemm_glds.h"
 #include "nsc_gat_banded.h"
 
@@ -327,12 +330,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float *__restrict__ 
     for (int j = 0; j < 4; ++j) {
         const int col = (cg + j < N) ? cg + j : N - 1;
         if (EPI != 0) bias[j] = ep.bias[col];
-        if (EPI == 1) {
-            // torch batch_norm eval: alpha = invstd * weight, beta = bias - mean * alpha
-            const float invstd = 1.0f / sqrtf(ep.bn_var[col] + ep.bn_eps);
-            bn_scale[j] = invstd * ep.bn_w[col];
-            bn_shift[j] = ep.bn_b[col] - ep.bn_mean[col] * bn_scale[j];
-        }
+        if (EPI == 1) bn_fold(ep.bn_var, ep.bn_eps, ep.bn_w, ep.bn_b, ep.bn_mean, col, bn_scale[j], bn_shift[j]);
     }
     const bool vec = (cg + 3 < n_main) && !(ldc & 3) && !(reinterpret_cast<unsigned long long>(C) & 15) &&
                      (EPI != 2 || !ep.resid || (!(ep.ldr & 3) && !(reinterpret_cast<unsigned long long>(ep.resid) & 15)));
@@ -345,10 +343,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float *__restrict__ 
         f32x4 rs = zero;
         if (EPI == 2 && ep.resid && vec) rs = *reinterpret_cast<const f32x4 *>(ep.resid + (long long)row * ep.ldr + cg);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (EPI != 0) v[j] = v[j] + bias[j];
-            if (EPI == 1) v[j] = fmaxf(v[j] * bn_scale[j] + bn_shift[j], 0.0f);
-        }
+        for (int j = 0; j < 4; ++j) v[j] = epi_value<EPI>(v[j], bias[j], bn_scale[j], bn_shift[j]);
         if (vec) {
             if (EPI == 2 && ep.resid) { v[0] += rs.x; v[1] += rs.y; v[2] += rs.z; v[3] += rs.w; }
             *reinterpret_cast<f32x4 *>(C + (long long)row * ldc + cg) = f32x4{v[0], v[1], v[2], v[3]};
@@ -362,12 +357,24 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float *__restrict__ 
                     if (EPI == 2 && ep.resid) o = o + ep.resid[(long long)row * ep.ldr + col];
                     C[(long long)row * ldc + col] = o;
                 } else {
-                    float *aux = (col == n_main) ? ep.aux0 : ep.aux1;
-                    aux[row] = v[j];
+                    epi_store_aux(v[j], ep.aux0, ep.aux1, row, col, n_main);
                 }
             }
         }
     }
+}
+
+// The co-resident GEMMs load coalesced (lane L: row L >> 2, k offset 4 (L & 3)) and move each dword to the MFMA operand layout
+// by ds_bpermute (the LDS crossbar, no LDS allocation): lane (r, q) pulls from lane 4 r + q, perm = 4 (4 r + q).
+__device__ __forceinline__ f32x4 to_operand(int perm, const f32x4 &v)
+{
+    f32x4 o;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const float e = v[t];                      // (bit_cast straight from a vector element reads element 0)
+        o[t] = __int_as_float(__builtin_amdgcn_ds_bpermute(perm, __float_as_int(e)));
+    }
+    return o;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -411,16 +418,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56))) void gemm
     const int lcol = (n0 + wave * 16 + lr) < N ? (n0 + wave * 16 + lr) : N - 1;
     const float *pb = ((lcol < n_main) ? B + (long long)lcol * ldb : Bx + (long long)(lcol - n_main) * ldb) + 4 * lq;
     const int col = cb < N ? cb : N - 1;
-    auto to_operand = [&](const f32x4 &v) {
-        f32x4 o;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float e = v[t];                  // (bit_cast straight from a vector element reads element 0)
-            o[t] = __int_as_float(__builtin_amdgcn_ds_bpermute(perm, __float_as_int(e)));
-        }
-        return o;
-    };
-
 
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 acc[ACC];
@@ -444,8 +441,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56))) void gemm
             if (blk < nblk) {                      // workgroup-uniform
                 f32x4 xa[ACC];
 #pragma unroll
-                for (int h = 0; h < ACC; ++h) xa[h] = to_operand(ra[s][h]);
-                const f32x4 xb = to_operand(rb[s]);
+                for (int h = 0; h < ACC; ++h) xa[h] = to_operand(perm, ra[s][h]);
+                const f32x4 xb = to_operand(perm, rb[s]);
                 if (blk + P < nblk) load_blk(blk + P, ra[s], rb[s]);
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
@@ -461,11 +458,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56))) void gemm
     // 56 VGPRs for two of its waves to share a SIMD with five encoder workgroups; their round trip hides under other waves)
     float bias = 0.f, bn_scale = 1.f, bn_shift = 0.f;
     if (EPI != 0) bias = ep.bias[col];
-    if (EPI == 1) {
-        const float invstd = 1.0f / sqrtf(ep.bn_var[col] + ep.bn_eps);
-        bn_scale = invstd * ep.bn_w[col];
-        bn_shift = ep.bn_b[col] - ep.bn_mean[col] * bn_scale;
-    }
+    if (EPI == 1) bn_fold(ep.bn_var, ep.bn_eps, ep.bn_w, ep.bn_b, ep.bn_mean, col, bn_scale, bn_shift);
     const bool main_col = cb < n_main;
 #pragma unroll
     for (int h = 0; h < ACC; ++h) {
@@ -473,15 +466,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56))) void gemm
         for (int reg = 0; reg < 4; ++reg) {
             const int row = m0 + 16 * h + 4 * q + reg;
             if (row >= M) continue;
-            float v = acc[h][reg];
             if (main_col) {
-                if (EPI != 0) v = v + bias;
-                if (EPI == 1) v = fmaxf(v * bn_scale + bn_shift, 0.0f);
+                float v = epi_value<EPI>(acc[h][reg], bias, bn_scale, bn_shift);
                 if (EPI == 2 && ep.resid) v = v + ep.resid[(long long)row * ep.ldr + cb];
                 C[(long long)row * ldc + cb] = v;
             } else {
-                float *aux = (cb == n_main) ? ep.aux0 : ep.aux1;
-                aux[row] = v;
+                epi_store_aux(acc[h][reg], ep.aux0, ep.aux1, row, cb, n_main);
             }
         }
     }
@@ -525,15 +515,6 @@ __global__ __launch_bounds__(256) void gemm_nt_share_kernel(const float *__restr
     gc = gc < N ? gc : N - 1;
     const float *pb = ((gc < n_main) ? B + (long long)gc * ldb : Bx + (long long)(gc - n_main) * ldb) + 4 * sq;
     const int sidx = sc * LDB + 4 * sq;
-    auto to_operand = [&](const f32x4 &v) {
-        f32x4 o;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float e = v[t];
-            o[t] = __int_as_float(__builtin_amdgcn_ds_bpermute(perm, __float_as_int(e)));
-        }
-        return o;
-    };
     const int ncb = min(4, (N - n0 + 15) >> 4);    // 16-column blocks of this tile that hold real columns (uniform)
 
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -556,7 +537,7 @@ __global__ __launch_bounds__(256) void gemm_nt_share_kernel(const float *__restr
                 const float *bs = Bs[s];
                 // B of block blk + 1 goes to the other buffer (last read in iteration blk - 1, a barrier ago)
                 if (blk + 1 < nblk) *reinterpret_cast<f32x4 *>(&Bs[s ^ 1][sidx]) = rb[s ^ 1];
-                const f32x4 xa = to_operand(ra[s]);
+                const f32x4 xa = to_operand(perm, ra[s]);
                 if (blk + 2 < nblk) {              // both register sets of this parity are free: refill two blocks ahead
                     const int k = (blk + 2) << 4;
                     ra[s] = *reinterpret_cast<const f32x4 *>(pa + k);
@@ -583,24 +564,17 @@ __global__ __launch_bounds__(256) void gemm_nt_share_kernel(const float *__restr
         const bool main_col = cb < n_main;
         float bias = 0.f, bn_scale = 1.f, bn_shift = 0.f;
         if (EPI != 0 && main_col) bias = ep.bias[cb];
-        if (EPI == 1 && main_col) {
-            const float invstd = 1.0f / sqrtf(ep.bn_var[cb] + ep.bn_eps);
-            bn_scale = invstd * ep.bn_w[cb];
-            bn_shift = ep.bn_b[cb] - ep.bn_mean[cb] * bn_scale;
-        }
+        if (EPI == 1 && main_col) bn_fold(ep.bn_var, ep.bn_eps, ep.bn_w, ep.bn_b, ep.bn_mean, cb, bn_scale, bn_shift);
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int row = m0 + 4 * q + reg;
             if (row >= M) continue;
-            float v = acc[g][reg];
             if (main_col) {
-                if (EPI != 0) v = v + bias;
-                if (EPI == 1) v = fmaxf(v * bn_scale + bn_shift, 0.0f);
+                float v = epi_value<EPI>(acc[g][reg], bias, bn_scale, bn_shift);
                 if (EPI == 2 && ep.resid) v = v + ep.resid[(long long)row * ep.ldr + cb];
                 C[(long long)row * ldc + cb] = v;
             } else {
-                float *aux = (cb == n_main) ? ep.aux0 : ep.aux1;
-                aux[row] = v;
+                epi_store_aux(acc[g][reg], ep.aux0, ep.aux1, row, cb, n_main);
             }
         }
     }
@@ -623,19 +597,6 @@ struct AggArgs {
     float bn_eps, slope;
     int N, H, edge_dim, relu;
 };
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sumf(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // CH = ceil(H / 256): float4 chunks per lane; UR neighbour rows in flight; PRE: epilogue operands prefetched.
 // <CH, 8, true> is the standalone configuration; <1, 4, false> stays under 64 VGPRs for NSC_GAT_CORESIDENT.
@@ -702,9 +663,9 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(AggArgs a)
         int j = 0;
         float l = -INFINITY;
         if (e < end) l = logit(e, j);
-        const float m = wave_max(l);
+        const float m = nsc_wave_max(l);
         const float p = (e < end) ? expf(l - m) : 0.0f;
-        const float den = wave_sumf(p) + 1e-16f;                  // PyG softmax
+        const float den = nsc_wave_sum(p) + 1e-16f;                  // PyG softmax
         const float al = p / den;
         if (a.alpha_out && e < end) a.alpha_out[e] = al;
         for (int t0 = 0; t0 < deg; t0 += UR) {                    // UR neighbour rows in flight
@@ -735,10 +696,10 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(AggArgs a)
     } else {
         float m = -INFINITY;
         for (int e = beg + lane; e < end; e += 64) { int j; m = fmaxf(m, logit(e, j)); }
-        m = wave_max(m);
+        m = nsc_wave_max(m);
         float s = 0.0f;
         for (int e = beg + lane; e < end; e += 64) { int j; s += expf(logit(e, j) - m); }
-        s = wave_sumf(s);
+        s = nsc_wave_sum(s);
         const float den = s + 1e-16f;
         for (int c0 = beg; c0 < end; c0 += 64) {
             const int e = c0 + lane;
@@ -778,9 +739,8 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(AggArgs a)
         for (int t = 0; t < 4; ++t) {
             float v = o[t] + ep_bias[c][t];
             if (a.bn_w) {
-                const float invstd = 1.0f / sqrtf(ep_var[c][t] + a.bn_eps);
-                const float sc = invstd * ep_w[c][t];
-                v = v * sc + (ep_b[c][t] - ep_mean[c][t] * sc);
+                const float sc = bn_scale(ep_var[c][t], a.bn_eps, ep_w[c][t]);
+                v = v * sc + bn_shift(ep_b[c][t], ep_mean[c][t], sc);
             }
             if (a.relu) v = fmaxf(v, 0.0f);
             if (a.resid) v += ep_res[c][t];
@@ -864,13 +824,9 @@ GatWs gat_ws(const NscGatModel *m, int N, void *base)
 int check_model(const NscGatModel *m)
 {
     if (!m) return NSC_EINVAL;
-    if (m->n_layers < 1 || m->n_layers > NSC_GAT_MAX_LAYERS) return NSC_EUNSUPPORTED;
-    if (m->hidden < 16 || m->hidden > 1024 || (m->hidden & 15)) return NSC_EUNSUPPORTED;   // GEMM k-blocks of 16
-    if (m->in_dim < 16 || (m->in_dim & 15) || m->out_dim < 1) return NSC_EUNSUPPORTED;
-    if (!m->in_bn_w || !m->in_bn_b || !m->in_bn_mean || !m->in_bn_var) return NSC_EINVAL;
-    if (m->edge_dim < 0 || m->edge_dim > NSC_GAT_MAX_EDGE_DIM) return NSC_EUNSUPPORTED;
+    const int stt = check_gat_dims(m, false, true);
+    if (stt != NSC_OK) return stt;
     if (!m->in_w || !m->in_b || !m->out_w || !m->out_b) return NSC_EINVAL;
-    if (m->residual && m->in_dim != m->out_dim && (!m->res_w || !m->res_b)) return NSC_EINVAL;
     for (int l = 0; l < m->n_layers; ++l) {
         const NscGatLayer &L = m->layers[l];
         if (!L.lin_w || !L.att_src || !L.att_dst || !L.bias) return NSC_EINVAL;
@@ -879,46 +835,36 @@ int check_model(const NscGatModel *m)
     return NSC_OK;
 }
 
+// The kernel set of a forward, decoded once from nsc_gat_forward_ex's flags (NSC_GAT_GENERIC only keeps the stand-alone set
+// off the banded layer: it is not a set of its own here).
+enum class KernelSet {
+    STANDALONE,     // gemm_glds_kernel where it can run, else the LDS-tiled kernels; banded layers on banded graphs
+    DIRECT,         // NSC_GAT_CORESIDENT: gemm_nt_direct_kernel, no LDS
+    SHARED_B,       // NSC_GAT_CORESIDENT | NSC_GAT_SHARED_B: gemm_nt_share_kernel, 10 KB of LDS
+    LDS_TILED,      // NSC_GAT_LDS_TILED: gemm_nt_kernel (round 2)
+};
 
 template <int EPI>
-void launch_gemm(hipStream_t st, int cores, const float *A, int lda, const float *B, int ldb, const float *Bx,
+void launch_gemm(hipStream_t st, KernelSet set, const float *A, int lda, const float *B, int ldb, const float *Bx,
                  int M, int N, int n_main, int K, float *C, int ldc, const GemmEpi &ep)
 {
     // Tile choice (measured at M = 1 024 and 4 541, round 2): 32-row tiles (two accumulators share the B operand, 1.7x
     // less operand traffic per MFMA) as soon as they still give >= 1.5 workgroups per CU; below that 16-row tiles, so
     // that every SIMD of the chip gets a wave -- these GEMMs are operand-latency-, not MFMA-bound.
-    // cores: 0 stand-alone (gemm_glds_kernel where it can run), 1 / 2 the co-resident sets, 3 the round-2 LDS-tiled kernels
-    if (cores == 0 && launch_glds<EPI>(st, A, lda, B, ldb, Bx, M, N, n_main, K, C, ldc, ep)) return;
-    const bool coresident = cores == 1 || cores == 2;
-    if (cores == 2) {                              // small-LDS co-resident form: 64 x 64 tiles, B shared through 10 KB of LDS
+    if (set == KernelSet::STANDALONE && launch_glds<EPI>(st, A, lda, B, ldb, Bx, M, N, n_main, K, C, ldc, ep)) return;
+    if (set == KernelSet::SHARED_B) {              // small-LDS co-resident form: 64 x 64 tiles, B shared through 10 KB of LDS
         const dim3 gs((N + 63) / 64, (M + 63) / 64);
         hipLaunchKernelGGL((gemm_nt_share_kernel<EPI>), gs, dim3(256), 0, st, A, lda, B, ldb, Bx, M, N, n_main, K, C, ldc, ep);
         return;
     }
     const long long w2 = (long long)((N + 63) / 64) * ((M + 31) / 32);
     const long long w4 = (long long)((N + 63) / 64) * ((M + 63) / 64);
-    bool two = w2 >= 384 && !coresident;
+    const bool coresident = set == KernelSet::DIRECT;
+    const bool two = w2 >= 384 && !coresident;
     // 64 x 64 tiles with 32 x 32 wave tiles (a third less LDS traffic per FLOP) where they still give two workgroups to
     // every CU (70 KB of LDS each): output_proj at M = 4 541 (923 tiles); input_proj and lin there have 284 / 355
-    bool four = w4 >= 512 && !coresident;
-    if (four) {
-        // The 64 x 64 form takes 69.6 KB of dynamic LDS: above 64 KB a kernel has to be opted in, and the attribute is
-        // per DEVICE.  State: one atomic per (instantiation, device) -- 0 not tried, 1 opted in, 2 refused (then the
-        // 32-row tiles run: same results, bit for bit).  Racing threads at worst both set the attribute (idempotent).
-        static std::atomic<int> opted[16];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) {
-            four = false;
-        } else {
-            int s = opted[dev].load(std::memory_order_acquire);
-            if (s == 0) {
-                s = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_nt_kernel<2, EPI, 2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess ? 1 : 2;
-                opted[dev].store(s, std::memory_order_release);
-            }
-            if (s != 1) four = false;
-        }
-    }
+    // (69.6 KB of dynamic LDS: where the device refuses the opt-in the 32-row tiles run -- same results, bit for bit)
+    const bool four = w4 >= 512 && !coresident && nsc_opt_in_lds<&gemm_nt_kernel<2, EPI, 2>>(96 * 1024);
     const int bm = four ? 64 : two ? 32 : 16;
     const dim3 grid((N + 63) / 64, (M + bm - 1) / bm);
     const unsigned lds = (unsigned)(2 * (bm + 64) * 68 * sizeof(float));
@@ -1070,7 +1016,8 @@ int nsc_gat_forward_ex(const NscGatModel *m, const NscGraph *g, const float *x, 
     if (flags & ~(uint32_t)(NSC_GAT_CORESIDENT | NSC_GAT_SHARED_B | NSC_GAT_LDS_TILED | NSC_GAT_GENERIC)) return NSC_EINVAL;
     if ((flags & NSC_GAT_SHARED_B) && !(flags & NSC_GAT_CORESIDENT)) return NSC_EINVAL;
     if ((flags & NSC_GAT_LDS_TILED) && (flags & NSC_GAT_CORESIDENT)) return NSC_EINVAL;
-    const int cores = (flags & NSC_GAT_CORESIDENT) ? ((flags & NSC_GAT_SHARED_B) ? 2 : 1) : (flags & NSC_GAT_LDS_TILED) ? 3 : 0;
+    const KernelSet set = (flags & NSC_GAT_CORESIDENT) ? ((flags & NSC_GAT_SHARED_B) ? KernelSet::SHARED_B : KernelSet::DIRECT)
+                          : (flags & NSC_GAT_LDS_TILED) ? KernelSet::LDS_TILED : KernelSet::STANDALONE;
     int stt = check_model(m);
     if (stt != NSC_OK) return stt;
     if (!g || g->n_nodes < 0) return NSC_EINVAL;
@@ -1091,11 +1038,11 @@ int nsc_gat_forward_ex(const NscGatModel *m, const NscGraph *g, const float *x, 
     ep.bn_w = m->in_bn_w; ep.bn_b = m->in_bn_b; ep.bn_mean = m->in_bn_mean; ep.bn_var = m->in_bn_var;
     ep.bn_eps = m->bn_eps;
     ep.relu = 1;
-    launch_gemm<1>(st, cores, x, m->in_dim, m->in_w, m->in_dim, nullptr, N, H, H, m->in_dim, h0, H, ep);
+    launch_gemm<1>(st, set, x, m->in_dim, m->in_w, m->in_dim, nullptr, N, H, H, m->in_dim, h0, H, ep);
 
     // A banded graph (nsc_graph_band_entries vouches: sources within NSC_BAND_HALO rows of their target, at most
     // NSC_BAND_SLOTS entries per target) takes ONE launch per layer; its entries carry the edge attributes, edge_dim 2 only.
-    const bool banded = !(flags & NSC_GAT_GENERIC) && cores == 0 && g->band_entries && g->band > 0 && g->band <= NSC_BAND_HALO &&
+    const bool banded = !(flags & NSC_GAT_GENERIC) && set == KernelSet::STANDALONE && g->band_entries && g->band > 0 && g->band <= NSC_BAND_HALO &&
                         (!use_edge || m->edge_dim == 2);
 
     float *cur = h0, *nxt = h1;
@@ -1123,7 +1070,7 @@ int nsc_gat_forward_ex(const NscGatModel *m, const NscGraph *g, const float *x, 
         GemmEpi e2 = {};
         e2.aux0 = a_src;
         e2.aux1 = a_dst;
-        launch_gemm<0>(st, cores, cur, H, Ly.lin_w, H, auxl, N, H + 2, H, H, G, H, e2);
+        launch_gemm<0>(st, set, cur, H, Ly.lin_w, H, auxl, N, H + 2, H, H, G, H, e2);
 
         AggArgs a = {};
         a.row_ptr = g->row_ptr; a.src = g->src; a.eid = g->eid;
@@ -1141,15 +1088,13 @@ int nsc_gat_forward_ex(const NscGatModel *m, const NscGraph *g, const float *x, 
         a.alpha_out = alpha_out ? alpha_out + (size_t)l * g->nnz : nullptr;
         a.N = N; a.H = H; a.edge_dim = m->edge_dim;
         const dim3 grid((N + 3) / 4), block(256);
-        switch ((H + 255) / 256) {
-        case 1:
-            if (cores) hipLaunchKernelGGL((gat_aggregate_kernel<1, 4, false>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((gat_aggregate_kernel<1, 8, true>), grid, block, 0, st, a);
-            break;
-        case 2: hipLaunchKernelGGL((gat_aggregate_kernel<2, 8, true>), grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL((gat_aggregate_kernel<3, 8, true>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((gat_aggregate_kernel<4, 8, true>), grid, block, 0, st, a); break;
-        }
+        // (the < 64 VGPR form exists for one chunk per lane only; every set but the stand-alone one takes it there)
+        if (set != KernelSet::STANDALONE && H <= 256)
+            hipLaunchKernelGGL((gat_aggregate_kernel<1, 4, false>), grid, block, 0, st, a);
+        else
+            dispatch_ch(H, [&](auto ch) {
+                hipLaunchKernelGGL((gat_aggregate_kernel<decltype(ch)::value, 8, true>), grid, block, 0, st, a);
+            });
         float *t = cur; cur = nxt; nxt = t;
     }
 
@@ -1157,13 +1102,13 @@ int nsc_gat_forward_ex(const NscGatModel *m, const NscGraph *g, const float *x, 
     GemmEpi e3 = {};
     e3.bias = m->out_b;
     if (m->residual && m->in_dim == m->out_dim) { e3.resid = x; e3.ldr = m->in_dim; }
-    launch_gemm<2>(st, cores, cur, H, m->out_w, H, nullptr, N, m->out_dim, m->out_dim, H, out, m->out_dim, e3);
+    launch_gemm<2>(st, set, cur, H, m->out_w, H, nullptr, N, m->out_dim, m->out_dim, H, out, m->out_dim, e3);
     if (m->residual && m->in_dim != m->out_dim) {
         // out += residual_proj(x): second GEMM accumulating through the residual epilogue
         GemmEpi e4 = {};
         e4.bias = m->res_b;
         e4.resid = out; e4.ldr = m->out_dim;
-        launch_gemm<2>(st, cores, x, m->in_dim, m->res_w, m->in_dim, nullptr, N, m->out_dim, m->out_dim, m->in_dim, out,
+        launch_gemm<2>(st, set, x, m->in_dim, m->res_w, m->in_dim, nullptr, N, m->out_dim, m->out_dim, m->in_dim, out,
                        m->out_dim, e4);
     }
     return launch_status();

@@ -32,7 +32,7 @@
 // d = 0..3, t = 0..3, operand element t of lane (r, q) = k 64 c + 16 d + 4 q + t), a_src / a_dst the same chain as fmas; the
 // softmax reduces with the same xor butterfly (a 16-lane group here, the 64-lane wave there: with at most 16 entries the
 // upper levels of the 64-lane butterfly only add zeros); the aggregation is the same fma chain in CSR entry order; the
-// epilogue is the same expression.  tests/test_gat_gpu.py compares the sets bit for bit.
+// epilogue is the same functions (bn_fold, bn_apply, layer_act of nsc_gat_epilogue.h).  tests/test_gat_gpu.py compares the sets bit for bit.
 //
 // The graph comes as banded entries (nsc_graph_band_entries, built once per graph next to the CSR): 8 slots of 16 bytes per
 // target {source node, edge_attr[0], edge_attr[1], CSR entry index (-1 = empty slot)} in CSR order (self loop last, its
@@ -222,14 +222,10 @@ __global__ __launch_bounds__(640) void gat_layer_banded_kernel(BandArgs a, const
         if (tid == 256) NSC_BAND_STAMP(6);
         if (tid < 256 + 64) {
             // BatchNorm (eval) of this tile's 64 columns folded to scale / shift by the staging waves, idle from their last
-            // chunk on (gat_aggregate_kernel's expression: sc = invstd * w, shift = b - mean * sc)
+            // chunk on
             const int col = n0 + tid - 256;
             bn_pre[2] = a.bias[col];
-            if (a.bn_w) {
-                const float invstd = 1.0f / sqrtf(a.bn_var[col] + a.bn_eps);
-                bn_pre[0] = invstd * a.bn_w[col];
-                bn_pre[1] = a.bn_b[col] - a.bn_mean[col] * bn_pre[0];
-            }
+            if (a.bn_w) bn_fold(a.bn_var, a.bn_eps, a.bn_w, a.bn_b, a.bn_mean, col, bn_pre[0], bn_pre[1]);
         }
     } else {
         // ---- computing waves
@@ -403,7 +399,7 @@ __global__ __launch_bounds__(640) void gat_layer_banded_kernel(BandArgs a, const
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             float v = o[t] + bnbi[t];
-            if (a.bn_w) v = v * bnsc[t] + bnsh[t];
+            if (a.bn_w) v = bn_apply(v, bnsc[t], bnsh[t]);
             if (a.relu) v = fmaxf(v, 0.0f);
             if (a.resid) v += rs[pass][t];
             o[t] = v;
@@ -435,18 +431,7 @@ bool launch_banded_cfg(hipStream_t st, const BandArgs &a)
 {
     constexpr unsigned lds = NST * (16 * ACC + 64) * 256;
     static_assert(lds <= 160 * 1024, "LDS of a CU");
-    if (lds > 64 * 1024) {                                         // per-device opt-in, as launch_glds_cfg
-        static std::atomic<int> opted[16];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
-        int s = opted[dev].load(std::memory_order_acquire);
-        if (s == 0) {
-            s = hipFuncSetAttribute(reinterpret_cast<const void *>(&gat_layer_banded_kernel<ACC, NST>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 1 : 2;
-            opted[dev].store(s, std::memory_order_release);
-        }
-        if (s != 1) return false;
-    }
+    if (!nsc_opt_in_lds<&gat_layer_banded_kernel<ACC, NST>>(lds)) return false;
     constexpr int own = 16 * ACC - 2 * NSC_BAND_HALO;
     const dim3 grid(a.H / 64, (a.M + own - 1) / own);
     hipLaunchKernelGGL((gat_layer_banded_kernel<ACC, NST>), grid, dim3(640), lds, st, a, a.Bx);

@@ -13,9 +13,11 @@
 // float64 partials, deterministic), (b) a per-target kernel for the softmax / leaky-ReLU backward,
 // (c) a per-source kernel (transposed CSR, no atomics) for the feature gradient, (d) f32-MFMA GEMMs in
 // NT / NN / TN form with split-K slabs for the weight gradients (deterministic reduce).
+// Shared with the inference forward (nsc_gat.hip): the LDS-DMA GEMM of the projections (nsc_gemm_glds.h) with its epilogue, the
+// CH dispatch of the attention kernels and the model's dimension checks (nsc_gat_epilogue.h); the opt-in for more than 64 KB
+// of LDS and the wave reductions are nsc_util.h's.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 #include "../../include/nsc.h"
@@ -24,6 +26,7 @@
 
 namespace {
 
+#include "nsc_gat_epilogue.h"
 #include "nsc_gemm_glds.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -364,17 +367,8 @@ template <int TM>
 int launch_tn_glds_cfg(hipStream_t st, const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C,
                        int accumulate, Region slabs, SlabBatch &batch)
 {
-    constexpr unsigned lds = 3 * (64 * 64 * TM + 64 * 64) * 4;     // 96 / 144 KB: above 64 KB a kernel is opted in, per device
-    static std::atomic<int> opted[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return NSC_EUNSUPPORTED;
-    int o = opted[dev].load(std::memory_order_acquire);
-    if (o == 0) {
-        o = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_glds_kernel<TM>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) == hipSuccess ? 1 : 2;
-        opted[dev].store(o, std::memory_order_release);
-    }
-    if (o != 1) return NSC_EUNSUPPORTED;
+    constexpr unsigned lds = 3 * (64 * 64 * TM + 64 * 64) * 4;     // 96 / 144 KB
+    if (!nsc_opt_in_lds<&gemm_tn_glds_kernel<TM>>(lds)) return NSC_EUNSUPPORTED;
     const int tiles = ((M + 64 * TM - 1) / (64 * TM)) * ((N + 63) / 64);
     int splits = 256 / tiles;                                       // about one round of workgroups on the 256 CUs
     splits = splits < 1 ? 1 : (splits > SPLITK_SLABS ? SPLITK_SLABS : splits);
@@ -739,19 +733,6 @@ __global__ __launch_bounds__(256) void add_inplace_kernel(float *__restrict__ a,
 // ---------------------------------------------------------------------------------------------
 // attention (training): logits from the true definition a_src = <g, att_src>, a_dst = <g, att_dst>
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sumf(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_maxf(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 // a_src[i] = <g_i, att_src>, a_dst[i] = <g_i, att_dst>; one wave per node
 // (round 4: the last workgroup of the grid computes v = W_edge^T att_edge instead -- edge_vec_kernel's body, which was a launch
 // of its own per layer and batch)
@@ -767,7 +748,7 @@ __global__ __launch_bounds__(256) void att_dots_kernel(const float *__restrict__
         for (int d = threadIdx.x >> 6; d < edge_dim; d += 4) {
             float s = 0.0f;
             for (int c = lane; c < H; c += 64) s = __builtin_fmaf(w_edge[(long long)c * edge_dim + d], att_edge[c], s);
-            s = wave_sumf(s);
+            s = nsc_wave_sum(s);
             if (lane == 0) v[d] = s;
         }
         return;
@@ -779,7 +760,7 @@ __global__ __launch_bounds__(256) void att_dots_kernel(const float *__restrict__
         s = __builtin_fmaf(g, att_s[c], s);
         d = __builtin_fmaf(g, att_d[c], d);
     }
-    s = wave_sumf(s); d = wave_sumf(d);
+    s = nsc_wave_sum(s); d = nsc_wave_sum(d);
     if (lane == 0) { a_src[i] = s; a_dst[i] = d; }
 }
 
@@ -832,9 +813,9 @@ __global__ __launch_bounds__(256) void agg_train_kernel(TrainAgg a)
         int j = i;
         float l = -INFINITY;
         if (e < end) { l = edge_raw(a.lg, i, e, j); l = l > 0.f ? l : a.slope * l; }
-        const float m = wave_maxf(l);
+        const float m = nsc_wave_max(l);
         const float pe = (e < end) ? expf(l - m) : 0.0f;
-        const float s = wave_sumf(pe) + 1e-16f;                      // PyG softmax
+        const float s = nsc_wave_sum(pe) + 1e-16f;                      // PyG softmax
         float ald = 0.0f;
         if (e < end) {
             const float al = pe / s;
@@ -883,10 +864,10 @@ __global__ __launch_bounds__(256) void agg_train_kernel(TrainAgg a)
     }
     float m = -INFINITY;
     for (int e = beg + lane; e < end; e += 64) { int j; float l = edge_raw(a.lg, i, e, j); l = l > 0.f ? l : a.slope * l; m = fmaxf(m, l); }
-    m = wave_maxf(m);
+    m = nsc_wave_max(m);
     float s = 0.0f;
     for (int e = beg + lane; e < end; e += 64) { int j; float l = edge_raw(a.lg, i, e, j); l = l > 0.f ? l : a.slope * l; s += expf(l - m); }
-    s = wave_sumf(s) + 1e-16f;                                   // PyG softmax
+    s = nsc_wave_sum(s) + 1e-16f;                                   // PyG softmax
     // H <= 1024: up to 16 columns per lane; softmax weights travel between lanes by shuffle only
     float acc[16];
 #pragma unroll
@@ -980,7 +961,7 @@ __global__ __launch_bounds__(256) void att_bwd_target_kernel(AttBwdA a)
                     d = __builtin_fmaf(dy[k].z, g[u][k].z, d);
                     d = __builtin_fmaf(dy[k].w, g[u][k].w, d);
                 }
-                const float sum = wave_sumf(d) * keep_scale(a.p, seed, a.stream, (unsigned long long)(beg + t0 + u));
+                const float sum = nsc_wave_sum(d) * keep_scale(a.p, seed, a.stream, (unsigned long long)(beg + t0 + u));
                 if (lane == t0 + u) da = sum;
             }
         }
@@ -1004,7 +985,7 @@ __global__ __launch_bounds__(256) void att_bwd_target_kernel(AttBwdA a)
         float d = 0.0f;
         for (int c = lane; c < a.H; c += 64)
             d = __builtin_fmaf(a.dY[(long long)i * a.H + c], a.G[(long long)j * a.H + c], d);
-        return wave_sumf(d) * keep_scale(a.p, a.seed.get(), a.stream, (unsigned long long)e);
+        return nsc_wave_sum(d) * keep_scale(a.p, a.seed.get(), a.stream, (unsigned long long)e);
     };
     float inner = 0.0f;                                       // sum_e alpha_e dalpha_e (wave-uniform)
     for (int e = beg; e < end; ++e) inner += a.alpha[e] * dalpha(e);
@@ -1292,7 +1273,7 @@ __global__ __launch_bounds__(256) void triplet_kernel(const float *__restrict__ 
         dp = __builtin_fmaf(x, x, dp);
         dn = __builtin_fmaf(y, y, dn);
     }
-    dp = wave_sumf(dp); dn = wave_sumf(dn);
+    dp = nsc_wave_sum(dp); dn = nsc_wave_sum(dn);
     const float l = dp - dn + margin;
     if (lane == 0) per_triplet[t] = l > 0.0f ? l : 0.0f;
     if (grad && l > 0.0f) {
@@ -1506,17 +1487,6 @@ ColExtra bn_backward(hipStream_t st, const float *dh, const float *z, const floa
     return ColExtra{part2, R, acc, g_bias};
 }
 
-// CH = ceil(H / 256) of the attention kernels (H <= 1024: check_train) as a compile-time constant: f(std::integral_constant<int, CH>)
-template <class F> void dispatch_ch(int H, F f)
-{
-    switch ((H + 255) / 256) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 3: f(std::integral_constant<int, 3>{}); break;
-    default: f(std::integral_constant<int, 4>{}); break;
-    }
-}
-
 inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
 
 // Layer l's logit operands; use_edge: the forward had edge attributes and an edge projection (else the logit has no edge term)
@@ -1529,11 +1499,8 @@ EdgeLogit edge_logit(const NscGraph *g, const float *edge_attr, bool use_edge, c
 int check_train(const NscGatModel *m, const NscGraph *g)
 {
     if (!m || !g) return NSC_EINVAL;
-    if (m->n_layers < 1 || m->n_layers > NSC_GAT_MAX_LAYERS) return NSC_EUNSUPPORTED;
-    if (m->hidden < 16 || m->hidden > 1024 || (m->hidden & 15)) return NSC_EUNSUPPORTED;
-    if (m->in_dim < 16 || (m->in_dim & 15) || m->out_dim < 4 || (m->out_dim & 3)) return NSC_EUNSUPPORTED;
-    if (m->edge_dim < 0 || m->edge_dim > NSC_GAT_MAX_EDGE_DIM) return NSC_EUNSUPPORTED;
-    if (m->residual && m->in_dim != m->out_dim && (!m->res_w || !m->res_b)) return NSC_EINVAL;   // model.py:91-94
+    const int stt = check_gat_dims(m, true, false);
+    if (stt != NSC_OK) return stt;
     if (!g->row_ptr || !g->src || !g->eid) return NSC_EINVAL;
     return NSC_OK;
 }

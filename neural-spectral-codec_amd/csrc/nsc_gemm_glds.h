@@ -1,11 +1,10 @@
 // The stand-alone f32-MFMA GEMM of the GNN path, C[M,N] = A[M,K] * B[N,K]^T with fused epilogues: LDS-DMA staged, wave-
-// specialised (gemm_glds_kernel), plus what it shares with the other GEMM kernels of nsc_gat.hip (epilogue descriptor,
-// XCD-aware tile order).  Included by nsc_gat.hip (inference forward, reference src/gnn/model.py:116,127,144) and by
-// nsc_gat_train.hip (the same three projections in the training forward, src/gnn/trainer.py:205); everything lives in
-// the including file's anonymous namespace (the includer has <hip/hip_runtime.h> and <atomic> before it opens that namespace).
+// specialised (gemm_glds_kernel), plus the XCD-aware tile order it shares with the other GEMM kernels of nsc_gat.hip.  Its
+// epilogue (descriptor, value, stores) is nsc_gat_epilogue.h's, its LDS opt-in nsc_util.h's.  Included by nsc_gat.hip
+// (inference forward, reference src/gnn/model.py:116,127,144) and by nsc_gat_train.hip (the same three projections in the
+// training forward, src/gnn/trainer.py:205) after nsc_gat_epilogue.h; everything lives in the including file's anonymous
+// namespace (the includer has <hip/hip_runtime.h> before it opens that namespace).
 #pragma once
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // XCD-aware tile order.  Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md, dispatch), each with
 // its own L2: with the natural order the 4 (or 13) column blocks that share an A row block -- and neighbouring
@@ -20,21 +19,6 @@ __device__ __forceinline__ unsigned xcd_tile(unsigned id, unsigned n)
     const unsigned xcd = id & 7u, q = n >> 3, r = n & 7u;
     return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + (id >> 3);
 }
-
-// Columns >= n_main of a GEMM come from the extra rows Bx (the folded attention vectors of the inference forward) and are
-// written to aux0 / aux1 instead of C.
-struct GemmEpi {
-    const float *bias;                              // per column, nullable
-    const float *bn_w, *bn_b, *bn_mean, *bn_var;    // BatchNorm eval, nullable as a group
-    float bn_eps;
-    int relu;
-    const float *resid;                             // (M, ldr) added last, nullable
-    int ldr;
-    float *aux0, *aux1;                             // columns n_main, n_main+1 (M each), nullable
-};
-
-// EPI: 0 = plain store + aux columns (lin), 1 = bias + BatchNorm + ReLU (input_proj),
-//      2 = bias + residual (output_proj / residual_proj)
 
 // ---------------------------------------------------------------------------------------------
 // Round 3: the stand-alone GEMM (one launch owns the chip).  What the round-2 ablations showed about gemm_nt_kernel:
@@ -208,12 +192,9 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(const float *__restrict_
         if (EPI == 1 && tid < 256 + BN) {
             // BatchNorm (eval) of this tile's columns, folded to a scale and a shift by the staging waves, idle from their last
             // chunk on; handed over through LDS behind the tile (the 20 loads per thread that every wave used to issue after
-            // the second epilogue barrier were an exposed round trip).  torch batch_norm eval: alpha = invstd * weight,
-            // beta = bias - mean * alpha.
+            // the second epilogue barrier were an exposed round trip).
             const int cl = tid - 256, col = (n0 + cl < N) ? n0 + cl : N - 1;
-            const float invstd = 1.0f / sqrtf(ep.bn_var[col] + ep.bn_eps);
-            bn_pre[0] = invstd * ep.bn_w[col];
-            bn_pre[1] = ep.bn_b[col] - ep.bn_mean[col] * bn_pre[0];
+            bn_fold(ep.bn_var, ep.bn_eps, ep.bn_w, ep.bn_b, ep.bn_mean, col, bn_pre[0], bn_pre[1]);
             bn_pre[2] = ep.bias[col];
         }
     } else {
@@ -342,10 +323,7 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(const float *__restrict_
         const f32x4 t = *reinterpret_cast<const f32x4 *>(&Cs[lr * LD + 4 * c4t]);
         float v[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (EPI != 0) v[j] = v[j] + bias[j];
-            if (EPI == 1) v[j] = fmaxf(v[j] * bn_scale[j] + bn_shift[j], 0.0f);
-        }
+        for (int j = 0; j < 4; ++j) v[j] = epi_value<EPI>(v[j], bias[j], bn_scale[j], bn_shift[j]);
         if (vec) {
             if (EPI == 2 && ep.resid) { v[0] += rs[pass].x; v[1] += rs[pass].y; v[2] += rs[pass].z; v[3] += rs[pass].w; }
             *reinterpret_cast<f32x4 *>(C + (long long)row * ldc + cg) = f32x4{v[0], v[1], v[2], v[3]};
@@ -359,35 +337,22 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(const float *__restrict_
                     if (EPI == 2 && ep.resid) o = o + ep.resid[(long long)row * ep.ldr + col];
                     C[(long long)row * ldc + col] = o;
                 } else {
-                    float *aux = (col == n_main) ? ep.aux0 : ep.aux1;
-                    aux[row] = v[j];
+                    epi_store_aux(v[j], ep.aux0, ep.aux1, row, col, n_main);
                 }
             }
         }
     }
 }
 
-// One configuration of gemm_glds_kernel.  Above 64 KB of dynamic LDS a kernel has to be opted in, and the attribute is
-// per DEVICE: one atomic per (instantiation, device) -- 0 not tried, 1 opted in, 2 refused.  Returns false when the
-// configuration cannot run here (the caller then takes gemm_nt_kernel: same results, bit for bit).
+// One configuration of gemm_glds_kernel.  Returns false when the configuration cannot run here (the device refuses its LDS:
+// the caller then takes gemm_nt_kernel -- same results, bit for bit).
 template <int ACC, int EPI, int NST = 3, int BC = 1, bool BKM = false>
 bool launch_glds_cfg(hipStream_t st, const float *A, int lda, const float *B, int ldb, const float *Bx, int M, int N,
                      int n_main, int K, float *C, int ldc, const GemmEpi &ep)
 {
     constexpr unsigned lds = NST * (16 * ACC + 64 * BC) * 256;
     static_assert(lds <= 160 * 1024, "LDS of a CU");
-    if (lds > 64 * 1024) {
-        static std::atomic<int> opted[16];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
-        int s = opted[dev].load(std::memory_order_acquire);
-        if (s == 0) {
-            s = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_glds_kernel<ACC, EPI, NST, BC, BKM>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 1 : 2;
-            opted[dev].store(s, std::memory_order_release);
-        }
-        if (s != 1) return false;
-    }
+    if (!nsc_opt_in_lds<&gemm_glds_kernel<ACC, EPI, NST, BC, BKM>>(lds)) return false;
     const dim3 grid((N + 64 * BC - 1) / (64 * BC), (M + 16 * ACC - 1) / (16 * ACC));
     hipLaunchKernelGGL((gemm_glds_kernel<ACC, EPI, NST, BC, BKM>), grid, dim3(512), lds, st, A, lda, B, ldb, Bx, M, N, n_main, K, C,
                        ldc, ep);

@@ -22,13 +22,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_sumf(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // inclusive CDF of one row held as PER consecutive bins per lane; returns the row sum
 template <int PER>
 __device__ __forceinline__ float row_cdf(float (&v)[PER], int lane, float eps, int divide_plain)
@@ -36,7 +29,7 @@ __device__ __forceinline__ float row_cdf(float (&v)[PER], int lane, float eps, i
     float tot = 0.0f;
 #pragma unroll
     for (int k = 0; k < PER; ++k) tot += v[k];
-    const float sum = wave_sumf(tot);
+    const float sum = nsc_wave_sum(tot);
     // wasserstein.py:153-163: query / sum (if sum > eps); database row / (sum + eps) (if sum > eps)
     float scale = 1.0f;
     if (sum > eps) scale = divide_plain ? sum : sum + eps;
@@ -113,7 +106,7 @@ __global__ __launch_bounds__(256) void w1_dist_kernel(const float *__restrict__ 
             const int c = lane * PER + k;
             if (c < D) s += fabsf(v[k] - w[k]);
         }
-        s = wave_sumf(s);
+        s = nsc_wave_sum(s);
         if (db_pos && q_pos && w1_too_close(p, q_pos + q * 3, min_dist)) s = INFINITY;
         if (lane == 0) dist[(long long)q * N + i] = s;
     }
@@ -172,7 +165,7 @@ __global__ __launch_bounds__(256) void w1_stream_kernel(const float *__restrict_
                 a += fabsf(cur[j].z - qv[t][j].z);
                 a += fabsf(cur[j].w - qv[t][j].w);
             }
-            s[t] = wave_sumf(a);
+            s[t] = nsc_wave_sum(a);
         }
         if (lane == 0) {
 #pragma unroll
@@ -359,7 +352,7 @@ __global__ __launch_bounds__(256) void mine_kernel(const double *__restrict__ po
                 const float *cb = cdf + (long long)cand * D;
                 float s = 0.0f;
                 for (int c = lane; c < D; c += 64) s += fabsf(ca[c] - cb[c]);
-                s = wave_sumf(s);
+                s = nsc_wave_sum(s);
                 if (s < best) { best = s; hard = cand; }
                 if (s != s && first_nan < 0) first_nan = cand;
             }
@@ -389,7 +382,7 @@ __global__ __launch_bounds__(256) void mine_kernel(const double *__restrict__ po
                 const float *cb = cdf + (long long)(c0 + b) * D;
                 float sd = 0.0f;
                 for (int c = lane; c < D; c += 64) sd += fabsf(ca[c] - cb[c]);
-                sd = wave_sumf(sd);
+                sd = nsc_wave_sum(sd);
                 if (lane == b) row[c0 + b] = (sd != sd) ? 0x7fc00000u : __float_as_uint(sd);
             }
         }

@@ -1,8 +1,10 @@
 // nsc_util.h -- the small jobs every .hip of the library does the same way: the status of an entry point's launches, the
-// 64-lane butterfly sum, the workspace carver, and the scan and row sort of the two CSR builders (nsc_graph_build_csr,
-// nsc_graph_transpose).  Included at file scope; the namespace below gives each file its own copy.
+// 64-lane butterfly sum and maximum, the opt-in for more than 64 KB of dynamic LDS, the workspace carver, and the scan and
+// row sort of the two CSR builders (nsc_graph_build_csr, nsc_graph_transpose).  Included at file scope; the namespace below
+// gives each file its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <stdint.h>
 
 #include "../../include/nsc.h"
@@ -19,6 +21,13 @@ template <class T> __device__ __forceinline__ T nsc_wave_sum(T v)
     return v;
 }
 
+// the maximum over the 64 lanes of a wave, in every lane: the same butterfly
+__device__ __forceinline__ float nsc_wave_max(float v)
+{
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
 // the inclusive scan of an integer over the 64 lanes of a wave: lane l gets the sum of lanes 0 .. l
 __device__ __forceinline__ int nsc_wave_scan(int v)
 {
@@ -28,6 +37,26 @@ __device__ __forceinline__ int nsc_wave_scan(int v)
         if (lane >= o) v += u;
     }
     return v;
+}
+
+// ---- more than 64 KB of dynamic LDS.  Above 64 KB a kernel has to be opted in, and the attribute is per DEVICE.  One atomic
+// per (kernel instantiation, device): 0 not tried, 1 opted in, 2 refused; racing threads at worst both set the attribute
+// (idempotent).  false: the device refuses, or its index is outside the table -- the caller falls back or reports.  The kernel is
+// a template ARGUMENT, not a function argument: instantiations of one kernel template share their pointer type, and with it
+// they would share the table.
+template <auto KERNEL> bool nsc_opt_in_lds(unsigned bytes)
+{
+    if (bytes <= 64 * 1024) return true;
+    static std::atomic<int> opted[16];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
+    int s = opted[dev].load(std::memory_order_acquire);
+    if (s == 0) {
+        s = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) ==
+                    hipSuccess ? 1 : 2;
+        opted[dev].store(s, std::memory_order_release);
+    }
+    return s == 1;
 }
 
 // ---- workspaces.  A workspace is laid out by ONE function that maps (base or null, shape) to a struct of typed pointers

@@ -211,6 +211,41 @@ def test_odd_dimensions_all_kernel_sets(dims):
     _check(outs[0], m, g)
 
 
+@pytest.mark.parametrize("residual", [True, False])
+@pytest.mark.parametrize("dims", [(32, 32), (32, 50)])
+@pytest.mark.parametrize("edge_dim", [None, 2])
+@pytest.mark.parametrize("hidden", [64, 48])
+def test_every_epilogue_branch_in_every_kernel_set(hidden, edge_dim, dims, residual):
+    """The epilogues of the six GNN kernels take their arithmetic from one set of functions (csrc/nsc_gat_epilogue.h) and keep
+    their own row passes and branches; this visits every branch in every kernel set at the smallest shapes that reach it.  Nodes 1 / 17 / 33 / 70: a single partial tile, row
+    counts off the 16- and 32-row grain, more than one 64-row tile.  hidden 64 takes the one-launch banded layer in the default
+    set, hidden 48 makes it refuse (lin GEMM with the two aux columns + gat_aggregate_kernel).  (32, 32): identity residual
+    in output_proj's epilogue, float4 stores; (32, 50): residual_proj as a second accumulating GEMM, a row stride that is
+    no multiple of 4, the column-by-column store.  Three layers: ReLU on two, the middle-layer residual on one.  All five
+    sets give the same bytes, and the default set sits within the oracle bar."""
+    i, o = dims
+    torch.manual_seed(hidden + i + o)
+    m = SpectralGNN(input_dim=i, hidden_dim=hidden, output_dim=o, n_layers=3, edge_dim=edge_dim, residual=residual)
+    go.randomize_bn_stats(m, 5)
+    with torch.no_grad():
+        for c in m.convs:
+            c.bias.normal_(0, 0.1)
+    m = m.to("cuda").eval()
+    for n in (1, 17, 33, 70):
+        g = gm.synthetic_chain_graph(n, device="cuda", seed=n, features=torch.rand(n, i))
+        outs = []
+        with torch.no_grad():
+            for ks in (False, True, "shared_b", "lds_tiled", "generic"):
+                m.coresident = ks
+                outs.append(m(g))
+            m.coresident = False
+        assert outs[0].shape == (n, o)
+        ref = outs[0].cpu().numpy().tobytes()
+        for ks, t in zip((True, "shared_b", "lds_tiled", "generic"), outs[1:]):
+            assert t.cpu().numpy().tobytes() == ref, f"kernel set {ks!r} differs from the default set at n = {n}"
+        _check(outs[0], m, g)
+
+
 def test_pipelined_path_matches_serial():
     """ShardedDescriptorPath(pipeline=True): encoder of batch k+1 on one stream over the GNN of batch k on a
     second one, double-buffered descriptors -- every step's results equal the one-stream path's."""

@@ -146,15 +146,15 @@ static void shape(const Shape &s, int M, int reps, int pick_only)
     ep.aux0 = aux0; ep.aux1 = aux1;
 
     printf("%s: M=%d N=%d (+%d aux) K=%d  %.3f GFLOP\n", s.name, M, s.n_main, s.N - s.n_main, s.K, 2.0 * M * s.n_main * s.K / 1e9);
-    // reference: gemm_nt_kernel through the round-2 dispatcher (cores = 3: never the glds path)
-    launch_gemm<EPI>(0, 3, A, s.K, B, s.K, s.N > s.n_main ? Bx : nullptr, M, s.N, s.n_main, s.K, C, s.n_main, ep);
+    // reference: gemm_nt_kernel through the round-2 dispatcher (KernelSet::LDS_TILED: never the glds path)
+    launch_gemm<EPI>(0, KernelSet::LDS_TILED, A, s.K, B, s.K, s.N > s.n_main ? Bx : nullptr, M, s.N, s.n_main, s.K, C, s.n_main, ep);
     hipDeviceSynchronize();
     const size_t nc = (size_t)M * s.n_main;
     std::vector<float> ref(nc), ra0(M), ra1(M);
     hipMemcpy(ref.data(), C, nc * 4, hipMemcpyDeviceToHost);
     hipMemcpy(ra0.data(), aux0, M * 4, hipMemcpyDeviceToHost);
     hipMemcpy(ra1.data(), aux1, M * 4, hipMemcpyDeviceToHost);
-    const float us = time_us([&] { launch_gemm<EPI>(0, 3, A, s.K, B, s.K, s.N > s.n_main ? Bx : nullptr, M, s.N, s.n_main, s.K, C, s.n_main, ep); }, reps);
+    const float us = time_us([&] { launch_gemm<EPI>(0, KernelSet::LDS_TILED, A, s.K, B, s.K, s.N > s.n_main ? Bx : nullptr, M, s.N, s.n_main, s.K, C, s.n_main, ep); }, reps);
     const double tf = 2.0 * M * s.n_main * s.K / us / 1e6;
     printf("  gemm_nt_kernel (round 2):            %7.2f us  %6.1f TF/s (%4.1f %%)\n", us, tf, tf / 157.3 * 100);
     const float *bx = s.N > s.n_main ? Bx : nullptr;
