@@ -35,6 +35,14 @@ class GatLayer(C.Structure):
 ABI_VERSION = 4            # NSC_ABI_VERSION of include/nsc.h
 GAT_MAX_LAYERS = 8
 GAT_MAX_EDGE_DIM = 8
+# include/nsc.h: the ``flags`` of nsc_gat_forward_ex, by the value of SpectralGNN.coresident that selects them
+GAT_KERNEL_SETS = {
+    False: 0,            # the stand-alone forward (LDS-DMA GEMMs, one-launch layers on a banded graph)
+    True: 1,             # NSC_GAT_CORESIDENT
+    "shared_b": 1 | 2,   # NSC_GAT_CORESIDENT | NSC_GAT_SHARED_B
+    "lds_tiled": 4,      # NSC_GAT_LDS_TILED
+    "generic": 8,        # NSC_GAT_GENERIC
+}
 
 
 class GatModel(C.Structure):
@@ -362,6 +370,34 @@ def stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+STREAM = object()      # in call()'s arguments: where the hipStream_t goes (not always last: nsc_posegraph_*_robust)
+
+
+def call(name, device, *args):
+    """The one way into a launching ABI function: ``name`` runs with ``device`` current, on its current stream, and a
+    non-zero status raises NscError("<name> failed: ...").  Tensors become device pointers, None a null pointer, ctypes
+    structures go by reference, STREAM is replaced by the stream; anything else (numbers, ready-made pointers) passes as it
+    is.  ``*_workspace_bytes`` and ``*_default_params`` launch nothing and are called directly."""
+    fn = getattr(lib(), name)
+    with torch.cuda.device(device):
+        conv = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else stream_ptr(device) if a is STREAM
+                else C.byref(a) if isinstance(a, C.Structure) else a for a in args]
+        status = fn(*conv)
+    check(status, name)
+
+
+def capture(device, fn, stream=None):
+    """Record the launches of ``fn()`` as a hipGraph (on ``stream``, or on torch's capture stream) and return
+    (CUDAGraph, fn's result): nothing has run yet, ``replay()`` runs it.  Run ``fn`` once eagerly beforehand, so that no lazy
+    set-up is recorded.  Thread-local error mode: HIP calls of OTHER threads (RCCL's proxy / watchdog) do not invalidate the
+    capture.  What to do when this raises, and how long to keep the graph, is the caller's policy."""
+    torch.cuda.synchronize(device)
+    cg = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(cg, stream=stream, capture_error_mode="thread_local"):
+        result = fn()
+    return cg, result
+
+
 # Parameter epoch: bumped after every optimizer step of the process.  torch's fused Adam / AdamW / SGD write the parameters
 # without bumping their version counters, so caches derived from parameter VALUES (the GNN's folded attention vectors, the
 # encoder's bin LUT) carry this integer in their keys next to (data_ptr, _version).  Writes through ``.data`` bypass both.
@@ -389,7 +425,7 @@ class ScratchCache:
     (device, stream, host thread, use): work on different streams may overlap and two host threads issuing on one stream
     interleave their launches, work issued by one thread on one stream is ordered.
 
-    Bounded (round 4): at most ``cap`` keys, least recently used first, keys of host threads that no longer exist before
+    Bounded: at most ``cap`` keys, least recently used first, keys of host threads that no longer exist before
     any other.  A buffer is NEVER replaced by a bigger one -- a larger request adds a buffer to the key and the smaller
     ones stay, because a captured hipGraph replays the address it recorded; keys touched while a stream capture is open
     are pinned until ``release()`` (a replay does not come through here, so use-recency says nothing about them)."""

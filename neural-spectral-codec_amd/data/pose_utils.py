@@ -67,11 +67,8 @@ def compute_overlap_batch(points1: Sequence, points2: Sequence, transforms, voxe
     t1, t2 = int(sum(n1)), int(sum(n2))
     nbytes = L.nsc_voxel_overlap_workspace_bytes(t1, t2)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        st = L.nsc_voxel_overlap(_lib.ptr(p1), _lib.ptr(off1), _lib.ptr(p2), _lib.ptr(off2), P, t1, t2, max_pair,
-                                 stride, _lib.ptr(T), float(voxel_size), _lib.ptr(counts), _lib.ptr(iou),
-                                 _lib.ptr(ws), nbytes, _lib.stream_ptr(device))
-    _lib.check(st, "nsc_voxel_overlap")
+    _lib.call("nsc_voxel_overlap", device, p1, off1, p2, off2, P, t1, t2, max_pair, stride, T, float(voxel_size), counts, iou,
+              ws, nbytes, _lib.STREAM)
     return (iou, counts) if return_counts else iou
 
 

@@ -13,12 +13,22 @@ The reference is single-process; this is the MI355X-side
   nodes beyond the shard (6 for the reference's L = 3, M = 5).  With eval-mode BatchNorm (pointwise)
   the owned rows are exactly the rows of the full-graph forward.
 """
+import collections
+import contextlib
+import logging
+import time
 from typing import Optional, Tuple
 
 import torch
 import torch.distributed as dist
 
+from . import _lib
+from .gnn.model import SpectralGNN, unwrap
 from .keyframe.graph_manager import Data, chain_edges, edge_features
+
+# One captured GNN forward of ShardedDescriptorPath (one per rotating slot): its key, the hipGraph, the output tensor a replay
+# writes, and what the capture baked in (SpectralGNN.capture_state's tensors, the window graph), kept alive with it
+CapturedForward = collections.namedtuple("CapturedForward", "key graph out folded csr data")
 
 
 def shard_range(n_total: int, rank: int, world: int) -> Tuple[int, int]:
@@ -90,7 +100,6 @@ def hw_queue_classes(streams, spin_cycles: int = 250_000):
     on them cannot overlap.  Probe (setup only, a few milliseconds): a one-thread spin kernel on each of two streams --
     distinct queues run them side by side, a shared queue one after the other.  Returns a class id per stream (equal
     ids share a queue), or None when the spin kernel is not available."""
-    import time
     if not streams or not hasattr(torch.cuda, "_sleep"):
         return None
     dev = streams[0].device
@@ -126,7 +135,7 @@ def concurrent_streams(device, n: int, candidates: int = 12):
     """``n`` streams that sit on ``n`` different hardware queues (see hw_queue_classes), none of them the queue of the
     caller's current stream when that can be had.  Falls back to plain new streams when the probe is unavailable or the
     device has fewer queues than asked for.  All at the default priority: a high-priority encoder (or GNN) stream was
-    measured 40-60 % slower per step (round 3: the other side starves and the buffer rotation stalls)."""
+    measured 40-60 % slower per step (the other side starves and the buffer rotation stalls)."""
     cur = torch.cuda.current_stream(device)
     pool = [torch.cuda.Stream(device) for _ in range(candidates)]
     cls = hw_queue_classes([cur] + pool)
@@ -184,11 +193,11 @@ class ShardedDescriptorPath:
         self.pipeline = pipeline
         self.encoder_streams = max(1, int(encoder_streams))
         self.gnn_streams = max(1, int(gnn_streams))
-        # replay the GNN forward as a captured hipGraph (pipeline mode, eval).  Default: on for one rank (round 3: +1.3 %
+        # replay the GNN forward as a captured hipGraph (pipeline mode, eval).  Default: on for one rank (+1.3 %
         # per step at 200 steps, host issue 0.12 -> 0.09 ms per step), off beside RCCL (its threads issue HIP calls of their
         # own while a capture is open; not measurable here)
         self.gnn_graph = gnn_graph
-        self._gnn_graphs, self._gnn_warm = {}, {}
+        self._gnn_graphs, self._gnn_warm = {}, {}      # slot -> CapturedForward; slot -> the key seen once
         self.coresident_gnn = True         # pipeline mode: launch the GNN in its NSC_GAT_CORESIDENT form
         self._k = 0
         self._streams = None
@@ -222,18 +231,11 @@ class ShardedDescriptorPath:
         self._desc_all = {}                # gathered-matrix buffers, one per pipeline slot
 
     def _window_graph(self, like: torch.Tensor):
-        """Sub-chain graph over [lo-halo, hi+halo) n [0, n_total) with a placeholder x."""
-        wlo, whi = halo_window(self.n_total, self.lo, self.hi, self.L, self.M)
-        n = whi - wlo
-        edges = chain_edges(n, self.M)
-        dev = like.device
-        edge_index = (torch.from_numpy(edges.T.copy()).to(dev) if len(edges)
-                      else torch.empty((2, 0), dtype=torch.long, device=dev))
-        edge_attr = None
-        if self.poses is not None and len(edges):
-            edge_attr = torch.from_numpy(edge_features(self.poses[wlo:whi], edges)).to(dev)
-        self._graph = Data(x=None, edge_index=edge_index, edge_attr=edge_attr, num_nodes=n)
-        self._own0, self._wlo = self.lo - wlo, wlo
+        """Sub-chain graph over [lo-halo, hi+halo) n [0, n_total) with a placeholder x (every step sets its own)."""
+        rows = like.new_empty((self.n_total, 0))         # shard_graph reads its row count and device
+        self._graph, self._own0 = shard_graph(rows, self.lo, self.hi, self.poses, self.L, self.M)
+        self._graph.x = None
+        self._wlo = self.lo - self._own0
 
     # -- two-stream software pipeline -----------------------------------------------------------
     _PIPE_BUFFERS = 4      # descriptor buffers in rotation: the encoder stream never has to wait for the GNN
@@ -241,8 +243,8 @@ class ShardedDescriptorPath:
                            # runs several ranks as threads of one process turns the timing probe off
 
     def _pipe_setup(self, device):
-        inner = getattr(self.gnn, "gnn", self.gnn)
-        if hasattr(inner, "coresident"):
+        inner = unwrap(self.gnn)
+        if isinstance(inner, SpectralGNN):
             # the kernel set this path asked for, whatever was set before (True, False or "shared_b")
             inner.coresident = self.coresident_gnn if self.coresident_gnn == "shared_b" else bool(self.coresident_gnn)
         n_local, d = self.hi - self.lo, int(getattr(self.encoder, "output_dim", 800))
@@ -338,47 +340,47 @@ class ShardedDescriptorPath:
         self._k += 1
         return res
 
-    def _gather(self, out, local):
-        """The step's descriptor all-gather (blocking form), bracketed by the caller's HIP events when asked for."""
-        ce = self.collective_events
-        if ce and local.is_cuda:
-            a, b = ce[self._k % len(ce)]
-            a.record()
-            dist.all_gather_into_tensor(out, local, group=self.group)
-            b.record()
-        else:
-            dist.all_gather_into_tensor(out, local, group=self.group)
+    @contextlib.contextmanager
+    def _timed_collective(self, local):
+        """Bracket the step's collective with the caller's event pair k (``collective_events``) on the current stream: the
+        start event on entry, the end event on exit -- so the block ends where the collective is complete (the overlap form:
+        after ``work.wait()``).  Without events, on host tensors or on a path that issues no collective: nothing."""
+        ce = self.collective_events if (local.is_cuda and self._collect) else None
+        if ce:
+            start, end = ce[self._k % len(ce)]
+            start.record()
+        yield
+        if ce:
+            end.record()
 
     def _exchange_and_enhance(self, local):
         if self._graph is None:
             self._window_graph(local)
         n_local, h = self.hi - self.lo, self.halo
-        work = None
         if self.overlap:
             # 1. boundary rows only (tiny, blocking): [first h rows | last h rows] of every rank
             d = int(local.shape[1])
             mine = torch.cat([local[:h], local[n_local - h:]], 0)
             edges_all = torch.empty((self.world * 2 * h, d), dtype=local.dtype, device=local.device)
-            ce = self.collective_events if local.is_cuda else None
-            if ce:                                   # (this form's window spans the GNN forward the big gather overlaps)
-                ce[self._k % len(ce)][0].record()
-            dist.all_gather_into_tensor(edges_all, mine, group=self.group)
-            # 2. the full matrix, asynchronously
-            slot = 0                                 # (overlap is off in pipeline mode, see __init__)
-            if slot not in self._desc_all:
-                self._desc_all[slot] = torch.empty((self.n_total, d), dtype=local.dtype, device=local.device)
-            gathered = self._desc_all[slot]
-            work = dist.all_gather_into_tensor(gathered, local.contiguous(), group=self.group,
-                                               async_op=True)
-            parts = []
-            if self.rank > 0:                       # previous rank's last h rows
-                parts.append(edges_all[(self.rank - 1) * 2 * h + h:(self.rank - 1) * 2 * h + 2 * h])
-            parts.append(local)
-            if self.rank < self.world - 1:          # next rank's first h rows
-                parts.append(edges_all[(self.rank + 1) * 2 * h:(self.rank + 1) * 2 * h + h])
-            self._graph.x = torch.cat(parts, 0) if len(parts) > 1 else local
-            desc_all = gathered
-        elif self.pipeline and self._collect and self.n_total % self.world == 0:
+            with self._timed_collective(local):      # (this form's window spans the GNN forward the big gather overlaps)
+                dist.all_gather_into_tensor(edges_all, mine, group=self.group)
+                # 2. the full matrix, asynchronously
+                slot = 0                             # (overlap is off in pipeline mode, see __init__)
+                if slot not in self._desc_all:
+                    self._desc_all[slot] = torch.empty((self.n_total, d), dtype=local.dtype, device=local.device)
+                desc_all = self._desc_all[slot]
+                work = dist.all_gather_into_tensor(desc_all, local.contiguous(), group=self.group, async_op=True)
+                parts = []
+                if self.rank > 0:                   # previous rank's last h rows
+                    parts.append(edges_all[(self.rank - 1) * 2 * h + h:(self.rank - 1) * 2 * h + 2 * h])
+                parts.append(local)
+                if self.rank < self.world - 1:      # next rank's first h rows
+                    parts.append(edges_all[(self.rank + 1) * 2 * h:(self.rank + 1) * 2 * h + h])
+                self._graph.x = torch.cat(parts, 0) if len(parts) > 1 else local
+                emb = self._enhance()
+                work.wait()
+            return desc_all, emb[self._own0:self._own0 + n_local]
+        if self.pipeline and self._collect and self.n_total % self.world == 0:
             # pipeline mode: ONE all-gather straight into this step's slot of the rotating gathered-matrix buffers
             # (valid for _PIPE_BUFFERS - 1 further steps, like the descriptor buffers; no allocation per step)
             slot = self._k % self._PIPE_BUFFERS
@@ -386,74 +388,49 @@ class ShardedDescriptorPath:
                 self._desc_all[slot] = torch.empty((self.n_total, int(local.shape[1])), dtype=local.dtype,
                                                    device=local.device)
             desc_all = self._desc_all[slot]
-            self._gather(desc_all, local.contiguous())
-            self._graph.x = desc_all[self._wlo:self._wlo + self._graph.num_nodes]
+            with self._timed_collective(local):
+                dist.all_gather_into_tensor(desc_all, local.contiguous(), group=self.group)
         else:
-            ce = self.collective_events if (local.is_cuda and self._collect) else None
-            if ce:
-                ce[self._k % len(ce)][0].record()
-            desc_all = all_gather_descriptors(local, self.n_total, self.group, self._collect)    # fresh tensor per step
-            if ce:
-                ce[self._k % len(ce)][1].record()
-            self._graph.x = desc_all[self._wlo:self._wlo + self._graph.num_nodes]
+            with self._timed_collective(local):
+                desc_all = all_gather_descriptors(local, self.n_total, self.group, self._collect)    # fresh tensor per step
+        self._graph.x = desc_all[self._wlo:self._wlo + self._graph.num_nodes]
         emb = self._enhance()
-        if work is not None:
-            work.wait()
-            if self.collective_events and local.is_cuda:
-                self.collective_events[self._k % len(self.collective_events)][1].record()
         return desc_all, emb[self._own0:self._own0 + n_local]
 
     def _enhance(self):
         """GNN forward over the window graph.  Pipeline mode on a HIP device: the forward's kernel launches are captured
         once per rotating buffer into a hipGraph (torch.cuda.CUDAGraph: the C ABI only enqueues kernels on the stream it
         is given, so a capturing stream records them) and replayed -- one graph launch per step instead of eight kernel
-        launches plus their Python plumbing (host issue 77 -> 19 us at 1 024 keyframes, device 77 -> 57 us alone; round
-        3).  A capture is keyed on the input's storage and the model's parameter versions: new weights or a new input
-        buffer recapture; an input that is not one of the rotating buffers (ragged shards) runs eagerly."""
+        launches plus their Python plumbing (host issue 77 -> 19 us at 1 024 keyframes, device 77 -> 57 us alone).  A
+        capture is keyed on the input's storage and on SpectralGNN.capture_state: new weights, another kernel set or a new
+        input buffer recapture; an input that is not one of the rotating buffers (ragged shards) runs eagerly, and so does
+        a ``gnn`` that is not a SpectralGNN (a plain callable)."""
         x = self._graph.x
-        inner = getattr(self.gnn, "gnn", self.gnn)
+        inner = unwrap(self.gnn)
         if not (self.gnn_graph and self.pipeline and x.is_cuda and not torch.is_grad_enabled()
-                and not getattr(self.gnn, "training", False)
-                and (hasattr(inner, "_live_tensors") or hasattr(inner, "parameters"))):     # (a plain callable runs eagerly)
+                and isinstance(inner, SpectralGNN) and not self.gnn.training):
             return self.gnn(self._graph)
         slot = self._k % self._PIPE_BUFFERS
-        folded = None
-        live = inner._live_tensors() if hasattr(inner, "_live_tensors") else list(inner.parameters()) + list(inner.buffers())
-        if hasattr(inner, "_model_struct"):
-            # the capture bakes in the folded attention vectors the model caches: make sure they exist for the current
-            # weights, and key on their generation -- an optimizer that writes through a multi-tensor kernel does not bump
-            # the parameters' version counters; every optimizer step bumps _lib.param_epoch instead (a new generation)
-            inner._model_struct(live)
-            folded = inner._struct_cache[2]
-        # the capture also bakes in the window graph's CSR arrays: key on that GraphCSR and keep it (and the graph) in the
-        # entry, so that its memory cannot go back to the allocator while a replay may read it
-        csr = None
-        if hasattr(inner, "_csr"):
-            use_edge = getattr(self._graph, "edge_attr", None) is not None and getattr(inner, "edge_dim", None) is not None
-            csr = inner._csr(self._graph, use_edge)
-        key = (x.data_ptr(), tuple(x.shape), tuple((t.data_ptr(), t._version) for t in live),
-               getattr(inner, "coresident", False), getattr(inner, "_fold_generation", 0), id(csr))
+        state = inner.capture_state(self._graph)
+        key = (x.data_ptr(), tuple(x.shape), state.key)
         ent = self._gnn_graphs.get(slot)
-        if ent is not None and ent[0] == key:
-            ent[1].replay()
-            return ent[2]
+        if ent is not None and ent.key == key:
+            ent.graph.replay()
+            return ent.out
         if self._gnn_warm.get(slot) != key:              # first sight of this (buffer, weights): run it eagerly once
             self._gnn_warm[slot] = key                   # (lazy set-up inside the forward must not be captured)
             return self.gnn(self._graph)
         try:
-            cg = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(cg, stream=torch.cuda.current_stream(x.device), capture_error_mode="thread_local"):
-                out = self.gnn(self._graph)
+            cg, out = _lib.capture(x.device, lambda: self.gnn(self._graph), stream=torch.cuda.current_stream(x.device))
             cg.replay()                                  # the capture itself ran nothing
         except Exception as ex:  # noqa: BLE001 -- whatever keeps a capture from closing: issue the forward eagerly from now on
-            import logging
             logging.getLogger(__name__).warning("hipGraph capture of the GNN forward failed (%s: %s); issuing it eagerly "
                                                 "from now on", type(ex).__name__, ex)
             self.gnn_graph = False
             self._gnn_graphs.clear()
             return self.gnn(self._graph)
         # (folded, csr, graph: kept alive as long as the capture that reads them)
-        self._gnn_graphs[slot] = (key, cg, out, folded, csr, self._graph)
+        self._gnn_graphs[slot] = CapturedForward(key, cg, out, state.folded, state.csr, self._graph)
         return out
 
     def release(self):

@@ -33,10 +33,7 @@ def quantize_batch(histograms: torch.Tensor, epsilon: float = 1e-8) -> torch.Ten
     _lib.require_cuda(histograms, "histograms")
     h = histograms.detach().to(torch.float32).contiguous()
     out = torch.empty(h.shape, dtype=torch.uint16, device=h.device)
-    with torch.cuda.device(h.device):
-        st = _lib.lib().nsc_quantize_descriptors(_lib.ptr(h), int(h.shape[0]), int(h.shape[1]), float(epsilon),
-                                                 _lib.ptr(out), _lib.stream_ptr(h.device))
-    _lib.check(st, "nsc_quantize_descriptors")
+    _lib.call("nsc_quantize_descriptors", h.device, h, int(h.shape[0]), int(h.shape[1]), float(epsilon), out, _lib.STREAM)
     return out
 
 
@@ -47,10 +44,7 @@ def dequantize_batch(quantized: torch.Tensor, epsilon: float = 1e-8) -> torch.Te
     if q.dtype != torch.uint16:
         raise _lib.NscError(f"quantized must be uint16 (got {q.dtype})")
     out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
-    with torch.cuda.device(q.device):
-        st = _lib.lib().nsc_dequantize_descriptors(_lib.ptr(q), int(q.shape[0]), int(q.shape[1]), float(epsilon),
-                                                   _lib.ptr(out), _lib.stream_ptr(q.device))
-    _lib.check(st, "nsc_dequantize_descriptors")
+    _lib.call("nsc_dequantize_descriptors", q.device, q, int(q.shape[0]), int(q.shape[1]), float(epsilon), out, _lib.STREAM)
     return out
 
 
@@ -76,10 +70,7 @@ def pack_records(quantized: torch.Tensor, poses7: torch.Tensor, timestamps: torc
     if p7.shape != (n, 7) or ts.shape != (n,) or ids.shape != (n,) or hs.shape != (n, 20):
         raise _lib.NscError("pack_records: metadata shapes must be (n,7), (n,), (n,), (n,20)")
     rec = torch.empty((n, record_bytes(dim)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().nsc_pack_records(_lib.ptr(q), _lib.ptr(p7), _lib.ptr(ts), _lib.ptr(ids), _lib.ptr(hs),
-                                         n, dim, _lib.ptr(rec), _lib.stream_ptr(dev))
-    _lib.check(st, "nsc_pack_records")
+    _lib.call("nsc_pack_records", dev, q, p7, ts, ids, hs, n, dim, rec, _lib.STREAM)
     return rec
 
 
@@ -96,10 +87,7 @@ def unpack_records(records: torch.Tensor, n_bins: int):
     ts = torch.empty((n,), dtype=torch.float64, device=dev)
     ids = torch.empty((n,), dtype=torch.uint32, device=dev)
     hs = torch.empty((n, 20), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().nsc_unpack_records(_lib.ptr(rec), n, int(n_bins), _lib.ptr(q), _lib.ptr(p7), _lib.ptr(ts),
-                                           _lib.ptr(ids), _lib.ptr(hs), _lib.stream_ptr(dev))
-    _lib.check(st, "nsc_unpack_records")
+    _lib.call("nsc_unpack_records", dev, rec, n, int(n_bins), q, p7, ts, ids, hs, _lib.STREAM)
     return q, p7, ts, ids, hs
 
 

@@ -85,10 +85,7 @@ class RangeImageProjector:
         if not (keep_intensity and stride == 4):
             return raw[0].cpu().numpy(), None
         inten = torch.empty_like(raw)
-        with torch.cuda.device(dev):
-            st = _lib.lib().nsc_project_intensity(_lib.ptr(t), _lib.ptr(off), 1, n, p, _lib.ptr(raw), _lib.ptr(inten),
-                                                  _lib.stream_ptr(dev))
-        _lib.check(st, "nsc_project_intensity")
+        _lib.call("nsc_project_intensity", dev, t, off, 1, n, p, raw, inten, _lib.STREAM)
         return raw[0].cpu().numpy(), inten[0].cpu().numpy()
 
 
@@ -115,10 +112,7 @@ def interpolate_range_image(range_image: np.ndarray, method: str = "linear",
     if x.shape[2] != 360:
         raise ValueError("range images must have 360 azimuth columns")
     out = torch.empty_like(x)
-    with torch.cuda.device(dev):
-        st = _lib.lib().nsc_interpolate_range_images_ex(_lib.ptr(x), int(x.shape[0]), int(x.shape[1]),
-                                                        _lib.ptr(_default_lut(dev)), 1 if method == "linear" else 2,
-                                                        _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(st, "nsc_interpolate_range_images_ex")
+    _lib.call("nsc_interpolate_range_images_ex", dev, x, int(x.shape[0]), int(x.shape[1]), _default_lut(dev),
+              1 if method == "linear" else 2, out, _lib.STREAM)
     res = out if batched else out[0]
     return res.cpu().numpy()

@@ -71,11 +71,8 @@ def _run_encode_clouds(pts, offsets, n_clouds, total_points, stride, p, lut, wan
         itp = torch.empty_like(raw)
     nbytes = L.nsc_encode_clouds_workspace_bytes(n_clouds, total_points, p)
     ws = _workspace(dev, nbytes)
-    with torch.cuda.device(dev):
-        st = L.nsc_encode_clouds(_lib.ptr(pts), _lib.ptr(offsets), n_clouds, total_points, stride, p,
-                                 _lib.ptr(lut), _lib.ptr(desc), _lib.ptr(raw), _lib.ptr(itp),
-                                 _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
-    _lib.check(st, "nsc_encode_clouds")
+    _lib.call("nsc_encode_clouds", dev, pts, offsets, n_clouds, total_points, stride, p, lut, desc, raw, itp, ws, nbytes,
+              _lib.STREAM)
     return desc, raw, itp
 
 
@@ -149,11 +146,7 @@ class SpectralEncoder(nn.Module):
         x = x.detach().to(device=dev, dtype=torch.float32).contiguous()
         n, rows = int(x.shape[0]), int(x.shape[1])
         out = torch.empty((n, self.output_dim), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = _lib.lib().nsc_encode_range_images(_lib.ptr(x), n, rows, self._params(),
-                                                    _lib.ptr(self._lut(dev)), _lib.ptr(out),
-                                                    _lib.stream_ptr(dev))
-        _lib.check(st, "nsc_encode_range_images")
+        _lib.call("nsc_encode_range_images", dev, x, n, rows, self._params(), self._lut(dev), out, _lib.STREAM)
         return out
 
     def encode_batch(self, range_images: torch.Tensor) -> torch.Tensor:

@@ -7,6 +7,7 @@ fused BatchNorm/ReLU/residual epilogues and a wavefront-per-node attention/aggre
 The module must live on a HIP device; there is no CPU fallback.
 """
 import collections
+import copy
 import ctypes as C
 import os
 from typing import Optional
@@ -18,8 +19,8 @@ from .. import _lib
 from .gat_conv import GATConv
 
 def _ws(device, nbytes, tag):
-    # one scratch buffer per (device, stream, host thread, use), bounded and capture-safe: _lib.ScratchCache (round 3: two
-    # rank threads building their CSR in one shared scratch faulted the aggregate kernel; round 4: the dict only grew)
+    # one scratch buffer per (device, stream, host thread, use), bounded and capture-safe: _lib.ScratchCache (two rank
+    # threads building their CSR in one shared scratch faulted the aggregate kernel; an unbounded dict only grew)
     return _lib.scratch.get(device, nbytes, tag)
 
 
@@ -49,13 +50,8 @@ class GraphCSR:
         self.edge_attr = ea
         nbytes = L.nsc_graph_workspace_bytes(n_nodes, E)
         ws = _ws(dev, nbytes, "graph")
-        with torch.cuda.device(dev):
-            st = L.nsc_graph_build_csr(_lib.ptr(ei), E, n_nodes, _lib.ptr(ea), self.edge_dim,
-                                       _lib.ptr(self.row_ptr), _lib.ptr(self.src), _lib.ptr(self.eid),
-                                       _lib.ptr(self.loop_attr), _lib.ptr(ws), nbytes,
-                                       _lib.stream_ptr(dev))
-        _lib.check(st, "nsc_graph_build_csr")
-
+        _lib.call("nsc_graph_build_csr", dev, ei, E, n_nodes, ea, self.edge_dim, self.row_ptr, self.src, self.eid,
+                  self.loop_attr, ws, nbytes, _lib.STREAM)
         self.t_ptr = self.t_entry = self.tgt = None
         # Banded form (nsc_graph_band_entries): the temporal chain of every reference caller has its sources within 2 rows
         # of the target (graph_manager.py:520-532), and such a graph runs a GATConv layer as ONE launch.  Whether THIS graph
@@ -64,11 +60,7 @@ class GraphCSR:
         if n_nodes > 0 and self.edge_dim in (0, 2):
             ent = torch.empty((n_nodes, 8, 4), dtype=torch.float32, device=dev)
             info = torch.empty(2, dtype=torch.int32, device=dev)
-            g = self.struct()
-            with torch.cuda.device(dev):
-                st = L.nsc_graph_band_entries(C.byref(g), _lib.ptr(ea), self.edge_dim, _lib.ptr(ent), _lib.ptr(info),
-                                              _lib.stream_ptr(dev))
-            _lib.check(st, "nsc_graph_band_entries")
+            _lib.call("nsc_graph_band_entries", dev, self.struct(), ea, self.edge_dim, ent, info, _lib.STREAM)
             max_off, max_deg = info.tolist()
             if max_off <= 2 and max_deg <= 8:
                 self.band, self.band_entries = 2, ent
@@ -84,11 +76,7 @@ class GraphCSR:
         self.tgt = torch.empty(self.capacity, dtype=torch.int32, device=dev)
         nbytes = L.nsc_graph_transpose_workspace_bytes(self.n_nodes)
         ws = _ws(dev, nbytes, "graph")
-        g = self.struct()
-        with torch.cuda.device(dev):
-            st = L.nsc_graph_transpose(C.byref(g), _lib.ptr(self.t_ptr), _lib.ptr(self.t_entry),
-                                       _lib.ptr(self.tgt), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
-        _lib.check(st, "nsc_graph_transpose")
+        _lib.call("nsc_graph_transpose", dev, self.struct(), self.t_ptr, self.t_entry, self.tgt, ws, nbytes, _lib.STREAM)
 
     def struct(self) -> _lib.Graph:
         g = _lib.Graph()
@@ -100,15 +88,41 @@ class GraphCSR:
         g.loop_attr = self.loop_attr.data_ptr() if self.loop_attr is not None else None
         if self.t_ptr is not None:
             g.t_ptr, g.t_entry, g.tgt = self.t_ptr.data_ptr(), self.t_entry.data_ptr(), self.tgt.data_ptr()
-        if getattr(self, "band", 0):
+        if self.band:
             g.band_entries, g.band = self.band_entries.data_ptr(), self.band
         return g
+
+
+# One row per tensor NscGatModel points at: ``owner[key]`` is the live tensor (the owning module's own ``_parameters`` /
+# ``_buffers`` dict), ``field`` its NscGatModel / NscGatLayer member, ``grad`` its NscGatGrads / NscGatGradLayer member (None:
+# running statistics, which have no gradient), ``layer`` the index into ``layers[]`` (None: a member of the model itself).
+ParamRow = collections.namedtuple("ParamRow", "owner key field grad layer")
+# SpectralGNN._struct_cache: the NscGatModel of the eval forward, its folded attention vectors and the tensors of its key
+FoldedStruct = collections.namedtuple("FoldedStruct", "key model folded live")
+# SpectralGNN.capture_state(): what a captured eval forward over one graph bakes in
+CaptureState = collections.namedtuple("CaptureState", "csr folded key")
+
+# Derived state of a SpectralGNN (device pointers, what a capture in progress set): (name, default).  Created by __init__,
+# reset by __getstate__, so deepcopy / pickle / torch.save carry none of it.
+_PRIVATE = (
+    ("_csr_cache", collections.OrderedDict()),   # graph key -> GraphCSR, least recently used first
+    ("_struct_cache", None),           # FoldedStruct of the eval forward
+    ("_train_struct_cache", None),     # (parameter addresses, NscGatModel) of the training calls
+    ("_fold_generation", 0),           # counts the re-folds: a captured forward bakes the folded tensor in
+    ("_seed_dev", None),               # device int64[1]: dropout seed the kernels read at run time (captured steps)
+    ("_direct_grads", False),          # backward adds straight into the parameters' .grad tensors (GNNTrainer's steps)
+    ("_nbt_flat", None),               # the BatchNorm step counters as one vector (_bump_batches_tracked)
+)
+
+
+def unwrap(model):
+    """The SpectralGNN inside a LocalUpdateGNN, or ``model`` itself (a SpectralGNN, or any other callable)."""
+    return model.gnn if isinstance(model, LocalUpdateGNN) else model
 
 
 def _train_forward_raw(gnn, x, csr, dropout_p, seed):
     """nsc_gat_forward_train: returns (out, state); state holds the workspace with the saved activations for
     _train_backward_raw.  Used by the autograd Function below and, without autograd, by GNNTrainer's direct step."""
-    L = _lib.lib()
     dev = x.device
     m = gnn._train_struct()
     csr.ensure_transpose()
@@ -116,18 +130,15 @@ def _train_forward_raw(gnn, x, csr, dropout_p, seed):
     cfg = _lib.GatTrainCfg()
     cfg.dropout_p, cfg.bn_momentum = float(dropout_p), float(gnn.input_norm.momentum or 0.1)
     cfg.seed, cfg.update_running_stats = int(seed), 1
-    sd = getattr(gnn, "_seed_dev", None)          # a device word the kernels read the seed from (captured steps)
+    sd = gnn._seed_dev                            # a device word the kernels read the seed from (captured steps)
     cfg.seed_dev = sd.data_ptr() if sd is not None else None
     n = int(x.shape[0])
     out = torch.empty((n, gnn.output_dim), dtype=torch.float32, device=dev)
-    nbytes = L.nsc_gat_train_workspace_bytes(C.byref(m), C.byref(g))
+    nbytes = _lib.lib().nsc_gat_train_workspace_bytes(C.byref(m), C.byref(g))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # holds the saved activations
     if os.environ.get("NSC_DEBUG_WS_NAN") == "1":              # debugging: a read of never-written workspace shows up as NaN
         ws.fill_(0xFF)
-    with torch.cuda.device(dev):
-        st = L.nsc_gat_forward_train(C.byref(m), C.byref(g), _lib.ptr(x), _lib.ptr(csr.edge_attr),
-                                     C.byref(cfg), _lib.ptr(out), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
-    _lib.check(st, "nsc_gat_forward_train")
+    _lib.call("nsc_gat_forward_train", dev, m, g, x, csr.edge_attr, cfg, out, ws, nbytes, _lib.STREAM)
     _bump_batches_tracked(gnn)
     return out, (csr, cfg, ws, nbytes, x, sd)
 
@@ -140,7 +151,7 @@ def _bump_batches_tracked(gnn):
     if not bns:
         return
     bufs = [bn.num_batches_tracked for bn in bns]
-    flat = gnn.__dict__.get("_nbt_flat")
+    flat = gnn._nbt_flat
     ok = (flat is not None and flat.numel() == len(bufs) and flat.device == bufs[0].device
           and all(b_.dtype == flat.dtype and b_.dim() == 0 and b_.device == flat.device
                   and b_.data_ptr() == flat.data_ptr() + i * flat.element_size() for i, b_ in enumerate(bufs)))
@@ -153,7 +164,7 @@ def _bump_batches_tracked(gnn):
         flat = torch.stack([b_.detach() for b_ in bufs])
         for i, bn in enumerate(bns):
             bn._buffers["num_batches_tracked"] = flat[i]
-        gnn.__dict__["_nbt_flat"] = flat
+        gnn._nbt_flat = flat
     flat += 1
 
 
@@ -161,31 +172,14 @@ def _train_backward_raw(gnn, state, grad_out, grads, accumulate, need_x):
     """nsc_gat_backward into ``grads`` (tensors in _train_params() order; accumulate: added to what they hold).  Returns the
     gradient w.r.t. x or None."""
     csr, cfg, ws, nbytes, x, _sd = state
-    L = _lib.lib()
-    dev = x.device
-    m = gnn._train_struct()
-    g = csr.struct()
     cfg.accumulate_grads = 1 if accumulate else 0
     gs = _lib.GatGrads()
-    it = iter(grads)
-    gs.in_w, gs.in_b = next(it).data_ptr(), next(it).data_ptr()
-    gs.in_bn_w, gs.in_bn_b = next(it).data_ptr(), next(it).data_ptr()
-    gs.out_w, gs.out_b = next(it).data_ptr(), next(it).data_ptr()
-    if gnn.residual_proj is not None:
-        gs.res_w, gs.res_b = next(it).data_ptr(), next(it).data_ptr()
-    for l, conv in enumerate(gnn.convs):
-        gl = gs.layers[l]
-        gl.lin_w, gl.att_src, gl.att_dst = next(it).data_ptr(), next(it).data_ptr(), next(it).data_ptr()
-        if conv.lin_edge is not None:
-            gl.lin_edge_w, gl.att_edge = next(it).data_ptr(), next(it).data_ptr()
-        gl.bias, gl.bn_w, gl.bn_b = next(it).data_ptr(), next(it).data_ptr(), next(it).data_ptr()
+    for row, t in zip(gnn._grad_rows, grads):
+        setattr(gs if row.layer is None else gs.layers[row.layer], row.grad, t.data_ptr())
     gx = torch.empty_like(x) if need_x else None
     gs.x = gx.data_ptr() if gx is not None else None
-    with torch.cuda.device(dev):
-        st = L.nsc_gat_backward(C.byref(m), C.byref(g), _lib.ptr(x), _lib.ptr(csr.edge_attr),
-                                C.byref(cfg), _lib.ptr(grad_out), C.byref(gs), _lib.ptr(ws), nbytes,
-                                _lib.stream_ptr(dev))
-    _lib.check(st, "nsc_gat_backward")
+    _lib.call("nsc_gat_backward", x.device, gnn._train_struct(), csr.struct(), x, csr.edge_attr, cfg, grad_out, gs, ws, nbytes,
+              _lib.STREAM)
     return gx
 
 
@@ -193,6 +187,20 @@ def _direct_ok(params) -> bool:
     """The backward may add straight into the .grad tensors of ``params`` (_train_params() order): every one is trained and
     has a contiguous .grad.  A frozen parameter (requires_grad False) takes the autograd path, which drops its gradient."""
     return all(p.requires_grad and p.grad is not None and p.grad.is_contiguous() for p in params)
+
+
+def _triplet_loss(out, ia, ip, in_, margin, scale, want_grad):
+    """nsc_triplet_loss over the rows ``ia`` / ``ip`` / ``in_`` (int64 device vectors) of ``out`` (N, D) contiguous float32:
+    returns (loss (1,), d loss / d out or None)."""
+    dev = out.device
+    n, d, t = int(out.shape[0]), int(out.shape[1]), int(ia.numel())
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(out) if want_grad else None
+    nbytes = _lib.lib().nsc_triplet_workspace_bytes(t)
+    ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
+    _lib.call("nsc_triplet_loss", dev, out, ia, ip, in_, t, n, d, float(margin), float(scale), loss, grad, ws, nbytes,
+              _lib.STREAM)
+    return loss, grad
 
 
 class _GatTrainFunction(torch.autograd.Function):
@@ -211,7 +219,7 @@ class _GatTrainFunction(torch.autograd.Function):
         params = gnn._train_params()
         # GNNTrainer's steps: the kernels ADD into the existing .grad tensors (NscGatTrainCfg.accumulate_grads) and autograd
         # gets no parameter gradients back -- no AccumulateGrad axpy per parameter (30 small kernels per batch)
-        direct = bool(getattr(gnn, "_direct_grads", False)) and _direct_ok(params)
+        direct = gnn._direct_grads and _direct_ok(params)
         grads = [p.grad for p in params] if direct else [torch.empty_like(p) for p in params]
         go = grad_out.contiguous().float()
         gx = _train_backward_raw(gnn, ctx.state, go, grads, direct, ctx.need_x)
@@ -244,30 +252,55 @@ class SpectralGNN(nn.Module):
             self.residual_proj = nn.Linear(input_dim, output_dim)
         else:
             self.residual_proj = None
-        self._csr_cache = collections.OrderedDict()     # graph key -> GraphCSR, least recently used first
-        self._struct_cache = None          # (key, GatModel, folded tensor, the tensors of the key)
-        # True: launch the LDS-free, low-VGPR kernel set (NSC_GAT_CORESIDENT) whose workgroups fit beside a
-        # resident encoder grid -- used by distributed.ShardedDescriptorPath(pipeline=True).  "shared_b": that set with
-        # the small-LDS GEMMs (NSC_GAT_SHARED_B).  "lds_tiled": the stand-alone forward with the round-2 GEMMs
-        # (NSC_GAT_LDS_TILED) instead of the LDS-DMA GEMM.  "generic": the stand-alone forward without the one-launch
-        # layers of a banded graph (NSC_GAT_GENERIC).  Same output, bit for bit.
+        # The kernel set of the eval forward (_lib.GAT_KERNEL_SETS).  True: the LDS-free, low-VGPR set (NSC_GAT_CORESIDENT)
+        # whose workgroups fit beside a resident encoder grid -- used by distributed.ShardedDescriptorPath(pipeline=True).
+        # "shared_b": that set with the small-LDS GEMMs (NSC_GAT_SHARED_B).  "lds_tiled": the stand-alone forward with the
+        # register-staged GEMMs (NSC_GAT_LDS_TILED) instead of the LDS-DMA GEMM.  "generic": the stand-alone forward
+        # without the one-launch layers of a banded graph (NSC_GAT_GENERIC).  Same output, bit for bit.
         self.coresident = False
-        self._seed_dev = None              # device int64[1]: dropout seed read by the kernels at run time (captured steps)
-        self._direct_grads = False         # backward adds straight into the parameters' .grad tensors (GNNTrainer's steps)
+        for name, default in _PRIVATE:
+            setattr(self, name, copy.copy(default))
+        self._set_table()
 
     # -- plumbing ---------------------------------------------------------------------------
     def __getstate__(self):
         # device-pointer caches are rebuilt on demand; keep them out of deepcopy / pickle / torch.save
         state = self.__dict__.copy()
-        state["_csr_cache"] = collections.OrderedDict()
-        state["_struct_cache"] = None
-        state["_train_struct_cache"] = None
-        state["_seed_dev"] = None
-        state["_fold_generation"] = 0
-        state.pop("_live_slots", None)
-        state.pop("_nbt_flat", None)
-        state["_direct_grads"] = False
+        for name, default in _PRIVATE:
+            state[name] = copy.copy(default)
+        for name in ("_table", "_grad_rows", "_slots"):
+            del state[name]
         return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for name, default in _PRIVATE:     # (a module pickled before one of them existed)
+            self.__dict__.setdefault(name, copy.copy(default))
+        self._set_table()                  # over the copy's own parameter dicts
+
+    def _set_table(self):
+        """The parameter table (ParamRow), in the order NscGatGrads lists its members; an optional piece (residual_proj,
+        lin_edge / att_edge) has its rows or has none.  Built once: the module tree is fixed after __init__."""
+        def linear(mod, w, b):
+            return [(mod._parameters, "weight", w, w), (mod._parameters, "bias", b, b)]
+
+        def norm(bn, pre):
+            return [(bn._parameters, "weight", pre + "w", pre + "w"), (bn._parameters, "bias", pre + "b", pre + "b"),
+                    (bn._buffers, "running_mean", pre + "mean", None), (bn._buffers, "running_var", pre + "var", None)]
+
+        rows = [ParamRow(*r, None) for r in linear(self.input_proj, "in_w", "in_b") + norm(self.input_norm, "in_bn_")
+                + linear(self.output_proj, "out_w", "out_b")
+                + (linear(self.residual_proj, "res_w", "res_b") if self.residual_proj is not None else [])]
+        for l, (conv, bn) in enumerate(zip(self.convs, self.batch_norms)):
+            cp = conv._parameters
+            edge = [] if conv.lin_edge is None else [(conv.lin_edge._parameters, "weight", "lin_edge_w", "lin_edge_w"),
+                                                     (cp, "att_edge", "att_edge", "att_edge")]
+            rows += [ParamRow(*r, l) for r in [(conv.lin_src._parameters, "weight", "lin_w", "lin_w"),
+                                               (cp, "att_src", "att_src", "att_src"), (cp, "att_dst", "att_dst", "att_dst")]
+                     + edge + [(cp, "bias", "bias", "bias")] + norm(bn, "bn_")]
+        self._table = tuple(rows)
+        self._grad_rows = tuple(r for r in rows if r.grad is not None)
+        self._slots = tuple((r.owner, r.key) for r in rows)      # what the per-step path walks
 
     def _csr(self, data, use_edge_attr: bool) -> GraphCSR:
         ei = data.edge_index
@@ -287,71 +320,64 @@ class SpectralGNN(nn.Module):
             cache.move_to_end(key)
         return csr
 
-    @staticmethod
-    def _p(t):
-        if t is None:
-            return None
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise _lib.NscError("GNN parameters must be contiguous float32 tensors on the HIP device")
-        return t.data_ptr()
+    def _uses_edge_attr(self, data) -> bool:
+        return getattr(data, "edge_attr", None) is not None and self.edge_dim is not None       # model.py:126
 
     def _live_tensors(self):
-        """Every tensor NscGatModel points into.  Looked up through the modules' own ``_parameters`` / ``_buffers`` dicts (the
-        (dict, name) pairs are collected once: the module tree is fixed after __init__): always the current tensor, without
-        nn.Module.__getattr__ -- 113 attribute walks per call were a third of the host time of a pipelined step (round 4;
-        nn.Module.parameters() / buffers() before that: 40 %, round 3)."""
-        slots = self.__dict__.get("_live_slots")
-        if slots is None:
-            slots = [(self.input_proj._parameters, "weight"), (self.input_proj._parameters, "bias")]
-            for bn in [self.input_norm] + list(self.batch_norms):
-                slots += [(bn._parameters, "weight"), (bn._parameters, "bias"), (bn._buffers, "running_mean"),
-                          (bn._buffers, "running_var")]
-            slots += [(self.output_proj._parameters, "weight"), (self.output_proj._parameters, "bias")]
-            if self.residual_proj is not None:
-                slots += [(self.residual_proj._parameters, "weight"), (self.residual_proj._parameters, "bias")]
-            for conv in self.convs:
-                slots += [(conv.lin_src._parameters, "weight"), (conv._parameters, "att_src"), (conv._parameters, "att_dst"),
-                          (conv._parameters, "bias")]
-                if conv.lin_edge is not None:
-                    slots += [(conv.lin_edge._parameters, "weight"), (conv._parameters, "att_edge")]
-            self.__dict__["_live_slots"] = slots
-        return [d[n] for d, n in slots]
+        """Every tensor NscGatModel points into, in table order.  Looked up through the modules' own ``_parameters`` /
+        ``_buffers`` dicts: always the current tensor, without nn.Module.__getattr__ -- 113 attribute walks per call were a
+        third of the host time of a pipelined step (nn.Module.parameters() / buffers() before that: 40 %; DESIGN.md section
+        7, experiment 50)."""
+        return [d[n] for d, n in self._slots]
 
-    def _model_struct(self, live=None) -> _lib.GatModel:
+    def _model_struct(self, live=None, versions=None) -> _lib.GatModel:
         """NscGatModel over the live parameter storage.  Rebuilt (and the attention vectors re-folded
         by nsc_gat_fold_weights) only when a parameter was modified or moved, or an optimizer stepped (_lib.param_epoch: fused
-        optimizers do not bump version counters).  ``live``: the caller's _live_tensors()."""
+        optimizers do not bump version counters).  ``live``: the caller's _live_tensors(); ``versions``: its
+        (data_ptr, _version) tuple over them, when it has built one."""
         if live is None:
             live = self._live_tensors()
-        key = (_lib.param_epoch, tuple((t.data_ptr(), t._version) for t in live))
-        if self._struct_cache is not None and self._struct_cache[0] == key:
-            return self._struct_cache[1]
-        m = self._build_struct()
-        L = _lib.lib()
-        dev = self.input_proj.weight.device
-        folded = torch.empty(int(L.nsc_gat_folded_floats(C.byref(m))), dtype=torch.float32, device=dev)
+        if versions is None:
+            versions = tuple((t.data_ptr(), t._version) for t in live)
+        key = (_lib.param_epoch, versions)
+        if self._struct_cache is not None and self._struct_cache.key == key:
+            return self._struct_cache.model
+        m = self._build_struct(live)
+        dev = live[0].device
+        folded = torch.empty(int(_lib.lib().nsc_gat_folded_floats(C.byref(m))), dtype=torch.float32, device=dev)
         m.folded = folded.data_ptr()
-        with torch.cuda.device(dev):
-            st = L.nsc_gat_fold_weights(C.byref(m), _lib.ptr(folded), _lib.stream_ptr(dev))
-        _lib.check(st, "nsc_gat_fold_weights")
+        _lib.call("nsc_gat_fold_weights", dev, m, folded, _lib.STREAM)
         # the entry holds the tensors of its key: a replaced parameter cannot be freed and its address handed to the
         # replacement (same address, version 0 again) while the cache still describes it
-        self._struct_cache = (key, m, folded, live)
-        self._fold_generation = getattr(self, "_fold_generation", 0) + 1     # a captured forward bakes `folded` in: see
-        return m                                                              # ShardedDescriptorPath._enhance
+        self._struct_cache = FoldedStruct(key, m, folded, live)
+        self._fold_generation += 1         # a captured forward bakes `folded` in: part of capture_state()'s key
+        return m
+
+    def capture_state(self, data) -> CaptureState:
+        """What a captured eval forward over ``data`` bakes in besides ``data.x``: the graph's GraphCSR, the folded
+        attention vectors of the current weights (made now if need be), and a hashable key that changes whenever a replay
+        would no longer compute ``self(data)``: parameter addresses and versions, the fold generation (an optimizer that
+        writes through a multi-tensor kernel bumps no version counter, but every optimizer step bumps _lib.param_epoch and
+        so forces a new fold), the kernel set and the identity of the GraphCSR.  Keep ``csr`` and ``folded`` alive as long
+        as the capture: a replay reads them, and the key holds the GraphCSR's id."""
+        live = self._live_tensors()
+        versions = tuple((t.data_ptr(), t._version) for t in live)
+        self._model_struct(live, versions)
+        csr = self._csr(data, self._uses_edge_attr(data))
+        return CaptureState(csr, self._struct_cache.folded, (versions, self._fold_generation, self.coresident, id(csr)))
 
     def _train_struct(self) -> _lib.GatModel:
         """NscGatModel for nsc_gat_forward_train / nsc_gat_backward: pointers into the live parameter storage, no folded
         attention vectors (the training kernels compute the attention dot products themselves, so an optimizer step
         does not force a re-fold before the next forward).  Rebuilt only when a parameter's storage moves."""
-        key = tuple(t.data_ptr() for t in self._live_tensors())
-        c = getattr(self, "_train_struct_cache", None)
+        live = self._live_tensors()
+        key = tuple(t.data_ptr() for t in live)
+        c = self._train_struct_cache
         if c is None or c[0] != key:
-            c = (key, self._build_struct())
-            self._train_struct_cache = c
+            c = self._train_struct_cache = (key, self._build_struct(live))
         return c[1]
 
-    def _build_struct(self) -> _lib.GatModel:
+    def _build_struct(self, live) -> _lib.GatModel:
         m = _lib.GatModel()
         m.in_dim, m.hidden, m.out_dim = self.input_dim, self.hidden_dim, self.output_dim
         m.n_layers = self.n_layers
@@ -359,37 +385,21 @@ class SpectralGNN(nn.Module):
         m.residual = int(bool(self.residual))
         m.bn_eps = float(self.input_norm.eps)
         m.negative_slope = float(self.convs[0].negative_slope)
-        p = self._p
-        m.in_w, m.in_b = p(self.input_proj.weight), p(self.input_proj.bias)
-        bn = self.input_norm
-        m.in_bn_w, m.in_bn_b = p(bn.weight), p(bn.bias)
-        m.in_bn_mean, m.in_bn_var = p(bn.running_mean), p(bn.running_var)
-        m.out_w, m.out_b = p(self.output_proj.weight), p(self.output_proj.bias)
-        if self.residual_proj is not None:
-            m.res_w, m.res_b = p(self.residual_proj.weight), p(self.residual_proj.bias)
-        for l, (conv, bn) in enumerate(zip(self.convs, self.batch_norms)):
-            ly = m.layers[l]
-            ly.lin_w = p(conv.lin_src.weight)
-            ly.att_src, ly.att_dst = p(conv.att_src), p(conv.att_dst)
-            if conv.lin_edge is not None:
-                ly.lin_edge_w, ly.att_edge = p(conv.lin_edge.weight), p(conv.att_edge)
-            ly.bias = p(conv.bias)
-            ly.bn_w, ly.bn_b = p(bn.weight), p(bn.bias)
-            ly.bn_mean, ly.bn_var = p(bn.running_mean), p(bn.running_var)
+        for row, t in zip(self._table, live):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise _lib.NscError("GNN parameters must be contiguous float32 tensors on the HIP device")
+            setattr(m if row.layer is None else m.layers[row.layer], row.field, t.data_ptr())
         return m
 
     def _train_params(self):
         """Parameters in the order NscGatGrads lists them."""
-        ps = [self.input_proj.weight, self.input_proj.bias, self.input_norm.weight, self.input_norm.bias,
-              self.output_proj.weight, self.output_proj.bias]
-        if self.residual_proj is not None:
-            ps += [self.residual_proj.weight, self.residual_proj.bias]
-        for conv, bn in zip(self.convs, self.batch_norms):
-            ps += [conv.lin_src.weight, conv.att_src, conv.att_dst]
-            if conv.lin_edge is not None:
-                ps += [conv.lin_edge.weight, conv.att_edge]
-            ps += [conv.bias, bn.weight, bn.bias]
-        return ps
+        return [r.owner[r.key] for r in self._grad_rows]
+
+    def _dropout_seed(self) -> int:
+        """Seed of the counter-based dropout masks: one draw from torch's CPU generator per training forward with dropout;
+        none when a captured step (GNNTrainer) keeps the seed in a device word (self._seed_dev), rewritten before every
+        replay."""
+        return int(torch.randint(0, 2 ** 62, (1,)).item()) if (self.dropout > 0 and self._seed_dev is None) else 0
 
     def _run_train(self, data, use_edge_attr: bool):
         """model.train() forward with autograd (trainer.py:205): batch-statistics BatchNorm, feature and
@@ -398,13 +408,10 @@ class SpectralGNN(nn.Module):
         _lib.require_cuda(x, "data.x")
         x = x.to(torch.float32).contiguous()
         csr = self._csr(data, use_edge_attr)
-        # seed of the counter-based dropout masks from torch's CPU generator; a captured step (GNNTrainer) keeps it in a
-        # device word instead (self._seed_dev), rewritten before every replay
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (self.dropout > 0 and getattr(self, "_seed_dev", None) is None) else 0
-        return _GatTrainFunction.apply(self, x, csr, float(self.dropout), seed, *self._train_params())
+        return _GatTrainFunction.apply(self, x, csr, float(self.dropout), self._dropout_seed(), *self._train_params())
 
     def train_step_direct(self, data, anchor_idx, positive_idx, negative_idx, margin: float, scale: float):
-        """forward (train mode) + TripletLoss + backward WITHOUT autograd (GNNTrainer's steps, round 4): nsc_gat_forward_train,
+        """forward (train mode) + TripletLoss + backward WITHOUT autograd (GNNTrainer's steps): nsc_gat_forward_train,
         nsc_triplet_loss (which returns d loss / d emb) and nsc_gat_backward adding into the parameters' existing .grad
         tensors -- what ``loss = criterion(model(graph)[a], ...); loss.backward()`` (trainer.py:205-213) computes, minus the
         autograd plumbing around the three ABI calls (a (N, 800) multiply by the upstream scalar, two dtype / layout copies and
@@ -412,25 +419,12 @@ class SpectralGNN(nn.Module):
         x = data.x
         _lib.require_cuda(x, "data.x")
         x = x.detach().to(torch.float32).contiguous()
-        edge_attr = getattr(data, 'edge_attr', None)
-        csr = self._csr(data, edge_attr is not None and self.edge_dim is not None)
+        csr = self._csr(data, self._uses_edge_attr(data))
         params = self._train_params()
         if not _direct_ok(params):
             raise _lib.NscError("train_step_direct adds into the existing contiguous .grad tensors of trained parameters")
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (self.dropout > 0 and getattr(self, "_seed_dev", None) is None) else 0
-        out, state = _train_forward_raw(self, x, csr, float(self.dropout), seed)
-        L = _lib.lib()
-        dev = x.device
-        n, d, t = int(out.shape[0]), int(out.shape[1]), int(anchor_idx.numel())
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        grad = torch.empty_like(out)
-        nbytes = L.nsc_triplet_workspace_bytes(t)
-        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            st = L.nsc_triplet_loss(_lib.ptr(out), _lib.ptr(anchor_idx), _lib.ptr(positive_idx), _lib.ptr(negative_idx), t, n, d,
-                                    float(margin), float(scale), _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(ws), nbytes,
-                                    _lib.stream_ptr(dev))
-        _lib.check(st, "nsc_triplet_loss")
+        out, state = _train_forward_raw(self, x, csr, float(self.dropout), self._dropout_seed())
+        loss, grad = _triplet_loss(out, anchor_idx, positive_idx, negative_idx, margin, scale, True)
         _train_backward_raw(self, state, grad, [p.grad for p in params], True, False)
         return loss[0]
 
@@ -445,27 +439,20 @@ class SpectralGNN(nn.Module):
         x = x.detach().to(torch.float32).contiguous()
         n = int(x.shape[0])
         csr = self._csr(data, use_edge_attr)
-        L = _lib.lib()
         m = self._model_struct()
-        g = csr.struct()
         out = torch.empty((n, self.output_dim), dtype=torch.float32, device=dev)
         alpha = (torch.zeros((self.n_layers, csr.capacity), dtype=torch.float32, device=dev)
                  if want_alpha else None)
-        nbytes = L.nsc_gat_workspace_bytes(C.byref(m), n)
+        nbytes = _lib.lib().nsc_gat_workspace_bytes(C.byref(m), n)
         ws = _ws(dev, nbytes, "gat")
-        with torch.cuda.device(dev):
-            st = L.nsc_gat_forward_ex(C.byref(m), C.byref(g), _lib.ptr(x), _lib.ptr(csr.edge_attr),
-                                      _lib.ptr(out), _lib.ptr(alpha), _lib.ptr(ws), nbytes,
-                                      {False: 0, True: 1, "shared_b": 3, "lds_tiled": 4, "generic": 8}[getattr(self, "coresident", False)],
-                                      _lib.stream_ptr(dev))
-        _lib.check(st, "nsc_gat_forward_ex")
+        _lib.call("nsc_gat_forward_ex", dev, m, csr.struct(), x, csr.edge_attr, out, alpha, ws, nbytes,
+                  _lib.GAT_KERNEL_SETS[self.coresident], _lib.STREAM)
         return out, alpha, csr
 
     # -- reference API ----------------------------------------------------------------------
     def forward(self, data) -> torch.Tensor:
         """model.py:96-153: data.x (N,in), data.edge_index (2,E), optional data.edge_attr (E,edge_dim)."""
-        edge_attr = getattr(data, 'edge_attr', None)
-        use_edge = edge_attr is not None and self.edge_dim is not None       # :126
+        use_edge = self._uses_edge_attr(data)
         if self.training:
             return self._run_train(data, use_edge)
         out, _, _ = self._run(data, use_edge, False)

@@ -7,38 +7,32 @@ compute inside them runs through the C ABI: full-graph forward + backward per 1 
 (gnn/triplet_miner.py), loop-closure recall on the device.  The epoch / early-stopping / checkpoint loop around
 them is host code, as in the reference.
 """
+import collections
 import logging
-import os
 import time
 from pathlib import Path
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 import torch.optim as optim
 
 from .. import _lib
-from .model import _direct_ok
+from .. import distributed as nd
+from .model import SpectralGNN, _direct_ok, _triplet_loss, unwrap
+
+# One captured training step (GNNTrainer._captured): the hipGraph first, then the static buffers a replay reads (idx: the
+# three rows of idx_all; seed), its loss, the gradient tensors it adds into, and what it baked in (CSR arrays, graph tensors),
+# kept alive with it
+CapturedStep = collections.namedtuple("CapturedStep", "graph idx seed loss grads keepalive idx_all")
 
 
 class _TripletFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, emb, ia, ip, in_, margin, scale):
-        L = _lib.lib()
-        dev = emb.device
-        emb = emb.contiguous()
-        n, d, t = int(emb.shape[0]), int(emb.shape[1]), int(ia.numel())
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        grad = torch.empty_like(emb) if emb.requires_grad else None
-        nbytes = L.nsc_triplet_workspace_bytes(t)
-        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            st = L.nsc_triplet_loss(_lib.ptr(emb), _lib.ptr(ia), _lib.ptr(ip), _lib.ptr(in_), t, n, d,
-                                    float(margin), float(scale), _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(ws),
-                                    nbytes, _lib.stream_ptr(dev))
-        _lib.check(st, "nsc_triplet_loss")
-        ctx.grad = grad
+        loss, ctx.grad = _triplet_loss(emb.contiguous(), ia, ip, in_, margin, scale, emb.requires_grad)
         return loss[0]
 
     @staticmethod
@@ -99,13 +93,12 @@ class GNNTrainer:
         self.epochs_without_improvement = 0
         # Adam(lr, weight_decay) over the model parameters (:115-119).  On a HIP device: torch's FUSED implementation (one
         # multi-tensor kernel for the 25 parameter tensors instead of ~25 small launches per foreach op: the optimizer step was
-        # 0.34 ms per 4 batches, round 3).  It updates parameters without bumping their version counters, which the eval-mode
-        # forward's cache of folded attention vectors is keyed on: train_batches drops that cache after every step, and a
-        # captured GNN forward is keyed on the fold generation (distributed.ShardedDescriptorPath._enhance).  Same state-dict
-        # layout as the default implementation: checkpoints stay interchangeable with the reference's.
-        fused = torch.device(device).type == "cuda" and torch.cuda.is_available() and os.environ.get("NSC_TRAINER_FUSED_ADAM", "1") == "1"
+        # 0.34 ms per 4 batches).  It updates parameters without bumping their version counters, which the eval-mode
+        # forward's cache of folded attention vectors is keyed on: that cache and a captured GNN forward are therefore also
+        # keyed on _lib.param_epoch, which every optimizer step of the process bumps (SpectralGNN.capture_state).  Same
+        # state-dict layout as the default implementation: checkpoints stay interchangeable with the reference's.
         try:
-            self.optimizer = optim.Adam(model.parameters(), lr=learning_rate, weight_decay=weight_decay, fused=fused)
+            self.optimizer = optim.Adam(model.parameters(), lr=learning_rate, weight_decay=weight_decay, fused=self._on_hip)
         except (TypeError, RuntimeError):       # an older torch without the fused path
             self.optimizer = optim.Adam(model.parameters(), lr=learning_rate, weight_decay=weight_decay)
         self.criterion = TripletLoss(margin=margin)                                                   # :121
@@ -118,9 +111,9 @@ class GNNTrainer:
         self.max_captures = 4                      # captured steps kept (LRU); each pins a hipGraph + its workspace pool
         # the backward adds into the existing .grad tensors itself instead of handing gradients to autograd's AccumulateGrad
         self.direct_grads = direct_grads
-        import collections
-        self._captured, self._seen_once, self._capture_failed = collections.OrderedDict(), set(), False
+        self._captured, self._seen_once, self._capture_failed = collections.OrderedDict(), set(), False    # key -> CapturedStep
         self._full_T = None                        # size of a full batch (slice) of the current train_batches() call
+        self._flat_grad = self._flat_views = None  # gradient storage as views of one buffer (_ensure_flat_grads)
         # the reference creates 'checkpoints/' eagerly (:123-124); here the directory appears with the first save
         self.checkpoint_dir = Path(checkpoint_dir if checkpoint_dir is not None else 'checkpoints')
         self.log_interval = log_interval
@@ -130,20 +123,21 @@ class GNNTrainer:
         self.train_losses = []
         self.val_metrics = []
 
+    @property
+    def _on_hip(self) -> bool:
+        return torch.device(self.device).type == "cuda" and torch.cuda.is_available()
+
     # -- validation (trainer.py:238-387) ------------------------------------------------------
     def _recall_ranks(self, embeddings: torch.Tensor, poses: np.ndarray, max_k: int,
                       distance_threshold: float, skip_frames: int):
         """Rank of the first correct candidate among the max_k nearest, per loop-closure query."""
         from ..retrieval.wasserstein import _topk
-        L = _lib.lib()
         dev = embeddings.device
         emb = embeddings.detach().float().contiguous()
         n, d = int(emb.shape[0]), int(emb.shape[1])
         pos = torch.as_tensor(np.asarray(poses)[:, :3, 3].astype(np.float64)).to(dev).contiguous()
         first = torch.empty(n, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.nsc_revisit_queries(_lib.ptr(pos), n, skip_frames, float(distance_threshold),
-                                             _lib.ptr(first), _lib.stream_ptr(dev)), "nsc_revisit_queries")
+        _lib.call("nsc_revisit_queries", dev, pos, n, skip_frames, float(distance_threshold), first, _lib.STREAM)
         qidx = first[first >= 0].contiguous()                     # one query per earlier frame i (:342-348)
         nq = int(qidx.numel())
         if nq == 0:
@@ -154,16 +148,11 @@ class GNNTrainer:
         for q0 in range(0, nq, chunk):
             qs = qidx[q0:q0 + chunk].contiguous()
             dist = torch.empty((int(qs.numel()), n), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(L.nsc_pairwise_l2(_lib.ptr(emb), _lib.ptr(qs), int(qs.numel()), n, d, skip_frames,
-                                             _lib.ptr(dist), _lib.stream_ptr(dev)), "nsc_pairwise_l2")
+            _lib.call("nsc_pairwise_l2", dev, emb, qs, int(qs.numel()), n, d, skip_frames, dist, _lib.STREAM)
             idx, val = _topk(dist, k)
             idx = torch.where(torch.isinf(val), torch.full_like(idx, -1), idx)    # fewer than k candidates
-            with torch.cuda.device(dev):
-                _lib.check(L.nsc_recall_rank(_lib.ptr(pos), _lib.ptr(qs), _lib.ptr(idx.contiguous()),
-                                             int(qs.numel()), k, float(distance_threshold),
-                                             _lib.ptr(ranks[q0:q0 + chunk]), _lib.stream_ptr(dev)),
-                           "nsc_recall_rank")
+            _lib.call("nsc_recall_rank", dev, pos, qs, idx.contiguous(), int(qs.numel()), k, float(distance_threshold),
+                      ranks[q0:q0 + chunk], _lib.STREAM)
         return ranks
 
     def _compute_recall_loop_closure(self, embeddings, poses: np.ndarray, k: int,
@@ -271,15 +260,14 @@ class GNNTrainer:
 
     # -- the per-batch step, captured --------------------------------------------------------------------------
     def _eager_step(self, graph, ia, ip, in_, scale):
-        inner = getattr(self.model, "gnn", self.model)
+        inner = unwrap(self.model)
         # the backward adds straight into the .grad tensors (they exist: zero_grad keeps them) -- no AccumulateGrad pass.
         # Every tensor the backward writes must be trained and have its .grad: a frozen parameter takes the autograd path
-        direct = (self.direct_grads and hasattr(inner, "_direct_grads") and hasattr(inner, "_train_params")
-                  and _direct_ok(inner._train_params()))
-        if direct and os.environ.get("NSC_TRAINER_NO_DIRECT") != "1" and hasattr(inner, "train_step_direct") and self.model.training and all(
+        direct = self.direct_grads and isinstance(inner, SpectralGNN) and _direct_ok(inner._train_params())
+        if direct and self.model.training and all(
                 isinstance(i, torch.Tensor) and i.is_cuda and i.dtype == torch.int64 for i in (ia, ip, in_)):
             # device-resident indices (the captured step's static buffers, an epoch's uploaded triplets): the three ABI calls
-            # back to back, no autograd graph (round 4)
+            # back to back, no autograd graph
             return inner.train_step_direct(graph, ia.contiguous(), ip.contiguous(), in_.contiguous(),
                                            self.criterion.margin, scale).detach()
         if direct:
@@ -295,15 +283,16 @@ class GNNTrainer:
 
     def _captured_step(self, graph, bt, scale, bt_dev=None):
         """forward + TripletLoss + backward of one batch as ONE hipGraph launch.  The step is ~75 small kernels
-        (1.2-1.8 ms per batch issued one by one, launch-bound; 0.73-1.04 ms replayed, round 3): everything it touches
+        (1.2-1.8 ms per batch issued one by one, launch-bound; 0.73-1.04 ms replayed): everything it touches
         is static -- the replicated graph, the parameter and gradient storage, the workspace of the capture's own
         memory pool -- except three things fed through device buffers the capture reads: the triplet indices, and the
         dropout seed (NscGatTrainCfg.seed_dev).  Gradients ACCUMULATE into the existing .grad tensors (the capture
         holds their addresses: zero_grad must keep them, set_to_none=False).  Returns the loss, or None when capture is
         not possible (then the caller runs the step eagerly)."""
-        if not self._graph_enabled() or not torch.cuda.is_available() or torch.device(self.device).type != "cuda":
+        if not (self._graph_enabled() and self._on_hip):
             return None
-        inner = getattr(self.model, "gnn", self.model)
+        inner = unwrap(self.model)
+        is_gnn = isinstance(inner, SpectralGNN)
         params = [p for p in self.model.parameters() if p.requires_grad]
         T = int(len(bt))
         # only FULL batches are captured: the ragged last batch of an epoch has a different triplet count every epoch
@@ -311,8 +300,7 @@ class GNNTrainer:
         if self._full_T is not None and T != self._full_T:
             return None
         ea = getattr(graph, "edge_attr", None)
-        use_edge = ea is not None and getattr(inner, "edge_dim", None) is not None
-        csr = inner._csr(graph, use_edge) if hasattr(inner, "_csr") else None     # the capture bakes its arrays in
+        csr = inner._csr(graph, inner._uses_edge_attr(graph)) if is_gnn else None     # the capture bakes its arrays in
         key = (id(graph), graph.x.data_ptr(), graph.edge_index.data_ptr(), None if ea is None else ea.data_ptr(), id(csr),
                T, float(scale), tuple(p.data_ptr() for p in params))
         ent = self._captured.get(key)
@@ -333,16 +321,13 @@ class GNNTrainer:
                 for p in params:
                     if p.grad is None:
                         p.grad = torch.zeros_like(p)
-                inner._seed_dev = seed
-                torch.cuda.synchronize(dev)
-                cg = torch.cuda.CUDAGraph()
-                # thread-local error mode: HIP calls of OTHER threads (RCCL's proxy / watchdog) do not invalidate the capture
-                with torch.cuda.graph(cg, capture_error_mode="thread_local"):   # records the launches; nothing runs until replay()
-                    loss = self._eager_step(graph, idx[0], idx[1], idx[2], scale)
+                if is_gnn:
+                    inner._seed_dev = seed
+                cg, loss = _lib.capture(dev, lambda: self._eager_step(graph, idx[0], idx[1], idx[2], scale))
                 # the entry keeps what the capture baked in alive (CSR arrays, graph tensors): while it exists their ids
                 # and addresses in the key cannot be recycled
-                ent = (cg, idx, seed, loss, [p.grad for p in params], (csr, graph, ea), idx_all)
-                self._captured[key] = ent
+                ent = self._captured[key] = CapturedStep(cg, idx, seed, loss, [p.grad for p in params], (csr, graph, ea),
+                                                         idx_all)
                 while len(self._captured) > self.max_captures:
                     self._captured.popitem(last=False)      # least recently used capture: graph + pool are dropped
             except Exception as ex:  # noqa: BLE001 -- any capture problem: fall back to issuing the step eagerly
@@ -350,10 +335,10 @@ class GNNTrainer:
                 self._capture_failed = True
                 return None
             finally:
-                inner._seed_dev = None
+                if is_gnn:
+                    inner._seed_dev = None
         self._captured.move_to_end(key)
-        cg, idx, seed, loss, grads = ent[:5]
-        for p, g in zip(params, grads):
+        for p, g in zip(params, ent.grads):
             if p.grad is not g:                             # someone dropped / replaced the static gradient tensor
                 if p.grad is not None:
                     g.copy_(p.grad)
@@ -366,15 +351,14 @@ class GNNTrainer:
             raise IndexError(f"triplet index out of range for {n} embeddings")
         # bt_dev: the batch's (3, T) index rows already on the device (train_batches uploads an epoch's triplets once: a
         # per-batch copy from pageable host memory would block the host until the stream has drained); ONE copy for the three rows
-        ent[6].copy_(bt_dev if bt_dev is not None else torch.from_numpy(np.ascontiguousarray(h.T)), non_blocking=True)
-        seed.fill_(int(torch.randint(0, 2 ** 62, (1,)).item()) if float(getattr(inner, "dropout", 0.0)) > 0 else 0)
-        cg.replay()                                         # (num_batches_tracked is incremented inside the capture)
-        return loss.detach().clone()
+        ent.idx_all.copy_(bt_dev if bt_dev is not None else torch.from_numpy(np.ascontiguousarray(h.T)), non_blocking=True)
+        ent.seed.fill_(inner._dropout_seed() if is_gnn else 0)
+        ent.graph.replay()                                  # (num_batches_tracked is incremented inside the capture)
+        return ent.loss.detach().clone()
 
     def _graph_enabled(self) -> bool:
         if self.use_graph is not None:
             return bool(self.use_graph)
-        import torch.distributed as dist
         return not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
 
     def release(self):
@@ -384,9 +368,9 @@ class GNNTrainer:
 
     def _ensure_flat_grads(self, params) -> None:
         """Gradient storage as views of ONE flat buffer (256-byte aligned slices): zeroing the gradients after an optimizer
-        step is one fill instead of one per parameter (25 launches of 2.3 us per step in the round-3 trace).  Existing
+        step is one fill instead of one per parameter (25 launches of 2.3 us per step in the trace).  Existing
         gradients are carried over; anything unusual (mixed devices / dtypes) keeps per-tensor storage."""
-        views = getattr(self, "_flat_views", None)
+        views = self._flat_views
         if views is not None and len(views) == len(params) and all(p.grad is v for p, v in zip(params, views)):
             return
         if not params or any(p.device != params[0].device or p.dtype != torch.float32 or not p.is_cuda for p in params):
@@ -407,7 +391,7 @@ class GNNTrainer:
         self._flat_grad, self._flat_views = flat, views
 
     def _zero_grads(self, params) -> None:
-        views = getattr(self, "_flat_views", None)
+        views = self._flat_views
         if views is not None and len(views) == len(params) and all(p.grad is v for p, v in zip(params, views)):
             self._flat_grad.zero_()
         else:
@@ -419,14 +403,12 @@ class GNNTrainer:
         triplets = np.asarray(triplets)
         n_batches = (len(triplets) + self.batch_size - 1) // self.batch_size
         losses = []
-        from .. import distributed as nd
-        import torch.distributed as dist
         world = dist.get_world_size() if dist.is_initialized() else 1
         rank = dist.get_rank() if dist.is_initialized() else 0
         params = [p for p in self.model.parameters() if p.requires_grad]
         # gradients keep their storage across optimizer steps (a captured step holds their addresses)
-        use_graph = self._graph_enabled()
-        if use_graph and torch.device(self.device).type == "cuda" and torch.cuda.is_available():
+        use_graph = self._graph_enabled() and self._on_hip
+        if use_graph:
             self._ensure_flat_grads(params)
         self._zero_grads(params)
         trip_dev = None
@@ -434,7 +416,7 @@ class GNNTrainer:
         if len(triplets):
             flo, fhi = nd.shard_range(min(self.batch_size, len(triplets)), rank, world) if world > 1 else (0, min(self.batch_size, len(triplets)))
             self._full_T = fhi - flo
-        if use_graph and len(triplets) and torch.device(self.device).type == "cuda" and torch.cuda.is_available():
+        if use_graph and len(triplets):
             trip_dev = torch.from_numpy(np.ascontiguousarray(triplets.T, dtype=np.int64)).to(graph.x.device)   # (3, n), once
         for b in range(n_batches):
             b0 = b * self.batch_size
@@ -457,12 +439,6 @@ class GNNTrainer:
                 nd.all_reduce_gradients(params)                            # one 2.46 MB RCCL all-reduce
                 self.optimizer.step()
                 self._zero_grads(params)
-                # the eval-mode forward caches folded attention vectors keyed on the parameters' version counters; an
-                # optimizer that writes through a multi-tensor kernel need not bump them (torch's fused Adam does not:
-                # measured, round 3) -- drop the cache explicitly
-                inner_ = getattr(self.model, "gnn", self.model)
-                if hasattr(inner_, "_struct_cache"):
-                    inner_._struct_cache = None
         if not losses:
             return 0.0
         return float(torch.stack(losses).mean().item() * self.accumulation_steps)

@@ -10,7 +10,6 @@ candidate at position len // 2 of the W1 order, :352-357, "random" a uniform one
 The positive is a uniform random candidate (``np.random.choice`` in the reference, unseeded): chosen
 here by a counter-based hash seeded from numpy's global RNG, so ``np.random.seed`` still controls it.
 """
-import ctypes as C
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -62,11 +61,8 @@ class TripletMiner:
         L = _lib.lib()
         nbytes = L.nsc_mine_workspace_bytes(n, p.strategy)       # semi-hard: one row of candidate distances per anchor
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-        with torch.cuda.device(dev):
-            st = L.nsc_mine_triplets_ws(_lib.ptr(pos), _lib.ptr(cdf), n, int(desc.shape[1]), C.byref(p),
-                                        _lib.ptr(out_pos), _lib.ptr(out_neg), _lib.ptr(counts), _lib.ptr(ws), nbytes,
-                                        _lib.stream_ptr(dev))
-        _lib.check(st, "nsc_mine_triplets_ws")
+        _lib.call("nsc_mine_triplets_ws", dev, pos, cdf, n, int(desc.shape[1]), p, out_pos, out_neg, counts, ws, nbytes,
+                  _lib.STREAM)
         ok = (out_pos >= 0) & (out_neg >= 0)
         a_loc = torch.arange(n, device=dev).unsqueeze(1).expand_as(out_pos)[ok]
         trip = torch.stack([idx[a_loc], idx[out_pos[ok].long()], idx[out_neg[ok].long()]], 1)

@@ -98,10 +98,8 @@ def chain_graph_device(n_nodes: int, temporal_neighbors: int, device, poses=None
                              if not isinstance(poses, torch.Tensor) else poses)
         pd = pd.to(device=device, dtype=torch.float64).reshape(n_nodes, 16).contiguous()
         edge_attr = torch.empty((E, 2), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        st = L.nsc_build_chain_graph(_lib.ptr(pd), n_nodes, temporal_neighbors, _lib.ptr(loops), n_loops,
-                                     _lib.ptr(edge_index), _lib.ptr(edge_attr), _lib.stream_ptr(device))
-    _lib.check(st, "nsc_build_chain_graph")
+    _lib.call("nsc_build_chain_graph", device, pd, n_nodes, temporal_neighbors, loops, n_loops, edge_index, edge_attr,
+              _lib.STREAM)
     return edge_index, edge_attr
 
 

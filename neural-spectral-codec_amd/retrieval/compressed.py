@@ -41,9 +41,7 @@ def quantized_cdf(quantized):
     n, d = int(q.shape[0]), int(q.shape[1])
     cdf = torch.empty((n, d), dtype=torch.uint16, device=q.device)
     ok = torch.empty((n,), dtype=torch.uint8, device=q.device)
-    with torch.cuda.device(q.device):
-        st = _lib.lib().nsc_w1q_cdf(_lib.ptr(q), n, d, _lib.ptr(cdf), _lib.ptr(ok), _lib.stream_ptr(q.device))
-    _lib.check(st, "nsc_w1q_cdf")
+    _lib.call("nsc_w1q_cdf", q.device, q, n, d, cdf, ok, _lib.STREAM)
     return cdf, ok
 
 
@@ -65,11 +63,7 @@ def w1_distances_quantized(db_cdf, db_canonical, q_cdf, q_canonical, db_pos=None
     dbp = None if db_pos is None else _pos_f32(db_pos, dev)
     qp = None if q_pos is None else _pos_f32(q_pos, dev)
     dist = torch.empty((q, n), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().nsc_w1q_distances(_lib.ptr(db_cdf), _lib.ptr(db_ok), n, d, _lib.ptr(q_cdf), _lib.ptr(q_ok), q,
-                                          _lib.ptr(dbp), _lib.ptr(qp), float(min_distance), _lib.ptr(dist),
-                                          _lib.stream_ptr(dev))
-    _lib.check(st, "nsc_w1q_distances")
+    _lib.call("nsc_w1q_distances", dev, db_cdf, db_ok, n, d, q_cdf, q_ok, q, dbp, qp, float(min_distance), dist, _lib.STREAM)
     return dist
 
 

@@ -48,7 +48,6 @@ off the two range images, good to a few degrees.  It does not cover a translatio
 of the prepared clouds (planar_alignment.py).  For roll and pitch pass ``init_transforms`` (odometry; host arrays or
 device tensors).
 """
-import ctypes as C
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -140,13 +139,8 @@ def register_packed(source_points, source_offsets, target_points, target_offsets
                    covariances=torch.empty((Ns + Nt, 6), **f64))
         st = _lib.GicpStages(*(out[k].data_ptr() for k in ("points", "counts", "covariances", "system0")))
     ws = _workspace(L.nsc_gicp_workspace_bytes(P, Ns, Nt), dev)
-    with torch.cuda.device(dev):
-        status = L.nsc_gicp_register(_lib.ptr(src), _lib.ptr(so), _lib.ptr(tgt), _lib.ptr(to), P, Ns, Nt, stride,
-                                     C.byref(p), _lib.ptr(init), _lib.ptr(out["transform"]), _lib.ptr(out["fit_rmse"]),
-                                     _lib.ptr(out["corr_iters"]), _lib.ptr(out["information"]),
-                                     C.byref(st) if st is not None else None, _lib.ptr(ws), int(ws.numel()),
-                                     _lib.stream_ptr(dev))
-    _lib.check(status, "nsc_gicp_register")
+    _lib.call("nsc_gicp_register", dev, src, so, tgt, to, P, Ns, Nt, stride, p, init, out["transform"], out["fit_rmse"],
+              out["corr_iters"], out["information"], st, ws, int(ws.numel()), _lib.STREAM)
     return _unpacked(out)
 
 
@@ -296,10 +290,7 @@ class PreparedClouds:
         p = _params(**self.params)
         L = _lib.lib()
         ws = _workspace(L.nsc_gicp_prepare_workspace_bytes(B, N), self.device)
-        with torch.cuda.device(self.device):
-            status = L.nsc_gicp_prepare(_lib.ptr(pts), _lib.ptr(off), B, N, int(pts.shape[1]), C.byref(p),
-                                        C.byref(st), _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(self.device))
-        _lib.check(status, "nsc_gicp_prepare")
+        _lib.call("nsc_gicp_prepare", self.device, pts, off, B, N, int(pts.shape[1]), p, st, ws, int(ws.numel()), _lib.STREAM)
         b = self._buf
         new = torch.cat([b["row_offsets"][n + 1:n + B + 1], b["slot_offsets"][n + B:n + B + 1]]).cpu().numpy()
         self._row_host = np.concatenate([self._row_host, new[:B]])
@@ -364,13 +355,8 @@ def register_prepared(sources: PreparedClouds, source_ids, targets: PreparedClou
     out = _outputs(P, dev, system0=stages)
     ss, ts = sources._set(), targets._set()
     ws = _workspace(L.nsc_gicp_register_prepared_workspace_bytes(P), dev)
-    with torch.cuda.device(dev):
-        status = L.nsc_gicp_register_prepared(C.byref(ss), C.byref(ts), _lib.ptr(sid), _lib.ptr(tid), P, C.byref(p),
-                                              _lib.ptr(init), _lib.ptr(out["transform"]), _lib.ptr(out["fit_rmse"]),
-                                              _lib.ptr(out["corr_iters"]), _lib.ptr(out["information"]),
-                                              _lib.ptr(out["system0"]) if stages else None, _lib.ptr(ws),
-                                              int(ws.numel()), _lib.stream_ptr(dev))
-    _lib.check(status, "nsc_gicp_register_prepared")
+    _lib.call("nsc_gicp_register_prepared", dev, ss, ts, sid, tid, P, p, init, out["transform"], out["fit_rmse"],
+              out["corr_iters"], out["information"], out["system0"] if stages else None, ws, int(ws.numel()), _lib.STREAM)
     return _unpacked(out)
 
 

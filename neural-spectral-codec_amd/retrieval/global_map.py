@@ -145,11 +145,10 @@ def _clouds(points, offsets, poses, pose_ids):
 
 
 def _row_args(c, params, new_poses=None):
-    """the ctypes arguments every map call starts with, from _clouds' tuple: the rows, the poses (the old and the new of a
-    replacement), the ids and the grid"""
-    poses = (_lib.ptr(c.pose),) if new_poses is None else (_lib.ptr(c.pose), _lib.ptr(new_poses))
-    return (_lib.ptr(c.pts), c.dtype, int(c.pts.shape[1]), _lib.ptr(c.off), c.B, c.N, *poses, c.P, _lib.ptr(c.ids),
-            C.byref(params))
+    """the arguments every map call starts with (as _lib.call takes them), from _clouds' tuple: the rows, the poses (the
+    old and the new of a replacement), the ids and the grid"""
+    poses = (c.pose,) if new_poses is None else (c.pose, new_poses)
+    return (c.pts, c.dtype, int(c.pts.shape[1]), c.off, c.B, c.N, *poses, c.P, c.ids, params)
 
 
 def _outputs(shapes, out, device):
@@ -228,11 +227,8 @@ class GlobalMap:
                             stats=((_lib.MAP_STATS,), torch.int64)), out, dev)
         L = _lib.lib()
         ws = _workspace(L.nsc_map_workspace_bytes(N, M), dev)
-        with torch.cuda.device(dev):
-            status = L.nsc_map_build(*_row_args(c, self.params), M, _lib.ptr(out["points"]), _lib.ptr(out["info"]),
-                                     _lib.ptr(out["keys"]), _lib.ptr(out["stats"]), _lib.ptr(ws), int(ws.numel()),
-                                     _lib.stream_ptr(dev))
-        _lib.check(status, "nsc_map_build")
+        _lib.call("nsc_map_build", dev, *_row_args(c, self.params), M, out["points"], out["info"], out["keys"], out["stats"],
+                  ws, int(ws.numel()), _lib.STREAM)
         return out
 
     def _result(self, out):

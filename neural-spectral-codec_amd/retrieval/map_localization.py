@@ -59,7 +59,6 @@ Not part of this module: source covariances (full VGICP), 27-voxel neighbourhood
 test, NDT's exponential score, detection of an unmatched removal that leaves a positive count, a resize in place or one
 that ``extend`` starts by itself (it would need a read-back), unary edges in the pose graph.
 """
-import ctypes as C
 
 import numpy as np
 import torch
@@ -157,12 +156,8 @@ class MapLocalizer:
         out = _outputs(self._shapes(M, keeps_moments, self.insertable), out, dev)
         L = _lib.lib()
         ws = _workspace(L.nsc_map_dist_workspace_bytes(N, M), dev)
-        with torch.cuda.device(dev):
-            status = L.nsc_map_build_dist(*_row_args(c, self.params), C.byref(self.dist), M, _lib.ptr(out["voxels"]),
-                                          _lib.ptr(out["index"]), _lib.ptr(out["info"]), _lib.ptr(out["keys"]),
-                                          _lib.ptr(out.get("moments")), _lib.ptr(out["stats"]), _lib.ptr(ws),
-                                          int(ws.numel()), _lib.stream_ptr(dev))
-        _lib.check(status, "nsc_map_build_dist")
+        _lib.call("nsc_map_build_dist", dev, *_row_args(c, self.params), self.dist, M, out["voxels"], out["index"],
+                  out["info"], out["keys"], out.get("moments"), out["stats"], ws, int(ws.numel()), _lib.STREAM)
         self._keep(out, M, out.get("moments"), out.get("cursor") if self.insertable else None)
         if self.cursor is not None:
             self.cursor[0].fill_(N)
@@ -193,9 +188,8 @@ class MapLocalizer:
         return {k: getattr(self, k) for k in ("voxels", "index", "info", "keys", "moments", "stats", "cursor")}
 
     def _kept_args(self):
-        """the ctypes arguments of the kept map, as every call on it takes them after the rows"""
-        return (C.byref(self.dist), self.capacity, _lib.ptr(self.voxels), _lib.ptr(self.index), _lib.ptr(self.info),
-                _lib.ptr(self.keys), _lib.ptr(self.moments), _lib.ptr(self.stats))
+        """the arguments of the kept map (as _lib.call takes them), as every call on it takes them after the rows"""
+        return (self.dist, self.capacity, self.voxels, self.index, self.info, self.keys, self.moments, self.stats)
 
     def _insertable_map(self, what):
         """the host-side refusals every insertion starts with"""
@@ -218,10 +212,8 @@ class MapLocalizer:
         c = _clouds(points, offsets, poses, pose_ids)
         L = _lib.lib()
         ws = _workspace(L.nsc_map_insert_workspace_bytes(c.N), dev)
-        with torch.cuda.device(dev):
-            status = L.nsc_map_insert_dist(*_row_args(c, self.params), *self._kept_args(), _lib.ptr(self.cursor),
-                                           _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
-        _lib.check(status, "nsc_map_insert_dist")
+        _lib.call("nsc_map_insert_dist", dev, *_row_args(c, self.params), *self._kept_args(), self.cursor, ws,
+                  int(ws.numel()), _lib.STREAM)
         self.complete = None
         return self._kept()
 
@@ -271,10 +263,8 @@ class MapLocalizer:
         L = _lib.lib()
         ws = _workspace(L.nsc_map_remove_workspace_bytes(c.N), dev)
         removed = torch.empty((_lib.MAP_REMOVE_STATS,), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            status = L.nsc_map_remove_dist(*_row_args(c, self.params), *self._kept_args(), _lib.ptr(removed), _lib.ptr(ws),
-                                           int(ws.numel()), _lib.stream_ptr(dev))
-        _lib.check(status, "nsc_map_remove_dist")
+        _lib.call("nsc_map_remove_dist", dev, *_row_args(c, self.params), *self._kept_args(), removed, ws, int(ws.numel()),
+                  _lib.STREAM)
         self.complete = None
         return dict(self._kept(), removed=removed)
 
@@ -325,11 +315,8 @@ class MapLocalizer:
         ws = _workspace(L.nsc_map_replace_workspace_bytes(c.N), dev)
         removed = torch.empty((_lib.MAP_REMOVE_STATS,), dtype=torch.int64, device=dev)
         placed = torch.empty((_lib.MAP_STATS,), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            status = L.nsc_map_replace_dist(*_row_args(c, self.params, new), *self._kept_args(), int(first_row),
-                                            int(first_cloud), _lib.ptr(removed), _lib.ptr(placed), _lib.ptr(ws),
-                                            int(ws.numel()), _lib.stream_ptr(dev))
-        _lib.check(status, "nsc_map_replace_dist")
+        _lib.call("nsc_map_replace_dist", dev, *_row_args(c, self.params, new), *self._kept_args(), int(first_row),
+                  int(first_cloud), removed, placed, ws, int(ws.numel()), _lib.STREAM)
         self.complete = None
         return dict(self._kept(), removed=removed, placed=placed)
 
@@ -425,14 +412,9 @@ class MapLocalizer:
         shapes.update(new_place=((old,), torch.int64), tile_base=((tiles + 1,), torch.int64),
                       rehashed=((_lib.MAP_REHASH_STATS,), torch.int64))
         out = _outputs(shapes, out, dev)
-        with torch.cuda.device(dev):
-            status = _lib.lib().nsc_map_rehash_dist(
-                _lib.ptr(self.voxels), _lib.ptr(self.info), _lib.ptr(self.keys), _lib.ptr(self.moments),
-                _lib.ptr(self.stats), _lib.ptr(self.cursor), old, 0 if compact else 1, _lib.ptr(out["voxels"]),
-                _lib.ptr(out["index"]), _lib.ptr(out["info"]), _lib.ptr(out["keys"]), _lib.ptr(out.get("moments")),
-                _lib.ptr(out["stats"]), _lib.ptr(out.get("cursor")), M, _lib.ptr(out["new_place"]),
-                _lib.ptr(out["tile_base"]), _lib.ptr(out["rehashed"]), _lib.stream_ptr(dev))
-        _lib.check(status, "nsc_map_rehash_dist")
+        _lib.call("nsc_map_rehash_dist", dev, self.voxels, self.info, self.keys, self.moments, self.stats, self.cursor, old,
+                  0 if compact else 1, out["voxels"], out["index"], out["info"], out["keys"], out.get("moments"),
+                  out["stats"], out.get("cursor"), M, out["new_place"], out["tile_base"], out["rehashed"], _lib.STREAM)
         self._keep(out, M, out["moments"] if self.moments is not None else None,
                    out["cursor"] if self.cursor is not None else None)
         self.max_voxels = M
@@ -512,19 +494,16 @@ class MapLocalizer:
         most = _lib.MAP_REGISTER_MAX_SCANS
         need = L.nsc_map_register_workspace_bytes if plain else L.nsc_map_register_robust_workspace_bytes
         ws = _workspace(need(min(S, most)), dev)
-        with torch.cuda.device(dev):
-            for a in range(0, S, most):
-                b = min(a + most, S)
-                head = (_lib.ptr(pts), dtype, int(pts.shape[1]), _lib.ptr(off[a:]), b - a, N, _lib.ptr(self.voxels),
-                        _lib.ptr(self.index), self.capacity, C.byref(self.params), C.byref(self.reg))
-                outs = (_lib.ptr(init[a:]), _lib.ptr(T[a:]), _lib.ptr(fr[a:]), _lib.ptr(cost[a:]), _lib.ptr(ci[a:]),
-                        _lib.ptr(info[a:]), None if sys0 is None else _lib.ptr(sys0[a:]))
-                tail = (_lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev))
-                if plain:
-                    _lib.check(L.nsc_map_register(*head, *outs, *tail), "nsc_map_register")
-                else:
-                    _lib.check(L.nsc_map_register_robust(*head, C.byref(self.robust), *outs, _lib.ptr(wp[a:]), *tail),
-                               "nsc_map_register_robust")
+        for a in range(0, S, most):
+            b = min(a + most, S)
+            head = (pts, dtype, int(pts.shape[1]), off[a:], b - a, N, self.voxels, self.index, self.capacity, self.params,
+                    self.reg)
+            outs = (init[a:], T[a:], fr[a:], cost[a:], ci[a:], info[a:], None if sys0 is None else sys0[a:])
+            tail = (ws, int(ws.numel()), _lib.STREAM)
+            if plain:
+                _lib.call("nsc_map_register", dev, *head, *outs, *tail)
+            else:
+                _lib.call("nsc_map_register_robust", dev, *head, self.robust, *outs, wp[a:], *tail)
         out = dict(transform=T, fitness=fr[:, 0], rmse=fr[:, 1], cost=cost, n_correspondences=ci[:, 0],
                    iterations=ci[:, 1], information=info)
         if wp is not None:

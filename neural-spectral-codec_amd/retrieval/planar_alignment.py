@@ -35,7 +35,6 @@ are integers, so the results do not depend on any order and equal the restatemen
 The guess carries no roll, pitch or z offset.  ``planar_support = peak / source rows taken`` is the number that tells
 a revisit from another place; GICP's fitness on two ground planes does not.
 """
-import ctypes as C
 import math
 
 import numpy as np
@@ -115,13 +114,8 @@ def estimate_planar(sources: PreparedClouds, source_ids, targets: PreparedClouds
     L = _lib.lib()
     ss, ts = sources._set(), targets._set()
     ws = _workspace(L.nsc_planar_align_workspace_bytes(P, H), dev)
-    with torch.cuda.device(dev):
-        status = L.nsc_planar_align(C.byref(ss), C.byref(ts), _lib.ptr(sid), _lib.ptr(tid), P, _lib.ptr(table), H,
-                                    C.byref(p), _lib.ptr(out["best"]), _lib.ptr(out["scores"]),
-                                    _lib.ptr(out["counts"]), _lib.ptr(out["init_transforms"]),
-                                    C.byref(st) if st is not None else None, _lib.ptr(ws), int(ws.numel()),
-                                    _lib.stream_ptr(dev))
-    _lib.check(status, "nsc_planar_align")
+    _lib.call("nsc_planar_align", dev, ss, ts, sid, tid, P, table, H, p, out["best"], out["scores"], out["counts"],
+              out["init_transforms"], st, ws, int(ws.numel()), _lib.STREAM)
     return out
 
 

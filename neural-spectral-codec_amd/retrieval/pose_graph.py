@@ -255,14 +255,8 @@ class PoseGraphOptimizer:
         L = _lib.lib()
         ws = torch.empty(max(int(L.nsc_posegraph_workspace_bytes(N, E, C.byref(self.params))), 1), dtype=torch.uint8,
                          device=dev)
-        with torch.cuda.device(dev):
-            status = L.nsc_posegraph_linearize_robust(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E,
-                                                      _lib.ptr(out["residuals"]), _lib.ptr(out["cost"]),
-                                                      _lib.ptr(out["gradient"]), _lib.ptr(out["blocks"]),
-                                                      _lib.ptr(out["skipped"]), _lib.ptr(ws), int(ws.numel()),
-                                                      _lib.stream_ptr(dev), self.kernel, _lib.ptr(c),
-                                                      _lib.ptr(out.get("weights")))
-        _lib.check(status, "nsc_posegraph_linearize_robust")
+        _lib.call("nsc_posegraph_linearize_robust", dev, X, N, e, Z, om, E, out["residuals"], out["cost"], out["gradient"],
+                  out["blocks"], out["skipped"], ws, int(ws.numel()), _lib.STREAM, self.kernel, c, out.get("weights"))
         return out
 
     def optimize_device(self, poses, edge_ij, measurements, information, fixed=None, poses_out=None, step0=False,
@@ -296,16 +290,12 @@ class PoseGraphOptimizer:
         else:
             need = L.nsc_posegraph_workspace_bytes(N, E, C.byref(self.params))
         ws = torch.empty(max(int(need), 1), dtype=torch.uint8, device=dev)
-        args = (_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E, _lib.ptr(fx), C.byref(self.params),
-                _lib.ptr(out["poses"]), _lib.ptr(out["stats"]), _lib.ptr(out["cost_history"]), _lib.ptr(out.get("step0")),
-                _lib.ptr(ws), int(ws.numel()), _lib.stream_ptr(dev), self.kernel, _lib.ptr(c), _lib.ptr(out.get("chi2")),
-                _lib.ptr(out.get("weights")))
-        with torch.cuda.device(dev):
-            if block:
-                _lib.check(L.nsc_posegraph_optimize_coarse(*args, block, _lib.ptr(out["coarse_stats"])),
-                           "nsc_posegraph_optimize_coarse")
-            else:
-                _lib.check(L.nsc_posegraph_optimize_robust(*args), "nsc_posegraph_optimize_robust")
+        args = (X, N, e, Z, om, E, fx, self.params, out["poses"], out["stats"], out["cost_history"], out.get("step0"),
+                ws, int(ws.numel()), _lib.STREAM, self.kernel, c, out.get("chi2"), out.get("weights"))
+        if block:
+            _lib.call("nsc_posegraph_optimize_coarse", dev, *args, block, out["coarse_stats"])
+        else:
+            _lib.call("nsc_posegraph_optimize_robust", dev, *args)
         return out
 
     def _fixed(self, fixed, dev, N):
@@ -361,14 +351,9 @@ class PoseGraphOptimizer:
         L = _lib.lib()
         ws = torch.empty(max(int(L.nsc_posegraph_covariance_workspace_bytes(N, E, Q, block)), 1), dtype=torch.uint8,
                          device=dev)
-        with torch.cuda.device(dev):
-            status = L.nsc_posegraph_covariance(_lib.ptr(X), N, _lib.ptr(e), _lib.ptr(Z), _lib.ptr(om), E, _lib.ptr(fx),
-                                                C.byref(self.params), _lib.ptr(sel), Q, _lib.ptr(out["joint"]),
-                                                _lib.ptr(out["residual"]), _lib.ptr(out["iterations"]),
-                                                _lib.ptr(out["stats"]), _lib.ptr(ws), int(ws.numel()),
-                                                _lib.stream_ptr(dev), self.kernel, _lib.ptr(c), block,
-                                                _lib.ptr(out.get("coarse_stats")))
-        _lib.check(status, "nsc_posegraph_covariance")
+        _lib.call("nsc_posegraph_covariance", dev, X, N, e, Z, om, E, fx, self.params, sel, Q, out["joint"], out["residual"],
+                  out["iterations"], out["stats"], ws, int(ws.numel()), _lib.STREAM, self.kernel, c, block,
+                  out.get("coarse_stats"))
         return out
 
     def covariance(self, poses, edge_ij, measurements, information, nodes, fixed=None, robust_scale=None):

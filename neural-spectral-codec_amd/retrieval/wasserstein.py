@@ -45,10 +45,7 @@ def _grow_rows(bufs, live: int, need: int, first: int = 1024):
 
 def _cdf(h: torch.Tensor, eps: float, divide_plain: bool) -> torch.Tensor:
     out = torch.empty_like(h)
-    with torch.cuda.device(h.device):
-        st = _lib.lib().nsc_w1_cdf(_lib.ptr(h), int(h.shape[0]), int(h.shape[1]), float(eps),
-                                   int(divide_plain), _lib.ptr(out), _lib.stream_ptr(h.device))
-    _lib.check(st, "nsc_w1_cdf")
+    _lib.call("nsc_w1_cdf", h.device, h, int(h.shape[0]), int(h.shape[1]), float(eps), int(divide_plain), out, _lib.STREAM)
     return out
 
 
@@ -56,11 +53,7 @@ def _distances(db: torch.Tensor, qcdf: torch.Tensor, eps: float, db_pos=None, q_
                min_dist: float = 0.0) -> torch.Tensor:
     n, d, q = int(db.shape[0]), int(db.shape[1]), int(qcdf.shape[0])
     dist = torch.empty((q, n), dtype=torch.float32, device=db.device)
-    with torch.cuda.device(db.device):
-        st = _lib.lib().nsc_w1_distances(_lib.ptr(db), n, d, float(eps), _lib.ptr(qcdf), q,
-                                         _lib.ptr(db_pos), _lib.ptr(q_pos), float(min_dist),
-                                         _lib.ptr(dist), _lib.stream_ptr(db.device))
-    _lib.check(st, "nsc_w1_distances")
+    _lib.call("nsc_w1_distances", db.device, db, n, d, float(eps), qcdf, q, db_pos, q_pos, float(min_dist), dist, _lib.STREAM)
     return dist
 
 
@@ -69,11 +62,7 @@ def _distances_cdf(db_cdf: torch.Tensor, qcdf: torch.Tensor, db_pos=None, q_pos=
     """W1 of query CDFs against rows that are already CDFs (nsc_w1_distances_cdf)."""
     n, d, q = int(db_cdf.shape[0]), int(db_cdf.shape[1]), int(qcdf.shape[0])
     dist = torch.empty((q, n), dtype=torch.float32, device=db_cdf.device)
-    with torch.cuda.device(db_cdf.device):
-        st = _lib.lib().nsc_w1_distances_cdf(_lib.ptr(db_cdf), n, d, _lib.ptr(qcdf), q, _lib.ptr(db_pos),
-                                             _lib.ptr(q_pos), float(min_dist), _lib.ptr(dist),
-                                             _lib.stream_ptr(db_cdf.device))
-    _lib.check(st, "nsc_w1_distances_cdf")
+    _lib.call("nsc_w1_distances_cdf", db_cdf.device, db_cdf, n, d, qcdf, q, db_pos, q_pos, float(min_dist), dist, _lib.STREAM)
     return dist
 
 

@@ -135,11 +135,7 @@ def estimate_yaw(query_images, query_ids, candidate_images, candidate_ids):
     shift = torch.empty(P, dtype=torch.int32, device=dev)
     scores = torch.empty((P, 2), dtype=torch.float64, device=dev)
     init = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        status = _lib.lib().nsc_yaw_align(_lib.ptr(qi), n_q, _lib.ptr(ci), n_c,
-                                          _lib.ptr(qid), _lib.ptr(cid), P, R, _lib.ptr(shift), _lib.ptr(scores),
-                                          _lib.ptr(init), _lib.stream_ptr(dev))
-    _lib.check(status, "nsc_yaw_align")
+    _lib.call("nsc_yaw_align", dev, qi, n_q, ci, n_c, qid, cid, P, R, shift, scores, init, _lib.STREAM)
     return dict(shift=shift, peak=scores[:, 0], runner_up=scores[:, 1], init_transforms=init)
 
 

@@ -242,6 +242,44 @@ def test_pipelined_capture_keeps_its_csr_alive():
     _check_window(m, piped, *want[-1])
 
 
+def test_capture_state_key_changes_with_everything_a_capture_bakes_in():
+    """SpectralGNN.capture_state: the key a captured forward is filed under moves with every change after which a replay
+    would no longer compute model(graph), and with nothing else."""
+    m = _model(edge_dim=2)
+    gnn = m.gnn
+    g = gm.synthetic_chain_graph(70, device="cuda", seed=1)
+    other = gm.Data(x=g.x, edge_index=g.edge_index[:, :-4].contiguous(), edge_attr=g.edge_attr[:-4].contiguous(),
+                    num_nodes=70)
+    states = []                                                   # kept: a key holds the id of its GraphCSR
+
+    def forward_checked(graph, kernel_set):
+        _forward_checked(m, graph, (kernel_set,))                 # (leaves coresident False)
+        gnn.coresident = kernel_set
+        try:
+            states.append(gnn.capture_state(graph))
+        finally:
+            gnn.coresident = False
+        assert states[-1].csr is gnn._csr(graph, True) and states[-1].folded is gnn._struct_cache.folded
+        assert gnn._model_struct().folded == states[-1].folded.data_ptr()
+        hash(states[-1].key)
+        return states[-1].key
+
+    keys = [forward_checked(g, False)]
+    assert forward_checked(g, False) == keys[0], "two forwards with nothing in between"
+    with torch.no_grad():
+        gnn.convs[1].att_src.mul_(1.5)                            # an in-place parameter write
+    keys.append(forward_checked(g, False))
+    opt = torch.optim.Adam(m.parameters(), lr=1e-2, fused=True)
+    _seeded_grads(m.parameters(), 3)
+    opt.step()                                                    # a fused step: no version counter need move
+    keys.append(forward_checked(g, False))
+    keys.append(forward_checked(g, True))                         # another kernel set
+    keys.append(forward_checked(other, True))                     # a graph with other edges
+    assert len(set(keys)) == len(keys), "a change a capture bakes in left the key as it was"
+    assert forward_checked(g, True) == keys[3], "back on the first graph: its CSR is cached, nothing else moved"
+    assert forward_checked(g, True) == keys[3]
+
+
 # ---- the CSR cache ---------------------------------------------------------------------------------------------------
 def test_csr_cache_evicts_least_recently_used():
     m = _model()
