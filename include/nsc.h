@@ -616,7 +616,8 @@ int    nsc_planar_align(const NscGicpCloudSet *sources, const NscGicpCloudSet *t
  * j = query.  information (n_edges,6,6), rotation first (the order of nsc_gicp_register's `information`), symmetric
  * positive definite; only the upper triangle is read.  fixed (n_poses) uint8: a pose with fixed != 0 is never changed.
  * An edge with i == j or an index outside [0, n_poses) is skipped: it contributes nothing and is counted.  A pose no
- * counted edge touches, or whose damped diagonal block is not positive definite, is not moved either.
+ * counted edge touches, or whose damped diagonal block is not positive definite (a pivot of its Cholesky factor that is
+ * not positive and finite: NaN and infinite entries count), is not moved either.
  *
  * Residual of an edge.  D = Z^-1 X_i^-1 X_j;  r = [Log_SO3(R_D); t_D];  cost F = sum r^T Omega r.
  *   Log_SO3(R): v = vee(R - R^T) / 2, theta = atan2(|v|, (tr R - 1) / 2), phi = v theta / |v|, and phi = v for
@@ -632,9 +633,9 @@ int    nsc_planar_align(const NscGicpCloudSet *sources, const NscGicpCloudSet *t
  * Solver.  Levenberg-Marquardt with Marquardt scaling.  Per outer iteration, at damping lambda:
  *   (H + lambda diag H) delta = -g over the poses that move, delta = 0 elsewhere, by preconditioned conjugate
  *   gradients from delta = 0.  Preconditioner: the Cholesky factor of each node's 6 x 6 diagonal block of the damped
- *   matrix.  An inner iteration is counted once its step is applied; the loop ends at |r| <= pcg_tolerance |g|, at
- *   max_pcg_iterations, or when p.Ap or r.z is not positive (that iteration applies no step).  No inner iteration
- *   runs for g = 0.
+ *   matrix.  An inner iteration is counted once its p.Ap is formed; the loop ends at |r| <= pcg_tolerance |g|, at
+ *   max_pcg_iterations, or when p.Ap or r.z is not positive (an iteration whose p.Ap is not positive applies no step
+ *   and is counted like any other).  No inner iteration runs for g = 0.
  *   Candidate poses = the update by delta; F_c = their cost; step = |delta| over all poses.
  *   F_c < F: accepted, the candidate replaces the poses, lambda <- max(lambda / lambda_factor, lambda_min), and the
  *     optimiser stops (converged) when F - F_c < relative_cost F.

@@ -494,7 +494,7 @@ __global__ __launch_bounds__(TB) void pg_edge_matvec_kernel(int n_edges, Buffers
 
 // ---- nodes -------------------------------------------------------------------------------------------------------
 
-// U^T U = M (upper triangle in place); false when a pivot is not positive
+// U^T U = M (upper triangle in place); false when a pivot is not positive and finite
 __device__ __forceinline__ bool cholesky6(double U[21])
 {
     bool ok = true;
@@ -503,7 +503,7 @@ __device__ __forceinline__ bool cholesky6(double U[21])
         double d = U[tri(r, r)];
 #pragma unroll
         for (int k = 0; k < r; ++k) d -= U[tri(k, r)] * U[tri(k, r)];
-        ok = ok && d > 0.0;
+        ok = ok && d > 0.0 && isfinite(d);
         d = sqrt(d);
         U[tri(r, r)] = d;
 #pragma unroll

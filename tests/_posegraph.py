@@ -49,31 +49,38 @@ def plain_linearize(X, e, Z, Om):
     return host(out)
 
 
-def abi_optimize(entry, X, e, Z, Om, scale=None, kernel=None, coarse_block=None, **params):
+def abi_optimize(entry, X, e, Z, Om, scale=None, kernel=None, coarse_block=None, fixed=None, ws=None, fill=None,
+                 **params):
     """nsc_posegraph_optimize (no ``kernel``), nsc_posegraph_optimize_robust, or nsc_posegraph_optimize_coarse with
-    ``coarse_block``, pose 0 fixed -> the outputs on the host: poses, stats, cost_history, step0, with a kernel chi2 and
-    weights, with ``coarse_block`` coarse_stats"""
+    ``coarse_block`` -> the outputs on the host: poses, stats, cost_history, step0, with a kernel chi2 and weights, with
+    ``coarse_block`` coarse_stats.  ``fixed``: the mask, pose 0 when None.  ``ws``: the caller's own uint8 workspace
+    tensor on the device, at least as large as the call needs.  ``fill``: a value every output holds before the call."""
     import torch
     from neural_spectral_codec_amd import _lib
     L, ptr = _lib.lib(), _lib.ptr
     prm = optimizer(**params).params
     dev = _device(X, e, Z, Om) if kernel is None else _device(X, e, Z, Om, scale)
     N, E = len(dev[0]), len(dev[1])
-    fixed = torch.from_numpy(first_fixed(N).astype(np.uint8)).cuda()
+    fixed = torch.from_numpy((first_fixed(N) if fixed is None else np.asarray(fixed) != 0).astype(np.uint8)).cuda()
     f64 = dict(dtype=torch.float64, device="cuda")
-    out = dict(poses=torch.empty((N, 4, 4), **f64), stats=torch.empty(_lib.POSEGRAPH_STATS, **f64),
-               cost_history=torch.empty(prm.max_iteration + 1, **f64), step0=torch.empty((N, 6), **f64))
+
+    def new(*shape):
+        return torch.empty(shape, **f64) if fill is None else torch.full(shape, float(fill), **f64)
+    out = dict(poses=new(N, 4, 4), stats=new(_lib.POSEGRAPH_STATS), cost_history=new(prm.max_iteration + 1),
+               step0=new(N, 6))
     need = L.nsc_posegraph_workspace_bytes(N, E, None) if coarse_block is None else \
         L.nsc_posegraph_coarse_workspace_bytes(N, E, coarse_block)
-    ws = torch.empty(max(int(need), 1), dtype=torch.uint8, device="cuda")
+    if ws is None:
+        ws = torch.empty(max(int(need), 1), dtype=torch.uint8, device="cuda")
+    assert ws.dtype == torch.uint8 and ws.is_cuda and ws.is_contiguous() and int(ws.numel()) >= int(need)
     args = (ptr(dev[0]), N, ptr(dev[1]), ptr(dev[2]), ptr(dev[3]), E, ptr(fixed), C.byref(prm), ptr(out["poses"]),
             ptr(out["stats"]), ptr(out["cost_history"]), ptr(out["step0"]), ptr(ws), int(ws.numel()),
             _lib.stream_ptr(ws.device))
     if kernel is not None:
-        out.update(chi2=torch.empty(E, **f64), weights=torch.empty(E, **f64))
+        out.update(chi2=new(E), weights=new(E))
         args += (kernel, ptr(dev[4]), ptr(out["chi2"]), ptr(out["weights"]))
     if coarse_block is not None:
-        out["coarse_stats"] = torch.empty(2, **f64)
+        out["coarse_stats"] = new(2)
         args += (coarse_block, ptr(out["coarse_stats"]))
     _lib.check(getattr(L, entry)(*args), entry)
     return host(out)
