@@ -1047,7 +1047,8 @@ int    nsc_map_build(const void *points, int32_t dtype, int32_t stride_floats, c
  *   + 6 J^T Omega d + n_corr + sum |d|^2 + sum d^T Omega d, reduced in a fixed shape) and finalize (one workgroup per scan:
  *   slabs summed in order, fitness = n_corr / rows, rmse = sqrt(sum |d|^2 / n_corr), Open3D's convergence test on both,
  *   6x6 Cholesky, T <- dT T with dT = [Rz Ry Rx of the three angles | translation]; without correspondences or a
- *   positive-definite system T stays).  1 + 2 (max_iteration + 1) launches and nothing else; a finished scan's later
+ *   positive-definite system T stays: a pivot counts only above 3.9e-9 of its diagonal term, so a scan of one row or of
+ *   collinear rows keeps its pose).  1 + 2 (max_iteration + 1) launches and nothing else; a finished scan's later
  *   rounds are no-ops.
  * Outputs per scan: transforms (4,4), fitness_rmse (2), cost = sum d^T Omega d at the result, corr_iterations (2) int64,
  *   information (6,6) = sum J^T Omega J at the result, rotation first; system0 (n_scans,NSC_MAP_REGISTER_SYSTEM) or

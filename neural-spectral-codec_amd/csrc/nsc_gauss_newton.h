@@ -17,8 +17,19 @@ __device__ void rot_zyx(double a, double b, double g, double R[3][3])
     R[2][0] = -sb;     R[2][1] = cb * sa;                R[2][2] = cb * ca;
 }
 
+// A pivot d_j of the factorisation below counts as positive only above GN_PIVOT_TAU times H[j][j], the original diagonal
+// term.  For a rank-deficient H (one or two source rows, collinear rows: a rotation the data says nothing about) d_j is
+// zero in exact arithmetic and rounding alone decides d_j > 0.  Measured in float64 in this pivot order
+// (tests/test_registration_degenerate_cpu.py, test_thresholds, which measures again and asserts both margins):
+//   (a) 4.7e-12  the largest |d_j| / H[j][j] at the rejecting or last pivot over the systems that are singular by
+//                construction (tests/registration_degenerate_cases.py) and the singular ones of many_small
+//   (b) 3.2e-6   the smallest d_j / H[j][j] over every regular system the suite has, at every round (a 40-row line and
+//                one row 0.1 m off it)
+// and GN_PIVOT_TAU is their geometric mean: (a) < tau / 100, (b) > 100 tau.
+constexpr double GN_PIVOT_TAU = 3.9e-9;
+
 // H x = -g by Cholesky, H the 21 upper-triangle terms sys[0..20] (row by row) and g = sys[21..26]; false, and x
-// untouched, without a positive-definite H
+// untouched, without an H that is positive definite by the pivot test above
 __device__ bool gn_solve6(const double *sys, double x[6])
 {
     double L[6][6];
@@ -28,9 +39,10 @@ __device__ bool gn_solve6(const double *sys, double x[6])
             for (int b = a; b < 6; ++b) { L[b][a] = sys[t]; ++t; }         // lower triangle of the symmetric H
     }
     for (int j = 0; j < 6; ++j) {
-        double dj = L[j][j];
+        const double hjj = L[j][j];                                       // still H[j][j]
+        double dj = hjj;
         for (int k = 0; k < j; ++k) dj -= L[j][k] * L[j][k];
-        if (!(dj > 0.0) || !isfinite(dj)) return false;
+        if (!(dj > GN_PIVOT_TAU * hjj) || !isfinite(dj)) return false;
         L[j][j] = sqrt(dj);
         for (int i = j + 1; i < 6; ++i) {
             double v = L[i][j];

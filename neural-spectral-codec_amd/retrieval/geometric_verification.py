@@ -22,7 +22,9 @@ used and rows with a non-finite coordinate are dropped.
 4. Gauss-Newton update from the correspondences of the current T: ``s' = T s``, ``d = s' - t``,
    ``M = C_t + R C_s R^T``, ``W = M^-1``, ``J = [-[s']x | I]``; solve ``(sum J^T W J) x = -sum J^T W d`` by
    Cholesky in float64; ``x = (alpha, beta, gamma, tx, ty, tz)`` gives dT with ``R = Rz(gamma) Ry(beta) Rx(alpha)``
-   and ``T <- dT T``.  Without correspondences, or when the system is not positive definite, dT = I.
+   and ``T <- dT T``.  Without correspondences, or when the system is not positive definite, dT = I: a pivot counts
+   only above 3.9e-9 of its diagonal term (csrc/nsc_gauss_newton.h), so one or two source rows, or collinear ones,
+   whose system is singular whatever the weights are, leave T as it is.
 5. Loop (Open3D ``RegistrationICP``): evaluate T0; up to ``max_iteration`` times update, then evaluate; stop when
    ``|d fitness| < relative_fitness`` and ``|d rmse| < relative_rmse``.  The last T and its evaluation are returned;
    ``iterations`` counts the updates applied.

@@ -6,6 +6,8 @@ csrc/nsc_geometry.hip documents; nothing here calls the library."""
 import numpy as np
 from scipy.spatial import cKDTree
 
+import gauss_newton_restatement as GN
+
 DEFAULTS = dict(voxel_size=0.5, max_correspondence_distance=1.0, max_iteration=30, relative_fitness=1e-6,
                 relative_rmse=1e-6, covariance_knn=20, epsilon=1e-3)
 
@@ -236,14 +238,10 @@ def register(source, target, init=None, exact=False, **params):
     lin = linearize(src, tgt, Cs, Ct, T, radius)
     it = 0
     for it in range(1, P["max_iteration"] + 1):
-        ok = lin["n_corr"] > 0
         x = np.zeros(6)
-        if ok:
-            try:
-                L = np.linalg.cholesky(lin["H"])
-                x = np.linalg.solve(L.T, np.linalg.solve(L, -lin["g"]))
-            except np.linalg.LinAlgError:
-                x = np.zeros(6)
+        if lin["n_corr"] > 0 and GN.regular(lin["H"]):           # no step on a singular system: the written rule
+            L = np.linalg.cholesky(lin["H"])
+            x = np.linalg.solve(L.T, np.linalg.solve(L, -lin["g"]))
         T = delta_transform(x) @ T
         prev = lin
         lin = linearize(src, tgt, Cs, Ct, T, radius)

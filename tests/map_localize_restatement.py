@@ -9,6 +9,7 @@ from fractions import Fraction
 
 import numpy as np
 
+import gauss_newton_restatement as GN
 import map_restatement as M
 
 Q = 1 << 16
@@ -181,9 +182,7 @@ def register_one(m, points, T0, max_iteration=30, relative_fitness=1e-6, relativ
         prev = (fitness, rmse)
         if nc > 0:
             H = full(s)
-            try:
-                np.linalg.cholesky(H)
-            except np.linalg.LinAlgError:
+            if not GN.regular(H):                                 # no step on a singular system: the written rule
                 continue
             T = update(np.linalg.solve(H, -s[21:27])) @ T
 

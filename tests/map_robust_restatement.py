@@ -6,6 +6,7 @@ With ``kernel=None`` and ``neighbours=1`` every array handed to numpy is the one
 the results are equal exactly."""
 import numpy as np
 
+import gauss_newton_restatement as GN
 import map_localize_restatement as R
 import map_restatement as M
 
@@ -130,9 +131,7 @@ def register_one(m, points, T0, kernel=None, scale=None, neighbours=1, max_itera
         prev = (fitness, rmse)
         if nc > 0:
             H = R.full(s)
-            try:
-                np.linalg.cholesky(H)
-            except np.linalg.LinAlgError:
+            if not GN.regular(H):                                 # no step on a singular system: the written rule
                 continue
             T = R.update(np.linalg.solve(H, -s[21:27])) @ T
 

@@ -312,7 +312,9 @@ def test_edges_in_one_batch(scene_map):
             assert out[k][i].tobytes() == alone[k][j].tobytes(), (i, k)
     assert out["n_correspondences"][1] == 0 and out["fitness"][1] == 0 and out["rmse"][1] == 0
     assert np.array_equal(out["transform"][1], init[1]) and not out["information"][1].any()
-    assert out["n_correspondences"][2] in (0, 1)
+    one = R.lookup(K.scene_reference()["map"], b[:1], init[2])[1]       # its voxel is usable, 0.14 voxels from a face
+    assert out["n_correspondences"][2] == int((one >= 0).sum()) == 1
+    assert np.array_equal(out["transform"][2], init[2]) and out["iterations"][2] == 1    # rank 3: no step
     assert out["n_correspondences"][3] == 0 and np.array_equal(out["transform"][3], init[3]) and out["cost"][3] == 0
     assert out["n_correspondences"][4] == -1 and out["iterations"][4] == 0
     for k in ("transform", "fitness", "rmse", "cost", "information", "system0"):

@@ -238,7 +238,9 @@ def test_edges_in_one_batch(scene_map):
         assert out["n_correspondences"][i] == 0 and out["n_pairs"][i] == 0 and out["weight_sum"][i] == 0
         assert out["fitness"][i] == 0 and out["rmse"][i] == 0 and out["cost"][i] == 0
         assert np.array_equal(out["transform"][i], init[i]) and not out["information"][i].any()
-    assert out["n_correspondences"][2] in (0, 1) and out["n_pairs"][2] <= 7
+    one = RR.linearize(K.scene_reference()["map"], b[:1], init[2], "cauchy", 3.0, 7)     # 0.14 voxels from a face
+    assert out["n_correspondences"][2] == one[27] == 1 and out["n_pairs"][2] == one[31] == 5
+    assert np.array_equal(out["transform"][2], init[2]) and out["iterations"][2] == 1    # rank 3: no step
     assert out["n_correspondences"][4] == -1 and out["n_pairs"][4] == -1 and out["iterations"][4] == 0
     for k in ("transform", "fitness", "rmse", "cost", "information", "system0", "weight_sum"):
         assert np.isnan(out[k][4]).all(), k
