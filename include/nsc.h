@@ -219,7 +219,24 @@ size_t nsc_gat_workspace_bytes(const NscGatModel *m, int32_t n_nodes);
  *   edge_attr  (E, edge_dim) float32 indexed by g->eid, or NULL (then the edge term is skipped,
  *              as model.py:126-129 does when data has no edge_attr)
  *   out        (n_nodes, out_dim) float32
- *   alpha_out  nullable (n_layers, nnz) attention coefficients (forward_with_attention) */
+ *   alpha_out  nullable (n_layers, nnz) attention coefficients (forward_with_attention)
+ * Inputs that are not finite go where the reference's arithmetic takes them: every ReLU of the path keeps a NaN
+ * (torch.relu; fmaxf would turn it into 0 and the row into one that looks real).
+ *   A row of x with a NaN entry makes EVERY output column of EVERY node within n_layers hops of it NaN.  Hops follow the
+ *   edge direction (source -> target); the node itself is in the ball (its own loop), a node without edges is its own
+ *   ball.  Layer l's attention coefficients are NaN for every entry of a target within l + 1 hops (one NaN logit makes the
+ *   target's whole softmax NaN: the maxima drop a NaN, expf(NaN - max) brings it back).  The rows of all other nodes, and
+ *   the coefficients of all other targets, are the bits of the same call without that entry, in every kernel set.
+ *   A +-inf entry does the same: the input projection makes the row +-inf in every column whose weight for that entry is
+ *   not zero, the ReLU keeps the +inf and zeroes the -inf, and the first lin GEMM adds +inf and -inf to NaN.  (Only a row
+ *   that reaches a ReLU as -inf in every column comes out as zeros, as in the reference; a weight row of one sign does that.)
+ *   A NaN in edge_attr is a NaN logit of the edge's target in every layer (its own loop carries the mean of the incoming
+ *   attributes as well): that target's coefficients are NaN from layer 0 on and the output is NaN within n_layers - 1 hops
+ *   of the target.  An infinite attribute makes the logit +-inf, layer by layer by the sign of the attribute's folded
+ *   weight v = W_edge^T att_edge: a logit of +inf is NaN coefficients as above (expf(inf - inf)), a logit of -inf is a
+ *   weight of exactly 0 in that layer and no NaN.
+ *   The poisoned row itself is NaN also without any layer, through the residual (x or residual_proj(x)).
+ * tests/gnn_edge_cases.py holds the cases, tests/test_gnn_edges_gpu.py runs them in every kernel set. */
 int nsc_gat_forward(const NscGatModel *m, const NscGraph *g, const float *x, const float *edge_attr,
                     float *out, float *alpha_out, void *ws, size_t ws_bytes, void *stream);
 /* Same forward with launch options.  NSC_GAT_CORESIDENT: every kernel uses 0 bytes of LDS and <= 56 VGPRs, so two waves
@@ -281,7 +298,12 @@ int    nsc_graph_transpose(const NscGraph *g, int32_t *t_ptr, int32_t *t_entry, 
                            size_t ws_bytes, void *stream);
 
 /* The workspace holds the activations the forward saves for the backward: pass the SAME buffer (and
- * cfg) to nsc_gat_backward.  residual && in_dim != out_dim trains residual_proj (m->res_w / res_b). */
+ * cfg) to nsc_gat_backward.  residual && in_dim != out_dim trains residual_proj (m->res_w / res_b).
+ * Inputs that are not finite (see nsc_gat_forward): in train mode the batch statistics of the first BatchNorm behind the
+ * poisoned value are NaN, so EVERY row of out is NaN, nsc_triplet_loss over it is NaN (relu keeps a NaN), the running
+ * statistics updated in place take the NaN as nn.BatchNorm1d's would, and the backward passes NaN gradients on (the ReLU's
+ * derivative passes the gradient where its input is NaN, as torch's does).  Nothing stays in the workspace: the next call
+ * with finite inputs writes everything it reads. */
 size_t nsc_gat_train_workspace_bytes(const NscGatModel *m, const NscGraph *g);
 int    nsc_gat_forward_train(const NscGatModel *m, const NscGraph *g, const float *x, const float *edge_attr,
                              const NscGatTrainCfg *cfg, float *out, void *ws, size_t ws_bytes, void *stream);

@@ -742,7 +742,7 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(AggArgs a)
                 const float sc = bn_scale(ep_var[c][t], a.bn_eps, ep_w[c][t]);
                 v = v * sc + bn_shift(ep_b[c][t], ep_mean[c][t], sc);
             }
-            if (a.relu) v = fmaxf(v, 0.0f);
+            if (a.relu) v = relu_nan(v);
             if (a.resid) v += ep_res[c][t];
             o[t] = v;
         }

@@ -32,7 +32,7 @@
 // d = 0..3, t = 0..3, operand element t of lane (r, q) = k 64 c + 16 d + 4 q + t), a_src / a_dst the same chain as fmas; the
 // softmax reduces with the same xor butterfly (a 16-lane group here, the 64-lane wave there: with at most 16 entries the
 // upper levels of the 64-lane butterfly only add zeros); the aggregation is the same fma chain in CSR entry order; the
-// epilogue is the same functions (bn_fold, bn_apply, layer_act of nsc_gat_epilogue.h).  tests/test_gat_gpu.py compares the sets bit for bit.
+// epilogue is the same functions (bn_fold, bn_apply, relu_nan of nsc_gat_epilogue.h).  tests/test_gat_gpu.py compares the sets bit for bit.
 //
 // The graph comes as banded entries (nsc_graph_band_entries, built once per graph next to the CSR): 8 slots of 16 bytes per
 // target {source node, edge_attr[0], edge_attr[1], CSR entry index (-1 = empty slot)} in CSR order (self loop last, its
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(640) void gat_layer_banded_kernel(BandArgs a, const
         for (int t = 0; t < 4; ++t) {
             float v = o[t] + bnbi[t];
             if (a.bn_w) v = bn_apply(v, bnsc[t], bnsh[t]);
-            if (a.relu) v = fmaxf(v, 0.0f);
+            if (a.relu) v = relu_nan(v);
             if (a.resid) v += rs[pass][t];
             o[t] = v;
         }

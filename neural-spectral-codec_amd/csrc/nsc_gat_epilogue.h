@@ -47,11 +47,18 @@ __device__ __forceinline__ void bn_fold(const float *var, float eps, const float
 // BatchNorm(eval) applied: the folded scale and shift on a value that already has its bias
 __device__ __forceinline__ float bn_apply(float v, float scale, float shift) { return v * scale + shift; }
 
+// ReLU as torch.relu computes it: a NaN stays a NaN.  fmaxf(NaN, 0) is 0, and a poisoned row came out as a row of zeros that
+// every later stage took for real (include/nsc.h, nsc_gat_forward).  For every other value this is what fmaxf(v, 0.0f)
+// returns, except -0, which stays -0 where fmaxf gives +0 (the value is added to sums and multiplied from here on: nothing
+// downstream tells the two apart).  A compare and a select, straight-line: every ReLU of the GNN path -- inference and
+// training, all kernel sets -- is this expression.
+__device__ __forceinline__ float relu_nan(float v) { return v < 0.0f ? 0.0f : v; }
+
 // a projection's value ahead of its residual
 template <int EPI> __device__ __forceinline__ float epi_value(float v, float bias, float scale, float shift)
 {
     if (EPI != 0) v = v + bias;
-    if (EPI == 1) v = fmaxf(bn_apply(v, scale, shift), 0.0f);
+    if (EPI == 1) v = relu_nan(bn_apply(v, scale, shift));
     return v;
 }
 

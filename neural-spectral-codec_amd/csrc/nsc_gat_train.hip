@@ -598,7 +598,7 @@ __global__ __launch_bounds__(256) void bn_bwd_colsum_kernel(const float *__restr
             float g = dhv * keep_scale(p, sd, stream, (unsigned long long)i);
             if (relu) {
                 const float v = (zv - m) * s * ga + be;
-                if (!(v > 0.0f)) g = 0.0f;
+                if (v <= 0.0f) g = 0.0f;                  // relu_nan's derivative: a NaN input passes the gradient, as torch's does
             }
             dv[i] = g;
             a += (double)g;
@@ -692,7 +692,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const float *__restrict__ z
         const float zv = r.x, rv = r.y;
         const long long i = (long long)n * C + c;
         float v = (zv - m) * s * ga + be;
-        if (relu) v = fmaxf(v, 0.0f);
+        if (relu) v = relu_nan(v);
         v *= keep_scale(p, sd, stream, (unsigned long long)i);
         if (resid) v += rv;
         out[i] = v;
@@ -1275,8 +1275,8 @@ __global__ __launch_bounds__(256) void triplet_kernel(const float *__restrict__ 
     }
     dp = nsc_wave_sum(dp); dn = nsc_wave_sum(dn);
     const float l = dp - dn + margin;
-    if (lane == 0) per_triplet[t] = l > 0.0f ? l : 0.0f;
-    if (grad && l > 0.0f) {
+    if (lane == 0) per_triplet[t] = relu_nan(l);              // NaN embeddings are a NaN loss (torch.relu), not a loss of 0
+    if (grad && !(l <= 0.0f)) {
         const float g = 2.0f * scale / (float)T;              // d(mean relu)/d(dist) * 2(a - .)
         float *ga = grad + a_i * D, *gp = grad + p_i * D, *gn = grad + n_i * D;
         for (int c = lane; c < D; c += 64) {

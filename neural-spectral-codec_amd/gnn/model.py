@@ -471,6 +471,7 @@ class SpectralGNN(nn.Module):
         n_kept = int(keep.sum().item())
         tgt = torch.repeat_interleave(torch.arange(csr.n_nodes, device=ei.device),
                                       (csr.row_ptr[1:] - csr.row_ptr[:-1]).long())
+        rank = torch.cat([rank, rank.new_zeros(1)])                         # a graph without edges: every entry is a loop (eid -1)
         pos = torch.where(eid >= 0, rank[eid.clamp(min=0)], n_kept + tgt)
         loops = torch.arange(csr.n_nodes, device=ei.device)
         ei_full = torch.cat([ei[:, keep], torch.stack([loops, loops])], 1)
