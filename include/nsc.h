@@ -550,8 +550,10 @@ int    nsc_gicp_register_prepared(const NscGicpCloudSet *sources, const NscGicpC
  * Pair i aligns image ids_q[i] of images_q (n_q, rows, 360) with image ids_c[i] of images_c (n_c, rows, 360); the
  * two arrays may be one.  Out: shift (n_pairs) int32, scores (n_pairs, 2) float64 = [peak, runner_up],
  * init_transforms (n_pairs, 4, 4) float64 row-major.  A pair with an id outside its array gets shift -1, NaN scores
- * and the identity; nothing of the images is read for it.  One kernel launch and nothing else, no workspace; a
- * pair's outputs depend on its two images alone.
+ * and the identity; nothing of the images is read for it.  A pair in which either image holds a NaN or +-inf pixel
+ * in its rows has NaN row means and so 360 NaN scores: it gets shift 0, the identity bit for bit, peak NaN and
+ * runner_up NaN (shift 0, not -1: the ids were valid).  Finite images, denormal or up to FLT_MAX, have finite
+ * scores.  One kernel launch and nothing else, no workspace; a pair's outputs depend on its two images alone.
  * A launch holds at most 2^32 - 1 threads, 768 per pair: more than NSC_YAW_MAX_PAIRS pairs return
  * NSC_EUNSUPPORTED before anything is launched and the caller splits the batch.
  * ------------------------------------------------------------------------------------------ */

@@ -9,6 +9,10 @@
 //   shift    = arg max score, ties to the smaller s; 0 when that score is not > 0 (flat or empty images)
 //   peak     = score[shift];  runner_up = max score over shifts more than NSC_YAW_GUARD_BINS bins from shift
 //   init     = Rz(-shift degrees wrapped to (-180, 180]); exactly the identity for shift 0
+// Images that are not finite: one NaN or +-inf pixel among the R rows of either image makes its row mean, and with it
+// every one of the 360 scores, NaN (finite float32 images cannot overflow float64: |score| < 64 * 360 * 2^258).  Such
+// a pair gets shift 0, the identity bit for bit, peak NaN and runner_up NaN.  It stays distinct from a pair with an id
+// outside its array, which gets shift -1 (and the identity and NaN scores) without an image read.
 //
 // One launch, one workgroup of 12 waves per pair, no workspace:
 //   rows are taken in chunks of 16.  Per chunk: row means (one wave per row, lane-strided float64 sums and a
@@ -173,9 +177,10 @@ __global__ __launch_bounds__(YAW_THREADS) void yaw_align_kernel(const float *__r
         init[lane] = v;
     }
     if (lane == 0) {
+        const double peak = score[shift];
         shift_out[pair] = shift;
-        scores_out[2 * pair] = score[shift];
-        scores_out[2 * pair + 1] = runner;
+        scores_out[2 * pair] = peak;
+        scores_out[2 * pair + 1] = peak != peak ? peak : runner;        // all scores NaN: no comparison above held
     }
 }
 

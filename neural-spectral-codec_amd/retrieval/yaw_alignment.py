@@ -18,6 +18,13 @@ Definition (the contract nsc_yaw_align and tests/yaw_restatement.py share), all 
     init     = Rz(yaw) as a (4,4) float64 matrix with zero translation: query into candidate coordinates;
                exactly the identity for shift 0
 
+Images that are not finite.  One NaN or +-inf pixel among the R rows of either image makes its row mean, and with it
+every one of the 360 scores, NaN.  Such a pair gets shift 0, the identity bit for bit, peak NaN and runner_up NaN,
+so stage 2 starts it where it would start without a guess; ``yaw_info`` reports ``init_yaw_deg`` 0.0 and a NaN
+``yaw_peak_ratio`` for it.  It stays distinct from a pair with an id outside its images, which gets shift -1 (and the
+identity and NaN scores).  Finite float32 images, denormal or as large as 3.4e38, cannot overflow or underflow the
+float64 sums: their scores are finite.
+
 A candidate sensor yawed by +theta against the query gives ``shift ~ theta`` (mod 360).  The guess carries no
 translation and no roll or pitch: a revisit offset by more than GICP's correspondence radius still needs odometry.
 """
@@ -107,7 +114,8 @@ def estimate_yaw(query_images, query_ids, candidate_images, candidate_ids):
     sequences.  Returns a dict of device tensors: shift (P,) int32, peak, runner_up (P,) float64 and
     init_transforms (P,4,4) float64 (query into candidate coordinates), as defined in the module docstring.
     Nothing is synchronised or allocated outside torch's allocator, so a call with device ids can be captured.  A
-    pair with an id outside its images gets shift -1, NaN peak and runner_up and the identity.  More than
+    pair with an id outside its images gets shift -1, NaN peak and runner_up and the identity; a pair with a NaN or
+    +-inf pixel in either image gets shift 0, NaN peak and runner_up and the identity.  More than
     MAX_PAIRS_PER_CALL pairs go to the library in several calls, with the same results."""
     qi = query_images.images if isinstance(query_images, YawImages) else query_images
     ci = candidate_images.images if isinstance(candidate_images, YawImages) else candidate_images
@@ -142,8 +150,13 @@ def estimate_yaw(query_images, query_ids, candidate_images, candidate_ids):
 def yaw_info(shift: int, peak: float, runner_up: float) -> dict:
     """Host values of one pair -> the keys stage 2 adds to a candidate's info: ``init_yaw_deg`` (-shift wrapped to
     (-180, 180]; NaN for an invalid pair) and ``yaw_peak_ratio`` (peak / runner_up, inf when runner_up <= 0): a
-    ratio near 1 marks an ambiguous pair."""
+    ratio near 1 marks an ambiguous pair.  A NaN peak (an image that is not finite, or an invalid id) gives a NaN
+    ratio whatever runner_up is: such a pair says nothing about ambiguity."""
     shift = int(shift)
+    peak, runner_up = float(peak), float(runner_up)
     deg = float("nan") if shift < 0 else float(-shift if shift < 180 else 360 - shift)
-    ratio = float(peak) / float(runner_up) if runner_up > 0 else float("inf")
+    if peak != peak:
+        ratio = float("nan")
+    else:
+        ratio = peak / runner_up if runner_up > 0 else float("inf")
     return dict(init_yaw_deg=deg, yaw_peak_ratio=ratio)

@@ -1,6 +1,8 @@
 """The yaw initial guess without a GPU: the float64 restatement (tests/yaw_restatement.py) on the oracle's range images
 of ray-cast revisits finds the yaw to 3 degrees, the restatement's GICP converges from that guess and, from the
-identity, ends 90 degrees wrong with a passing fitness; nsc_yaw_align validates its arguments on the host."""
+identity, ends 90 degrees wrong with a passing fitness; every claim of the constructed cases (tests/yaw_cases.py: exact
+ties, scalings, images that are not finite) holds on the restatement and on an int64 reference; yaw_info's contract;
+nsc_yaw_align validates its arguments on the host."""
 import ctypes as C
 
 import numpy as np
@@ -8,6 +10,7 @@ import pytest
 
 import gicp_restatement as G
 import nsc_oracle
+import yaw_cases as YC
 import yaw_restatement as Y
 from neural_spectral_codec_amd import synth
 from test_gicp_cpu import R_BAR, REVISITS, T_BAR, revisit
@@ -94,6 +97,132 @@ def test_identity_start_verifies_a_wrong_transform(rotated):
     print("fitness", out["fitness"], "rmse", out["rmse"], "rotation error deg", np.rad2deg(re))
     assert out["fitness"] >= 0.3 and out["rmse"] <= 0.5
     assert np.rad2deg(re) > 45.0
+
+
+# ------------------------------------------------------------------------------------------------
+# the constructed cases of yaw_cases.py: every claim, on the int64 reference and on the restatement
+# ------------------------------------------------------------------------------------------------
+IDENTITY = np.eye(4).tobytes()
+
+
+def test_case_family_is_the_one_described():
+    deltas, scaled, per = YC.delta_cases(), YC.scaled_delta_cases(), YC.periodic_cases()
+    assert len(YC.ROWS) == 11 and len(YC.TIE_PAIRS) == 9
+    assert len(deltas) == 11 * 10 and len(scaled) == 2 * 11 * 9 and len(per) == 3
+    assert len({c.name for c in YC.exact_cases()}) == len(YC.exact_cases())
+    assert sorted(YC.by_rows(YC.exact_cases())) == [1, 15, 16, 17, 31, 33, 48, 49, 63, 64]
+    for c in YC.exact_cases():
+        assert c.Iq.dtype == c.Ic.dtype == np.float32 and c.Iq.shape == c.Ic.shape == (c.rows, 360)
+        assert np.isfinite(c.Iq).all() and np.isfinite(c.Ic).all()
+    # the rows: the informative one is the last of a chunk, the first of the next, or closes a partial group
+    assert {(R, r0) for R, r0 in YC.ROWS if r0 % 16 == 15} == {(16, 15), (49, 47), (64, 63), (48, 47)}
+    assert {(R, r0) for R, r0 in YC.ROWS if r0 % 16 == 0} == {(1, 0), (17, 16), (33, 32), (64, 48)}
+    assert {(R, r0) for R, r0 in YC.ROWS if R % 16 == 15} == {(15, 14), (31, 30), (63, 62)}
+    # the scales: a float32 denormal and a large value, both exact
+    tiny, huge = np.float32(360.0) * np.float32(2.0 ** -140), np.float32(360.0) * np.float32(2.0 ** 100)
+    assert 0 < tiny < np.finfo(np.float32).tiny and float(tiny) == 360.0 * 2.0 ** -140
+    assert float(huge) == 360.0 * 2.0 ** 100
+
+
+@pytest.mark.parametrize("R", sorted(YC.by_rows(YC.delta_cases())))
+def test_delta_ties_on_reference_and_restatement(R):
+    for c in YC.by_rows(YC.delta_cases())[R]:
+        ref = YC.int_align(c.Iq, c.Ic)
+        sc = ref["scores"]
+        lo, hi = c.ties
+        assert ref["ties"] == c.ties and lo < hi, c.name
+        assert sc[lo] == sc[hi] == YC.DELTA_PEAK and np.all(np.delete(sc, [lo, hi]) == YC.DELTA_FLOOR), c.name
+        assert (ref["shift"], ref["peak"], ref["runner_up"]) == (c.shift, c.peak, c.runner_up) and c.shift == lo, c.name
+        near = min(hi - lo, 360 - (hi - lo)) <= Y.GUARD_BINS
+        assert c.runner_up == (YC.DELTA_FLOOR if near else c.peak), c.name
+        r = Y.align(c.Iq, c.Ic)
+        assert np.array_equal(r["scores"], sc), c.name        # float64 against int64: exact
+        assert (r["shift"], r["peak"], r["runner_up"], r["second"]) == (c.shift, c.peak, c.runner_up, c.peak), c.name
+        e = YC.expected(c)
+        assert r["init"].tobytes() == e["init_transforms"].tobytes() == Y.init_transform(c.shift).tobytes(), c.name
+        assert (int(e["shift"]), float(e["peak"]), float(e["runner_up"])) == (c.shift, c.peak, c.runner_up), c.name
+    # which of the pairs lie inside the guard
+    inside = {p for p in YC.TIE_PAIRS if YC.delta(16, 15, *p).runner_up == YC.DELTA_FLOOR}
+    assert inside == set(YC.TIE_PAIRS) - {(100, 300), (0, 64)}
+
+
+def test_delta_column_order_is_one_image():
+    a, b = YC.delta(17, 16, 0, 359), YC.delta(17, 16, 359, 0)
+    assert a.Ic.tobytes() == b.Ic.tobytes() and a[3:7] == b[3:7] and a.ties == (0, 359) and a.shift == 0
+
+
+def test_periodic_ties_on_reference_and_restatement():
+    for c, n in zip(YC.periodic_cases(), (3, 4, 72)):
+        ref = YC.int_align(c.Iq, c.Ic)
+        assert ref["ties"] == c.ties and len(c.ties) == n and c.ties[0] == 47 % (360 // n), c.name
+        assert (ref["shift"], ref["peak"], ref["runner_up"]) == (c.shift, c.peak, c.runner_up), c.name
+        assert c.shift == c.ties[0] and c.runner_up == c.peak > 0, c.name
+        r = Y.align(c.Iq, c.Ic)
+        assert np.array_equal(r["scores"], ref["scores"]), c.name
+        assert (r["shift"], r["peak"], r["runner_up"], r["second"]) == (c.shift, c.peak, c.peak, c.peak), c.name
+    p120, _, p5 = YC.periodic_cases()
+    assert p120.ties == (47, 167, 287)
+    d = YC.circular_distance(np.array(p5.ties), p5.shift)      # period 5: ties inside and outside the guard at once
+    assert p5.shift == 2 and (d[1:] <= Y.GUARD_BINS).any() and (d > Y.GUARD_BINS).any()
+
+
+@pytest.mark.parametrize("R", sorted(YC.by_rows(YC.scaled_delta_cases())))
+def test_scaling_is_exact_on_the_restatement(R):
+    base = {c.name: c for c in YC.delta_cases()}
+    for c in YC.by_rows(YC.scaled_delta_cases())[R]:
+        b, k = base[c.base], 2.0 ** c.scale_log2
+        assert c.scale_log2 in YC.SCALES and np.array_equal(c.Iq.astype(np.float64), b.Iq.astype(np.float64) * k), c.name
+        assert np.array_equal(c.Ic.astype(np.float64), b.Ic.astype(np.float64) * k), c.name
+        assert (c.shift, c.ties) == (b.shift, b.ties) and c.peak == b.peak * k * k > 0, c.name
+        assert c.runner_up == b.runner_up * k * k and np.isfinite(c.peak), c.name
+        r = Y.align(c.Iq, c.Ic)
+        e = YC.expected(c)
+        assert np.array_equal(r["scores"], e["scores"]), c.name
+        assert np.array_equal(e["scores"], YC.int_align(b.Iq, b.Ic)["scores"].astype(np.float64) * k * k), c.name
+        assert (r["shift"], r["peak"], r["runner_up"]) == (c.shift, c.peak, c.runner_up), c.name
+        assert (int(e["shift"]), float(e["peak"]), float(e["runner_up"])) == (c.shift, c.peak, c.runner_up), c.name
+    assert YC.DELTA_PEAK * 2.0 ** -280 > np.finfo(np.float64).tiny and YC.DELTA_PEAK * 2.0 ** 200 < 1e300
+
+
+def test_finite_maximum_on_the_restatement():
+    Iq, Ic, planted = YC.finite_maximum()
+    assert Iq.shape == (2, 360) and np.all(np.abs(Iq) == np.float32(3.4e38)) and np.isfinite(Iq).all()
+    r = Y.align(Iq, Ic)
+    assert np.isfinite(r["scores"]).all() and r["shift"] == planted == 2
+    assert 8.2e79 < r["peak"] < 8.4e79
+    assert_margin(r)
+
+
+@pytest.mark.parametrize("R", [1, 16, 17])
+def test_nonfinite_images_on_the_restatement(R):
+    pairs = YC.nonfinite_pairs(R)
+    assert len(pairs) == 3 * len(YC.NONFINITE) * (1 if R == 1 else 2)
+    for name, Iq, Ic in pairs:
+        bad_q, bad_c = ~np.isfinite(Iq), ~np.isfinite(Ic)
+        assert 1 <= bad_q.sum() + bad_c.sum() <= 4 and ("both" in name) == (bad_q.any() and bad_c.any()), name
+        rows = set(np.flatnonzero(bad_q.any(1))) | set(np.flatnonzero(bad_c.any(1)))
+        assert len(rows) == 1 and rows <= {0, R - 1}, name
+        with np.errstate(invalid="ignore"):
+            r = Y.align(Iq, Ic)
+        assert np.isnan(r["scores"]).all(), name             # one pixel: every one of the 360 scores
+        assert r["shift"] == 0 and np.isnan(r["peak"]) and np.isnan(r["runner_up"]), name
+        assert r["init"].tobytes() == IDENTITY and r["yaw_deg"] == 0.0, name
+
+
+def test_yaw_info_contract():
+    from neural_spectral_codec_amd.retrieval.yaw_alignment import yaw_info
+    nan, inf = float("nan"), float("inf")
+    assert yaw_info(350, 6.0, 4.0) == dict(init_yaw_deg=10.0, yaw_peak_ratio=1.5)           # finite peak and runner_up
+    assert yaw_info(90, 6.0, 0.0) == dict(init_yaw_deg=-90.0, yaw_peak_ratio=inf)           # runner_up <= 0
+    assert yaw_info(3, 128880.0, -720.0) == dict(init_yaw_deg=-3.0, yaw_peak_ratio=inf)
+    for shift, runner_up, deg in ((0, nan, 0.0),            # an image that is not finite
+                                  (0, -inf, 0.0),           # a NaN peak decides, whatever runner_up is
+                                  (-1, nan, nan)):          # an invalid id
+        info = yaw_info(shift, nan, runner_up)
+        assert set(info) == {"init_yaw_deg", "yaw_peak_ratio"} and np.isnan(info["yaw_peak_ratio"]), (shift, runner_up)
+        assert info["init_yaw_deg"] == deg or (np.isnan(deg) and np.isnan(info["init_yaw_deg"])), (shift, runner_up)
+    info = yaw_info(np.float64(180.0), np.float64(2.0), np.float64(1.0))                    # numpy scalars, as stage 2 passes
+    assert info == dict(init_yaw_deg=180.0, yaw_peak_ratio=2.0)
 
 
 @pytest.fixture(scope="module")

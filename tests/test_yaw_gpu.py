@@ -1,6 +1,8 @@
 """The yaw initial guess on the MI355X: nsc_yaw_align (estimate_yaw) against the float64 restatement
 (tests/yaw_restatement.py) on encoder images, random images and planted shifts; flat images, invalid ids, batch limits,
-determinism, hipGraph capture together with the registration; and the loop-closing paths that use the guess."""
+determinism, hipGraph capture together with the registration; the constructed cases of tests/yaw_cases.py (exact ties,
+chunk edges, denormal and very large pixels: bit for bit against an int64 reference; images that are not finite); and
+the loop-closing paths that use the guess."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -8,6 +10,7 @@ import pytest
 import torch
 
 import gicp_restatement as G
+import yaw_cases as C
 import yaw_restatement as Y
 from neural_spectral_codec_amd import synth
 from test_gicp_cpu import R_BAR, REVISITS, T_BAR, revisit
@@ -92,7 +95,7 @@ def test_encoder_images_match_restatement(encoder, rotated, revisits):
         assert abs(Y.wrap_deg(r["yaw_deg"] + o[2])) <= YAW_BAR_DEG, (o, r["shift"])
 
 
-@pytest.mark.parametrize("R", [1, 7, 16, 17, 64])
+@pytest.mark.parametrize("R", [1, 7, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64])
 def test_random_images_match_restatement(R):
     rng = np.random.default_rng(100 + R)
     q = rng.uniform(0.0, 80.0, (3, R, 360)).astype(np.float32)
@@ -155,6 +158,110 @@ def test_invalid_ids():
     store = _ya().YawImages(rows=16)                         # an empty store: every id is invalid
     got = estimate(store, [0], dev(c), [0])
     assert got["shift"][0] == -1 and got["init_transforms"][0].tobytes() == IDENTITY
+
+
+# ------------------------------------------------------------------------------------------------
+# the constructed cases of yaw_cases.py
+# ------------------------------------------------------------------------------------------------
+def assert_bits(got, i, want, what=""):
+    """pair i of estimate_yaw's outputs against yaw_cases.expected, bit for bit"""
+    for k in ("shift", "peak", "runner_up", "init_transforms"):
+        x, y = np.ascontiguousarray(got[k][i]), np.ascontiguousarray(want[k])
+        assert x.dtype == y.dtype and x.shape == y.shape, (what, k, x.dtype, y.dtype)
+        assert x.tobytes() == y.tobytes(), (what, k, x, y)
+
+
+def assert_not_finite_contract(got, i, what=""):
+    """a pair with a pixel that is not finite: shift 0 (not -1), the identity bit for bit, peak NaN, runner_up NaN"""
+    print(what, "shift", got["shift"][i], "peak", got["peak"][i], "runner_up", got["runner_up"][i])
+    assert got["shift"][i] == 0, (what, got["shift"][i])
+    assert got["init_transforms"][i].tobytes() == IDENTITY, what
+    assert np.isnan(got["peak"][i]), (what, got["peak"][i])
+    assert np.isnan(got["runner_up"][i]), (what, got["runner_up"][i])
+
+
+def test_exact_cases_bit_for_bit():
+    """Integer images whose float64 scores are exact in any order: two-way ties wherever the arg-max decides them (one
+    scan lane, across the butterfly, across the waves and lanes of the sums), the informative row at every chunk and
+    group edge, three-, four- and 72-way ties, and the same with denormal and with 2^100-scaled pixels.  One launch
+    per row count; every output equals the int64 reference's, with no tolerance."""
+    groups = C.by_rows(C.exact_cases())
+    assert sorted(groups) == [1, 15, 16, 17, 31, 33, 48, 49, 63, 64]
+    for R, cases in sorted(groups.items()):
+        n = len(cases)
+        got = estimate(dev(np.stack([c.Iq for c in cases])), list(range(n)),
+                       dev(np.stack([c.Ic for c in cases])), list(range(n)))
+        for i, c in enumerate(cases):
+            e = C.expected(c)
+            print(c.name, "shift", got["shift"][i], e["shift"], "peak", got["peak"][i], e["peak"], "runner_up",
+                  got["runner_up"][i], e["runner_up"])
+            assert (int(e["shift"]), float(e["peak"]), float(e["runner_up"])) == (c.shift, c.peak, c.runner_up), c.name
+            assert_bits(got, i, e, c.name)
+
+
+def test_tie_alone_and_between_ordinary_pairs():
+    rng = np.random.default_rng(12)
+    some = rng.uniform(0.0, 80.0, (4, 17, 360)).astype(np.float32)
+    ties = [C.delta(17, 16, 63, 64), C.delta(17, 16, 0, 64), C.delta(17, 16, 100, 300)]
+    q = np.concatenate([some[:2], np.stack([c.Iq for c in ties])])
+    c = np.concatenate([some[2:], np.stack([c.Ic for c in ties])])
+    pl = [(0, 0), (2, 2), (1, 1), (3, 3), (0, 1), (4, 4), (1, 0)]
+    got = estimate(dev(q), [a for a, _ in pl], dev(c), [b for _, b in pl])
+    for i, (a, b) in enumerate(pl):
+        if a >= 2:
+            assert a == b
+            assert_bits(got, i, C.expected(ties[a - 2]), ties[a - 2].name)
+            alone = estimate(dev(ties[a - 2].Iq[None]), [0], dev(ties[a - 2].Ic[None]), [0])
+            assert_same(alone, 0, got, i, "alone")
+        else:
+            assert_matches(got, i, q[a], c[b], (a, b))
+
+
+def test_finite_maximum():
+    Iq, Ic, planted = C.finite_maximum()
+    got = estimate(dev(Iq[None]), [0], dev(Ic[None]), [0])
+    r = assert_matches(got, 0, Iq, Ic, "3.4e38")
+    assert r["shift"] == planted == 2 and np.isfinite(got["peak"][0]) and np.isfinite(got["runner_up"][0])
+
+
+@pytest.mark.parametrize("R", [1, 16, 17])
+def test_images_that_are_not_finite(R):
+    """NaN, +inf, -inf and +inf with -inf in one row; in the query, the candidate and both; in the first row and in the
+    last (for 17 rows the last is alone in its chunk).  Every such pair gets (0, identity, NaN, NaN), and the valid pairs
+    of the same launch keep the bits of a launch without them."""
+    rng = np.random.default_rng(40 + R)
+    good_q = rng.uniform(0.0, 80.0, (2, R, 360)).astype(np.float32)
+    good_c = rng.uniform(0.0, 80.0, (2, R, 360)).astype(np.float32)
+    bad = C.nonfinite_pairs(R)
+    q = np.concatenate([good_q, np.stack([p[1] for p in bad])])
+    c = np.concatenate([good_c, np.stack([p[2] for p in bad])])
+    valid = [(0, 0), (1, 1), (0, 1)]
+    at = {0: valid[0], len(bad) // 2 + 1: valid[1], len(bad) + 2: valid[2]}      # first, in the middle, last
+    pl, k = [], 0
+    for i in range(len(bad) + 3):
+        if i in at:
+            pl.append(at[i])
+        else:
+            pl.append((2 + k, 2 + k))
+            k += 1
+    assert k == len(bad) and pl[0] == valid[0] and pl[-1] == valid[2]
+    got = estimate(dev(q), [a for a, _ in pl], dev(c), [b for _, b in pl])
+    ref = estimate(dev(good_q), [a for a, _ in valid], dev(good_c), [b for _, b in valid])
+    for i, (a, b) in enumerate(pl):
+        if i in at:
+            j = valid.index((a, b))
+            assert_same(got, i, ref, j, "beside")
+            assert_matches(got, i, good_q[a], good_c[b], ("beside", a, b))
+        else:
+            assert_not_finite_contract(got, i, bad[a - 2][0])
+    # a clean image against a poisoned one of the other array, and an invalid id beside them: -1 stays -1
+    mixed = estimate(dev(q), [0, 2, 0, 5], dev(c), [2, 0, len(c), 5])
+    assert not np.isfinite(q[2]).all() and np.isfinite(c[2]).all() and np.isfinite(q[0]).all()
+    assert_matches(mixed, 0, q[0], c[2], "clean query, clean candidate of a poisoned pair")
+    assert_not_finite_contract(mixed, 1, "poisoned query, clean candidate")
+    assert mixed["shift"][2] == -1 and np.isnan(mixed["peak"][2]) and np.isnan(mixed["runner_up"][2])
+    assert mixed["init_transforms"][2].tobytes() == IDENTITY
+    assert_not_finite_contract(mixed, 3, bad[3][0])
 
 
 def test_empty_and_split_batches(monkeypatch):
@@ -408,6 +515,47 @@ def test_keyframe_range_image_is_used(encoder, rotated, other):
         def encode_points_batch(self, *a, **kw):
             raise AssertionError("the keyframes carry their images")
     _same_closures(ref, _retrieval(kfs, yaw_init=True, yaw_encoder=NoEncoder()).get_loop_closures(query))
+
+
+def test_keyframe_image_with_a_nan_pixel(encoder, rotated, other):
+    """A database keyframe whose range_image holds one NaN pixel: its pair starts from the identity, as it would without
+    the guess, and says so (init_yaw_deg 0.0, yaw_peak_ratio NaN, not inf); the other candidates do not notice."""
+    targets = [p[1] for p in rotated[:3]]
+    poisoned_idx = 1
+    clouds = targets + [other, rotated[0][0]]
+    images = encoder.encode_points_batch(clouds, return_images=True)[2].cpu().numpy()
+    assert np.isfinite(images).all()
+
+    def candidates(poison, **kw):
+        kfs, qdesc = _database(targets, other)
+        query = SimpleNamespace(keyframe_id=7, scan_id=7, points=rotated[0][0], descriptor=qdesc[0], pose=None)
+        for kf, im in zip(kfs + [query], images):
+            kf.range_image = im.copy()
+        if poison:
+            kfs[poisoned_idx].range_image[9, 200] = np.nan
+        r = _retrieval(kfs, **kw)
+        everyone = r._global_retrieval(query)                # verified or not
+        r._geometric_verification(query.points, everyone,
+                                  query_image=r._range_images([query]) if r.yaw_images is not None else None)
+        assert len(everyone) == 4
+        return {c.database_idx: c for c in everyone}
+
+    def same_result(x, y):
+        assert x.verified == y.verified and x.fitness == y.fitness and x.rmse == y.rmse
+        assert np.asarray(x.transform).tobytes() == np.asarray(y.transform).tobytes()
+
+    bad = candidates(True, yaw_init=True)
+    clean = candidates(False, yaw_init=True)
+    identity = candidates(False, yaw_init=False)
+    c = bad[poisoned_idx]
+    assert c.info["init_yaw_deg"] == 0.0 and np.isnan(c.info["yaw_peak_ratio"]), c.info
+    assert not np.isnan(c.fitness) and np.isfinite(np.asarray(c.transform)).all()
+    same_result(c, identity[poisoned_idx])                   # it started from the identity
+    assert clean[poisoned_idx].info["init_yaw_deg"] != 0.0 and clean[poisoned_idx].info["yaw_peak_ratio"] > 1.0
+    for i in (0, 2, 3):                                      # the others: bitwise what they are without the poison
+        same_result(bad[i], clean[i])
+        assert bad[i].info["init_yaw_deg"] == clean[i].info["init_yaw_deg"]
+        assert bad[i].info["yaw_peak_ratio"] == clean[i].info["yaw_peak_ratio"]
 
 
 def test_off_is_todays_path(revisits, other, monkeypatch):
