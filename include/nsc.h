@@ -1237,6 +1237,90 @@ int    nsc_map_register_robust(const void *points, int32_t dtype, int32_t stride
                                double *fitness_rmse, double *cost, int64_t *corr_iterations, double *information,
                                double *system0, double *weight_pairs, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Seen-through voxels (nsc_map_cast_rays, nsc_map_flag_rows; restated in tests/map_rays_restatement.py): which voxels of
+ * a kept map did later scans look through, and which rows lie in them.  The map is read only.  Float64, every operation
+ * rounded on its own; sums of three products are (x0 y0 + x1 y1) + x2 y2.
+ *
+ * nsc_map_cast_rays.  Rows, poses, pose_ids and params in the formats of nsc_map_build; voxels, index and max_voxels of a
+ *   nsc_map_build_dist call with the same grid.
+ * A ray is one row of a cloud with a pose P: o_a = P[a][3] the sensor, w the placed row (nsc_map_build's w),
+ *   fo_a = (o_a - origin_a) / voxel, fw_a = (w_a - origin_a) / voxel, d = fw - fo, D = w - o (m),
+ *   L = sqrt((d_x^2 + d_y^2) + d_z^2) voxel.
+ * Dropped rays, each kind counted, the checks in this order: the cloud has no pose (pose_ids as in the build); xyz or w is
+ *   not finite; the voxel of o or of w lies outside the 2^21 voxels per axis; the ray is short: with t0 = min_range / L and
+ *   t1 = min(1 - end_margin / L, max_range / L), L > 0 is false or t0 < t1 is false.  A negative end_margin stands for one
+ *   voxel edge.
+ * The walk starts at k = floor(fo + t0 d).  Per axis the next face is tn_a = ((k_a + 1) - fo_a) / d_a for d_a > 0,
+ *   (k_a - fo_a) / d_a for d_a < 0, +inf for d_a = 0: from k every step, never accumulated.  The step axis is the one with
+ *   the smallest tn, the lowest axis winning a tie.  Voxel k is examined over [ta, tb]: ta = t0 for the first voxel, else
+ *   the tn of the step that entered it; tb = min(tn_axis, t1).  If tn_axis < t1 is false the ray has ended; else
+ *   k_axis +- 1.  A ray examines 3 (floor(max_range / voxel) + 2) voxels at most; one that has not ended by then stops and
+ *   is counted in rays_truncated (in exact arithmetic none is).
+ * Examining voxel k.  It is skipped when it is outside the grid or not in the index (nsc_map_register's probe), its place
+ *   is ~0 or not below max_voxels, its key is the key of the voxel of w, or it is not usable (record[15] != 1.0).  Else,
+ *   with the record's mean m and information Omega: a = o - m, num = D^T (Omega a), den = D^T (Omega D), Omega x formed
+ *   row by row; t* = -num / den if den > 0, else ta; t* = min(max(t*, ta), tb); x = a + t* D; s = x^T (Omega x).  The ray
+ *   crosses the voxel iff s <= gate^2: the segment comes within `gate` standard deviations of the voxel's own Gaussian.
+ *   A ray that only runs through the box of a voxel, beside what the voxel holds, does not count.
+ * Outputs.  crossed (max_voxels) int64: crossed[place] += 1 per crossing, ADDED to what the caller passes, so calls
+ *   accumulate.  ray_stats (NSC_MAP_RAY_STATS) int64, written: rays cast (truncated ones included), not finite, outside,
+ *   without pose, short, voxels examined, crossings, rays truncated.
+ * Launches.  NSC_MAP_RAY_LAUNCHES kernels (clear the stats; cast: one lane per ray) whose grids depend on total_rows alone;
+ *   integer atomics only, so two calls agree by bits and the cloud order changes nothing; no host synchronisation, no
+ *   memset or memcpy nodes.  No workspace.
+ *
+ * nsc_map_flag_rows.  The rows again, with index, info (nsc_map_build_dist's) and crossed.  The voxel at a place is seen
+ *   through iff count > 0, crossed >= min_crossings and (double)crossed >= ratio (double)count.  row_flags (total_rows)
+ *   uint8, every entry written: 1 iff the row's own voxel (nsc_map_build's key, the index's probe) is seen through.
+ *   flag_stats (NSC_MAP_FLAG_STATS) int64, written: rows flagged; rows kept; rows dropped (no pose, not finite or outside
+ *   the grid); rows missing (the voxel is not in the index or has no place below max_voxels).
+ *   A caller removes the flagged rows with nsc_map_remove_dist on the same cloud with every other row made NaN: a row that
+ *   is not finite is dropped by every call here, so this is a matched removal of a subset.
+ * Launches.  NSC_MAP_FLAG_LAUNCHES kernels (clear the stats; flag: one lane per row), as above.  No workspace.
+ * ------------------------------------------------------------------------------------------ */
+#define NSC_MAP_RAY_LAUNCHES        2       /* kernels of one nsc_map_cast_rays call */
+#define NSC_MAP_FLAG_LAUNCHES       2       /* kernels of one nsc_map_flag_rows call */
+#define NSC_MAP_RAY_MAX_REACH       65536   /* max_range / voxel_size at most */
+#define NSC_MAP_RAY_STATS           8       /* entries of `ray_stats` */
+#define NSC_MAP_RAY_STAT_CAST       0       /* rays walked                                           */
+#define NSC_MAP_RAY_STAT_NOT_FINITE 1       /* rays with a non-finite xyz or world coordinate        */
+#define NSC_MAP_RAY_STAT_OUTSIDE    2       /* rays whose sensor or end voxel is outside the grid    */
+#define NSC_MAP_RAY_STAT_NO_POSE    3       /* rays of clouds without a pose (and rows of no cloud)  */
+#define NSC_MAP_RAY_STAT_SHORT      4       /* rays with nothing between min_range and their end     */
+#define NSC_MAP_RAY_STAT_VISITED    5       /* voxels examined                                       */
+#define NSC_MAP_RAY_STAT_CROSSINGS  6       /* additions to `crossed`                                */
+#define NSC_MAP_RAY_STAT_TRUNCATED  7       /* of the rays cast: stopped by the step bound           */
+#define NSC_MAP_FLAG_STATS          4       /* entries of `flag_stats` */
+#define NSC_MAP_FLAG_STAT_FLAGGED   0
+#define NSC_MAP_FLAG_STAT_KEPT      1
+#define NSC_MAP_FLAG_STAT_DROPPED   2
+#define NSC_MAP_FLAG_STAT_MISSING   3
+
+typedef struct NscMapRayParams {
+    double  min_range;              /* 0      the walk starts this far from the sensor (m), >= 0 */
+    double  max_range;              /* 60     and ends here at the latest (m), > 0; at most NSC_MAP_RAY_MAX_REACH voxels */
+    double  end_margin;             /* -1     and this far in front of the row (m); negative: one voxel edge */
+    double  gate;                   /* 3      a crossing comes within this many standard deviations, > 0 */
+} NscMapRayParams;
+
+void   nsc_map_ray_default_params(NscMapRayParams *p);
+/* nsc_map_build's refusals, with voxels, index and crossed needed when max_voxels > 0 and ray_stats always; NSC_EINVAL also
+ * for a null `ray`, a field of it that is not finite, min_range < 0, max_range <= 0 or gate <= 0; NSC_EUNSUPPORTED for
+ * max_range / voxel_size above NSC_MAP_RAY_MAX_REACH: all before anything is launched. */
+int    nsc_map_cast_rays(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_clouds,
+                         int64_t total_rows, const double *poses, int32_t n_poses, const int64_t *pose_ids,
+                         const NscMapParams *params, const double *voxels, const uint64_t *index, int64_t max_voxels,
+                         const NscMapRayParams *ray, int64_t *crossed, int64_t *ray_stats, void *stream);
+/* nsc_map_build's refusals, with index, info and crossed needed when max_voxels > 0, row_flags when total_rows > 0 and
+ * flag_stats always; NSC_EINVAL also for min_crossings < 1 and a ratio not finite and positive: all before anything is
+ * launched. */
+int    nsc_map_flag_rows(const void *points, int32_t dtype, int32_t stride_floats, const int64_t *offsets, int32_t n_clouds,
+                         int64_t total_rows, const double *poses, int32_t n_poses, const int64_t *pose_ids,
+                         const NscMapParams *params, const uint64_t *index, const int64_t *info, const int64_t *crossed,
+                         int64_t max_voxels, int64_t min_crossings, double ratio, uint8_t *row_flags, int64_t *flag_stats,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

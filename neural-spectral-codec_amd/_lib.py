@@ -141,6 +141,11 @@ class MapRobustParams(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("neighbours", C.c_int32), ("scale", C.c_double)]
 
 
+class MapRayParams(C.Structure):
+    """struct NscMapRayParams"""
+    _fields_ = [("min_range", C.c_double), ("max_range", C.c_double), ("end_margin", C.c_double), ("gate", C.c_double)]
+
+
 # include/nsc.h NSC_MAP_DTYPE_F32, NSC_MAP_DTYPE_F64, NSC_MAP_STATS and NSC_MAP_STAT_*: the name of each entry of `stats`
 MAP_DTYPE_F32, MAP_DTYPE_F64, MAP_STATS = 0, 1, 7
 MAP_STAT_NAMES = ("voxels_found", "voxels_written", "rows_used", "rows_not_finite", "rows_outside", "rows_without_pose",
@@ -163,6 +168,12 @@ MAP_REHASH_STAT_NAMES = ("voxels_kept", "voxels_dropped", "source_keys_unplaced"
 MAP_REGISTER_ROBUST_SYSTEM = 32         # include/nsc.h NSC_MAP_REGISTER_ROBUST_SYSTEM
 # include/nsc.h NSC_MAP_KERNEL_*: the pose graph's names and numbers
 MAP_KERNELS = {None: 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
+# include/nsc.h NSC_MAP_RAY_LAUNCHES, NSC_MAP_FLAG_LAUNCHES, NSC_MAP_RAY_MAX_REACH, NSC_MAP_RAY_STATS and NSC_MAP_RAY_STAT_*,
+# NSC_MAP_FLAG_STATS and NSC_MAP_FLAG_STAT_*: the name of each entry of `ray_stats` and of `flag_stats`
+MAP_RAY_LAUNCHES, MAP_FLAG_LAUNCHES, MAP_RAY_MAX_REACH, MAP_RAY_STATS, MAP_FLAG_STATS = 2, 2, 65536, 8, 4
+MAP_RAY_STAT_NAMES = ("rays_cast", "rays_not_finite", "rays_outside", "rays_without_pose", "rays_short", "voxels_visited",
+                      "crossings", "rays_truncated")
+MAP_FLAG_STAT_NAMES = ("rows_flagged", "rows_kept", "rows_dropped", "rows_without_voxel")
 
 # include/nsc.h NSC_POSEGRAPH_MAX_EDGES, NSC_POSEGRAPH_MAX_LAUNCHES, NSC_POSEGRAPH_STATS
 POSEGRAPH_MAX_EDGES, POSEGRAPH_MAX_LAUNCHES, POSEGRAPH_STATS = 1073741823, 1000000, 10
@@ -317,6 +328,11 @@ SYMBOLS = {
     "nsc_map_register_robust": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _i64, C.POINTER(MapParams),
                                           C.POINTER(MapRegisterParams), C.POINTER(MapRobustParams), _vp, _vp, _vp, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nsc_map_ray_default_params": (None, [C.POINTER(MapRayParams)]),
+    "nsc_map_cast_rays": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, C.POINTER(MapParams), _vp, _vp, _i64,
+                                    C.POINTER(MapRayParams), _vp, _vp, _vp]),
+    "nsc_map_flag_rows": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, C.POINTER(MapParams), _vp, _vp, _vp,
+                                    _i64, _i64, C.c_double, _vp, _vp, _vp]),
     "nsc_triplet_workspace_bytes": (_sz, [_i32]),
     "nsc_triplet_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
                                    _sz, _vp]),

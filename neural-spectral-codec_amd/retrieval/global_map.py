@@ -24,8 +24,8 @@ A check without ground truth that an optimisation helped: a bent trajectory draw
 occupies more voxels than a consistent one -- compare ``voxels_found`` before and after.  ``revisited`` marks the voxels
 seen from keyframes far apart in the sequence, the places where a closure is what makes the map consistent.
 
-Not part of this module: insertion into a kept table, free space or ray casting, removal of dynamic objects, intensity or
-colour, meshes.
+Not part of this module: insertion into a kept table, and ray casting with the removal of what later scans saw through
+(``MapLocalizer`` has both, for its distribution map); intensity or colour, meshes.
 """
 import ctypes as C
 from collections import namedtuple

@@ -42,6 +42,16 @@ Definition (the contract the two entry points and tests/map_localize_restatement
                  and after.  A destination that is too small follows the build's overflow rule: the kept voxels in front
                  take the places, the others keep their key with place ~0.  ``new_place`` tells a caller who keeps side data
                  by place where every old place went.  An inconsistent voxel is kept with its integers
+    seen through (nsc_map_cast_rays, nsc_map_flag_rows; ``observe*``, ``seen_through``, ``flag_rows_device``, ``carve*``)
+                 the ray from a cloud's sensor (its pose's translation) to each of its placed rows is walked through the
+                 grid from ``ray_min_range`` to ``ray_end_margin`` in front of the row, ``ray_max_range`` at most, the next
+                 face recomputed from the voxel at every step.  A usable voxel other than the row's own is crossed when the
+                 segment inside it comes within ``ray_gate`` standard deviations of the voxel's own Gaussian
+                 (x^T Omega x <= gate^2 at the closest point): a ray that merely runs through the box of a floor voxel,
+                 beside the floor, does not count.  ``crossed`` counts crossings per place and accumulates; a voxel is seen
+                 through with count > 0, crossed >= ``min_crossings`` and crossed >= ``crossing_ratio`` x count.  Carving
+                 removes the rows of given clouds that lie in such voxels, as a matched removal of the clouds with every
+                 other row made NaN, and the map is then, bit for bit, the build over the rows kept
 
     robust      (nsc_map_register_robust; ``kernel``, ``robust_scale``, ``neighbours``) every pair (row, voxel) is weighted
                  by w = rho'(s), s = d^T Omega_v d, with the pose graph's kernels and one width c in units of sqrt(chi^2):
@@ -96,6 +106,12 @@ class MapLocalizer:
     kernel            None     robust kernel of the registration: None (quadratic), "huber", "cauchy" or "geman_mcclure"
     robust_scale      None     the kernel's width c, in units of sqrt(chi^2); needed with a kernel, refused without one
     neighbours        1        voxels a row is paired with: 1 (its own) or 7 (and the six face neighbours)
+    ray_min_range     0.0      ``observe*``: a ray is walked from this far off its sensor (m)
+    ray_max_range     60.0     to this far at most (m; at most ``_lib.MAP_RAY_MAX_REACH`` voxels)
+    ray_end_margin    None     and to this far in front of its row (m); None: one voxel edge
+    ray_gate          3.0      a ray crosses a voxel within this many standard deviations of its Gaussian
+    min_crossings     3        a voxel is seen through with at least this many crossings
+    crossing_ratio    0.5      and at least this many per row it holds
 
     With the defaults ``register*`` and ``extend`` call nsc_map_register; with a kernel or seven voxels they call
     nsc_map_register_robust, and ``extend`` still gates on ``fitness``.
@@ -109,8 +125,23 @@ class MapLocalizer:
     def __init__(self, voxel_size: float = 1.0, origin=(0.0, 0.0, 0.0), max_voxels=None, min_points: int = 6,
                  eigen_ratio: float = 1e-2, sigma_floor: float = 1e-3, max_iteration: int = 30,
                  relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, device="cuda", insertable: bool = False,
-                 kernel=None, robust_scale=None, neighbours: int = 1):
+                 kernel=None, robust_scale=None, neighbours: int = 1, ray_min_range: float = 0.0,
+                 ray_max_range: float = 60.0, ray_end_margin=None, ray_gate: float = 3.0, min_crossings: int = 3,
+                 crossing_ratio: float = 0.5):
         self._grid = GlobalMap(voxel_size, origin, max_voxels, device)       # its refusals are this class's
+        margin = -1.0 if ray_end_margin is None else ray_end_margin
+        if not (all(np.isfinite(v) for v in (ray_min_range, ray_max_range, margin, ray_gate)) and
+                float(ray_min_range) >= 0.0 and float(ray_max_range) > 0.0 and float(ray_gate) > 0.0 and
+                (ray_end_margin is None or float(margin) >= 0.0)):
+            raise _lib.NscError("MapLocalizer: finite ray ranges with ray_min_range >= 0, ray_max_range > 0, "
+                                "ray_end_margin >= 0 or None, and ray_gate > 0")
+        if float(ray_max_range) / float(voxel_size) > _lib.MAP_RAY_MAX_REACH:
+            raise _lib.NscError(f"MapLocalizer: ray_max_range reaches at most {_lib.MAP_RAY_MAX_REACH} voxels")
+        if int(min_crossings) < 1 or not (np.isfinite(crossing_ratio) and float(crossing_ratio) > 0.0):
+            raise _lib.NscError("MapLocalizer: min_crossings >= 1 and a finite positive crossing_ratio")
+        self.ray = _lib.MapRayParams(min_range=float(ray_min_range), max_range=float(ray_max_range),
+                                     end_margin=float(margin), gate=float(ray_gate))
+        self.min_crossings, self.crossing_ratio = int(min_crossings), float(crossing_ratio)
         if kernel not in _lib.MAP_KERNELS:
             raise _lib.NscError(f"MapLocalizer: unknown kernel {kernel!r}")
         if neighbours not in (1, 7):
@@ -136,6 +167,7 @@ class MapLocalizer:
         self.device = device
         self.insertable = bool(insertable)
         self.voxels = self.index = self.keys = self.info = self.stats = self.moments = self.cursor = None
+        self.crossed = None                  # (M,) int64 crossings per place, from the first ``observe*`` on
         self.complete = None
         self.capacity = None
 
@@ -162,6 +194,8 @@ class MapLocalizer:
         if self.cursor is not None:
             self.cursor[0].fill_(N)
             self.cursor[1].fill_(B)
+        if self.crossed is not None:                                     # the places are new: what was seen through them is not
+            self.crossed = self.crossed.fill_(0) if int(self.crossed.numel()) == M else None
         return out
 
     @staticmethod
@@ -376,6 +410,129 @@ class MapLocalizer:
         out["moved"] = moved
         return out
 
+    # ---- seen-through voxels: ray casting and carving ----------------------------------------------------------------
+
+    def _observable(self, what, points):
+        if self.voxels is None:
+            raise _lib.NscError(f"MapLocalizer.{what}: build a map first")
+        if points.device != self.voxels.device:
+            raise _lib.NscError(f"the clouds must be on the map's device ({self.voxels.device})")
+        if self.crossed is None:
+            self.crossed = torch.zeros((self.capacity,), dtype=torch.int64, device=self.voxels.device)
+
+    def observe_device(self, points, offsets, poses, pose_ids=None):
+        """Cast the rays of packed clouds through the kept map (nsc_map_cast_rays), on the device and without a
+        synchronisation: the ray of a row runs from its cloud's sensor, poses[id][:3, 3], to the placed row, and every
+        usable voxel it passes within ``ray_gate`` standard deviations of, before ``ray_end_margin`` in front of its end,
+        counts one crossing (include/nsc.h).  Arguments as ``build_device``.  The crossings are ADDED to ``crossed`` (M,)
+        int64, which is made of zeros by the first call and zeroed by every build and every ``carve*``.  The map is only
+        read.  Returns crossed and ray_stats (8,) int64 (``_lib.MAP_RAY_STAT_NAMES``), written anew by every call."""
+        self._observable("observe_device", points)
+        dev = self.voxels.device
+        c = _clouds(points, offsets, poses, pose_ids)
+        ray_stats = torch.empty((_lib.MAP_RAY_STATS,), dtype=torch.int64, device=dev)
+        _lib.call("nsc_map_cast_rays", dev, *_row_args(c, self.params), self.voxels, self.index, self.capacity, self.ray,
+                  self.crossed, ray_stats, _lib.STREAM)
+        return dict(crossed=self.crossed, ray_stats=ray_stats)
+
+    @staticmethod
+    def _observed(out):
+        """observe_device's dict -> the eight counts by name (the one synchronisation)"""
+        return dict(zip(_lib.MAP_RAY_STAT_NAMES, out["ray_stats"].cpu().tolist()))
+
+    def observe(self, clouds, poses, pose_ids=None):
+        """``observe_device`` on the input forms of ``build``.  Returns the eight counts of ray_stats by name; one
+        synchronisation."""
+        if self.voxels is None:
+            raise _lib.NscError("MapLocalizer.observe: build a map first")
+        return self._observed(self.observe_device(*_host_clouds(clouds, poses, pose_ids, self.voxels.device)))
+
+    def _store_range(self, what, store, start, stop):
+        n = len(store)
+        stop = n if stop is None else stop
+        if not 0 <= int(start) <= int(stop) <= n:
+            raise _lib.NscError(f"MapLocalizer.{what}: start and stop must satisfy 0 <= start <= stop <= {n}, got {start} "
+                                f"and {stop}")
+        return int(start), int(stop)
+
+    def observe_prepared(self, store: PreparedClouds, poses, pose_ids=None, start=0, stop=None):
+        """``observe`` on the clouds ``start`` to ``stop`` (the end, if None) of a ``PreparedClouds``; ``poses`` and
+        ``pose_ids`` have one entry per cloud of that range."""
+        if self.voxels is None:
+            raise _lib.NscError("MapLocalizer.observe_prepared: build a map first")
+        start, stop = self._store_range("observe_prepared", store, start, stop)
+        return self._observed(self.observe_device(*_prepared_clouds(store, poses, pose_ids, start, stop)))
+
+    def seen_through(self):
+        """(M,) bool: the voxels later scans looked through -- count > 0, crossed >= ``min_crossings`` and
+        crossed >= ``crossing_ratio`` x count.  Torch arithmetic on ``crossed`` and ``info``, for inspection;
+        ``flag_rows_device`` decides the same on the device, per row."""
+        if self.voxels is None or self.crossed is None:
+            raise _lib.NscError("MapLocalizer.seen_through: build a map and observe scans first")
+        count = self.info[:, 0]
+        return (count > 0) & (self.crossed >= self.min_crossings) & \
+            (self.crossed.to(torch.float64) >= self.crossing_ratio * count.to(torch.float64))
+
+    def flag_rows_device(self, points, offsets, poses, pose_ids=None):
+        """The rows of packed clouds whose own voxel is seen through (nsc_map_flag_rows), on the device and without a
+        synchronisation.  Arguments as ``build_device``.  Returns row_flags (N,) bool and flag_stats (4,) int64
+        (``_lib.MAP_FLAG_STAT_NAMES``: flagged, kept, dropped as a build drops rows, without a voxel in the map)."""
+        self._observable("flag_rows_device", points)
+        dev = self.voxels.device
+        c = _clouds(points, offsets, poses, pose_ids)
+        flags = torch.empty((c.N,), dtype=torch.bool, device=dev)
+        flag_stats = torch.empty((_lib.MAP_FLAG_STATS,), dtype=torch.int64, device=dev)
+        _lib.call("nsc_map_flag_rows", dev, *_row_args(c, self.params), self.index, self.info, self.crossed, self.capacity,
+                  self.min_crossings, self.crossing_ratio, flags, flag_stats, _lib.STREAM)
+        return dict(row_flags=flags, flag_stats=flag_stats)
+
+    @staticmethod
+    def without(points, mask):
+        """``points`` with the rows of ``mask`` (N,) bool made NaN, on the device.  Every map call drops and counts a row
+        that is not finite, so this is how a subset of a cloud's rows is given to a call that takes whole clouds."""
+        nan = torch.full((), float("nan"), dtype=points.dtype, device=points.device)
+        return torch.where(mask[:, None], nan, points)
+
+    def carve_device(self, points, offsets, poses, pose_ids=None):
+        """Take out of the kept map the rows of these clouds that lie in seen-through voxels: ``flag_rows_device``, then
+        ``remove_device`` on the clouds with every row that is NOT flagged made NaN -- a matched removal of a subset, with
+        no compaction and no read-back -- then ``crossed`` is zeroed.  The clouds must be in the map under these poses.
+        The map is afterwards, voxel by voxel, the build over the rows that were kept.  With device ``pose_ids`` (or none)
+        the sequence can be captured, ``observe_device`` in front of it included.  Returns the kept tensors, removed
+        (8,) (carved rows as rows_removed, the others as removed_not_finite), flag_stats (4,) and carved (N,) bool.
+
+        A cloud that has been carved must from then on be moved or removed as ``without(points, carved)``, its carved rows
+        NaN, in ``remove*``, ``replace*`` and ``update_prepared`` alike: the map no longer holds those rows, and taking
+        them out again sends the counts of their voxels below zero (``voxels_inconsistent``)."""
+        self._insertable_map("carve_device")
+        flagged = self.flag_rows_device(points, offsets, poses, pose_ids)
+        carved = flagged["row_flags"]
+        nan = torch.full((), float("nan"), dtype=points.dtype, device=points.device)
+        out = self.remove_device(torch.where(carved[:, None], points, nan), offsets, poses, pose_ids)   # without(points, ~carved)
+        self.crossed.fill_(0)                                    # a fill kernel, as the cursor's
+        return dict(out, flag_stats=flagged["flag_stats"], carved=carved)
+
+    def _carved(self, out):
+        """carve_device's dict -> ``remove``'s dict, the four counts of flag_stats by name and ``carved``"""
+        flag_stats = out["flag_stats"]
+        res = self._removed(out)                                 # the one synchronisation
+        res.update(zip(_lib.MAP_FLAG_STAT_NAMES, flag_stats.cpu().tolist()))
+        res["carved"] = out["carved"]
+        return res
+
+    def carve(self, clouds, poses, pose_ids=None):
+        """``carve_device`` on the input forms of ``build``.  Returns ``remove``'s dict, the four counts of flag_stats by
+        name and carved (N,) bool over the packed rows; one synchronisation."""
+        self._insertable_map("carve")
+        return self._carved(self.carve_device(*_host_clouds(clouds, poses, pose_ids, self.voxels.device)))
+
+    def carve_prepared(self, store: PreparedClouds, poses, pose_ids=None, start=0, stop=None):
+        """``carve`` on the clouds ``start`` to ``stop`` (the end, if None) of a ``PreparedClouds``, under the poses they
+        were placed by."""
+        self._insertable_map("carve_prepared")
+        start, stop = self._store_range("carve_prepared", store, start, stop)
+        return self._carved(self.carve_device(*_prepared_clouds(store, poses, pose_ids, start, stop)))
+
     # ---- resizing and compaction -------------------------------------------------------------------------------------
 
     def _resizable(self, what, max_voxels):
@@ -415,6 +572,11 @@ class MapLocalizer:
         _lib.call("nsc_map_rehash_dist", dev, self.voxels, self.info, self.keys, self.moments, self.stats, self.cursor, old,
                   0 if compact else 1, out["voxels"], out["index"], out["info"], out["keys"], out.get("moments"),
                   out["stats"], out.get("cursor"), M, out["new_place"], out["tile_base"], out["rehashed"], _lib.STREAM)
+        if self.crossed is not None:
+            # side data by place follows new_place; a place that was dropped adds to an entry past the end, which is cut off
+            moved = torch.zeros((M + 1,), dtype=torch.int64, device=dev)
+            moved.scatter_add_(0, torch.where(out["new_place"] >= 0, out["new_place"], M), self.crossed)
+            self.crossed = moved[:M]
         self._keep(out, M, out["moments"] if self.moments is not None else None,
                    out["cursor"] if self.cursor is not None else None)
         self.max_voxels = M
